@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - headline measurement (contract in the task statement; BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload roialign|step]
+    python bench.py --gpus N --steps K --warmup W [--workload roialign|step] [--dump-outputs DIR]
 
 Workloads
   roialign  BASELINE.json configs[1]: roi_align_2d fwd+bwd, 512 RoIs on a 256x200x272 map,
@@ -15,6 +15,9 @@ Workloads
             config.images_per_sec_f32_mfma.
   keypoint  BASELINE.json configs[4] per-GPU shape: the Keypoint R-CNN step of train_keypoints.py
             (17 keypoints, 56x56 heat maps), same batch / image size; a secondary line, never the default.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed is written as DIR/<name>.npy (float32; fixed seeded
+samples of the large tensors, 64 MB at most) - the inputs are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel, measured with HIP
 events inside the timed region on the launch stream; `cpu_baseline` is the NumPy oracle timed
@@ -129,6 +132,9 @@ def bench_roialign(args, rank, world):
         ev[k][0].record(); fwd(); ev[k][1].record(); bwd(); ev[k][2].record()
     sync_all(world)
     dt = time.perf_counter() - t0
+    if getattr(args, 'dump_outputs', None) and rank == 0:       # the last timed step's results, before the launches below overwrite them
+        from chainer_maskrcnn.bench_step import save_outputs, sample_flat
+        save_outputs(args.dump_outputs, {'roi_align_y': sample_flat(y), 'roi_align_gx': sample_flat(gx)})
     # a second run with the ADAPTIVE sampling grid (sampling_ratio 0 = ceil(roi / pooled) samples
     # per bin; the reference's configuration is 2) - reported, not part of `value`
     ad = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -300,7 +306,13 @@ def main():
     ap.add_argument('--gemm-arithmetic', default=None, choices=['f32', 'bf16x6_behind_backbone', 'bf16x6_backward', 'bf16x6'],
                     help='arithmetic of the convolution GEMMs of the step workloads (default: the shipped training default, train.py)')
     ap.add_argument('--graph', type=int, default=0, help='capture the step into a HIP graph (single GPU; measured slower than eager multi-stream launches on ROCm 7.2, so off by default)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (float32, <= 64 MB; large tensors as fixed seeded samples)')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup is not None and args.warmup < 0:
+        ap.error('--warmup must not be negative')
     world = int(os.environ.get('WORLD_SIZE', 1))
     rank = int(os.environ.get('RANK', 0))
     # one process per GPU: this rank's host threads stay on cores of its GPU's NUMA node (ranks sharing a node split it)
@@ -336,7 +348,7 @@ def main():
     args.keypoints = workload == 'keypoint'
     if workload in ('step', 'keypoint'):
         from chainer_maskrcnn.bench_step import bench_step
-        args.steps = args.steps or 20
+        args.steps = 20 if args.steps is None else args.steps
         args.warmup = 3 if args.warmup is None else args.warmup
         args.mask_rows = args.mask_rows
         out, model, dev = bench_step(args, rank, world)
@@ -348,7 +360,7 @@ def main():
             out['roi_align_microbench'] = {'workload': r['config']['workload'], 'bwd': r['roofline'], 'fwd': r['roi_align_fwd'],
                                            'forms_us': r['roi_align_bwd_forms_us']}
     else:
-        args.steps = args.steps or 200
+        args.steps = 200 if args.steps is None else args.steps
         args.warmup = 20 if args.warmup is None else args.warmup
         out = bench_roialign(args, rank, world)
     if rank == 0:

@@ -71,6 +71,8 @@ def bench_step(args, rank, world):
     dt = time.perf_counter() - t0
     per_rank_ms = _gather_over_ranks(dt / args.steps * 1e3, world, dev)
     dt = _max_over_ranks(dt, world, dev)
+    if getattr(args, 'dump_outputs', None) and rank == 0:       # the last timed step's results, copied out after the clock stopped
+        save_outputs(args.dump_outputs, step_outputs(chain, model.ps))
     loss = float(chain.observation['loss'])
     ips = N * world * args.steps / dt
 
@@ -286,6 +288,44 @@ def bench_step(args, rank, world):
     if getattr(args, 'cpu_affinity', None) is not None:
         out['config']['cpu_affinity_rank0'] = args.cpu_affinity
     return out, model, dev
+
+
+DUMP_SAMPLE = 1 << 22          # elements kept of a tensor too large to dump whole (16 MB of float32)
+DUMP_LIMIT = 64 << 20          # bytes of one dump in all
+
+
+def sample_flat(t, k=DUMP_SAMPLE, seed=0):
+    """Host float32 copy of t in logical (row-major) order - the whole tensor up to k elements, else a fixed seeded sample of
+    sorted element indices (the same ones for every tensor of that size)."""
+    flat = t.detach().reshape(-1)
+    n = flat.numel()
+    if n > k:
+        idx = np.unique(np.random.RandomState(seed).randint(0, n, size=k))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def step_outputs(chain, ps):
+    """What a training step hands its caller: the losses of chain.observation, the parameters after the update, the gradients
+    of the step (samples of the flat buffers: sample_flat) and the BatchNorm running statistics (in parameter-name order)."""
+    out = {k: v.detach().reshape(1).float().cpu().numpy() for k, v in chain.observation.items()}
+    out['params_sample'] = sample_flat(ps.params)
+    out['grads_sample'] = sample_flat(ps.grads)
+    if ps.buffers:
+        out['bn_running_stats'] = sample_flat(torch.cat([ps.buffers[k].reshape(-1) for k in sorted(ps.buffers)]))
+    return out
+
+
+def save_outputs(directory, arrays):
+    """bench.py --dump-outputs: every array as <directory>/<name>.npy (float32 / float64), at most DUMP_LIMIT bytes in all."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, 'dump of %d bytes exceeds %d' % (total, DUMP_LIMIT)
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + '.npy'), v)
 
 
 def _sync(world):

@@ -59,3 +59,28 @@ def test_committed_bench_line_of_the_round_has_the_contract_fields():
     cb = d['cpu_baseline']
     assert cb['kind'] in ('port', 'reference') and cb['cores'] >= 1 and cb['value'] > 0 and cb['sample']
     json.dumps(d)
+
+
+def test_dump_outputs_are_float_arrays_with_a_fixed_sample_under_the_limit(tmp_path):
+    """bench.py --dump-outputs: the losses, a seeded sample of the flat parameter / gradient buffers (the same elements in every run) and
+    the BatchNorm running statistics, as float32 .npy files, 64 MB at most; a dump over the limit is refused."""
+    import types
+
+    import numpy as np
+    import pytest
+    import torch
+    ps = types.SimpleNamespace(params=torch.arange(3 * bs.DUMP_SAMPLE, dtype=torch.float32), grads=torch.ones(1000),
+                               buffers={'b/avg_var': torch.ones(3), 'a/avg_mean': torch.zeros(2)})
+    chain = types.SimpleNamespace(observation={'loss': torch.tensor(1.5), 'mask_loss': torch.tensor(0.25)})
+    a, b = bs.step_outputs(chain, ps), bs.step_outputs(chain, ps)
+    assert sorted(a) == ['bn_running_stats', 'grads_sample', 'loss', 'mask_loss', 'params_sample']
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    assert a['loss'][0] == 1.5 and a['grads_sample'].shape == (1000,) and list(a['bn_running_stats']) == [0, 0, 1, 1, 1]
+    p = a['params_sample']
+    assert 0.8 * bs.DUMP_SAMPLE < p.size <= bs.DUMP_SAMPLE and np.all(np.diff(p) > 0)        # distinct elements in index order
+    bs.save_outputs(str(tmp_path), a)
+    assert sorted(os.listdir(str(tmp_path))) == sorted(k + '.npy' for k in a)
+    assert np.array_equal(np.load(str(tmp_path / 'params_sample.npy')), p)
+    with pytest.raises(AssertionError):
+        bs.save_outputs(str(tmp_path / 'big'), {'x': np.zeros(bs.DUMP_LIMIT // 4 + 1, np.float32)})
