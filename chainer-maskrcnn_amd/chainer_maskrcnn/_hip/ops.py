@@ -510,3 +510,38 @@ def mask_paste(mask_logits, label, bbox, size):
     check(lib().mrcnn_mask_paste_f32(ptr(mask_logits), D, S, Cm, ptr(label), ptr(bbox), size[0], size[1], ptr(out),
                                      stream_ptr()))
     return out
+
+
+def mask_iou_counts(a, b, a_label=None, b_label=None):
+    """Exact overlap counts of two mask sets: a (Da,H,W) or (Da,HW), b (Db,...) bool / uint8 device tensors (any nonzero byte is a set
+    pixel).  Returns (inter (Da,Db), area_a (Da,), area_b (Db,)) int32 on the device.  With labels ((Da,), (Db,) integer tensors, both
+    or neither), pairs of different labels get inter 0 and cost no word work.  The bit-packed masks live in a workspace of this call."""
+    if (a_label is None) != (b_label is None):
+        raise ValueError('mask_iou_counts: give both label arrays or neither')
+    _hip.require_cuda(a, b, a_label, b_label)
+    if a.dim() < 1 or b.dim() < 1 or a.shape[1:] != b.shape[1:]:
+        raise ValueError('mask_iou_counts: masks of different sizes %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    if a.dtype not in (torch.bool, torch.uint8) or b.dtype not in (torch.bool, torch.uint8):
+        raise TypeError('mask_iou_counts: bool or uint8 masks expected, got %s and %s' % (a.dtype, b.dtype))
+    Da, Db = a.shape[0], b.shape[0]
+    HW = 1
+    for s in a.shape[1:]:
+        HW *= int(s)
+    if HW > 0x7FFFFFFF:
+        raise ValueError('mask_iou_counts: %d pixels per mask > 2^31 - 1' % HW)
+    dev = a.device
+    a = a.contiguous().view(torch.uint8)
+    b = b.contiguous().view(torch.uint8)
+    if a_label is not None and Da and Db:
+        a_label = a_label.to(i32).contiguous()
+        b_label = b_label.to(i32).contiguous()
+    else:                       # labels change nothing when one side is empty
+        a_label = b_label = None
+    inter = torch.empty((Da, Db), dtype=i32, device=dev)
+    area_a = torch.empty((Da,), dtype=i32, device=dev)
+    area_b = torch.empty((Db,), dtype=i32, device=dev)
+    nb = lib().mrcnn_mask_iou_workspace_bytes(Da, Db, HW)
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
+    check(lib().mrcnn_mask_iou_counts_u8(ptr(a), Da, ptr(a_label), ptr(b), Db, ptr(b_label), HW, ptr(ws), nb, ptr(inter), ptr(area_a),
+                                         ptr(area_b), stream_ptr()))
+    return inter, area_a, area_b

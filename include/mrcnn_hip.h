@@ -642,6 +642,21 @@ int mrcnn_class_nms_f32(const float *cls_bbox, const float *prob, int R, int n_c
 int mrcnn_mask_paste_f32(const float *mask_logits, int D, int S, int Cm, const int32_t *label, const float *bbox,
                          int H, int W, unsigned char *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask-IoU counts of the instance-segmentation evaluator (evaluate.hip).  Replace the host NumPy of ChainerCV's mask_iou
+ * (chainercv/evaluations/eval_instance_segmentation_voc.py via chainercv/utils/mask/mask_iou.py; reference evaluator.py).
+ *   a (Da,HW), b (Db,HW) uint8, contiguous rows (no alignment needed); any nonzero byte is a set pixel (torch.bool, mask_paste)
+ *   a_label (Da), b_label (Db) int32: both NULL or both given; given = pairs with different labels get inter 0, no word work
+ *   inter (Da,Db), area_a (Da), area_b (Db) int32: exact pixel counts (|a_i & b_j|, |a_i|, |b_j|), independent of the launch split
+ *   ws: device scratch of mrcnn_mask_iou_workspace_bytes(Da, Db, HW) bytes (the bit-packed masks)
+ * Da == 0 or Db == 0 is valid (the areas of the other side are written).  Errors, before any launch: MRCNN_E_INVALID for a
+ * negative size, a NULL pointer of a non-empty side, or one label array only; MRCNN_E_WORKSPACE for a short workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t mrcnn_mask_iou_workspace_bytes(int Da, int Db, int HW);
+int mrcnn_mask_iou_counts_u8(const unsigned char *a, int Da, const int32_t *a_label, const unsigned char *b, int Db,
+                             const int32_t *b_label, int HW, void *ws, size_t ws_bytes, int32_t *inter, int32_t *area_a,
+                             int32_t *area_b, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
+
 
 def build_parser(keypoints=False):
     parser = argparse.ArgumentParser(description='Mask R-CNN')
@@ -69,6 +71,11 @@ def build_parser(keypoints=False):
     parser.add_argument('--profile', type=int, nargs=2, default=None, metavar=('FIRST', 'LAST'),
                         help='bracket iterations FIRST..LAST with roctx ranges (step / forward+backward / update) for '
                              '`rocprofv3 --marker-trace --kernel-trace -- python3 train.py ...`')
+    parser.add_argument('--eval-interval', type=int, default=0,
+                        help='iterations between validation mAP evaluations (InstanceSegmentationVOCEvaluator on the val split, '
+                             'reference train.py:164-166 uses 10000); 0 = off')
+    parser.add_argument('--eval-images', type=int, default=0,
+                        help='images of the val split per evaluation (0: the whole split; --synthetic 1: %d images)' % SYNTHETIC_VAL_IMAGES)
     return parser
 
 
@@ -79,6 +86,11 @@ def run(args, keypoints=False):
     from chainer_maskrcnn.utils.synthetic import make_batch
     world = int(os.environ.get('WORLD_SIZE', 1))
     rank = int(os.environ.get('RANK', 0))
+    if args.eval_interval > 0 and keypoints:
+        raise ValueError('--eval-interval: validation mAP is computed for mask heads only (no keypoint metric)')
+    if args.eval_interval > 0 and world > 1:
+        raise ValueError('--eval-interval: evaluation runs in single-process training only; with %d ranks it is not supported '
+                         '(the reference\'s multi-GPU branch has no test iterator either, train.py:117-121, and would fail there)' % world)
     local = int(os.environ.get('LOCAL_RANK', args.gpu))
     ndev = max(1, torch.cuda.device_count())
     lws = int(os.environ.get('LOCAL_WORLD_SIZE', 1))
@@ -164,8 +176,10 @@ def run(args, keypoints=False):
     if resume is not None:
         optimizer.load_state_dict(resume['optimizer'])
         first_it = resume['iteration'] + 1
+    evaluator = _make_evaluator(args, faster_rcnn, labels, n_fg) if args.eval_interval > 0 else None
     rtx = _Roctx() if args.profile else None
     t0 = time.time()
+    t_eval = 0.0            # seconds spent in evaluation: not part of the training throughput
     for it in range(first_it, args.iteration + 1):
         if loader is not None:
             b = next(loader)
@@ -191,13 +205,20 @@ def run(args, keypoints=False):
                     optimizer.update()
         else:
             optimizer.update(model, *batch, scale, img_sizes=sizes)
-        if it % args.log_interval == 0 or it == args.iteration:       # one device->host sync per log interval
+        validation = None
+        if evaluator is not None and it % args.eval_interval == 0:       # after the update of this iteration, like a trainer extension
+            te = time.time()
+            validation = {'validation/' + k: v for k, v in evaluator.evaluate().items()}
+            t_eval += time.time() - te
+        if it % args.log_interval == 0 or it == args.iteration or validation is not None:       # one device->host sync per log interval
             obs = {k: float(v) for k, v in model.observation.items()}
             if any(not np.isfinite(v) for v in obs.values()):
                 raise FloatingPointError('non-finite loss at iteration %d: %r' % (it, obs))
             entry = {'iteration': it, 'lr': optimizer.lr, 'elapsed_time': time.time() - t0,
-                     'images/sec': (it - first_it + 1) * bs * world / (time.time() - t0)}
+                     'images/sec': (it - first_it + 1) * bs * world / (time.time() - t0 - t_eval)}
             entry.update({'main/' + k: v for k, v in obs.items()})
+            if validation is not None:
+                entry.update(validation)
             if rank == 0:
                 log.write(json.dumps(entry) + '\n')
                 log.flush()
@@ -214,6 +235,20 @@ def run(args, keypoints=False):
                            os.path.join(args.out, 'trainer_%d.pt' % it))
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def _make_evaluator(args, faster_rcnn, labels, n_fg):
+    """The val split of the run (reference train.py:113-115: COCOMaskLoader(split='val') + EvaluatorTransform) and its
+    InstanceSegmentationVOCEvaluator.  --synthetic 1: deterministic make_batch images from seeds the training pool never uses."""
+    from chainer_maskrcnn.evaluator import InstanceSegmentationVOCEvaluator, SyntheticEvalDataset, TransformedDataset, coco_mask_example
+    if args.synthetic:
+        H, W = args.image_size
+        data = SyntheticEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_fg_class=n_fg)
+    else:
+        from chainer_maskrcnn.dataset.coco_dataset import COCOMaskLoader
+        val = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type, category_filter=labels)
+        data = TransformedDataset(val, coco_mask_example, n=args.eval_images or None)
+    return InstanceSegmentationVOCEvaluator(data, faster_rcnn, label_names=labels)
 
 
 def _all_rank_tickets(ticket, world, dev):
