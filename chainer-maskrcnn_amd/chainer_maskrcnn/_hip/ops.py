@@ -545,3 +545,31 @@ def mask_iou_counts(a, b, a_label=None, b_label=None):
     check(lib().mrcnn_mask_iou_counts_u8(ptr(a), Da, ptr(a_label), ptr(b), Db, ptr(b_label), HW, ptr(ws), nb, ptr(inter), ptr(area_a),
                                          ptr(area_b), stream_ptr()))
     return inter, area_a, area_b
+
+
+def keypoint_decode(heat, bbox, K, return_index=False):
+    """Keypoints from the keypoint branch's heat maps: heat (D,S,S,Cp) float32 NHWC (FPNRoIMaskHead.mask_branch of the keypoint head,
+    Cp = pad32(K)), bbox (D,4) float32 (y1,x1,y2,x2) in image coordinates.  Returns (D,K,4) float32 (y, x, logit, prob) on the device:
+    the first argmax over the S*S cells of channel k, the top-left corner of that cell mapped into the box, its logit and the softmax
+    probability over the cells there (include/mrcnn_hip.h, mrcnn_keypoint_decode_f32); with return_index also the (D,K) int32 flat
+    argmax cy * S + cx."""
+    _hip.require_cuda(heat, bbox)
+    if heat.dim() != 4 or heat.shape[1] != heat.shape[2]:
+        raise ValueError('keypoint_decode: heat maps (D,S,S,Cp) expected, got %s' % (tuple(heat.shape),))
+    if heat.dtype != f32 or bbox.dtype != f32:
+        raise TypeError('keypoint_decode: float32 heat maps and boxes expected, got %s and %s' % (heat.dtype, bbox.dtype))
+    D, S, Cp = heat.shape[0], heat.shape[1], heat.shape[3]
+    if not 0 < K <= Cp or Cp % 4:
+        raise ValueError('keypoint_decode: K %d against %d channels (a multiple of 4, >= K, is needed)' % (K, Cp))
+    if tuple(bbox.shape) != (D, 4):
+        raise ValueError('keypoint_decode: boxes (%d,4) expected, got %s' % (D, tuple(bbox.shape)))
+    heat, bbox = heat.contiguous(), bbox.contiguous()
+    if heat.data_ptr() % 16:                    # a view into its storage: the kernel reads 16-byte cells
+        heat = heat.clone()
+    out = _empty((D, K, 4), heat.device)
+    idx = _empty((D, K), heat.device, i32) if return_index else None
+    if D:
+        nb = lib().mrcnn_keypoint_decode_workspace_bytes(D, S, K)
+        ws = torch.empty((nb,), dtype=torch.uint8, device=heat.device)
+        check(lib().mrcnn_keypoint_decode_f32(ptr(heat), D, S, Cp, K, ptr(bbox), ptr(ws), nb, ptr(out), ptr(idx), stream_ptr()))
+    return (out, idx) if return_index else out

@@ -7,6 +7,7 @@ example tuples, so train.py's wiring is unchanged):
                             integer-truncated COCO (x,y,w,h), label (G,) int32 = rank of the category among the selected
                             categories (COCO ids are not contiguous), masks = list of G (H,W) uint8 arrays
   COCOKeypointsLoader[i] -> img, bbox (G,4) with w,h >= 1, keypoints (G,17,3) (x,y,v)
+  COCOKeypointsLoader.get_annotations(i) -> area, iscrowd, num_keypoints, raw bbox (x,y,w,h) of the same annotations (no image)
 
 Built differently from the reference: the annotation file is indexed ONCE at construction into a per-image table
 (boxes, labels and references to the segmentations), straight from ``coco_api.COCO``'s image->annotation index, so an
@@ -104,3 +105,15 @@ class COCOKeypointsLoader(_CocoSplit):
     def get_example(self, i):
         img, _ = self._record(i)
         return img, self._boxes[i].copy(), self._kps[i].copy()
+
+    def get_annotations(self, i):
+        """The kept annotations of example i without reading the image (what COCO's keypoint OKS and its ignore rule need):
+        {'area': (G,) float64, 'iscrowd': (G,) bool, 'num_keypoints': (G,) int64, 'bbox': (G, 4) float64 raw (x, y, w, h)}."""
+        if not 0 <= i < len(self.records):
+            raise IndexError('index is out of bounds.')
+        anns = self.records[i][2]
+        return {'area': np.array([a.get('area', 0.0) for a in anns], np.float64).reshape(-1),
+                'iscrowd': np.array([bool(a.get('iscrowd', 0)) for a in anns], bool).reshape(-1),
+                'num_keypoints': np.array([a.get('num_keypoints', int(np.count_nonzero(np.asarray(a['keypoints'])[2::3] > 0)))
+                                           for a in anns], np.int64).reshape(-1),
+                'bbox': np.array([a['bbox'] for a in anns], np.float64).reshape(-1, 4)}

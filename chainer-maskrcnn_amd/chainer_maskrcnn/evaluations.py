@@ -197,3 +197,194 @@ def eval_instance_segmentation_voc(pred_masks, pred_labels, pred_scores, gt_mask
                                                         iou_thresh=iou_thresh)
     ap = calc_detection_voc_ap(prec, rec, use_07_metric=use_07_metric)
     return {'ap': ap, 'map': nanmean(ap)}
+
+
+# ---- COCO keypoint AP (pycocotools COCOeval, iouType='keypoints') ----------------------------------------------------------------
+# computeOks / evaluateImg / accumulate / summarize of pycocotools/cocoeval.py for ONE category (person), with its keypoint
+# parameters: maxDets 20, OKS thresholds .50:.05:.95, 101 recall points, area ranges all / medium / large (closed intervals: a
+# value is out of range when a < lo or a > hi).  Ground truth is ranged by its annotation area, a detection by the area of its
+# keypoint extent box (loadRes).  Equal scores keep their input order within an image and image order across images (COCOeval's
+# two mergesorts).
+
+COCO_KEYPOINT_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+OKS_THRESHOLDS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+RECALL_THRESHOLDS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+KEYPOINT_AREA_RANGES = (('all', (0 ** 2, 1e5 ** 2)), ('medium', (32 ** 2, 96 ** 2)), ('large', (96 ** 2, 1e5 ** 2)))
+KEYPOINT_MAX_DETS = 20
+
+
+def keypoint_oks(dt_yx, gt_kp_yxv, gt_area, gt_bbox_xywh, sigmas=None):
+    """(D, G) float64 object keypoint similarity (computeOks): dt_yx (D, K, 2) detected (y, x), gt_kp_yxv (G, K, 3) (y, x, v),
+    gt_area (G,), gt_bbox_xywh (G, 4).  e = (dx^2 + dy^2) / (2 sigma)^2 / (area + eps) / 2; with labelled keypoints (v > 0) only
+    those count, without any the distance is to the ground-truth box expanded to [x - w, x + 2w] x [y - h, y + 2h]; oks =
+    mean(exp(-e)).  sigmas default to COCO's 17."""
+    sigmas = COCO_KEYPOINT_SIGMAS if sigmas is None else np.asarray(sigmas, dtype=np.float64)
+    dt = np.asarray(dt_yx, dtype=np.float64).reshape(-1, len(sigmas), 2)
+    gt = np.asarray(gt_kp_yxv, dtype=np.float64).reshape(-1, len(sigmas), 3)
+    gt_area = np.asarray(gt_area, dtype=np.float64).reshape(-1)
+    gt_bbox = np.asarray(gt_bbox_xywh, dtype=np.float64).reshape(-1, 4)
+    var = (sigmas * 2) ** 2
+    yd, xd = dt[:, :, 0], dt[:, :, 1]
+    oks = np.zeros((dt.shape[0], gt.shape[0]), dtype=np.float64)
+    for j in range(gt.shape[0]):
+        yg, xg, vg = gt[j, :, 0], gt[j, :, 1], gt[j, :, 2]
+        vis = vg > 0
+        if vis.any():
+            dx, dy = xd - xg, yd - yg
+        else:
+            bx, by, bw, bh = gt_bbox[j]
+            x0, x1, y0, y1 = bx - bw, bx + bw * 2, by - bh, by + bh * 2
+            dx = np.maximum(0, x0 - xd) + np.maximum(0, xd - x1)
+            dy = np.maximum(0, y0 - yd) + np.maximum(0, yd - y1)
+        e = (dx ** 2 + dy ** 2) / var / (gt_area[j] + np.spacing(1)) / 2
+        if vis.any():
+            e = e[:, vis]
+        oks[:, j] = np.exp(-e).sum(axis=1) / e.shape[1]
+    return oks
+
+
+def keypoint_extent_area(dt_yx):
+    """(D,) area of each detection's keypoint extent box, (max x - min x) * (max y - min y): COCO.loadRes for keypoint results."""
+    dt = np.asarray(dt_yx, dtype=np.float64)
+    if dt.shape[0] == 0:
+        return np.zeros((0,), dtype=np.float64)
+    return (dt[:, :, 1].max(1) - dt[:, :, 1].min(1)) * (dt[:, :, 0].max(1) - dt[:, :, 0].min(1))
+
+
+class COCOKeypointMatchAccumulator(object):
+    """Streaming state of COCO keypoint AP (evaluateImg per image, accumulate at the end) for one category.  Kept per detection: its
+    score and, per OKS threshold and area range, whether it matched a ground truth and whether it is ignored; per area range the
+    number of ground truths that are not ignored.  No keypoints or heat maps are kept."""
+
+    def __init__(self, max_dets=KEYPOINT_MAX_DETS, oks_thresholds=OKS_THRESHOLDS, area_ranges=KEYPOINT_AREA_RANGES):
+        self.max_dets = max_dets
+        self.thresholds = np.asarray(oks_thresholds, dtype=np.float64)
+        self.area_ranges = [tuple(r) for _, r in area_ranges]
+        self.area_names = [n for n, _ in area_ranges]
+        A = len(self.area_ranges)
+        self.scores = []                                  # per image, (D_i,) in evaluateImg's order
+        self.matched = [[] for _ in range(A)]             # per area range, per image (T, D_i) bool
+        self.ignored = [[] for _ in range(A)]
+        self.n_pos = np.zeros(A, dtype=np.int64)          # per area range: ground truths not ignored
+        self.n_images = 0                                 # images with a detection or a ground truth (COCOeval's non-None evalImgs)
+
+    def add_image(self, oks, dt_score, dt_area, gt_area, gt_ignore, gt_crowd):
+        """One image.  oks (D, G): OKS of detection d (input order) and ground truth g; dt_score (D,), dt_area (D,) (keypoint extent
+        areas); gt_area (G,); gt_ignore (G,) crowd or no labelled keypoint; gt_crowd (G,) (a crowd may absorb several detections)."""
+        dt_score = np.asarray(dt_score, dtype=np.float64).reshape(-1)
+        dt_area = np.asarray(dt_area, dtype=np.float64).reshape(-1)
+        gt_area = np.asarray(gt_area, dtype=np.float64).reshape(-1)
+        gt_ignore = np.asarray(gt_ignore, dtype=bool).reshape(-1)
+        gt_crowd = np.asarray(gt_crowd, dtype=bool).reshape(-1)
+        D, G, T = dt_score.shape[0], gt_area.shape[0], len(self.thresholds)
+        if D == 0 and G == 0:
+            return
+        self.n_images += 1
+        order = np.argsort(-dt_score, kind='mergesort')[:self.max_dets]
+        score, dt_area = dt_score[order], dt_area[order]
+        oks = np.asarray(oks, dtype=np.float64).reshape(D, G)[order] if D and G else np.zeros((len(order), G))
+        self.scores.append(score)
+        for a, (lo, hi) in enumerate(self.area_ranges):
+            g_ig = gt_ignore | (gt_area < lo) | (gt_area > hi)
+            gorder = np.argsort(g_ig, kind='mergesort')           # not ignored first
+            g_ig, crowd = g_ig[gorder], gt_crowd[gorder]
+            o = oks[:, gorder]
+            self.n_pos[a] += int(np.count_nonzero(~g_ig))
+            nd = len(order)
+            dtm = np.zeros((T, nd), dtype=bool)
+            dt_ig = np.zeros((T, nd), dtype=bool)
+            if nd and G:
+                for t, thr in enumerate(self.thresholds):
+                    gtm = np.zeros(G, dtype=bool)
+                    for d in range(nd):
+                        best, m = min(thr, 1 - 1e-10), -1
+                        for g in range(G):
+                            if gtm[g] and not crowd[g]:
+                                continue                          # taken, and not a crowd
+                            if m > -1 and not g_ig[m] and g_ig[g]:
+                                break                             # a real match found; only ignored ones remain
+                            if o[d, g] < best:
+                                continue
+                            best, m = o[d, g], g
+                        if m == -1:
+                            continue
+                        dt_ig[t, d] = g_ig[m]
+                        dtm[t, d] = True
+                        gtm[m] = True
+            out = (dt_area < lo) | (dt_area > hi)
+            dt_ig |= ~dtm & out[None, :]
+            self.matched[a].append(dtm)
+            self.ignored[a].append(dt_ig)
+
+    def precision_recall(self):
+        """COCOeval.accumulate: precision (T, R, A) at the 101 recall points and recall (T, A); -1 where an area range has no ground
+        truth that counts (or no image was added)."""
+        T, R, A = len(self.thresholds), len(RECALL_THRESHOLDS), len(self.area_ranges)
+        precision = -np.ones((T, R, A))
+        recall = -np.ones((T, A))
+        if self.n_images == 0:
+            return precision, recall
+        scores = np.concatenate(self.scores) if self.scores else np.zeros((0,))
+        inds = np.argsort(-scores, kind='mergesort')
+        for a in range(A):
+            npig = int(self.n_pos[a])
+            if npig == 0:
+                continue
+            dtm = np.concatenate(self.matched[a], axis=1)[:, inds]
+            dt_ig = np.concatenate(self.ignored[a], axis=1)[:, inds]
+            tps = np.logical_and(dtm, np.logical_not(dt_ig))
+            fps = np.logical_and(np.logical_not(dtm), np.logical_not(dt_ig))
+            tp_sum = np.cumsum(tps, axis=1).astype(np.float64)
+            fp_sum = np.cumsum(fps, axis=1).astype(np.float64)
+            for t in range(T):
+                tp, fp = tp_sum[t], fp_sum[t]
+                nd = len(tp)
+                rc = tp / npig
+                pr = tp / (fp + tp + np.spacing(1))
+                recall[t, a] = rc[-1] if nd else 0
+                pr = np.maximum.accumulate(pr[::-1])[::-1] if nd else pr        # precision envelope (right to left)
+                ri = np.searchsorted(rc, RECALL_THRESHOLDS, side='left')
+                q = np.zeros(R)
+                ok = ri < nd
+                q[ok] = pr[ri[ok]]
+                precision[t, :, a] = q
+        return precision, recall
+
+    def summarize(self):
+        """COCOeval.summarize for keypoints: {'AP', 'AP50', 'AP75', 'APm', 'APl', 'AR', 'AR50', 'AR75', 'ARm', 'ARl'}; a mean over
+        the cells that are not -1, -1 when there is none."""
+        precision, recall = self.precision_recall()
+        t50, t75 = int(np.argmin(np.abs(self.thresholds - .5))), int(np.argmin(np.abs(self.thresholds - .75)))
+        a_all, a_m, a_l = (self.area_names.index(n) for n in ('all', 'medium', 'large'))
+
+        def mean(s):
+            s = s[s > -1]
+            return float(np.mean(s)) if s.size else -1.0
+        return {'AP': mean(precision[:, :, a_all]), 'AP50': mean(precision[t50, :, a_all]), 'AP75': mean(precision[t75, :, a_all]),
+                'APm': mean(precision[:, :, a_m]), 'APl': mean(precision[:, :, a_l]),
+                'AR': mean(recall[:, a_all]), 'AR50': mean(recall[t50, a_all]), 'AR75': mean(recall[t75, a_all]),
+                'ARm': mean(recall[:, a_m]), 'ARl': mean(recall[:, a_l])}
+
+
+def eval_keypoint_coco(dt_yx, dt_scores, gt_kp_yxv, gt_areas, gt_crowds, gt_bboxes_xywh, sigmas=None):
+    """COCO keypoint AP over a dataset (iterables of per-image (D, K, 2) detected (y, x), (D,) scores, (G, K, 3) ground-truth
+    (y, x, v), (G,) areas, (G,) crowd flags, (G, 4) boxes (x, y, w, h)).  Ground truth without a labelled keypoint is ignored, as
+    COCO's num_keypoints == 0.  Returns COCOKeypointMatchAccumulator.summarize()'s dict."""
+    acc = COCOKeypointMatchAccumulator()
+    for dt, sc, gt, ga, gc, gb in zip(dt_yx, dt_scores, gt_kp_yxv, gt_areas, gt_crowds, gt_bboxes_xywh):
+        add_keypoint_image(acc, dt, sc, gt, ga, gc, gb, sigmas)
+    return acc.summarize()
+
+
+def add_keypoint_image(acc, dt_yx, dt_score, gt_kp_yxv, gt_area, gt_crowd, gt_bbox_xywh, sigmas=None):
+    """One image into a COCOKeypointMatchAccumulator: OKS of the (up to max_dets) best-scored detections, then the matching."""
+    K = len(COCO_KEYPOINT_SIGMAS if sigmas is None else sigmas)
+    dt_yx = np.asarray(dt_yx, dtype=np.float64).reshape(-1, K, 2)
+    dt_score = np.asarray(dt_score, dtype=np.float64).reshape(-1)
+    gt = np.asarray(gt_kp_yxv, dtype=np.float64).reshape(-1, K, 3)
+    gt_crowd = np.asarray(gt_crowd, dtype=bool).reshape(-1)
+    gt_ignore = gt_crowd | ((gt[:, :, 2] > 0).sum(1) == 0)
+    top = np.argsort(-dt_score, kind='mergesort')[:acc.max_dets]           # computeOks's cut; add_image sorts again (stable)
+    dt_yx, dt_score = dt_yx[top], dt_score[top]
+    oks = keypoint_oks(dt_yx, gt, gt_area, gt_bbox_xywh, sigmas) if len(top) and len(gt) else np.zeros((len(top), len(gt)))
+    acc.add_image(oks, dt_score, keypoint_extent_area(dt_yx), gt_area, gt_ignore, gt_crowd)

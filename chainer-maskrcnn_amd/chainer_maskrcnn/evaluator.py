@@ -1,4 +1,4 @@
-"""Validation mAP during training: the reference's ``InstanceSegmentationVOCEvaluator`` (reference evaluator.py, a copy of
+"""Validation metrics during training.  Mask heads: the reference's ``InstanceSegmentationVOCEvaluator`` (reference evaluator.py, a copy of
 ChainerCV's; attached to the val split in reference train.py:113-115,164-166), streaming.
 
 The reference runs ``apply_to_iterator(target.predict, ...)`` and keeps every predicted mask of the split in host memory before
@@ -6,6 +6,10 @@ The reference runs ``apply_to_iterator(target.predict, ...)`` and keeps every pr
 mask-IoU counts are computed there (``mask_iou_counts``, labels on, so cross-class pairs cost nothing), and the only copy to the
 host per image beyond ``predict``'s own is one buffer holding the (D, G) intersections, the areas, the labels and the scores.
 What is kept is one (score, match) per prediction and the positive count per class (evaluations.VOCMatchAccumulator).
+
+Keypoint heads: ``KeypointCOCOEvaluator``, COCO's keypoint AP (pycocotools COCOeval, iouType='keypoints') of
+``predict_keypoints``; the heat maps are decoded on the device (``keypoint_decode``) and one copy per image brings the scores and
+keypoint positions of the 20 best detections to the host, where OKS and the matching run in float64.
 """
 import numpy as np
 import torch
@@ -119,3 +123,108 @@ class SyntheticEvalDataset(object):
             raise IndexError(i)
         b = make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, n_fg_class=self.n_fg_class)
         return b['imgs'][0] * 255, b['masks'][0], b['labels'][0]
+
+
+# ---- COCO keypoint AP ----------------------------------------------------------------------------------------------------------------
+def coco_keypoint_example(loader, i):
+    """Example i of a COCOKeypointsLoader as the keypoint evaluator's (img, gt_kp (G, K, 3) (y, x, v), gt_area (G,), gt_crowd (G,),
+    gt_bbox_xywh (G, 4)): COCO's (x, y, v) keypoints in (y, x, v) order, the annotations' own area, iscrowd and raw bbox."""
+    img, _, kp = loader.get_example(i)
+    ann = loader.get_annotations(i)
+    kp = np.asarray(kp, dtype=np.float64).reshape(-1, loader.n_keypoints, 3)
+    return img, kp[:, :, [1, 0, 2]], ann['area'], ann['iscrowd'], ann['bbox']
+
+
+class COCOKeypointEvalDataset(object):
+    """The first n examples (all when n is None) of a COCOKeypointsLoader through coco_keypoint_example."""
+
+    def __init__(self, loader, n=None):
+        self.loader = loader
+        self.n = len(loader) if n is None else min(n, len(loader))
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        return coco_keypoint_example(self.loader, i)
+
+
+class KeypointCOCOEvaluator(object):
+    """COCO keypoint AP (pycocotools COCOeval, iouType='keypoints'; evaluations.COCOKeypointMatchAccumulator) of
+    ``target.predict_keypoints`` over ``dataset``, whose examples are (img (3,H,W) 0..255, gt_kp (G,K,3) (y,x,v), gt_area (G,),
+    gt_crowd (G,), gt_bbox_xywh (G,4)).  ``evaluate()`` returns {'main/map' (AP at OKS .50:.95), 'main/ap50', 'main/ap75',
+    'main/ap_medium', 'main/ap_large', 'main/ar'}; a trainer writes them with the prefix 'validation/'.
+
+    Per image: ``predict_keypoints``, then ONE device->host copy of the scores and the (y, x) of the (up to) 20 best-scored
+    detections; OKS in float64 and the matching on the host.  sigmas default to COCO's 17; other K need explicit sigmas.
+    ``target``'s preset is used as it is, and its training state is restored afterwards."""
+
+    default_name = 'validation'
+
+    def __init__(self, dataset, target, sigmas=None):
+        K = getattr(getattr(target, 'head', None), 'n_keypoints', None)
+        if sigmas is None and K is not None and K != len(evaluations.COCO_KEYPOINT_SIGMAS):
+            raise ValueError('KeypointCOCOEvaluator: COCO defines OKS sigmas for its %d keypoints only; this model has %d - pass sigmas'
+                             % (len(evaluations.COCO_KEYPOINT_SIGMAS), K))
+        self.dataset = dataset
+        self.target = target
+        self.sigmas = None if sigmas is None else np.asarray(sigmas, dtype=np.float64)
+
+    def evaluate(self):
+        from chainer_maskrcnn.nn import core
+        target = self.target
+        rpn, head = getattr(target, 'rpn', None), getattr(target, 'head', None)
+        keep = (target.train, core.TRAIN, getattr(rpn, 'train', None), getattr(head, 'train', None))
+        acc = evaluations.COCOKeypointMatchAccumulator()
+        try:
+            with torch.no_grad():
+                for i in range(len(self.dataset)):
+                    self._add_example(acc, self.dataset[i])
+        finally:
+            target.train, core.TRAIN = keep[0], keep[1]
+            if keep[2] is not None:
+                rpn.train = keep[2]
+            if keep[3] is not None:
+                head.train = keep[3]
+        s = acc.summarize()
+        return {'main/map': s['AP'], 'main/ap50': s['AP50'], 'main/ap75': s['AP75'], 'main/ap_medium': s['APm'],
+                'main/ap_large': s['APl'], 'main/ar': s['AR']}
+
+    def _add_example(self, acc, example):
+        img, gt_kp, gt_area, gt_crowd, gt_bbox = example[:5]
+        img = torch.as_tensor(np.asarray(img, dtype=np.float32)) if not isinstance(img, torch.Tensor) else img.to(torch.float32)
+        keypoints, _, scores = self.target.predict_keypoints([img])
+        kp, score = keypoints[0], scores[0].to(torch.float32)
+        D, K = int(kp.shape[0]), int(kp.shape[1])
+        n = min(D, acc.max_dets)
+        if D:
+            top = torch.sort(score, descending=True, stable=True)[1][:n]        # equal scores keep their order (COCOeval's mergesort)
+            host = torch.cat((score[top], kp[top][:, :, :2].reshape(-1))).cpu().numpy()      # the one copy of this image
+        else:
+            host = np.zeros((0,), dtype=np.float32)
+        dt_score, dt_yx = host[:n], host[n:].reshape(n, K, 2)
+        evaluations.add_keypoint_image(acc, dt_yx, dt_score, gt_kp, gt_area, gt_crowd, gt_bbox, self.sigmas)
+
+
+class SyntheticKeypointEvalDataset(object):
+    """Deterministic synthetic keypoint val split (utils/synthetic.make_batch with n_fg_class=1, n_keypoints=K, one image per seed):
+    examples (img 0..255, gt_kp (G,K,3) (y,x,v=2), gt_area, gt_crowd (zeros), gt_bbox_xywh).  gt_area is the box area h * w, a
+    stand-in for COCO's segmentation area.  Seeds start at ``first_seed``, far from the seeds of train.py's synthetic training pool."""
+
+    def __init__(self, n_images, H, W, n_keypoints=17, G=8, first_seed=1000003):
+        self.n, self.H, self.W, self.K, self.G, self.first_seed = n_images, H, W, n_keypoints, G, first_seed
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        from chainer_maskrcnn.utils.synthetic import make_batch
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        b = make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, n_fg_class=1, n_keypoints=self.K)
+        box = b['bboxes'][0].astype(np.float64)
+        h, w = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+        xywh = np.stack([box[:, 1], box[:, 0], w, h], axis=1)
+        return b['imgs'][0] * 255, b['keypoints'][0].astype(np.float64), h * w, np.zeros(self.G, dtype=bool), xywh

@@ -157,15 +157,7 @@ class MaskRCNN(object):
         self.train, core.TRAIN = False, False
         try:
             for img in imgs:
-                size = tuple(img.shape[1:])
-                x = self.prepare(img.to(self.device))
-                scale = x.shape[2] / size[1]
-                roi_cls_locs, roi_scores, rois, roi_indices, levels = self.__call__(x[None].contiguous(), scale=scale)
-                box_out = self.head.last_box_out
-                cls_bbox, prob = ops.detect_decode(rois.contiguous(), box_out, self.n_class, self.head.LOC0, scale,
-                                                   self.loc_normalize_mean, self.loc_normalize_std, size)
-                self.last_rois, self.last_decoded = rois, (cls_bbox, prob)      # parity tests read these
-                bbox, label, score, level = self._suppress(cls_bbox, prob, levels)
+                size, scale, bbox, label, score, level = self._detect(img)
                 D = bbox.shape[0]
                 if D > 0 and self.predict_mask:
                     xy5 = torch.cat((torch.zeros((D, 1), device=self.device), bbox[:, [1, 0, 3, 2]] * scale), dim=1).contiguous()
@@ -182,6 +174,61 @@ class MaskRCNN(object):
             self.train, core.TRAIN = keep_train, keep_core
         self.last_bboxes = bboxes
         return masks, labels, scores
+
+    def _detect(self, img):
+        """The detection part of ``predict`` for one image (inference mode set by the caller): prepare, forward, box decode and
+        per-class NMS.  Returns (size, scale, bbox (D,4) in image coordinates, label, score, level)."""
+        size = tuple(img.shape[1:])
+        x = self.prepare(img.to(self.device))
+        scale = x.shape[2] / size[1]
+        roi_cls_locs, roi_scores, rois, roi_indices, levels = self.__call__(x[None].contiguous(), scale=scale)
+        box_out = self.head.last_box_out
+        cls_bbox, prob = ops.detect_decode(rois.contiguous(), box_out, self.n_class, self.head.LOC0, scale,
+                                           self.loc_normalize_mean, self.loc_normalize_std, size)
+        self.last_rois, self.last_decoded = rois, (cls_bbox, prob)      # parity tests read these
+        bbox, label, score, level = self._suppress(cls_bbox, prob, levels)
+        return size, scale, bbox, label, score, level
+
+    def predict_keypoints(self, imgs, return_heatmaps=False):
+        """Keypoint R-CNN inference (head_arch 'fpn_keypoint'): the detections of ``predict`` (same prepare / forward / decode /
+        NMS, boxes kept in ``self.last_bboxes``), then the keypoint branch on the kept boxes and ``mrcnn_keypoint_decode_f32``.
+        Returns (keypoints, labels, scores), one entry per image: keypoints (D,K,4) float32 (y, x, logit, prob) on the device, y / x
+        in the image coordinates of the boxes (the top-left corner of the argmax cell of the 56 x 56 map, the reference viewer's
+        rule, viewer.py:86-107), prob = the softmax over the cells at the argmax.  return_heatmaps=True appends the heat maps in the
+        reference's format (maskrcnn.py:249: (D, K, 56*56), there with a fixed 20 for K).  Like ``predict``, one device->host copy
+        per image (the per-class keep counts)."""
+        from chainer_maskrcnn.nn import core
+        if self.head_arch != 'fpn_keypoint':
+            raise ValueError('predict_keypoints needs a keypoint model (head_arch \'fpn_keypoint\'), this one has %r' % self.head_arch)
+        K, S = self.head.n_keypoints, self.head.mask_size
+        keypoints, labels, scores, bboxes, heatmaps = [], [], [], [], []
+        keep_train, keep_core = self.train, core.TRAIN
+        self.train, core.TRAIN = False, False
+        try:
+            for img in imgs:
+                size, scale, bbox, label, score, level = self._detect(img)
+                D = bbox.shape[0]
+                if D > 0:
+                    bbox = bbox.contiguous()
+                    xy5 = torch.cat((torch.zeros((D, 1), device=self.device), bbox[:, [1, 0, 3, 2]] * scale), dim=1).contiguous()
+                    m = self.head.mask_branch(self.head.x, xy5, level.to(torch.int32).contiguous(), self.extractor.spatial_scales)
+                    kp = ops.keypoint_decode(m, bbox, K)
+                    if return_heatmaps:
+                        heatmaps.append(m[..., :K].permute(0, 3, 1, 2).reshape(D, K, S * S))
+                else:
+                    kp = torch.zeros((0, K, 4), dtype=torch.float32, device=self.device)
+                    if return_heatmaps:
+                        heatmaps.append(torch.zeros((0, K, S * S), dtype=torch.float32, device=self.device))
+                keypoints.append(kp)
+                labels.append(label)
+                scores.append(score)
+                bboxes.append(bbox)
+        finally:
+            self.train, core.TRAIN = keep_train, keep_core
+        self.last_bboxes = bboxes
+        if return_heatmaps:
+            return keypoints, labels, scores, heatmaps
+        return keypoints, labels, scores
 
     def _suppress(self, cls_bbox, prob, levels):
         """maskrcnn.py:278-312 on the device: for every foreground class l (skipping the LAST class when masks are

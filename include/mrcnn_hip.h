@@ -657,6 +657,26 @@ int mrcnn_mask_iou_counts_u8(const unsigned char *a, int Da, const int32_t *a_la
                              const int32_t *b_label, int HW, void *ws, size_t ws_bytes, int32_t *inter, int32_t *area_a,
                              int32_t *area_b, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Keypoint heat-map decode (keypoints.hip; MaskRCNN.predict_keypoints).  Replaces the host NumPy of the reference's viewer.py:86-107
+ * (argmax over the cells of predict()'s (D, K, S*S) heat maps, maskrcnn.py:247-251, mapped into the box).
+ *   heat (D,S,S,Cp) float32 NHWC, 16-byte aligned, Cp % 4 == 0, Cp >= K: the keypoint branch's output; channels k >= K are not used
+ *   bbox (D,4) float32 (y1,x1,y2,x2) in image coordinates
+ *   out (D,K,4) float32, 16-byte aligned: (y, x, logit, prob) of the maximum of channel k over the S*S cells, where
+ *     idx   = the FIRST flat index cy * S + cx of the maximum (np.argmax's tie-break; finite inputs)
+ *     y     = float(idx / S) * ((y2 - y1) / S) + y1,  x = float(idx % S) * ((x2 - x1) / S) + x1  (float32, no FMA: the cell's
+ *             top-left corner, the viewer's rule and the inverse of the training target's floor((kp - y0) / h * S))
+ *     logit = the maximum value (bit-exact), prob = 1 / sum_cells exp(l - logit) (the softmax over the cells, at the argmax)
+ *   index (D,K) int32 or NULL: idx
+ *   ws: device scratch of mrcnn_keypoint_decode_workspace_bytes(D, S, K) bytes (per-split partial reductions)
+ * Bit-identical from run to run.  D == 0 is a no-op.  Errors, before any launch: MRCNN_E_INVALID for bad sizes, Cp not a multiple
+ * of 4, a NULL or misaligned heat / out, a NULL bbox; MRCNN_E_UNSUPPORTED for K > 256 or S > 46340; MRCNN_E_WORKSPACE for a short
+ * or NULL workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t mrcnn_keypoint_decode_workspace_bytes(int D, int S, int K);
+int mrcnn_keypoint_decode_f32(const float *heat, int D, int S, int Cp, int K, const float *bbox, void *ws, size_t ws_bytes, float *out,
+                              int32_t *index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,9 @@ def build_parser(keypoints=False):
                              'reference train.py:164-166 uses 10000); 0 = off')
     parser.add_argument('--eval-images', type=int, default=0,
                         help='images of the val split per evaluation (0: the whole split; --synthetic 1: %d images)' % SYNTHETIC_VAL_IMAGES)
+    parser.add_argument('--eval-metric', default='mask_voc', choices=['mask_voc', 'keypoint_coco'],
+                        help='metric of --eval-interval: mask_voc = PASCAL VOC mask mAP (mask heads, InstanceSegmentationVOCEvaluator); '
+                             'keypoint_coco = COCO keypoint AP over OKS .50:.95 (keypoint heads, KeypointCOCOEvaluator)')
     return parser
 
 
@@ -86,8 +89,13 @@ def run(args, keypoints=False):
     from chainer_maskrcnn.utils.synthetic import make_batch
     world = int(os.environ.get('WORLD_SIZE', 1))
     rank = int(os.environ.get('RANK', 0))
-    if args.eval_interval > 0 and keypoints:
-        raise ValueError('--eval-interval: validation mAP is computed for mask heads only (no keypoint metric)')
+    if args.eval_interval > 0 and keypoints and args.eval_metric != 'keypoint_coco':
+        raise ValueError('--eval-interval: validation mAP (--eval-metric %s) is computed for mask heads only; keypoint runs take '
+                         '--eval-metric keypoint_coco' % args.eval_metric)
+    if args.eval_metric == 'keypoint_coco' and not keypoints:
+        raise ValueError('--eval-metric keypoint_coco: COCO keypoint AP needs a keypoint head (train_keypoints.py); mask heads take mask_voc')
+    if args.eval_metric == 'keypoint_coco' and getattr(args, 'dataset', 'coco') == 'depth':
+        raise ValueError('--eval-metric keypoint_coco: COCO defines OKS sigmas for its 17 keypoints only; --dataset depth has 20')
     if args.eval_interval > 0 and world > 1:
         raise ValueError('--eval-interval: evaluation runs in single-process training only; with %d ranks it is not supported '
                          '(the reference\'s multi-GPU branch has no test iterator either, train.py:117-121, and would fail there)' % world)
@@ -176,7 +184,7 @@ def run(args, keypoints=False):
     if resume is not None:
         optimizer.load_state_dict(resume['optimizer'])
         first_it = resume['iteration'] + 1
-    evaluator = _make_evaluator(args, faster_rcnn, labels, n_fg) if args.eval_interval > 0 else None
+    evaluator = _make_evaluator(args, faster_rcnn, labels, n_fg, K) if args.eval_interval > 0 else None
     rtx = _Roctx() if args.profile else None
     t0 = time.time()
     t_eval = 0.0            # seconds spent in evaluation: not part of the training throughput
@@ -237,10 +245,21 @@ def run(args, keypoints=False):
         torch.distributed.destroy_process_group()
 
 
-def _make_evaluator(args, faster_rcnn, labels, n_fg):
+def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
     """The val split of the run (reference train.py:113-115: COCOMaskLoader(split='val') + EvaluatorTransform) and its
-    InstanceSegmentationVOCEvaluator.  --synthetic 1: deterministic make_batch images from seeds the training pool never uses."""
+    InstanceSegmentationVOCEvaluator; with --eval-metric keypoint_coco, COCOKeypointsLoader(split='val') and KeypointCOCOEvaluator.
+    --synthetic 1: deterministic make_batch images from seeds the training pool never uses."""
     from chainer_maskrcnn.evaluator import InstanceSegmentationVOCEvaluator, SyntheticEvalDataset, TransformedDataset, coco_mask_example
+    if args.eval_metric == 'keypoint_coco':
+        from chainer_maskrcnn.evaluator import COCOKeypointEvalDataset, KeypointCOCOEvaluator, SyntheticKeypointEvalDataset
+        if args.synthetic:
+            H, W = args.image_size
+            data = SyntheticKeypointEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_keypoints=K)
+        else:
+            from chainer_maskrcnn.dataset.coco_dataset import COCOKeypointsLoader
+            val = COCOKeypointsLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type)
+            data = COCOKeypointEvalDataset(val, n=args.eval_images or None)
+        return KeypointCOCOEvaluator(data, faster_rcnn)
     if args.synthetic:
         H, W = args.image_size
         data = SyntheticEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_fg_class=n_fg)
