@@ -573,3 +573,30 @@ def keypoint_decode(heat, bbox, K, return_index=False):
         ws = torch.empty((nb,), dtype=torch.uint8, device=heat.device)
         check(lib().mrcnn_keypoint_decode_f32(ptr(heat), D, S, Cp, K, ptr(bbox), ptr(ws), nb, ptr(out), ptr(idx), stream_ptr()))
     return (out, idx) if return_index else out
+
+
+def mask_rle_encode(masks):
+    """COCO run-length codes of masks (D,H,W) bool / uint8 device tensor (any nonzero byte is a set pixel; rows may start at any byte
+    offset): runs over the column-major flattening, starting with a run of 0s (maskApi.c rleEncode).  Returns (offsets (D+1,),
+    counts (offsets[D],), area (D,)) int32 on the device: mask d's runs are counts[offsets[d]:offsets[d+1]], area its set pixels.
+    One device->host read, of offsets[D], sizes counts."""
+    _hip.require_cuda(masks)
+    if masks.dim() != 3:
+        raise ValueError('mask_rle_encode: masks (D,H,W) expected, got %s' % (tuple(masks.shape),))
+    if masks.dtype not in (torch.bool, torch.uint8):
+        raise TypeError('mask_rle_encode: bool or uint8 masks expected, got %s' % masks.dtype)
+    D, H, W = (int(s) for s in masks.shape)
+    if H * W > 0x7FFFFFFF or D * (H * W + 1) > 0x7FFFFFFF:
+        raise ValueError('mask_rle_encode: %d masks of %d x %d pixels: the run total may not fit int32' % (D, H, W))
+    dev = masks.device
+    m = masks.contiguous().view(torch.uint8)
+    offsets = torch.empty((D + 1,), dtype=i32, device=dev)
+    area = torch.empty((D,), dtype=i32, device=dev)
+    nb = lib().mrcnn_mask_rle_workspace_bytes(D, H, W)
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
+    check(lib().mrcnn_mask_rle_count_u8(ptr(m), D, H, W, ptr(ws), nb, ptr(offsets), ptr(area), stream_ptr()))
+    n = int(offsets[D].item()) if D else 0                 # the one device->host read: the size of counts
+    counts = torch.empty((n,), dtype=i32, device=dev)
+    if D:
+        check(lib().mrcnn_mask_rle_write_u8(ptr(m), D, H, W, ptr(ws), nb, ptr(offsets), ptr(counts), stream_ptr()))
+    return offsets, counts, area

@@ -3,7 +3,8 @@
 
 Parity unpinned: pycocotools 2.0 is an un-vendored dependency of the reference; the index methods restate its public
 Python (``coco.py``: createIndex / getCatIds / getImgIds / getAnnIds / loadImgs / loadAnns / annToRLE / annToMask)
-and the mask routines restate its C (``common/maskApi.c``: rleFrPoly, rleFrString, rleMerge-as-union, rleDecode).
+and the mask routines restate its C (``common/maskApi.c``: rleFrPoly, rleFrString, rleToString, rleEncode, rleMerge-as-union,
+rleDecode).
 Masks are column-major run-length codes; the polygon rasteriser works on a x5 up-sampled integer grid and keeps
 the pixels whose centres lie inside the polygon with maskApi's tie rules - restated operation for operation, so
 that real COCO annotations decode to the masks the reference trains on.
@@ -113,6 +114,42 @@ def rle_from_string(s):
             x += cnts[-2]
         cnts.append(x)
     return np.asarray(cnts, np.int64)
+
+
+def rle_to_string(counts):
+    """maskApi.c rleToString, the inverse of rle_from_string: every count after the second as a delta to the count two places
+    before, in 5-bit groups (least significant first) until the rest is the sign extension of the last group's bit 4, bit 5 =
+    continuation, each character offset by 48."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    return rle_to_strings(np.array([0, counts.shape[0]]), counts)[0]
+
+
+def rle_to_strings(offsets, counts):
+    """rle_to_string of every mask of a packed run list: mask d's runs are counts[offsets[d]:offsets[d+1]] (ops.mask_rle_encode's
+    layout).  Vectorised over all runs: a value takes the fewest 5-bit groups k with -2^(5k-1) <= x < 2^(5k-1)."""
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    c0 = np.asarray(counts, dtype=np.int64).reshape(-1)[:offsets[-1]]
+    mask_of = np.repeat(np.arange(offsets.shape[0] - 1), np.diff(offsets))
+    local = np.arange(c0.shape[0]) - offsets[mask_of]
+    x = c0.copy()
+    later = np.flatnonzero(local > 2)
+    x[later] -= c0[later - 2]
+    n = np.frexp(np.where(x < 0, ~x, x))[1].astype(np.int64) // 5 + 1        # bit length of x (of ~x below 0) // 5 + 1
+    first = np.cumsum(n) - n
+    idx = np.repeat(np.arange(x.shape[0]), n)
+    j = np.arange(idx.shape[0]) - first[idx]
+    c = ((x[idx] >> (5 * j)) & 0x1f) | np.where(j < n[idx] - 1, 0x20, 0)
+    text = (c + 48).astype(np.uint8).tobytes().decode('ascii')
+    ends = np.concatenate(([0], np.cumsum(n)))[offsets]                   # character offset of each mask's first run
+    return [text[ends[d]:ends[d + 1]] for d in range(offsets.shape[0] - 1)]
+
+
+def rle_encode(mask):
+    """maskApi.c rleEncode of one (h, w) mask (any nonzero value is set): the run lengths over the column-major flattening, starting
+    with a run of 0s.  Host NumPy; the device encoder is ``_hip.ops.mask_rle_encode``."""
+    flat = np.asarray(mask).T.reshape(-1) != 0
+    change = np.flatnonzero(flat != np.concatenate(([False], flat[:-1])))
+    return np.diff(np.concatenate(([0], change, [flat.shape[0]]))).astype(np.int64)
 
 
 def rle_from_polygon(xy, h, w):

@@ -388,3 +388,252 @@ def add_keypoint_image(acc, dt_yx, dt_score, gt_kp_yxv, gt_area, gt_crowd, gt_bb
     dt_yx, dt_score = dt_yx[top], dt_score[top]
     oks = keypoint_oks(dt_yx, gt, gt_area, gt_bbox_xywh, sigmas) if len(top) and len(gt) else np.zeros((len(top), len(gt)))
     acc.add_image(oks, dt_score, keypoint_extent_area(dt_yx), gt_area, gt_ignore, gt_crowd)
+
+
+# ---- COCO box and mask AP (pycocotools COCOeval, iouType='segm' / 'bbox', useCats=1) -------------------------------------------------
+# evaluateImg / accumulate / summarize of pycocotools/cocoeval.py with its default parameters: IoU thresholds .50:.05:.95, 101 recall
+# points, maxDets (1, 10, 100), area ranges all / small / medium / large (closed intervals), per (image, category) the detections in
+# descending score (a stable sort: equal scores keep their input order) cut at 100, ground truth ignored when it is a crowd (which can
+# absorb several detections) and sorted after the rest.  IoU is maskApi.c's: I / (A_dt + A_gt - I), or I / A_dt for a crowd, and 0
+# when the masks (boxes) do not overlap.  Ground truth is ranged by its annotation area, a segm detection by its pixel count, a bbox
+# detection by w * h (COCO.loadRes).
+
+COCO_IOU_THRESHOLDS = OKS_THRESHOLDS
+COCO_AREA_RANGES = (('all', (0 ** 2, 1e5 ** 2)), ('small', (0 ** 2, 32 ** 2)), ('medium', (32 ** 2, 96 ** 2)), ('large', (96 ** 2, 1e5 ** 2)))
+COCO_MAX_DETS = (1, 10, 100)
+COCO_STAT_NAMES = ('AP', 'AP50', 'AP75', 'APs', 'APm', 'APl', 'AR1', 'AR10', 'AR100', 'ARs', 'ARm', 'ARl')
+
+
+def segm_iou_from_counts(inter, dt_area, gt_area, gt_crowd):
+    """(D, G) float64 mask IoU from exact integer counts (maskApi.c rleIou): I / (A_dt + A_gt - I), I / A_dt for crowd ground truth,
+    0 where I == 0 (empty masks included)."""
+    inter = np.asarray(inter, dtype=np.float64).reshape(len(dt_area), len(gt_area))
+    da = np.asarray(dt_area, dtype=np.float64).reshape(-1, 1)
+    ga = np.asarray(gt_area, dtype=np.float64).reshape(1, -1)
+    union = np.where(np.asarray(gt_crowd, dtype=bool).reshape(1, -1), da, da + ga - inter)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(inter > 0, inter / union, 0.0)
+
+
+def bbox_iou_xywh(dt_xywh, gt_xywh, gt_crowd):
+    """(D, G) float64 box IoU of (x, y, w, h) boxes (maskApi.c bbIou): the overlap w * h over da + ga - overlap, or over da for crowd
+    ground truth; 0 where the boxes do not overlap."""
+    d = np.asarray(dt_xywh, dtype=np.float64).reshape(-1, 1, 4)
+    g = np.asarray(gt_xywh, dtype=np.float64).reshape(1, -1, 4)
+    w = np.minimum(d[..., 2] + d[..., 0], g[..., 2] + g[..., 0]) - np.maximum(d[..., 0], g[..., 0])
+    h = np.minimum(d[..., 3] + d[..., 1], g[..., 3] + g[..., 1]) - np.maximum(d[..., 1], g[..., 1])
+    i = w * h
+    da, ga = d[..., 2] * d[..., 3], g[..., 2] * g[..., 3]
+    u = np.where(np.asarray(gt_crowd, dtype=bool).reshape(1, -1), da, da + ga - i)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where((w > 0) & (h > 0), i / u, 0.0)
+
+
+class COCOInstanceMatchAccumulator(object):
+    """Streaming state of COCOeval for 'segm' or 'bbox' over all categories.  Per (image, category) with a detection, kept: the scores
+    of its (up to 100) detections in evaluateImg's order and, per IoU threshold and area range, whether each matched and whether it is
+    ignored; per (category, area range) the number of ground truths that are not ignored.  No mask or box is kept.
+
+    The greedy matching of evaluateImg runs for all categories, thresholds and area ranges of an image at once: the image's
+    detections are visited in descending score (which keeps each category's own order), and each takes, per (threshold, area range),
+    the available same-category ground truth of largest IoU >= the threshold (the last one among equal IoUs), preferring ground truth
+    that is not ignored - evaluateImg's loop over the ground truth sorted ignored-last."""
+
+    def __init__(self, max_dets=COCO_MAX_DETS, iou_thresholds=COCO_IOU_THRESHOLDS, area_ranges=COCO_AREA_RANGES):
+        self.max_dets = tuple(max_dets)
+        self.thresholds = np.asarray(iou_thresholds, dtype=np.float64)
+        self.area_names = [n for n, _ in area_ranges]
+        self.lo = np.array([r[0] for _, r in area_ranges], dtype=np.float64)
+        self.hi = np.array([r[1] for _, r in area_ranges], dtype=np.float64)
+        self.entries = defaultdict(list)           # category -> per image with a detection: (scores (n,), matched (T,A,n), ignored (T,A,n))
+        self.n_pos = defaultdict(lambda: np.zeros(len(self.lo), dtype=np.int64))      # category -> (A,) ground truths not ignored
+
+    def add_image(self, iou, dt_cat, dt_score, dt_area, gt_cat, gt_area, gt_crowd):
+        """One image.  iou (D, G): IoU of detection d (input order) and ground truth g (only same-category pairs are read); dt_cat (D,),
+        dt_score (D,), dt_area (D,); gt_cat (G,), gt_area (G,) (annotation areas), gt_crowd (G,) (iscrowd: ignored, absorbs
+        detections)."""
+        dt_cat = np.asarray(dt_cat).reshape(-1).astype(np.int64)
+        dt_score = np.asarray(dt_score, dtype=np.float64).reshape(-1)
+        dt_area = np.asarray(dt_area, dtype=np.float64).reshape(-1)
+        gt_cat = np.asarray(gt_cat).reshape(-1).astype(np.int64)
+        gt_area = np.asarray(gt_area, dtype=np.float64).reshape(-1)
+        gt_crowd = np.asarray(gt_crowd, dtype=bool).reshape(-1)
+        D, G, T, A = dt_score.shape[0], gt_area.shape[0], len(self.thresholds), len(self.lo)
+        g_ig = gt_crowd[None, :] | (gt_area[None, :] < self.lo[:, None]) | (gt_area[None, :] > self.hi[:, None])      # (A, G)
+        for c in np.unique(gt_cat):
+            self.n_pos[int(c)] += np.count_nonzero(~g_ig[:, gt_cat == c], axis=1)
+        if D == 0:
+            return
+        order = np.argsort(-dt_score, kind='mergesort')
+        cat_o = dt_cat[order]
+        rank = np.zeros(D, dtype=np.int64)             # rank of each detection within its category, in score order
+        for c in np.unique(cat_o):
+            sel = cat_o == c
+            rank[sel] = np.arange(np.count_nonzero(sel))
+        keep = order[rank < self.max_dets[-1]]
+        n = keep.shape[0]
+        cat_k = dt_cat[keep]
+        matched = np.zeros((T, A, n), dtype=bool)
+        ignored = np.zeros((T, A, n), dtype=bool)
+        if G:
+            io = np.where(cat_k[:, None] == gt_cat[None, :], np.asarray(iou, dtype=np.float64).reshape(D, G)[keep], -1.0)
+            thr = np.minimum(self.thresholds, 1 - 1e-10)[:, None, None]                # (T, 1, 1)
+            taken = np.zeros((T, A, G), dtype=bool)
+            rev = np.arange(G)[::-1]
+            for j in np.flatnonzero((io >= thr.min()).any(axis=1)):
+                ok = (io[j][None, None, :] >= thr) & (~taken | gt_crowd[None, None, :])          # (T, A, G)
+                real = ok & ~g_ig[None]
+                use = np.where(real.any(axis=-1, keepdims=True), real, ok & g_ig[None])
+                val = np.where(use, io[j][None, None, :], -np.inf)[..., rev]
+                m = G - 1 - np.argmax(val, axis=-1)                                     # the last maximum (T, A)
+                found = use.any(axis=-1)
+                ti, ai = np.nonzero(found)
+                taken[ti, ai, m[ti, ai]] = True
+                matched[:, :, j] = found
+                ignored[:, :, j] = found & g_ig[np.arange(A)[None, :], m]
+        out = (dt_area[keep][None, :] < self.lo[:, None]) | (dt_area[keep][None, :] > self.hi[:, None])     # (A, n)
+        ignored |= ~matched & out[None]
+        s = dt_score[keep]
+        for c in np.unique(cat_k):
+            sel = np.flatnonzero(cat_k == c)
+            self.entries[int(c)].append((s[sel], matched[:, :, sel], ignored[:, :, sel]))
+
+    def categories(self):
+        """The categories seen (ground truth or detections), ascending: COCOeval's sorted catIds, less those never seen (whose cells
+        are -1 and do not enter any mean)."""
+        return sorted(set(self.n_pos) | set(self.entries))
+
+    def precision_recall(self):
+        """COCOeval.accumulate: precision (T, R, K, A, M) at the 101 recall points and recall (T, K, A, M), K = categories(), M =
+        max_dets; -1 where a (category, area range) has no ground truth that counts."""
+        cats = self.categories()
+        T, R, K, A, M = len(self.thresholds), len(RECALL_THRESHOLDS), len(cats), len(self.lo), len(self.max_dets)
+        precision = -np.ones((T, R, K, A, M))
+        recall = -np.ones((T, K, A, M))
+        for k, c in enumerate(cats):
+            npig = self.n_pos[c] if c in self.n_pos else np.zeros(A, dtype=np.int64)
+            ents = self.entries.get(c, [])
+            for mi, md in enumerate(self.max_dets):
+                if ents:
+                    scores = np.concatenate([e[0][:md] for e in ents])
+                    inds = np.argsort(-scores, kind='mergesort')
+                    dtm = np.concatenate([e[1][:, :, :md] for e in ents], axis=2)[:, :, inds]
+                    dt_ig = np.concatenate([e[2][:, :, :md] for e in ents], axis=2)[:, :, inds]
+                else:
+                    dtm = dt_ig = np.zeros((T, A, 0), dtype=bool)
+                tp_sum = np.cumsum(dtm & ~dt_ig, axis=2).astype(np.float64)
+                fp_sum = np.cumsum(~dtm & ~dt_ig, axis=2).astype(np.float64)
+                nd = tp_sum.shape[2]
+                for a in range(A):
+                    if npig[a] == 0:
+                        continue
+                    rc = tp_sum[:, a] / npig[a]                                          # (T, nd)
+                    pr = tp_sum[:, a] / (fp_sum[:, a] + tp_sum[:, a] + np.spacing(1))
+                    recall[:, k, a, mi] = rc[:, -1] if nd else 0
+                    if nd:
+                        pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]         # precision envelope (right to left)
+                    for t in range(T):
+                        ri = np.searchsorted(rc[t], RECALL_THRESHOLDS, side='left')
+                        q = np.zeros(R)
+                        ok = ri < nd
+                        q[ok] = pr[t, ri[ok]]
+                        precision[t, :, k, a, mi] = q
+        return precision, recall
+
+    def summarize(self, precision_recall=None):
+        """COCOeval.summarize: {'AP', 'AP50', 'AP75', 'APs', 'APm', 'APl', 'AR1', 'AR10', 'AR100', 'ARs', 'ARm', 'ARl'}, each a mean
+        over the cells that are not -1, -1.0 when there is none."""
+        precision, recall = self.precision_recall() if precision_recall is None else precision_recall
+
+        def stat(ap, thr=None, area='all', max_det=100):
+            a, m = [self.area_names.index(area)], [self.max_dets.index(max_det)]
+            s = precision if ap else recall
+            if thr is not None:
+                s = s[np.where(np.isclose(self.thresholds, thr))[0]]
+            s = s[:, :, :, a, m] if ap else s[:, :, a, m]
+            return float(np.mean(s[s > -1])) if s[s > -1].size else -1.0
+        md = self.max_dets[-1]
+        vals = (stat(1), stat(1, .5), stat(1, .75), stat(1, area='small'), stat(1, area='medium'), stat(1, area='large'),
+                stat(0, max_det=self.max_dets[0]), stat(0, max_det=self.max_dets[1]), stat(0, max_det=md), stat(0, area='small'),
+                stat(0, area='medium'), stat(0, area='large'))
+        return dict(zip(COCO_STAT_NAMES, vals))
+
+    def category_ap(self, precision_recall=None):
+        """{category: AP over IoU .50:.95, area all, 100 detections} (-1.0 for a category without ground truth that counts)."""
+        precision, _ = self.precision_recall() if precision_recall is None else precision_recall
+        a, m = self.area_names.index('all'), len(self.max_dets) - 1
+        out = {}
+        for k, c in enumerate(self.categories()):
+            s = precision[:, :, k, a, m]
+            out[c] = float(np.mean(s[s > -1])) if s[s > -1].size else -1.0
+        return out
+
+
+def format_coco_stats(stats, iou_type):
+    """COCOeval.summarize's twelve printed lines under an 'iouType: <iou_type>' line."""
+    rows = (('Average Precision', '0.50:0.95', 'all', 100), ('Average Precision', '0.50', 'all', 100),
+            ('Average Precision', '0.75', 'all', 100), ('Average Precision', '0.50:0.95', 'small', 100),
+            ('Average Precision', '0.50:0.95', 'medium', 100), ('Average Precision', '0.50:0.95', 'large', 100),
+            ('Average Recall', '0.50:0.95', 'all', 1), ('Average Recall', '0.50:0.95', 'all', 10), ('Average Recall', '0.50:0.95', 'all', 100),
+            ('Average Recall', '0.50:0.95', 'small', 100), ('Average Recall', '0.50:0.95', 'medium', 100),
+            ('Average Recall', '0.50:0.95', 'large', 100))
+    lines = ['iouType: %s' % iou_type]
+    for (title, iou, area, md), name in zip(rows, COCO_STAT_NAMES):
+        lines.append(' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'.format(
+            title, '(AP)' if 'Precision' in title else '(AR)', iou, area, md, stats[name]))
+    return '\n'.join(lines)
+
+
+def _load_results(results):
+    import json
+    if isinstance(results, str):
+        with open(results) as f:
+            results = json.load(f)
+    return list(results)
+
+
+def evaluate_coco_results(gt_annotation_file, results, iou_type, img_ids=None):
+    """COCOeval(cocoGt, cocoGt.loadRes(results), iou_type) over ``img_ids`` (default: every image of the annotation file) and all its
+    categories, on the host: ``results`` is a COCO results file or list ({'image_id', 'category_id', 'segmentation' (RLE) or 'bbox',
+    'score'}); masks are decoded with dataset.coco_api.  As in COCO.loadRes, a segm detection's area is its pixel count unless the
+    results carry boxes too (then w * h: loadRes takes such a list as box results).  Returns summarize()'s dict of the 12 stats."""
+    from chainer_maskrcnn.dataset.coco_api import COCO, rle_decode, rle_from_string
+    if iou_type not in ('segm', 'bbox'):
+        raise ValueError("evaluate_coco_results: iou_type 'segm' or 'bbox', got %r" % (iou_type,))
+    gt = COCO(gt_annotation_file)
+    cat_ids = set(gt.getCatIds())
+    img_ids = sorted(set(gt.getImgIds() if img_ids is None else img_ids))
+    res = _load_results(results)
+    box_area = bool(res) and bool(res[0].get('bbox'))          # loadRes takes a list whose first entry has a box as box results
+    by_img = defaultdict(list)
+    for r in res:
+        if r['category_id'] in cat_ids:
+            by_img[r['image_id']].append(r)
+    acc = COCOInstanceMatchAccumulator()
+    for img_id in img_ids:
+        info = gt.imgs[img_id]
+        h, w = info['height'], info['width']
+        anns = [a for a in gt.imgToAnns.get(img_id, ()) if a['category_id'] in cat_ids]
+        dts = by_img.get(img_id, [])
+        gt_cat = np.array([a['category_id'] for a in anns], np.int64)
+        gt_area = np.array([a.get('area', 0.0) for a in anns], np.float64)
+        gt_crowd = np.array([bool(a.get('iscrowd', 0)) for a in anns], bool)
+        dt_cat = np.array([d['category_id'] for d in dts], np.int64)
+        dt_score = np.array([d['score'] for d in dts], np.float64)
+        if iou_type == 'segm':
+            def mask(s):
+                c = s['counts']
+                return rle_decode(rle_from_string(c) if isinstance(c, (str, bytes)) else np.asarray(c, np.int64), *s['size'])
+            dm = np.array([mask(d['segmentation']) for d in dts], np.float64).reshape(len(dts), h * w)
+            gm = np.array([gt.annToMask(a) for a in anns], np.float64).reshape(len(anns), h * w)
+            dt_area = dm.sum(axis=1)
+            iou = segm_iou_from_counts(dm @ gm.T, dt_area, gm.sum(axis=1), gt_crowd)
+            if box_area:
+                db = np.array([d['bbox'] for d in dts], np.float64).reshape(-1, 4)
+                dt_area = db[:, 2] * db[:, 3]
+        else:
+            db = np.array([d['bbox'] for d in dts], np.float64).reshape(-1, 4)
+            dt_area = db[:, 2] * db[:, 3]
+            iou = bbox_iou_xywh(db, np.array([a['bbox'] for a in anns], np.float64).reshape(-1, 4), gt_crowd)
+        acc.add_image(iou, dt_cat, dt_score, dt_area, gt_cat, gt_area, gt_crowd)
+    return acc.summarize()

@@ -10,6 +10,10 @@ What is kept is one (score, match) per prediction and the positive count per cla
 Keypoint heads: ``KeypointCOCOEvaluator``, COCO's keypoint AP (pycocotools COCOeval, iouType='keypoints') of
 ``predict_keypoints``; the heat maps are decoded on the device (``keypoint_decode``) and one copy per image brings the scores and
 keypoint positions of the 20 best detections to the host, where OKS and the matching run in float64.
+
+Mask heads, COCO's metric: ``InstanceSegmentationCOCOEvaluator``, mask and box AP over IoU .50:.95 (pycocotools COCOeval, iouType
+'segm' / 'bbox'), from the same device counts; optionally it writes COCO results entries, the masks run-length encoded on the device
+(``mask_rle_encode``).
 """
 import numpy as np
 import torch
@@ -228,3 +232,148 @@ class SyntheticKeypointEvalDataset(object):
         h, w = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
         xywh = np.stack([box[:, 1], box[:, 0], w, h], axis=1)
         return b['imgs'][0] * 255, b['keypoints'][0].astype(np.float64), h * w, np.zeros(self.G, dtype=bool), xywh
+
+
+# ---- COCO box and mask AP ------------------------------------------------------------------------------------------------------------
+_COCO_KEYS = (('map', 'AP'), ('ap50', 'AP50'), ('ap75', 'AP75'), ('ap_small', 'APs'), ('ap_medium', 'APm'), ('ap_large', 'APl'),
+              ('ar', 'AR100'))
+
+
+class InstanceSegmentationCOCOEvaluator(object):
+    """COCO mask and box AP (pycocotools COCOeval, iouType 'segm' / 'bbox'; evaluations.COCOInstanceMatchAccumulator) of
+    ``target.predict`` over ``dataset``, whose examples are (img (3,H,W) 0..255, gt_masks (G,H,W), gt_labels (G,), gt_area (G,),
+    gt_crowd (G,), gt_bbox_xywh (G,4), image_id) - COCOInstanceEvalDataset, SyntheticCOCOEvalDataset.  ``cat_ids[label]`` is a
+    label's COCO category id (default: ``dataset.cat_ids``, else the label itself).
+
+    ``evaluate()`` returns, for 'segm', {'main/map' (AP at IoU .50:.95), 'main/ap50', 'main/ap75', 'main/ap_small', 'main/ap_medium',
+    'main/ap_large', 'main/ar' (AR at 100 detections)}, the same keys under 'main/bbox/' for 'bbox', and 'main/ap/<label_names[l]>'
+    (segm AP of category l) when label_names is given; ``self.stats`` keeps all 12 stats of each type.  A trainer writes them with the
+    prefix 'validation/'.
+
+    Per image: ``predict``, then ``mask_iou_counts`` with labels on (exact intersections and areas on the device), then ONE copy to the
+    host of the labels, scores, boxes, intersections and areas; IoU in float64 and the matching on the host.  With ``results`` a list,
+    also ``mask_rle_encode`` on the device and one more copy (offsets and counts); one COCO results entry per detection is appended:
+    {'image_id', 'category_id', 'segmentation': {'size': [H, W], 'counts': <compressed RLE>}, 'bbox': [x, y, w, h], 'score'}
+    (split_coco_results makes the two results files).  No mask is kept on the host.  ``target``'s preset is used as it is, and its
+    training state is restored afterwards."""
+
+    default_name = 'validation'
+
+    def __init__(self, dataset, target, label_names=None, cat_ids=None, iou_types=('segm', 'bbox'), results=None):
+        if not iou_types or any(t not in ('segm', 'bbox') for t in iou_types):
+            raise ValueError("InstanceSegmentationCOCOEvaluator: iou_types from ('segm', 'bbox'), got %r" % (iou_types,))
+        self.dataset = dataset
+        self.target = target
+        self.label_names = label_names
+        self.cat_ids = list(cat_ids) if cat_ids is not None else getattr(dataset, 'cat_ids', None)
+        self.iou_types = tuple(iou_types)
+        self.results = results
+        self.stats = {}
+
+    def _cat(self, label):
+        label = np.asarray(label, dtype=np.int64)
+        return label if self.cat_ids is None else np.asarray(self.cat_ids, dtype=np.int64)[label]
+
+    def evaluate(self):
+        from chainer_maskrcnn.nn import core
+        target = self.target
+        rpn, head = getattr(target, 'rpn', None), getattr(target, 'head', None)
+        keep = (target.train, core.TRAIN, getattr(rpn, 'train', None), getattr(head, 'train', None))
+        accs = {t: evaluations.COCOInstanceMatchAccumulator() for t in self.iou_types}
+        try:
+            with torch.no_grad():
+                for i in range(len(self.dataset)):
+                    self._add_example(accs, self.dataset[i])
+        finally:
+            target.train, core.TRAIN = keep[0], keep[1]
+            if keep[2] is not None:
+                rpn.train = keep[2]
+            if keep[3] is not None:
+                head.train = keep[3]
+        report = {}
+        for t, acc in accs.items():
+            pr = acc.precision_recall()
+            s = self.stats[t] = acc.summarize(pr)
+            prefix = 'main/' if t == 'segm' else 'main/bbox/'
+            report.update({prefix + k: s[name] for k, name in _COCO_KEYS})
+            if t == 'segm' and self.label_names is not None:
+                ap = acc.category_ap(pr)
+                for l, name in enumerate(self.label_names):
+                    report['main/ap/%s' % name] = ap.get(int(self._cat(l)), -1.0)
+        return report
+
+    def _add_example(self, accs, example):
+        img, gt_mask, gt_label, gt_area, gt_crowd, gt_bbox, image_id = example[:7]
+        dev = self.target.device
+        img = torch.as_tensor(np.asarray(img, dtype=np.float32)) if not isinstance(img, torch.Tensor) else img.to(torch.float32)
+        masks, labels, scores = self.target.predict([img])
+        mask, label, score = masks[0], labels[0].to(torch.int32).contiguous(), scores[0].to(torch.float32).contiguous()
+        gt_label = np.asarray(gt_label.cpu() if isinstance(gt_label, torch.Tensor) else gt_label, dtype=np.int32).reshape(-1)
+        gt_crowd = np.asarray(gt_crowd, dtype=bool).reshape(-1)
+        gt_area = np.asarray(gt_area, dtype=np.float64).reshape(-1)
+        D, G = int(label.shape[0]), int(gt_label.shape[0])
+        H, W = int(mask.shape[1]), int(mask.shape[2])
+        if D:
+            bbox = self.target.last_bboxes[0].to(torch.float32).contiguous()
+            gm = gt_mask.to(dev) if isinstance(gt_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_mask)).to(dev)
+            gm = gm.reshape(G, H, W)
+            inter, area_dt, area_gt = ops.mask_iou_counts(mask, gm, label, torch.from_numpy(gt_label).to(dev))
+            host = torch.cat((label, score.view(torch.int32), bbox.view(torch.int32).reshape(-1), inter.reshape(-1), area_dt,
+                              area_gt)).cpu().numpy()                      # the one copy of this image
+            o = 2 * D
+            dt_label, dt_score = host[:D], host[D:o].view(np.float32)
+            yx = host[o:o + 4 * D].view(np.float32).reshape(D, 4).astype(np.float64)
+            o += 4 * D
+            inter_h = host[o:o + D * G].reshape(D, G)
+            area_dt_h, area_gt_h = host[o + D * G:o + D * G + D], host[o + D * G + D:]
+            xywh = np.stack([yx[:, 1], yx[:, 0], yx[:, 3] - yx[:, 1], yx[:, 2] - yx[:, 0]], axis=1)
+        else:
+            dt_label, dt_score = np.zeros((0,), np.int32), np.zeros((0,), np.float32)
+            xywh, inter_h, area_dt_h, area_gt_h = np.zeros((0, 4)), np.zeros((0, G)), np.zeros((0,)), np.zeros((G,))
+        dt_cat, gt_cat = self._cat(dt_label), self._cat(gt_label)
+        for t, acc in accs.items():
+            if t == 'segm':
+                iou, dt_area = evaluations.segm_iou_from_counts(inter_h, area_dt_h, area_gt_h, gt_crowd), area_dt_h
+            else:
+                iou, dt_area = evaluations.bbox_iou_xywh(xywh, gt_bbox, gt_crowd), xywh[:, 2] * xywh[:, 3]
+            acc.add_image(iou, dt_cat, dt_score, dt_area, gt_cat, gt_area, gt_crowd)
+        if self.results is not None and D:
+            from chainer_maskrcnn.dataset.coco_api import rle_to_strings
+            offsets, counts, _ = ops.mask_rle_encode(mask)
+            rle = torch.cat((offsets, counts)).cpu().numpy()                   # the second copy: the run lengths
+            strings = rle_to_strings(rle[:D + 1], rle[D + 1:])
+            for d in range(D):
+                self.results.append({'image_id': int(image_id), 'category_id': int(dt_cat[d]),
+                                     'segmentation': {'size': [H, W], 'counts': strings[d]},
+                                     'bbox': [float(v) for v in xywh[d]], 'score': float(dt_score[d])})
+
+
+def split_coco_results(results):
+    """The evaluator's results list as the two COCO results lists (segm: without boxes, so that COCO.loadRes ranges a detection by
+    its pixel count; bbox: without masks)."""
+    segm = [{k: r[k] for k in ('image_id', 'category_id', 'segmentation', 'score')} for r in results]
+    bbox = [{k: r[k] for k in ('image_id', 'category_id', 'bbox', 'score')} for r in results]
+    return segm, bbox
+
+
+class SyntheticCOCOEvalDataset(object):
+    """SyntheticEvalDataset with COCO's annotation fields (utils/synthetic.make_batch, one image per seed): examples (img 0..255, masks,
+    labels, area = each mask's pixel count, iscrowd (none), bbox_xywh from make_batch's boxes, image_id = the seed index).  Category
+    ids are the labels.  Seeds start at ``first_seed``, far from the seeds of train.py's synthetic training pool."""
+
+    def __init__(self, n_images, H, W, n_fg_class=80, G=8, first_seed=1000003):
+        self.n, self.H, self.W, self.n_fg_class, self.G, self.first_seed = n_images, H, W, n_fg_class, G, first_seed
+        self.cat_ids = list(range(n_fg_class))
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        from chainer_maskrcnn.utils.synthetic import make_batch
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        b = make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, n_fg_class=self.n_fg_class)
+        masks, box = b['masks'][0], b['bboxes'][0].astype(np.float64)
+        xywh = np.stack([box[:, 1], box[:, 0], box[:, 3] - box[:, 1], box[:, 2] - box[:, 0]], axis=1)
+        area = (masks != 0).reshape(len(masks), -1).sum(axis=1).astype(np.float64)
+        return b['imgs'][0] * 255, masks, b['labels'][0], area, np.zeros(len(masks), dtype=bool), xywh, i

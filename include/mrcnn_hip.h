@@ -677,6 +677,27 @@ size_t mrcnn_keypoint_decode_workspace_bytes(int D, int S, int K);
 int mrcnn_keypoint_decode_f32(const float *heat, int D, int S, int Cp, int K, const float *bbox, void *ws, size_t ws_bytes, float *out,
                               int32_t *index, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * COCO run-length encoding of masks (rle.hip; InstanceSegmentationCOCOEvaluator, evaluate.py).  Replaces pycocotools' maskApi.c rleEncode
+ * on host copies of the masks.
+ *   m (D,H,W) uint8, contiguous rows (no alignment needed); any nonzero byte is a set pixel (torch.bool, mask_paste)
+ *   runs over the column-major flattening p = x * H + y, alternating 0 / 1 and starting with a run of 0s (a mask whose pixel (0,0) is
+ *   set starts with a 0-length run; an all-zero mask is [H * W])
+ *   count: offsets (D+1) int32 = exclusive prefix sum of the masks' run counts (offsets[D] = the total); area (D) int32 or NULL = the
+ *          set-pixel count of each mask
+ *   write: counts[offsets[d] .. offsets[d+1]) = the runs of mask d; ws must be the workspace count used, unmodified (it holds the
+ *          per-segment ranks count computed), and offsets count's output
+ *   ws: device scratch of mrcnn_mask_rle_workspace_bytes(D, H, W) bytes
+ * Exact integers, identical from run to run and independent of the launch split.  D == 0 is valid (count writes offsets[0] = 0).
+ * Errors, before any launch: MRCNN_E_INVALID for a negative size or a NULL pointer of a non-empty side; MRCNN_E_WORKSPACE for a short
+ * workspace; MRCNN_E_UNSUPPORTED when H * W or the worst-case run total D * (H * W + 1) does not fit int32.
+ * ---------------------------------------------------------------------------------------- */
+size_t mrcnn_mask_rle_workspace_bytes(int D, int H, int W);
+int mrcnn_mask_rle_count_u8(const unsigned char *m, int D, int H, int W, void *ws, size_t ws_bytes, int32_t *offsets, int32_t *area,
+                            void *stream);
+int mrcnn_mask_rle_write_u8(const unsigned char *m, int D, int H, int W, const void *ws, size_t ws_bytes, const int32_t *offsets,
+                            int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

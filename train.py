@@ -76,8 +76,9 @@ def build_parser(keypoints=False):
                              'reference train.py:164-166 uses 10000); 0 = off')
     parser.add_argument('--eval-images', type=int, default=0,
                         help='images of the val split per evaluation (0: the whole split; --synthetic 1: %d images)' % SYNTHETIC_VAL_IMAGES)
-    parser.add_argument('--eval-metric', default='mask_voc', choices=['mask_voc', 'keypoint_coco'],
+    parser.add_argument('--eval-metric', default='mask_voc', choices=['mask_voc', 'mask_coco', 'keypoint_coco'],
                         help='metric of --eval-interval: mask_voc = PASCAL VOC mask mAP (mask heads, InstanceSegmentationVOCEvaluator); '
+                             'mask_coco = COCO mask and box AP over IoU .50:.95 (mask heads, InstanceSegmentationCOCOEvaluator); '
                              'keypoint_coco = COCO keypoint AP over OKS .50:.95 (keypoint heads, KeypointCOCOEvaluator)')
     return parser
 
@@ -93,7 +94,8 @@ def run(args, keypoints=False):
         raise ValueError('--eval-interval: validation mAP (--eval-metric %s) is computed for mask heads only; keypoint runs take '
                          '--eval-metric keypoint_coco' % args.eval_metric)
     if args.eval_metric == 'keypoint_coco' and not keypoints:
-        raise ValueError('--eval-metric keypoint_coco: COCO keypoint AP needs a keypoint head (train_keypoints.py); mask heads take mask_voc')
+        raise ValueError('--eval-metric keypoint_coco: COCO keypoint AP needs a keypoint head (train_keypoints.py); mask heads take mask_voc '
+                         'or mask_coco')
     if args.eval_metric == 'keypoint_coco' and getattr(args, 'dataset', 'coco') == 'depth':
         raise ValueError('--eval-metric keypoint_coco: COCO defines OKS sigmas for its 17 keypoints only; --dataset depth has 20')
     if args.eval_interval > 0 and world > 1:
@@ -247,7 +249,8 @@ def run(args, keypoints=False):
 
 def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
     """The val split of the run (reference train.py:113-115: COCOMaskLoader(split='val') + EvaluatorTransform) and its
-    InstanceSegmentationVOCEvaluator; with --eval-metric keypoint_coco, COCOKeypointsLoader(split='val') and KeypointCOCOEvaluator.
+    InstanceSegmentationVOCEvaluator; with --eval-metric mask_coco, every image of the val annotation file (COCOInstanceEvalDataset) and
+    InstanceSegmentationCOCOEvaluator; with --eval-metric keypoint_coco, COCOKeypointsLoader(split='val') and KeypointCOCOEvaluator.
     --synthetic 1: deterministic make_batch images from seeds the training pool never uses."""
     from chainer_maskrcnn.evaluator import InstanceSegmentationVOCEvaluator, SyntheticEvalDataset, TransformedDataset, coco_mask_example
     if args.eval_metric == 'keypoint_coco':
@@ -260,6 +263,16 @@ def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
             val = COCOKeypointsLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type)
             data = COCOKeypointEvalDataset(val, n=args.eval_images or None)
         return KeypointCOCOEvaluator(data, faster_rcnn)
+    if args.eval_metric == 'mask_coco':
+        from chainer_maskrcnn.evaluator import InstanceSegmentationCOCOEvaluator, SyntheticCOCOEvalDataset
+        if args.synthetic:
+            H, W = args.image_size
+            data = SyntheticCOCOEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_fg_class=n_fg)
+        else:
+            from chainer_maskrcnn.dataset.coco_dataset import COCOInstanceEvalDataset
+            data = COCOInstanceEvalDataset(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type,
+                                           category_filter=labels, n=args.eval_images or None)
+        return InstanceSegmentationCOCOEvaluator(data, faster_rcnn, label_names=getattr(data, 'label_names', None) or labels)
     if args.synthetic:
         H, W = args.image_size
         data = SyntheticEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_fg_class=n_fg)
