@@ -5,6 +5,7 @@ kernels on the current stream.  No arithmetic happens in torch.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from chainer_maskrcnn import _hip
@@ -216,6 +217,46 @@ def image_resize_f32(img, oh, ow, div=1.0):
     C, H, W = img.shape
     out = _empty((C, oh, ow), img.device)
     check(lib().mrcnn_image_resize_f32(ptr(img), C, H, W, ptr(out), oh, ow, oh, ow, float(div), stream_ptr()))
+    return out
+
+
+# ---- batched training resizes with an optional horizontal flip (augment.hip) -------------------------------------------------------
+# mrcnn_resize_desc_t of include/mrcnn_hip.h, one row per example of the batch
+RESIZE_DESC = np.dtype([('src_offset', '<i8'), ('H', '<i4'), ('W', '<i4'), ('oh', '<i4'), ('ow', '<i4'), ('flip', '<i4'), ('count', '<i4')])
+assert RESIZE_DESC.itemsize == 32
+
+
+def resize_descs(rows):
+    """[(src_offset, H, W, oh, ow, flip, count)] -> the host descriptor table the two batched kernels take."""
+    return np.array([tuple(int(v) for v in r) for r in rows], RESIZE_DESC)
+
+
+def image_resize_batch_u8(src, desc, dst_h, dst_w, div=255.0):
+    """src: 1-D uint8 device tensor holding the batch's (H,W,3) images packed at desc['src_offset']; desc: resize_descs(...).  Returns
+    the zero-padded (N,3,dst_h,dst_w) float32 batch: resize_linear of each image, mirrored where desc['flip'] is 1, / div.  One launch."""
+    _ck(src)
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError('image_resize_batch_u8: src must be a 1-D uint8 tensor')
+    desc = np.ascontiguousarray(desc, RESIZE_DESC)
+    N = len(desc)
+    out = _empty((N, 3, dst_h, dst_w), src.device)
+    check(lib().mrcnn_image_resize_batch_u8_f32(ptr(src), src.numel(), desc.ctypes.data, N, ptr(out), dst_h, dst_w, float(div),
+                                                stream_ptr()))
+    return out
+
+
+def mask_resize_batch_u8(src, desc, G, dst_h, dst_w):
+    """src: 1-D uint8 device tensor holding each example's (count,H,W) masks packed at desc['src_offset']; desc: resize_descs(...).
+    Returns the zero-padded (N,G,dst_h,dst_w) uint8 batch: resize_nearest of each mask, mirrored where desc['flip'] is 1; rows past an
+    example's count are zero.  One launch."""
+    _ck(src)
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError('mask_resize_batch_u8: src must be a 1-D uint8 tensor')
+    desc = np.ascontiguousarray(desc, RESIZE_DESC)
+    N = len(desc)
+    out = torch.empty((N, G, dst_h, dst_w), dtype=torch.uint8, device=src.device)
+    check(lib().mrcnn_mask_resize_batch_nearest_u8(ptr(src) if src.numel() else ptr(None), src.numel(), desc.ctypes.data, N, G, ptr(out),
+                                                   dst_h, dst_w, stream_ptr()))
     return out
 
 

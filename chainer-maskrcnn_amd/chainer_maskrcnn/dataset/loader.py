@@ -7,6 +7,9 @@ assembled in pinned host memory and copied on a dedicated HIP stream so that the
 batch at PCIe 5 rates) overlaps the previous step.  Batch layout = ``utils.synthetic.make_batch``:
   imgs (N,3,H,W) f32 (zero-padded bottom/right to the largest image of the batch), bboxes (N,G,4) f32,
   labels (N,G) i32 with -1 on padded rows, masks (N,G,H,W) u8  |  keypoints (N,G,K,3) f32.
+Augmentation (``augment=dataset.augment.Augment``, off by default): every example's (flip, min_size) follows from its ticket and goes
+to the transform; on the device path the batch's raw images and masks are then uploaded packed and resized, mirrored where drawn, by
+one launch per tensor (csrc/augment.hip).
 """
 import queue
 import threading
@@ -77,13 +80,33 @@ class _PinnedRing(object):
             out.view(-1).view(torch.uint8).copy_(buf[:n], non_blocking=True)
         return out
 
+    @staticmethod
+    def upload_packed(slot, name, arrays, dev):
+        """The arrays' bytes back to back in one staging buffer and one copy: (1-D uint8 device tensor, byte offset of each array)."""
+        import torch
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        offsets = np.cumsum([0] + [a.nbytes for a in arrays])
+        n = int(offsets[-1])
+        buf = slot['bufs'].get(name)
+        if buf is None or buf.numel() < n:
+            buf = torch.empty((max(n, 1) * 5 // 4,), dtype=torch.uint8).pin_memory()
+            slot['bufs'][name] = buf
+        host = buf.numpy()
+        for a, o in zip(arrays, offsets[:-1]):
+            np.copyto(host[o:o + a.nbytes], a.reshape(-1).view(np.uint8))
+        out = torch.empty((n,), dtype=torch.uint8, device=dev)
+        if n:
+            out.copy_(buf[:n], non_blocking=True)
+        return out, [int(o) for o in offsets[:-1]]
+
 
 class BatchLoader(object):
-    """Endless iterator of device batches.  ``rank``/``world`` shard the (seeded, per-epoch) permutation."""
+    """Endless iterator of device batches.  ``rank``/``world`` shard the (seeded, per-epoch) permutation.  ``augment``: a
+    dataset.augment.Augment; the transform is then called as transform(example, augment.params(rank, ticket))."""
 
     def __init__(self, dataset, transform, batch_size=1, shuffle=True, seed=0, rank=0, world=1, num_workers=4,
-                 prefetch=4, max_gt=None, keypoints=False, device=None, skip_empty=True, start_ticket=0):
-        self.dataset, self.transform = dataset, transform
+                 prefetch=4, max_gt=None, keypoints=False, device=None, skip_empty=True, start_ticket=0, augment=None):
+        self.dataset, self.transform, self.augment = dataset, transform, augment
         self.bs, self.shuffle, self.seed, self.rank, self.world = batch_size, shuffle, seed, rank, world
         self.max_gt, self.keypoints, self.device, self.skip_empty = max_gt, keypoints, device, skip_empty
         self._idx = queue.Queue(maxsize=prefetch * batch_size * 2)
@@ -131,7 +154,10 @@ class BatchLoader(object):
                 while ticket >= self._next_get + self._window and not self._stop:
                     self._cv.wait(0.1)
             try:
-                ex = self.transform(self.dataset[i])
+                if self.augment is None:
+                    ex = self.transform(self.dataset[i])
+                else:
+                    ex = self.transform(self.dataset[i], self.augment.params(self.rank, ticket))
             except Exception as e:                           # surfaced in the consumer thread
                 ex = e
             with self._cv:
@@ -164,7 +190,6 @@ class BatchLoader(object):
         """transform = RawTransform: raw uint8 images / masks are uploaded at their original size and resized on the GPU
         into the padded batch tensors (10x fewer PCIe bytes, no host resize)."""
         import torch
-        from chainer_maskrcnn._hip import lib, check, ptr
         dev = torch.device(self.device)
         exs = [self._next_example() for _ in range(self.bs)]
         N = len(exs)
@@ -180,22 +205,10 @@ class BatchLoader(object):
         slot = self._ring.next_slot()
         with torch.cuda.stream(self._stream):
             st = self._stream.cuda_stream
-            imgs = torch.zeros((N, 3, H, W), dtype=torch.float32, device=dev)
-            extra = (torch.zeros((N, G, exs[0][3].shape[1], 3), dtype=torch.float32, device=dev) if self.keypoints
-                     else torch.zeros((N, G, H, W), dtype=torch.uint8, device=dev))
-            keep = []
-            for i, (img, bbox, label, ext, scale, (oh, ow)) in enumerate(exs):
-                g = min(G, bbox.shape[0])
-                bboxes[i, :g], labels[i, :g], scales[i], sizes[i] = bbox[:g], label[:g], scale, (oh, ow)
-                raw = self._ring.upload(slot, 'img%d' % i, img, dev)
-                check(lib().mrcnn_image_resize_u8_f32(ptr(raw), img.shape[0], img.shape[1], ptr(imgs[i]), oh, ow, H, W, 255.0, st))
-                keep.append(raw)
-                if self.keypoints:
-                    extra[i, :g] = self._ring.upload(slot, 'kp%d' % i, ext[:g], dev)
-                elif g > 0:
-                    m = self._ring.upload(slot, 'mask%d' % i, ext[:g], dev)
-                    check(lib().mrcnn_mask_resize_nearest_u8(ptr(m), g, ext.shape[1], ext.shape[2], ptr(extra[i]), oh, ow, H, W, st))
-                    keep.append(m)
+            if self.augment is not None:
+                imgs, extra, keep = self._resize_packed(exs, slot, G, H, W, dev, bboxes, labels, scales, sizes)
+            else:
+                imgs, extra, keep = self._resize_each(exs, slot, G, H, W, dev, st, bboxes, labels, scales, sizes)
             out = {'imgs': imgs, 'bboxes': self._ring.upload(slot, 'bboxes', bboxes, dev),
                    'labels': self._ring.upload(slot, 'labels', labels, dev),
                    'keypoints' if self.keypoints else 'masks': extra, 'scales': scales, 'sizes': sizes}
@@ -207,6 +220,55 @@ class BatchLoader(object):
             if torch.is_tensor(v):
                 v.record_stream(cur)
         return out
+
+    def _resize_each(self, exs, slot, G, H, W, dev, st, bboxes, labels, scales, sizes):
+        """Unaugmented: one resize launch per image and per image's masks into zeroed batch tensors."""
+        import torch
+        from chainer_maskrcnn._hip import lib, check, ptr
+        N = len(exs)
+        imgs = torch.zeros((N, 3, H, W), dtype=torch.float32, device=dev)
+        extra = (torch.zeros((N, G, exs[0][3].shape[1], 3), dtype=torch.float32, device=dev) if self.keypoints
+                 else torch.zeros((N, G, H, W), dtype=torch.uint8, device=dev))
+        keep = []
+        for i, (img, bbox, label, ext, scale, (oh, ow)) in enumerate(exs):
+            g = min(G, bbox.shape[0])
+            bboxes[i, :g], labels[i, :g], scales[i], sizes[i] = bbox[:g], label[:g], scale, (oh, ow)
+            raw = self._ring.upload(slot, 'img%d' % i, img, dev)
+            check(lib().mrcnn_image_resize_u8_f32(ptr(raw), img.shape[0], img.shape[1], ptr(imgs[i]), oh, ow, H, W, 255.0, st))
+            keep.append(raw)
+            if self.keypoints:
+                extra[i, :g] = self._ring.upload(slot, 'kp%d' % i, ext[:g], dev)
+            elif g > 0:
+                m = self._ring.upload(slot, 'mask%d' % i, ext[:g], dev)
+                check(lib().mrcnn_mask_resize_nearest_u8(ptr(m), g, ext.shape[1], ext.shape[2], ptr(extra[i]), oh, ow, H, W, st))
+                keep.append(m)
+        return imgs, extra, keep
+
+    def _resize_packed(self, exs, slot, G, H, W, dev, bboxes, labels, scales, sizes):
+        """Augmented (RawTransform outputs carry the flip flag as a 7th item): the batch's raw images - and masks - uploaded packed,
+        each tensor written whole, padding included, by one launch of the batched kernels."""
+        import torch
+        from chainer_maskrcnn._hip import ops
+        N = len(exs)
+        gs = [min(G, e[1].shape[0]) for e in exs]
+        for i, (img, bbox, label, ext, scale, (oh, ow), flip) in enumerate(exs):
+            g = gs[i]
+            bboxes[i, :g], labels[i, :g], scales[i], sizes[i] = bbox[:g], label[:g], scale, (oh, ow)
+        raw, offs = self._ring.upload_packed(slot, 'imgs', [e[0] for e in exs], dev)
+        desc = ops.resize_descs([(o, e[0].shape[0], e[0].shape[1], e[5][0], e[5][1], e[6], 0) for o, e in zip(offs, exs)])
+        imgs = ops.image_resize_batch_u8(raw, desc, H, W, 255.0)
+        keep = [raw]
+        if self.keypoints:
+            extra = torch.zeros((N, G, exs[0][3].shape[1], 3), dtype=torch.float32, device=dev)
+            for i, e in enumerate(exs):
+                if gs[i] > 0:
+                    extra[i, :gs[i]] = self._ring.upload(slot, 'kp%d' % i, e[3][:gs[i]], dev)
+        else:
+            m, moffs = self._ring.upload_packed(slot, 'masks', [e[3][:g] for e, g in zip(exs, gs)], dev)
+            mdesc = ops.resize_descs([(o, e[3].shape[1], e[3].shape[2], e[5][0], e[5][1], e[6], g) for o, e, g in zip(moffs, exs, gs)])
+            extra = ops.mask_resize_batch_u8(m, mdesc, G, H, W)
+            keep.append(m)
+        return imgs, extra, keep
 
     def __next__(self):
         if getattr(self.transform, 'out_size', None) is not None and self.device is not None and str(self.device).startswith('cuda'):

@@ -10,6 +10,8 @@ coordinate rules (parity unpinned; the float path is checked against the indepen
 """
 import numpy as np
 
+from chainer_maskrcnn.dataset.augment import flip_bbox, flip_keypoints, hflip
+
 F = np.float32
 
 
@@ -71,15 +73,21 @@ def prepare(img, min_size=600, max_size=1000):
 
 
 class Transform(object):
-    """train.py:21-37.  in: (img, bbox, label, masks list) -> (img, bbox, label, masks (G,oH,oW) uint8, scale)."""
+    """train.py:21-37.  in: (img, bbox, label, masks list) -> (img, bbox, label, masks (G,oH,oW) uint8, scale).
+    aug (dataset.augment.AugmentParams, optional): the example is mirrored first (augment.hflip) when aug.flip, and resized to
+    aug.min_size when that is given."""
 
     def __init__(self, faster_rcnn):
         self.min_size, self.max_size = faster_rcnn.min_size, faster_rcnn.max_size
 
-    def __call__(self, in_data):
+    def __call__(self, in_data, aug=None):
+        min_size = self.min_size
+        if aug is not None:
+            in_data = hflip(in_data) if aug.flip else in_data
+            min_size = aug.min_size or min_size
         img, bbox, label, label_img = in_data
         _, H, W = img.shape
-        img = prepare(img, self.min_size, self.max_size)
+        img = prepare(img, min_size, self.max_size)
         _, o_H, o_W = img.shape
         scale = o_H / H
         bbox = resize_bbox(bbox, (H, W), (o_H, o_W))
@@ -90,15 +98,20 @@ class Transform(object):
 
 
 class KeypointTransform(object):
-    """train_keypoints.py:51-68.  in: (img, bbox, keypoints (G,17,(x,y,v))) -> (img, bbox, label = 0, kp (G,17,(y,x,v)), scale)."""
+    """train_keypoints.py:51-68.  in: (img, bbox, keypoints (G,17,(x,y,v))) -> (img, bbox, label = 0, kp (G,17,(y,x,v)), scale).
+    aug: as Transform; a flip needs aug.keypoint_perm."""
 
     def __init__(self, faster_rcnn):
         self.min_size, self.max_size = faster_rcnn.min_size, faster_rcnn.max_size
 
-    def __call__(self, in_data):
+    def __call__(self, in_data, aug=None):
+        min_size = self.min_size
+        if aug is not None:
+            in_data = hflip(in_data, aug.keypoint_perm) if aug.flip else in_data
+            min_size = aug.min_size or min_size
         img, bbox, keypoints = in_data
         _, H, W = img.shape
-        img = prepare(img, self.min_size, self.max_size)
+        img = prepare(img, min_size, self.max_size)
         _, o_H, o_W = img.shape
         scale = o_H / H
         bbox = resize_bbox(bbox, (H, W), (o_H, o_W))
@@ -112,28 +125,34 @@ class KeypointTransform(object):
 class RawTransform(object):
     """Host half of the device-side Transform: everything except the two resizes, which run on the GPU
     (mrcnn_image_resize_u8_f32 / mrcnn_mask_resize_nearest_u8) on the raw uint8 data.  Returns
-    (img_u8 (H,W,3), bbox, label, masks_u8 (G,H,W) | keypoints, scale, (oH,oW))."""
+    (img_u8 (H,W,3), bbox, label, masks_u8 (G,H,W) | keypoints, scale, (oH,oW)).
+    aug (dataset.augment.AugmentParams, optional): (oH,oW) follow aug.min_size when given; with aug.flip the boxes and keypoints are
+    mirrored here, while the image and masks stay as decoded - they are mirrored by the batched resize kernels, which read the 7th item
+    of the output, the flip flag (returned whenever aug is given)."""
 
     def __init__(self, faster_rcnn, keypoints=False):
         self.min_size, self.max_size, self.keypoints = faster_rcnn.min_size, faster_rcnn.max_size, keypoints
 
-    def out_size(self, H, W):
-        scale = self.min_size / min(H, W)
+    def out_size(self, H, W, min_size=None):
+        scale = (min_size or self.min_size) / min(H, W)
         if scale * max(H, W) > self.max_size:
             scale = self.max_size / max(H, W)
         return int(H * scale), int(W * scale)
 
-    def __call__(self, in_data):
+    def __call__(self, in_data, aug=None):
         img = in_data[0]
         _, H, W = img.shape
-        o_H, o_W = self.out_size(H, W)
+        flip = bool(aug is not None and aug.flip)
+        o_H, o_W = self.out_size(H, W, aug.min_size if aug is not None else None)
         scale = o_H / H
         img_u8 = np.ascontiguousarray(img.transpose(1, 2, 0)).astype(np.uint8)      # decoded JPEGs are integer-valued
-        bbox = resize_bbox(in_data[1], (H, W), (o_H, o_W))
+        bbox = resize_bbox(flip_bbox(in_data[1], W) if flip else in_data[1], (H, W), (o_H, o_W))
+        tail = () if aug is None else (int(flip),)
         if self.keypoints:
-            keypoints = in_data[2].astype(np.float32)
+            keypoints = flip_keypoints(in_data[2], W, aug.keypoint_perm) if flip else in_data[2]
+            keypoints = keypoints.astype(np.float32)
             kp = np.concatenate([keypoints[:, :, [1, 0]] * scale, keypoints[:, :, 2, None]], axis=2)
-            return img_u8, bbox, np.zeros(bbox.shape[0], dtype=np.int32), kp, scale, (o_H, o_W)
+            return (img_u8, bbox, np.zeros(bbox.shape[0], dtype=np.int32), kp, scale, (o_H, o_W)) + tail
         bbox[:, 2:] = np.maximum(bbox[:, 2:], bbox[:, 2:] + 1)
         masks = np.stack([np.asarray(m, np.uint8) for m in in_data[3]]) if len(in_data[3]) else np.zeros((0, H, W), np.uint8)
-        return img_u8, bbox, np.asarray(in_data[2], np.int32), masks, scale, (o_H, o_W)
+        return (img_u8, bbox, np.asarray(in_data[2], np.int32), masks, scale, (o_H, o_W)) + tail

@@ -13,6 +13,7 @@
 // all reductions are two-stage with a fixed summation order (bit-reproducible, no float atomics).
 // Roofline: HBM; algorithmic bytes are stated per kernel.
 #include "common.h"
+#include "resize_common.h"
 
 namespace {
 
@@ -836,18 +837,8 @@ __global__ __launch_bounds__(NT) void k_deconv_merge_bwd_w2(const float *__restr
 // in chainer_maskrcnn/dataset/transforms.py (bit-identical results: same float operations, no contraction):
 //   INTER_LINEAR  fx = (float)((dx + 0.5) * (src/dst) - 0.5), sx = floor(fx), clamped taps; horizontal then vertical
 //   INTER_NEAREST sx = min(floor(dx * (src/dst)), src - 1)
+// The taps (linear_tap, nearest_tap) live in resize_common.h, shared with the batched kernels of augment.hip.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void linear_tap(int d, int dst, int src, int &s0, int &s1, float &a0, float &a1) {
-    const double scale = 1.0 / ((double)dst / (double)src);
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= src - 1) { f = 0.f; s = src - 1; }
-    s0 = s; s1 = min(s + 1, src - 1);
-    a0 = 1.0f - f; a1 = f;
-}
-
 // src (H,W,3) uint8 -> dst[c][y][x] (planes of dst_h x dst_w, written for y < oh, x < ow), values / div
 __global__ __launch_bounds__(NT) void k_image_resize_u8(const uint8_t *__restrict__ src, int H, int W, float *__restrict__ dst,
                                                         int oh, int ow, int dst_h, int dst_w, float div) {
@@ -894,8 +885,8 @@ __global__ __launch_bounds__(NT) void k_mask_resize_nearest_u8(const uint8_t *__
     const int x = (int)(i % ow);
     const int y = (int)((i / ow) % oh);
     const int g = (int)(i / ((size_t)ow * oh));
-    const int sx = min((int)floor((double)x * (1.0 / ((double)ow / (double)W))), W - 1);
-    const int sy = min((int)floor((double)y * (1.0 / ((double)oh / (double)H))), H - 1);
+    const int sx = nearest_tap(x, ow, W);
+    const int sy = nearest_tap(y, oh, H);
     dst[((size_t)g * dst_h + y) * dst_w + x] = src[((size_t)g * H + sy) * W + sx];
 }
 

@@ -698,6 +698,32 @@ int mrcnn_mask_rle_count_u8(const unsigned char *m, int D, int H, int W, void *w
 int mrcnn_mask_rle_write_u8(const unsigned char *m, int D, int H, int W, const void *ws, size_t ws_bytes, const int32_t *offsets,
                             int32_t *counts, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched training resizes with an optional horizontal flip (augment.hip; dataset/loader.py BatchLoader(augment=...)).  The device
+ * side of Transform(hflip(example)) for a whole batch: every raw example of the batch is packed into one uint8 buffer and resized,
+ * mirrored or not, straight into the zero-padded batch tensor in ONE launch per tensor, padding included (no memset).
+ *   desc (N) HOST array, read at the call (passed to the kernel by value): per example
+ *     src_offset  byte offset of the example's source in src (image: (H,W,3) HWC; masks: (count,H,W))
+ *     H, W        source size;  oh, ow  resized size (oh <= dst_h, ow <= dst_w);  flip  0 or 1: source column s is read as W-1-s
+ *     count       masks: instances of the example (<= G; rows [count, G) are written zero); images: ignored
+ *   src_bytes   size of src: every example's source must lie inside it
+ *   image: dst (N,3,dst_h,dst_w) float32, 16-byte aligned: dst[n,c,y,x] = resize_linear(src_n[..., ::-1] if flip else src_n)[c,y,x] / div
+ *          for y < oh, x < ow (the taps of mrcnn_image_resize_u8_f32, bit-identical), 0 elsewhere
+ *   masks: dst (N,G,dst_h,dst_w) uint8, 16-byte aligned: resize_nearest(mask[:, ::-1] if flip else mask) for g < count, y < oh, x < ow
+ *          (the rule of mrcnn_mask_resize_nearest_u8), 0 elsewhere
+ * Errors, before any launch: MRCNN_E_INVALID for N outside 1..MRCNN_RESIZE_BATCH_MAX, bad sizes, a flip other than 0 / 1, a count
+ * outside 0..G, a source outside src_bytes, a NULL desc / dst, a NULL src with a non-empty source, a misaligned dst.
+ * ---------------------------------------------------------------------------------------- */
+#define MRCNN_RESIZE_BATCH_MAX 32
+typedef struct mrcnn_resize_desc {
+    long long src_offset;
+    int H, W, oh, ow, flip, count;
+} mrcnn_resize_desc_t;          /* 32 bytes */
+int mrcnn_image_resize_batch_u8_f32(const unsigned char *src, size_t src_bytes, const mrcnn_resize_desc_t *desc, int N, float *dst,
+                                    int dst_h, int dst_w, float div, void *stream);
+int mrcnn_mask_resize_batch_nearest_u8(const unsigned char *src, size_t src_bytes, const mrcnn_resize_desc_t *desc, int N, int G,
+                                       unsigned char *dst, int dst_h, int dst_w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
+AUGMENT_SEED = 5678                 # seed of the per-example augmentation decisions (dataset/augment.py), recorded in trainer_<it>.pt
+NO_AUGMENT = {'hflip': 0, 'min_sizes': None, 'seed': AUGMENT_SEED}     # what a trainer state without the 'augment' key was trained with
 
 
 def build_parser(keypoints=False):
@@ -80,7 +82,42 @@ def build_parser(keypoints=False):
                         help='metric of --eval-interval: mask_voc = PASCAL VOC mask mAP (mask heads, InstanceSegmentationVOCEvaluator); '
                              'mask_coco = COCO mask and box AP over IoU .50:.95 (mask heads, InstanceSegmentationCOCOEvaluator); '
                              'keypoint_coco = COCO keypoint AP over OKS .50:.95 (keypoint heads, KeypointCOCOEvaluator)')
+    parser.add_argument('--hflip', type=int, default=0, choices=[0, 1],
+                        help='1: mirror each training example with probability 0.5 (images, masks, boxes; keypoints with their left / right '
+                             'channels swapped); --synthetic 0 only')
+    parser.add_argument('--min-sizes', type=int, nargs='+', default=None, metavar='N',
+                        help='scale jitter: each training example\'s short side is drawn uniformly from these sizes (the long side stays '
+                             'capped by the model\'s max_size); --synthetic 0 only.  Default: the model\'s min_size')
     return parser
+
+
+def augment_settings(args):
+    """The augmentation of a run as recorded in trainer_<it>.pt (NO_AUGMENT when off)."""
+    return {'hflip': int(args.hflip), 'min_sizes': [int(s) for s in args.min_sizes] if args.min_sizes else None, 'seed': AUGMENT_SEED}
+
+
+def _check_augment_args(args):
+    if (args.hflip or args.min_sizes) and args.synthetic:
+        raise ValueError('--hflip / --min-sizes augment the dataset loader (--synthetic 0); the synthetic batches (--synthetic 1) are not '
+                         'augmented')
+    if args.min_sizes and any(s <= 0 for s in args.min_sizes):
+        raise ValueError('--min-sizes: every size must be positive, got %s' % args.min_sizes)
+
+
+def _keypoint_flip_perm(args, data):
+    """The flip map of a keypoint dataset: COCO's names from the annotation file's person category (COCO's 17 names when the file has
+    none), the depth dataset's 20 joints.  ValueError when the names do not pair completely."""
+    from chainer_maskrcnn.dataset import augment
+    if args.dataset == 'depth':
+        names = augment.DEPTH_KEYPOINT_NAMES
+    else:
+        names = data.coco.cats.get(1, {}).get('keypoints') or augment.COCO_KEYPOINT_NAMES
+    if len(names) != data.n_keypoints:
+        raise ValueError('--hflip 1: %d keypoint names for %d keypoints' % (len(names), data.n_keypoints))
+    try:
+        return augment.flip_permutation(names)
+    except ValueError as e:
+        raise ValueError('--hflip 1: this keypoint dataset has no complete left / right flip map (%s)' % e)
 
 
 def run(args, keypoints=False):
@@ -101,6 +138,27 @@ def run(args, keypoints=False):
     if args.eval_interval > 0 and world > 1:
         raise ValueError('--eval-interval: evaluation runs in single-process training only; with %d ranks it is not supported '
                          '(the reference\'s multi-GPU branch has no test iterator either, train.py:117-121, and would fail there)' % world)
+    _check_augment_args(args)
+    resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
+    if resume is not None and resume.get('augment', NO_AUGMENT) != augment_settings(args):
+        raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
+                         % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
+    data = None
+    if not args.synthetic:          # the training set (before any device work: a keypoint set's flip map is checked here)
+        from chainer_maskrcnn.dataset.coco_dataset import COCOMaskLoader, COCOKeypointsLoader
+        if keypoints and args.dataset == 'depth':
+            from chainer_maskrcnn.dataset.depth_dataset import DepthDataset
+            data = DepthDataset(path=args.depth_list, root=args.depth_root)
+        elif keypoints:
+            data = COCOKeypointsLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type)
+        else:
+            data = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type,
+                                  category_filter=_read_labels(args.label_file))
+    augment = None
+    if args.hflip or args.min_sizes:
+        from chainer_maskrcnn.dataset.augment import Augment
+        augment = Augment(hflip_prob=0.5 if args.hflip else 0.0, min_sizes=args.min_sizes, seed=AUGMENT_SEED,
+                          keypoint_perm=_keypoint_flip_perm(args, data) if keypoints and args.hflip else None)
     local = int(os.environ.get('LOCAL_RANK', args.gpu))
     ndev = max(1, torch.cuda.device_count())
     lws = int(os.environ.get('LOCAL_WORLD_SIZE', 1))
@@ -157,26 +215,21 @@ def run(args, keypoints=False):
     keys = ('loss', 'rpn_loc_loss', 'rpn_cls_loss', 'roi_loc_loss', 'roi_cls_loss', 'mask_loss')
     acc = {k: 0.0 for k in keys}
     loader = None
-    resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
     if not args.synthetic:          # train.py:111-126: COCOMaskLoader(category_filter=labels, data_type='2017') + Transform
-        from chainer_maskrcnn.dataset.coco_dataset import COCOMaskLoader, COCOKeypointsLoader
         from chainer_maskrcnn.dataset.transforms import RawTransform
         from chainer_maskrcnn.dataset.loader import BatchLoader
         if keypoints and args.dataset == 'depth':       # train_keypoints.py:103-109, 135: DepthDataset -> DepthTransformer -> Transform, on the host
-            from chainer_maskrcnn.dataset.depth_dataset import DepthDataset, DepthTransformer
+            from chainer_maskrcnn.dataset.depth_dataset import DepthTransformer
             from chainer_maskrcnn.dataset.transforms import KeypointTransform
-            data = DepthDataset(path=args.depth_list, root=args.depth_root)
             jitter, kt = DepthTransformer(np.random.RandomState(4321 + rank)), KeypointTransform(faster_rcnn)
-            tf = lambda ex: kt(jitter(ex))
+            tf = lambda ex, aug=None: kt(jitter(ex), aug)
         elif keypoints:
-            data = COCOKeypointsLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type)
             tf = RawTransform(faster_rcnn, keypoints=True)      # host decodes, the GPU resizes (dataset/loader.py)
         else:
-            data = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type, category_filter=labels)
             tf = RawTransform(faster_rcnn)
         loader = BatchLoader(data, tf, batch_size=bs, shuffle=True, seed=1234, rank=rank, world=world,
                              num_workers=args.num_workers, max_gt=args.max_gt or None, keypoints=keypoints, device=dev,
-                             start_ticket=_rank_ticket(resume['loader_ticket'], rank) if resume else 0)
+                             start_ticket=_rank_ticket(resume['loader_ticket'], rank) if resume else 0, augment=augment)
     pool = []
     if loader is None:
         for j in range(8):
@@ -241,8 +294,11 @@ def run(args, keypoints=False):
             tickets = _all_rank_tickets(loader.ticket if loader is not None else 0, world, dev)
             if rank == 0:
                 save_npz(os.path.join(args.out, 'model_%d.npz' % it), faster_rcnn)      # snapshot_object, train.py:134-137
-                torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets},
+                torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets,
+                            'augment': augment_settings(args)},
                            os.path.join(args.out, 'trainer_%d.pt' % it))
+    if loader is not None:
+        loader.close()
     if world > 1:
         torch.distributed.destroy_process_group()
 
@@ -281,6 +337,14 @@ def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
         val = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type, category_filter=labels)
         data = TransformedDataset(val, coco_mask_example, n=args.eval_images or None)
     return InstanceSegmentationVOCEvaluator(data, faster_rcnn, label_names=labels)
+
+
+def _read_labels(label_file):
+    """The category names of --label_file (None when the file does not exist: every category)."""
+    if not os.path.exists(label_file):
+        return None
+    with open(label_file) as f:
+        return f.read().strip().split('\n')
 
 
 def _all_rank_tickets(ticket, world, dev):
