@@ -641,3 +641,122 @@ def mask_rle_encode(masks):
     if D:
         check(lib().mrcnn_mask_rle_write_u8(ptr(m), D, H, W, ptr(ws), nb, ptr(offsets), ptr(counts), stream_ptr()))
     return offsets, counts, area
+
+
+# ---- test-time augmentation (tta.hip) -----------------------------------------------------------------------------------------------------
+# mrcnn_tta_view_t of include/mrcnn_hip.h, one row per view
+TTA_VIEW = np.dtype([('R', '<i4'), ('mirror', '<i4'), ('scale', '<f4')])
+assert TTA_VIEW.itemsize == 12
+TTA_VIEWS_MAX = 8
+CLASS_NMS_WS_MAX = 4096
+
+
+def tta_views(rows):
+    """[(R, mirror, scale)] -> the host view table the TTA calls take."""
+    return np.array([(int(r), int(m), float(s)) for r, m, s in rows], TTA_VIEW)
+
+
+def _dev_ptrs(ts):
+    """A host array of device pointers (NULL for None / empty tensors); kept alive by the caller for the call."""
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])
+
+
+def image_resize_mirror_f32(img, oh, ow, mirror, div=1.0):
+    """img (C,H,W) float32 -> (C,oh,ow): image_resize_f32 of img, or of img.flip(-1) with mirror=1 (same bits), then / div."""
+    _ck(img)
+    C, H, W = img.shape
+    out = _empty((C, oh, ow), img.device)
+    check(lib().mrcnn_image_resize_mirror_f32(ptr(img), C, H, W, ptr(out), oh, ow, oh, ow, int(mirror), float(div), stream_ptr()))
+    return out
+
+
+def tta_detect_decode(rois, box_outs, mirrors, scales, n_class, loc0, mean, std, size):
+    """Per view v: rois[v] (R_v,4), box_outs[v] (R_v,ld), mirror, scale.  Returns the union cls_bbox (R,4), prob (R,n_class), rows in view
+    order: detect_decode of each view with its scale, a mirrored view's boxes mapped back to (y1, W-x2, y2, W-x1).  One launch."""
+    _ck(*rois)
+    _ck(*box_outs)
+    V = len(rois)
+    if not (len(box_outs) == len(mirrors) == len(scales) == V):
+        raise ValueError('tta_detect_decode: %d views of rois against %d / %d / %d' % (V, len(box_outs), len(mirrors), len(scales)))
+    ld = box_outs[0].shape[1]
+    if any(b.dim() != 2 or b.shape[1] != ld or b.shape[0] != r.shape[0] for r, b in zip(rois, box_outs)):
+        raise ValueError('tta_detect_decode: box outputs (R_v, %d) matching the rois expected' % ld)
+    views = tta_views([(r.shape[0], m, s) for r, m, s in zip(rois, mirrors, scales)])
+    R = int(views['R'].sum())
+    dev = rois[0].device
+    cls_bbox, prob = _empty((R, 4), dev), _empty((R, n_class), dev)
+    pr, pb = _dev_ptrs(rois), _dev_ptrs(box_outs)
+    m4 = (ctypes.c_float * 4)(*mean)
+    s4 = (ctypes.c_float * 4)(*std)
+    check(lib().mrcnn_tta_detect_decode_f32(ctypes.cast(pr, ctypes.c_void_p), ctypes.cast(pb, ctypes.c_void_p), views.ctypes.data, V, ld,
+                                            n_class, loc0, ctypes.cast(m4, ctypes.c_void_p), ctypes.cast(s4, ctypes.c_void_p),
+                                            float(size[0]), float(size[1]), ptr(cls_bbox), ptr(prob), stream_ptr()))
+    return cls_bbox, prob
+
+
+def class_nms_ws(cls_bbox, prob, l_begin, l_end, score_thresh, nms_thresh):
+    """class_nms for up to 4096 candidates (the union of the TTA views) -> keep_idx (n_class,R) int32, keep_cnt (n_class,) int32; the
+    same keep lists.  R <= 512 runs class_nms's kernel; above, the sorted candidates and the IoU bitmask live in a workspace of this call."""
+    _ck(cls_bbox, prob)
+    R, n_class = prob.shape
+    keep_idx = torch.full((n_class, max(R, 1)), -1, dtype=i32, device=prob.device)
+    keep_cnt = torch.zeros((n_class,), dtype=i32, device=prob.device)
+    if R > 0:
+        nb = lib().mrcnn_class_nms_workspace_bytes(R, n_class)
+        ws = torch.empty((nb,), dtype=torch.uint8, device=prob.device) if nb else None
+        check(lib().mrcnn_class_nms_ws_f32(ptr(cls_bbox), ptr(prob), R, n_class, l_begin, l_end, float(score_thresh), float(nms_thresh),
+                                           ptr(keep_idx), ptr(keep_cnt), ptr(ws), nb, stream_ptr()))
+    return keep_idx, keep_cnt
+
+
+def tta_mask_merge(mask_logits, mirrors, label):
+    """mask_logits: per view (D,S,S,Cm) NHWC; label (D,) int32.  Returns prob (D,S,S) float32 = the mean over the views, in order, of
+    sigmoid(logit) of channel label[d], read at column S-1-x in a mirrored view."""
+    _ck(*mask_logits)
+    _ck(label)
+    V = len(mask_logits)
+    if len(mirrors) != V:
+        raise ValueError('tta_mask_merge: %d views of logits against %d mirror flags' % (V, len(mirrors)))
+    shape = tuple(mask_logits[0].shape)
+    if len(shape) != 4 or shape[1] != shape[2] or any(tuple(m.shape) != shape for m in mask_logits):
+        raise ValueError('tta_mask_merge: (D,S,S,Cm) logits of one shape expected, got %s' % [tuple(m.shape) for m in mask_logits])
+    D, S, _, Cm = shape
+    views = tta_views([(0, m, 1.0) for m in mirrors])
+    out = _empty((D, S, S), label.device)
+    p = _dev_ptrs(mask_logits)
+    check(lib().mrcnn_tta_mask_merge_f32(ctypes.cast(p, ctypes.c_void_p), views.ctypes.data, V, D, S, Cm, ptr(label), ptr(out),
+                                         stream_ptr()))
+    return out
+
+
+def mask_paste_prob(prob, bbox, size):
+    """prob (D,S,S) float32, bbox (D,4) -> (D,H,W) uint8: mask_paste's resize, threshold and paste rule from probabilities."""
+    _ck(prob, bbox)
+    D, S = prob.shape[0], prob.shape[1]
+    out = torch.empty((D, size[0], size[1]), dtype=torch.uint8, device=prob.device)
+    check(lib().mrcnn_mask_paste_prob_f32(ptr(prob), D, S, ptr(bbox), size[0], size[1], ptr(out), stream_ptr()))
+    return out
+
+
+def tta_keypoint_merge(heat, mirrors, K, perm=None):
+    """heat: per view (D,S,S,Cp) NHWC heat maps.  Returns (D,S,S,Cp) float32 = the mean over the views, in order, of heat[u][d, y, x_u, k_u]:
+    x_u = S-1-x and k_u = perm[k] (k < K) in a mirrored view.  perm: K ints, needed when a view is mirrored."""
+    _ck(*heat)
+    V = len(heat)
+    if len(mirrors) != V:
+        raise ValueError('tta_keypoint_merge: %d views of heat maps against %d mirror flags' % (V, len(mirrors)))
+    shape = tuple(heat[0].shape)
+    if len(shape) != 4 or shape[1] != shape[2] or any(tuple(h.shape) != shape for h in heat):
+        raise ValueError('tta_keypoint_merge: (D,S,S,Cp) heat maps of one shape expected, got %s' % [tuple(h.shape) for h in heat])
+    D, S, _, Cp = shape
+    views = tta_views([(0, m, 1.0) for m in mirrors])
+    pa = None
+    if perm is not None:
+        pa = np.ascontiguousarray(perm, np.int32)
+        if pa.shape != (K,):
+            raise ValueError('tta_keypoint_merge: a permutation of %d channels expected, got %d' % (K, pa.size))
+    out = _empty(shape, heat[0].device)
+    p = _dev_ptrs(heat)
+    check(lib().mrcnn_tta_keypoint_merge_f32(ctypes.cast(p, ctypes.c_void_p), views.ctypes.data, V, D, S, Cp, K,
+                                             pa.ctypes.data if pa is not None else None, ptr(out), stream_ptr()))
+    return out

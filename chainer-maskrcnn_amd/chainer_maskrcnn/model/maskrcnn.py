@@ -87,6 +87,7 @@ class MaskRCNN(object):
         self.loc_normalize_std = (0.1, 0.1, 0.2, 0.2)
         self.use_preset('visualize')
         self.train = True
+        self.tta = None                 # test-time augmentation, off (use_test_augmentation)
         self.device = torch.device(device)
         self.ps.materialise(self.device, seed)
 
@@ -101,6 +102,50 @@ class MaskRCNN(object):
             self.nms_thresh, self.score_thresh = 0.3, 0.05
         else:
             raise ValueError('preset must be visualize or evaluate')
+
+    def use_test_augmentation(self, sizes, hflip=False, max_size=None, keypoint_flip_perm=None):
+        """Test-time augmentation of ``predict`` / ``predict_keypoints`` (Detectron's TEST.BBOX_AUG / MASK_AUG / KPS_AUG; DESIGN.md
+        §3.12): every image runs as the views (s, mirror=False) then, with hflip, (s, mirror=True) for each short side s of ``sizes``, the long
+        side capped by ``max_size`` (default: the model's); the union of the views' box candidates is suppressed together, the mask
+        probabilities and the keypoint heat maps (left / right channels swapped by ``keypoint_flip_perm`` in a mirrored view) are averaged
+        over the views.  ``sizes=None`` turns it off (the initial state)."""
+        if sizes is None:
+            self.tta = None
+            return
+        sizes = [int(s) for s in sizes]
+        if not sizes or any(s <= 0 for s in sizes):
+            raise ValueError('use_test_augmentation: sizes must be positive, got %r' % (sizes,))
+        if len(set(sizes)) != len(sizes):
+            raise ValueError('use_test_augmentation: duplicate sizes in %r' % (sizes,))
+        if max_size is not None and int(max_size) <= 0:
+            raise ValueError('use_test_augmentation: max_size must be positive, got %r' % (max_size,))
+        n_views = len(sizes) * (2 if hflip else 1)
+        if n_views > ops.TTA_VIEWS_MAX:
+            raise ValueError('use_test_augmentation: %d views, at most %d' % (n_views, ops.TTA_VIEWS_MAX))
+        perm = None
+        if self.head_arch == 'fpn_keypoint':
+            if hflip and keypoint_flip_perm is None:
+                raise ValueError('use_test_augmentation: hflip on a keypoint model needs keypoint_flip_perm (coordinates are never mirrored '
+                                 'without swapping the left / right channels)')
+            if keypoint_flip_perm is not None:
+                perm = [int(k) for k in keypoint_flip_perm]
+                if sorted(perm) != list(range(self.head.n_keypoints)):
+                    raise ValueError('use_test_augmentation: keypoint_flip_perm is not a permutation of the %d keypoints'
+                                     % self.head.n_keypoints)
+        self.tta = {'sizes': sizes, 'hflip': bool(hflip), 'max_size': None if max_size is None else int(max_size),
+                    'keypoint_flip_perm': perm}
+
+    def test_views(self, H, W):
+        """The test-time views of an H x W image: [(oh, ow, mirror)] in view order (``prepare_size``'s rule with min_size = s)."""
+        t = self.tta
+        max_size = t['max_size'] or self.max_size
+        views = []
+        for s in t['sizes']:
+            oh, ow = scaled_size(H, W, s, max_size)
+            views.append((oh, ow, False))
+            if t['hflip']:
+                views.append((oh, ow, True))
+        return views
 
     def to_nhwc4(self, x):
         """(N,3,H,W) float32 images on the device -> the extractor's (N,H,W,4) operand."""
@@ -157,6 +202,20 @@ class MaskRCNN(object):
         self.train, core.TRAIN = False, False
         try:
             for img in imgs:
+                if getattr(self, 'tta', None) is not None:
+                    size, bbox, label, score, level, view, views = self._detect_tta(img)
+                    D = bbox.shape[0]
+                    if D > 0 and self.predict_mask:
+                        m = self._branch_per_view(bbox, level, view, views, size[1])
+                        p = ops.tta_mask_merge(m, [v[2] for v in views], label.contiguous())
+                        mask = ops.mask_paste_prob(p, bbox.contiguous(), size).bool()
+                    else:
+                        mask = torch.zeros((D,) + size, dtype=torch.bool, device=self.device)
+                    masks.append(mask)
+                    labels.append(label)
+                    scores.append(score)
+                    bboxes.append(bbox)
+                    continue
                 size, scale, bbox, label, score, level = self._detect(img)
                 D = bbox.shape[0]
                 if D > 0 and self.predict_mask:
@@ -189,6 +248,43 @@ class MaskRCNN(object):
         bbox, label, score, level = self._suppress(cls_bbox, prob, levels)
         return size, scale, bbox, label, score, level
 
+    def _detect_tta(self, img):
+        """``_detect`` over the test-time views: per view the mirrored / resized image and its own N = 1 forward (features kept), then ONE
+        decode of all views' candidates (mirrored boxes mapped back) and the class NMS over their union.  Returns (size, bbox, label, score,
+        level, view, views): level / view = the proposal level and the view of each kept detection; views = [(features, scale, mirror)]."""
+        size = tuple(img.shape[1:])
+        H, W = size
+        src = img.to(self.device, torch.float32).contiguous()
+        views, rois_v, box_v, level_v = [], [], [], []
+        for oh, ow, mirror in self.test_views(H, W):
+            x = ops.image_resize_mirror_f32(src, oh, ow, int(mirror), 255.0)
+            scale = x.shape[2] / W
+            _, _, rois, _, levels = self.__call__(x[None].contiguous(), scale=scale)
+            views.append((self.head.x, scale, mirror))
+            rois_v.append(rois.contiguous())
+            box_v.append(self.head.last_box_out)
+            level_v.append(levels)
+        cls_bbox, prob = ops.tta_detect_decode(rois_v, box_v, [v[2] for v in views], [v[1] for v in views], self.n_class, self.head.LOC0,
+                                               self.loc_normalize_mean, self.loc_normalize_std, size)
+        self.last_rois, self.last_decoded = rois_v, (cls_bbox, prob)
+        view = torch.cat([torch.full((r.shape[0],), v, dtype=torch.int32, device=self.device) for v, r in enumerate(rois_v)])
+        bbox, label, score, level, view = self._suppress(cls_bbox, prob, torch.cat(level_v), view=view)
+        return size, bbox, label, score, level, view, views
+
+    def _branch_per_view(self, bbox, level, view, views, W):
+        """The mask / keypoint branch of every view on the final boxes bbox (D,4) (original image): mirrored into a mirrored view, scaled
+        by the view's scale; a detection keeps its proposal's level in its own view and takes map_rois_to_fpn_levels of the box in every
+        other view.  Returns the per-view branch outputs (D,S,S,C)."""
+        D = bbox.shape[0]
+        out = []
+        for u, (feats, scale, mirror) in enumerate(views):
+            b = torch.stack((bbox[:, 0], W - bbox[:, 3], bbox[:, 2], W - bbox[:, 1]), dim=1) if mirror else bbox
+            b = b * scale
+            lv = torch.where(view == u, level, ops.map_rois_to_fpn_levels(b.contiguous()).clamp(0, len(feats) - 1))
+            xy5 = torch.cat((torch.zeros((D, 1), device=self.device), b[:, [1, 0, 3, 2]]), dim=1).contiguous()
+            out.append(self.head.mask_branch(feats, xy5, lv.to(torch.int32).contiguous(), self.extractor.spatial_scales))
+        return out
+
     def predict_keypoints(self, imgs, return_heatmaps=False):
         """Keypoint R-CNN inference (head_arch 'fpn_keypoint'): the detections of ``predict`` (same prepare / forward / decode /
         NMS, boxes kept in ``self.last_bboxes``), then the keypoint branch on the kept boxes and ``mrcnn_keypoint_decode_f32``.
@@ -206,9 +302,20 @@ class MaskRCNN(object):
         self.train, core.TRAIN = False, False
         try:
             for img in imgs:
-                size, scale, bbox, label, score, level = self._detect(img)
+                tta = getattr(self, 'tta', None) is not None
+                if tta:
+                    size, bbox, label, score, level, view, views = self._detect_tta(img)
+                else:
+                    size, scale, bbox, label, score, level = self._detect(img)
                 D = bbox.shape[0]
-                if D > 0:
+                if D > 0 and tta:
+                    bbox = bbox.contiguous()
+                    hv = self._branch_per_view(bbox, level, view, views, size[1])
+                    m = ops.tta_keypoint_merge(hv, [v[2] for v in views], K, self.tta['keypoint_flip_perm'])
+                    kp = ops.keypoint_decode(m, bbox, K)
+                    if return_heatmaps:
+                        heatmaps.append(m[..., :K].permute(0, 3, 1, 2).reshape(D, K, S * S))
+                elif D > 0:
                     bbox = bbox.contiguous()
                     xy5 = torch.cat((torch.zeros((D, 1), device=self.device), bbox[:, [1, 0, 3, 2]] * scale), dim=1).contiguous()
                     m = self.head.mask_branch(self.head.x, xy5, level.to(torch.int32).contiguous(), self.extractor.spatial_scales)
@@ -230,12 +337,14 @@ class MaskRCNN(object):
             return keypoints, labels, scores, heatmaps
         return keypoints, labels, scores
 
-    def _suppress(self, cls_bbox, prob, levels):
+    def _suppress(self, cls_bbox, prob, levels, view=None):
         """maskrcnn.py:278-312 on the device: for every foreground class l (skipping the LAST class when masks are
         predicted - the reference's off-by-one guard, :288-291): prob[:, l] > score_thresh, NMS(nms_thresh) in
-        descending score order; results concatenated over classes, labels l-1."""
+        descending score order; results concatenated over classes, labels l-1.  With ``view`` (the test-time views' union, up to 4096
+        candidates) the selection runs through class_nms_ws and the kept rows of ``view`` are returned last."""
         l_end = self.n_class - 1 if self.predict_mask else self.n_class
-        keep_idx, keep_cnt = ops.class_nms(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
+        nms = ops.class_nms if view is None else ops.class_nms_ws
+        keep_idx, keep_cnt = nms(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
         cnt = keep_cnt.cpu().tolist()                   # the one host sync of predict()
         sel, lab = [], []
         for l in range(1, l_end):
@@ -244,14 +353,21 @@ class MaskRCNN(object):
                 lab.append(torch.full((cnt[l],), l - 1, dtype=torch.int32, device=prob.device))
         if not sel:
             z = torch.zeros((0,), dtype=torch.long, device=prob.device)
-            return cls_bbox[z], z.to(torch.int32), prob[z, 0], levels[z]
+            out = (cls_bbox[z], z.to(torch.int32), prob[z, 0], levels[z])
+            return out if view is None else out + (view[z],)
         sel = torch.cat(sel).long()
         lab = torch.cat(lab)
-        return cls_bbox[sel], lab, prob[sel, (lab + 1).long()], levels[sel]
+        out = (cls_bbox[sel], lab, prob[sel, (lab + 1).long()], levels[sel])
+        return out if view is None else out + (view[sel],)
 
     def prepare_size(self, H, W):
         """Scaled size of maskrcnn.py:261-271 (min side -> min_size unless the max side would exceed max_size)."""
-        scale = self.min_size / min(H, W)
-        if scale * max(H, W) > self.max_size:
-            scale = self.max_size / max(H, W)
-        return int(H * scale), int(W * scale)
+        return scaled_size(H, W, self.min_size, self.max_size)
+
+
+def scaled_size(H, W, min_size, max_size):
+    """maskrcnn.py:261-271: the size of an H x W image whose short side goes to min_size unless the long side would exceed max_size."""
+    scale = min_size / min(H, W)
+    if scale * max(H, W) > max_size:
+        scale = max_size / max(H, W)
+    return int(H * scale), int(W * scale)

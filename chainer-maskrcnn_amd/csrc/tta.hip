@@ -1,0 +1,466 @@
+// Test-time augmentation (TTA) post-processing for gfx950 (MaskRCNN.use_test_augmentation): every image runs at
+// several short sides, optionally mirrored, one N = 1 forward per view; the kernels here merge the views after the forward pass.
+//   mirrored resize        the taps of resize_common.h; a mirrored view reads source column s as W-1-s (= resizing img[..., ::-1])
+//   multi-view decode      k_detect_decode's arithmetic per view (scale_v), mirrored views mapped back to (y1, W-x2, y2, W-x1)
+//   union class NMS        R <= 4096 candidates: per class an LDS bitonic sort, an IoU bitmask in the caller's workspace, a one-wave sweep
+//   mask merge + paste     mean over the views of sigmoid(logit) at the mirrored column, then k_mask_paste's resize / threshold rule
+//   keypoint merge         mean over the views of the heat maps, mirrored column and left / right channels swapped
+// Float arithmetic restates predict.hip operation for operation (FP contraction off), so one unmirrored view gives predict()'s bits.
+#include "common.h"
+#include "resize_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int NT = 256;
+constexpr int UNION_MAX = MRCNN_CLASS_NMS_WS_MAX;
+constexpr int LDS_NMS_CAP = 512;               // mrcnn_class_nms_f32's CN_CAP (predict.hip)
+
+// ---- mirrored float32 resize (k_image_resize_f32 of nn.hip with the mirrored source column) -------------------------------------------
+__global__ __launch_bounds__(NT) void k_image_resize_mirror_f32(const float *__restrict__ src, int C, int H, int W, float *__restrict__ dst,
+                                                                int oh, int ow, int dst_h, int dst_w, int mirror, float div) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= oh * ow) return;
+    const int y = i / ow, x = i - y * ow;
+    int x0, x1, y0, y1;
+    float a0, a1, b0, b1;
+    linear_tap(x, ow, W, x0, x1, a0, a1);
+    linear_tap(y, oh, H, y0, y1, b0, b1);
+    if (mirror) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
+    for (int c = 0; c < C; ++c) {
+        const float *r0 = src + ((size_t)c * H + y0) * W, *r1 = src + ((size_t)c * H + y1) * W;
+        const float top = r0[x0] * a0 + r0[x1] * a1;
+        const float bot = r1[x0] * a0 + r1[x1] * a1;
+        dst[((size_t)c * dst_h + y) * dst_w + x] = (top * b0 + bot * b1) / div;
+    }
+}
+
+// ---- multi-view decode ------------------------------------------------------------------------------------------------------------------
+struct DecodeViews {
+    const float *rois[MRCNN_TTA_VIEWS_MAX];
+    const float *box[MRCNN_TTA_VIEWS_MAX];
+    int off[MRCNN_TTA_VIEWS_MAX + 1];            // first union row of each view; off[V] = R
+    int mirror[MRCNN_TTA_VIEWS_MAX];
+    float scale[MRCNN_TTA_VIEWS_MAX];
+};
+
+// One thread per union row: the arithmetic of k_detect_decode (predict.hip) with the row's view's scale, then the mirror back.
+__global__ __launch_bounds__(NT) void k_tta_detect_decode(const DecodeViews vs, int V, int ld, int n_class, int loc0, float4 mean, float4 stdv,
+                                                          float size_h, float size_w, float *__restrict__ cls_bbox, float *__restrict__ prob) {
+    const int g = blockIdx.x * NT + threadIdx.x;
+    if (g >= vs.off[V]) return;
+    int v = 0;
+    while (g >= vs.off[v + 1]) ++v;
+    const int i = g - vs.off[v];
+    const float scale = vs.scale[v];
+    const float4 rr = *reinterpret_cast<const float4 *>(vs.rois[v] + (size_t)i * 4);
+    const float4 r = make_float4(rr.x / scale, rr.y / scale, rr.z / scale, rr.w / scale);
+    const float *o = vs.box[v] + (size_t)i * ld;
+    const float dy = o[loc0] * stdv.x + mean.x, dx = o[loc0 + 1] * stdv.y + mean.y;
+    const float dh = o[loc0 + 2] * stdv.z + mean.z, dw = o[loc0 + 3] * stdv.w + mean.w;
+    const float h = r.z - r.x, w = r.w - r.y;
+    const float cy = r.x + 0.5f * h, cx = r.y + 0.5f * w;
+    const float ncy = dy * h + cy, ncx = dx * w + cx;
+    const float nh = expf(dh) * h, nw = expf(dw) * w;
+    float y1 = ncy - 0.5f * nh, x1 = ncx - 0.5f * nw, y2 = ncy + 0.5f * nh, x2 = ncx + 0.5f * nw;
+    y1 = fmaxf(fminf(y1, size_h), 0.f); y2 = fmaxf(fminf(y2, size_h), 0.f);
+    x1 = fmaxf(fminf(x1, size_w), 0.f); x2 = fmaxf(fminf(x2, size_w), 0.f);
+    if (vs.mirror[v]) {
+        const float m1 = size_w - x2, m2 = size_w - x1;
+        x1 = m1; x2 = m2;
+    }
+    *reinterpret_cast<float4 *>(cls_bbox + (size_t)g * 4) = make_float4(y1, x1, y2, x2);
+    float m = -INFINITY;
+    for (int c = 0; c < n_class; ++c) m = fmaxf(m, o[c]);
+    float s = 0.f;
+    for (int c = 0; c < n_class; ++c) s += expf(o[c] - m);
+    for (int c = 0; c < n_class; ++c) prob[(size_t)g * n_class + c] = expf(o[c] - m) / s;
+}
+
+// ---- union class NMS (R <= 4096) --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned orderable(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+struct UnionLayout {
+    size_t sboxes, sidx, n_valid, mask, total;
+    int nblk;
+};
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+UnionLayout union_layout(int R, int n_class) {
+    UnionLayout L;
+    L.nblk = (R + 63) / 64;
+    size_t o = 0;
+    L.sboxes = o;  o = al256(o + (size_t)n_class * R * 16);
+    L.sidx = o;    o = al256(o + (size_t)n_class * R * 4);
+    L.n_valid = o; o = al256(o + (size_t)n_class * 4);
+    L.mask = o;    o = al256(o + (size_t)n_class * R * L.nblk * 8);
+    L.total = o;
+    return L;
+}
+
+// One workgroup per class l: the keys of k_class_nms (prob > thresh; score descending, then index descending) bitonic-sorted in LDS over
+// P = pow2 >= R; the n candidates' boxes and indices in sort order go to the workspace.  Slot s = l - l_begin.
+constexpr int SORT_T = 1024;
+__global__ __launch_bounds__(SORT_T) void k_union_sort(const float *__restrict__ cls_bbox, const float *__restrict__ prob, int R, int P,
+                                                      int n_class, int l_begin, float score_thresh, float4 *__restrict__ sboxes,
+                                                      int32_t *__restrict__ sidx, int32_t *__restrict__ n_valid) {
+    __shared__ u64 skey[UNION_MAX];
+    __shared__ int s_n;
+    const int s = blockIdx.x, l = l_begin + s, tid = threadIdx.x;
+    if (tid == 0) s_n = 0;
+    int mine = 0;
+    for (int i = tid; i < P; i += SORT_T) {
+        u64 k = 0ull;
+        if (i < R) {
+            const float p = prob[(size_t)i * n_class + l];
+            if (p > score_thresh) { k = (1ull << 63) | ((u64)orderable(p) << 31) | (u64)i; ++mine; }
+        }
+        skey[i] = k;
+    }
+    __syncthreads();
+    if (mine) atomicAdd(&s_n, mine);
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += SORT_T) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const u64 a = skey[i], b = skey[ixj];
+                    const bool up = (i & k) == 0;
+                    if ((a < b) == up) { skey[i] = b; skey[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    const int n = s_n;
+    for (int i = tid; i < n; i += SORT_T) {
+        const int idx = (int)(skey[i] & 0x7FFFFFFFull);
+        sboxes[(size_t)s * R + i] = *reinterpret_cast<const float4 *>(cls_bbox + (size_t)idx * 4);
+        sidx[(size_t)s * R + i] = idx;
+    }
+    if (tid == 0) n_valid[s] = n;
+}
+
+// mask[(s*R + i)*nblk + cb] bit j: sorted box i suppresses sorted box cb*64+j (> i), IoU >= thresh decided as k_class_nms does
+// (ai / u >= thresh, correctly rounded).  Grid (nblk, cdiv(nblk, 4), classes), 4 waves = 4 row blocks; only words cb >= rb are written,
+// the only ones the sweep reads.
+__global__ __launch_bounds__(256) void k_union_mask(const float4 *__restrict__ sboxes, const int32_t *__restrict__ n_valid, int R, int nblk,
+                                                    float thresh, u64 *__restrict__ mask) {
+    const int s = blockIdx.z, cb = blockIdx.x;
+    const int n = n_valid[s];
+    if (cb * 64 >= n || blockIdx.y * 256 >= n || (int)blockIdx.y * 4 > cb) return;
+    __shared__ float4 cbox[64];
+    const float4 *bx = sboxes + (size_t)s * R;
+    const int lane = threadIdx.x & 63, rb = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (threadIdx.x < 64) {
+        const int cj = cb * 64 + lane;
+        cbox[lane] = cj < n ? bx[cj] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    const int i = rb * 64 + lane;
+    if (rb > cb || i >= n) return;
+    const float4 b = bx[i];
+    const float area_i = (b.z - b.x) * (b.w - b.y);
+    u64 bits = 0ull;
+    const int jmax = min(64, n - cb * 64);
+    for (int j = 0; j < jmax; ++j) {
+        const float4 c = cbox[j];
+        const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y), bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
+        const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
+        const float ai = hgt * wid;
+        const float iou = ai / ((area_i + (c.z - c.x) * (c.w - c.y)) - ai);
+        if (iou >= thresh && cb * 64 + j > i) bits |= 1ull << j;
+    }
+    mask[((size_t)s * R + i) * nblk + cb] = bits;
+}
+
+// One wave per class: the greedy sweep over the sorted candidates, 64 at a time.  Lane w holds word w of the removed set (nblk <= 64).
+// Inside a chunk only boxes whose diagonal word is non-zero can remove a later box of the chunk; they are visited in order.  The kept
+// boxes' rows then go into the later words, 8 independent loads at a time.
+__global__ __launch_bounds__(64) void k_union_sweep(const u64 *__restrict__ mask, const int32_t *__restrict__ sidx,
+                                                    const int32_t *__restrict__ n_valid, int R, int nblk, int l_begin,
+                                                    int32_t *__restrict__ keep_idx, int32_t *__restrict__ keep_cnt) {
+    const int s = blockIdx.x, l = l_begin + s, lane = threadIdx.x;
+    const int n = n_valid[s];
+    const int nb = (n + 63) / 64;
+    const u64 *mk = mask + (size_t)s * R * nblk;
+    const int32_t *si = sidx + (size_t)s * R;
+    int32_t *kp = keep_idx + (size_t)l * R;
+    u64 rem = 0ull;
+    int cnt = 0;
+    for (int c = 0; c < nb; ++c) {
+        const int box = c * 64 + lane;
+        const u64 diag = box < n ? mk[(size_t)box * nblk + c] : 0ull;
+        const u64 remc = __shfl(rem, c, 64);
+        u64 alive = ~remc;
+        const int m = min(64, n - c * 64);
+        if (m < 64) alive &= (1ull << m) - 1ull;
+        u64 pend = alive & __ballot(diag != 0ull);
+        while (pend) {
+            const int b = __builtin_ctzll(pend);
+            const u64 Db = __shfl(diag, b, 64);
+            alive &= ~Db;
+            pend &= ~Db;
+            pend &= ~(1ull << b);
+        }
+        if ((alive >> lane) & 1ull) kp[cnt + __popcll(alive & ((1ull << lane) - 1ull))] = si[box];
+        cnt += __popcll(alive);
+        if (c + 1 < nb) {
+            const bool mine = lane > c && lane < nb;
+            u64 acc = 0ull, left = alive;
+            while (left) {
+                int bs[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    bs[q] = left ? __builtin_ctzll(left) : -1;
+                    if (left) left &= left - 1ull;
+                }
+                u64 v[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) v[q] = (mine && bs[q] >= 0) ? mk[(size_t)(c * 64 + bs[q]) * nblk + lane] : 0ull;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc |= v[q];
+            }
+            rem |= acc;
+        }
+    }
+    if (lane == 0) keep_cnt[l] = cnt;
+}
+
+// ---- mask merge + paste -----------------------------------------------------------------------------------------------------------------
+struct MergeViews {
+    const float *src[MRCNN_TTA_VIEWS_MAX];
+    int mirror[MRCNN_TTA_VIEWS_MAX];
+};
+
+// prob[d, y, x] = (sum over views u, in order, of sigmoid(logits_u[d, y, x_u, label[d]])) / V; x_u = S-1-x for a mirrored view.
+__global__ __launch_bounds__(NT) void k_tta_mask_merge(const MergeViews vs, int V, int D, int S, int Cm, const int32_t *__restrict__ label,
+                                                       float *__restrict__ prob) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= D * S * S) return;
+    const int d = i / (S * S), yx = i - d * S * S, y = yx / S, x = yx - y * S;
+    const int ch = label[d];
+    float acc = 0.f;
+    for (int u = 0; u < V; ++u) {
+        const int xu = vs.mirror[u] ? S - 1 - x : x;
+        const float z = vs.src[u][(((size_t)d * S + y) * S + xu) * Cm + ch];
+        const float p = 1.0f / (1.0f + expf(-z));
+        acc = u == 0 ? p : acc + p;
+    }
+    prob[i] = acc / (float)V;
+}
+
+// k_mask_paste (predict.hip) reading the probabilities instead of sigmoid(logit)
+__global__ __launch_bounds__(256) void k_mask_paste_prob(const float *__restrict__ prob, int S, const float *__restrict__ bbox, int H, int W,
+                                                         unsigned char *__restrict__ out) {
+    const int d = blockIdx.y;
+    const float4 b = *reinterpret_cast<const float4 *>(bbox + (size_t)d * 4);
+    const int mw = (int)(b.w - b.y), mh = (int)(b.z - b.x);
+    const int s0 = (int)b.x, t0 = (int)b.y;
+    unsigned char *o = out + (size_t)d * H * W;
+    const float *pr = prob + (size_t)d * S * S;
+    const double sy = mh > 0 ? 1.0 / ((double)mh / (double)S) : 0.0, sx = mw > 0 ? 1.0 / ((double)mw / (double)S) : 0.0;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < H * W; p += gridDim.x * 256) {
+        const int y = p / W, x = p % W;
+        const int dy = y - s0, dx = x - t0;
+        unsigned char v = 0;
+        if (dy >= 0 && dy < mh && dx >= 0 && dx < mw) {
+            float fy = (float)(((double)dy + 0.5) * sy - 0.5), fx = (float)(((double)dx + 0.5) * sx - 0.5);
+            int iy = (int)floorf(fy), ix = (int)floorf(fx);
+            fy -= (float)iy; fx -= (float)ix;
+            if (iy < 0) { fy = 0.f; iy = 0; }
+            if (iy >= S - 1) { fy = 0.f; iy = S - 1; }
+            if (ix < 0) { fx = 0.f; ix = 0; }
+            if (ix >= S - 1) { fx = 0.f; ix = S - 1; }
+            const int iy1 = min(iy + 1, S - 1), ix1 = min(ix + 1, S - 1);
+            auto pv = [&](int yy, int xx) { return pr[(size_t)yy * S + xx]; };
+            const float r0 = pv(iy, ix) * (1.0f - fx) + pv(iy, ix1) * fx;
+            const float r1 = pv(iy1, ix) * (1.0f - fx) + pv(iy1, ix1) * fx;
+            const float m = r0 * (1.0f - fy) + r1 * fy;
+            const int q = (int)(m * 255.0f);
+            v = (unsigned char)((q & 0xFF) > 127 ? 1 : 0);
+        }
+        o[p] = v;
+    }
+}
+
+// ---- keypoint heat-map merge ------------------------------------------------------------------------------------------------------------
+struct KpViews {
+    const float *src[MRCNN_TTA_VIEWS_MAX];
+    int mirror[MRCNN_TTA_VIEWS_MAX];
+    unsigned char perm[MRCNN_TTA_KEYPOINTS_MAX];
+};
+
+// out[d, y, x, k] = (sum over views u, in order, of heat_u[d, y, x_u, k_u]) / V; mirrored view: x_u = S-1-x, k_u = perm[k] for k < K.
+__global__ __launch_bounds__(NT) void k_tta_keypoint_merge(const KpViews vs, int V, int D, int S, int Cp, int K, float *__restrict__ out) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= D * S * S * Cp) return;
+    const int k = i % Cp, pix = i / Cp;
+    const int x = pix % S;
+    const size_t row = (size_t)(pix - x);                // (d * S + y) * S
+    float acc = 0.f;
+    for (int u = 0; u < V; ++u) {
+        const bool mr = vs.mirror[u] != 0;
+        const int xu = mr ? S - 1 - x : x;
+        const int ku = (mr && k < K) ? (int)vs.perm[k] : k;
+        const float h = vs.src[u][(row + xu) * Cp + ku];
+        acc = u == 0 ? h : acc + h;
+    }
+    out[i] = acc / (float)V;
+}
+
+int check_views(const char *who, const mrcnn_tta_view_t *views, int V) {
+    if (!views) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: null view table", who);
+    if (V < 1 || V > MRCNN_TTA_VIEWS_MAX) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: V = %d outside 1..%d", who, V, MRCNN_TTA_VIEWS_MAX);
+    for (int v = 0; v < V; ++v)
+        if (views[v].mirror != 0 && views[v].mirror != 1)
+            return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: view %d has mirror %d (0 or 1 expected)", who, v, views[v].mirror);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mrcnn_image_resize_mirror_f32(const float *src, int C, int H, int W, float *dst, int oh, int ow, int dst_h, int dst_w,
+                                             int mirror, float div, void *stream) {
+    if (!src || !dst) return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: null pointer");
+    if (C <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0 || dst_h < oh || dst_w < ow || (long long)oh * ow > 0x7FFFFFFFLL)
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: bad sizes");
+    if (mirror != 0 && mirror != 1) return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: mirror %d (0 or 1 expected)", mirror);
+    hipLaunchKernelGGL(k_image_resize_mirror_f32, dim3(mrcnn::cdiv((long long)oh * ow, NT)), dim3(NT), 0, (hipStream_t)stream, src, C, H, W,
+                       dst, oh, ow, dst_h, dst_w, mirror, div);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrcnn_tta_detect_decode_f32(const float *const *rois, const float *const *box_out, const mrcnn_tta_view_t *views, int V,
+                                           int ld, int n_class, int loc0, const float *loc_mean4, const float *loc_std4, float size_h,
+                                           float size_w, float *cls_bbox, float *prob, void *stream) {
+    if (int e = check_views("tta_detect_decode", views, V)) return e;
+    if (!rois || !box_out || !loc_mean4 || !loc_std4 || n_class <= 0 || loc0 < 0 || ld < loc0 + 4 || ld < n_class || !(size_h > 0.f) ||
+        !(size_w > 0.f))
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_detect_decode: bad arguments");
+    DecodeViews vs = {};
+    long long R = 0;
+    for (int v = 0; v < V; ++v) {
+        const mrcnn_tta_view_t &w = views[v];
+        if (w.R < 0 || !(w.scale > 0.f) || (w.R > 0 && (!rois[v] || !box_out[v])))
+            return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_detect_decode: bad view %d (R %d, scale %g)", v, w.R, (double)w.scale);
+        vs.rois[v] = rois[v];
+        vs.box[v] = box_out[v];
+        vs.mirror[v] = w.mirror;
+        vs.scale[v] = w.scale;
+        vs.off[v] = (int)R;
+        R += w.R;
+        if (R > 0x7FFFFF00LL) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_detect_decode: %lld rows", R);
+    }
+    vs.off[V] = (int)R;
+    if (R == 0) return 0;
+    if (!cls_bbox || !prob) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_detect_decode: null output");
+    hipLaunchKernelGGL(k_tta_detect_decode, dim3(mrcnn::cdiv(R, NT)), dim3(NT), 0, (hipStream_t)stream, vs, V, ld, n_class, loc0,
+                       make_float4(loc_mean4[0], loc_mean4[1], loc_mean4[2], loc_mean4[3]),
+                       make_float4(loc_std4[0], loc_std4[1], loc_std4[2], loc_std4[3]), size_h, size_w, cls_bbox, prob);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t mrcnn_class_nms_workspace_bytes(int R, int n_class) {
+    if (R <= LDS_NMS_CAP || R > UNION_MAX || n_class <= 0) return 0;
+    return union_layout(R, n_class).total;
+}
+
+extern "C" int mrcnn_class_nms_ws_f32(const float *cls_bbox, const float *prob, int R, int n_class, int l_begin, int l_end,
+                                      float score_thresh, float nms_thresh, int32_t *keep_idx, int32_t *keep_cnt, void *ws, size_t ws_bytes,
+                                      void *stream) {
+    if (!cls_bbox || !prob || !keep_idx || !keep_cnt || R <= 0 || n_class <= 0 || l_begin < 0 || l_end > n_class || l_begin > l_end)
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "class_nms_ws: bad arguments");
+    if (R > UNION_MAX) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "class_nms_ws: %d RoIs > %d", R, UNION_MAX);
+    if (R <= LDS_NMS_CAP)           // the single-view kernel: one workgroup per class, everything in LDS
+        return mrcnn_class_nms_f32(cls_bbox, prob, R, n_class, l_begin, l_end, score_thresh, nms_thresh, keep_idx, keep_cnt, stream);
+    const UnionLayout L = union_layout(R, n_class);
+    if (!ws || ws_bytes < L.total)
+        return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "class_nms_ws: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return mrcnn::fail_arg(MRCNN_E_INVALID, "class_nms_ws: workspace not 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    MRCNN_HIP_TRY(hipMemsetAsync(keep_cnt, 0, sizeof(int32_t) * n_class, st));
+    const int nc = l_end - l_begin;
+    if (nc == 0) return 0;
+    char *w = static_cast<char *>(ws);
+    float4 *sboxes = reinterpret_cast<float4 *>(w + L.sboxes);
+    int32_t *sidx = reinterpret_cast<int32_t *>(w + L.sidx), *n_valid = reinterpret_cast<int32_t *>(w + L.n_valid);
+    u64 *mask = reinterpret_cast<u64 *>(w + L.mask);
+    int P = 64;
+    while (P < R) P <<= 1;
+    hipLaunchKernelGGL(k_union_sort, dim3(nc), dim3(SORT_T), 0, st, cls_bbox, prob, R, P, n_class, l_begin, score_thresh, sboxes, sidx, n_valid);
+    MRCNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_union_mask, dim3(L.nblk, (L.nblk + 3) / 4, nc), dim3(256), 0, st, sboxes, n_valid, R, L.nblk, nms_thresh, mask);
+    MRCNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_union_sweep, dim3(nc), dim3(64), 0, st, mask, sidx, n_valid, R, L.nblk, l_begin, keep_idx, keep_cnt);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrcnn_tta_mask_merge_f32(const float *const *mask_logits, const mrcnn_tta_view_t *views, int V, int D, int S, int Cm,
+                                        const int32_t *label, float *prob, void *stream) {
+    if (int e = check_views("tta_mask_merge", views, V)) return e;
+    if (D < 0 || S <= 0 || Cm <= 0 || (long long)D * S * S > 0x7FFFFFFFLL)
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_mask_merge: bad sizes (D %d, S %d, Cm %d)", D, S, Cm);
+    if (D == 0) return 0;
+    if (!mask_logits || !label || !prob) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_mask_merge: null pointer");
+    MergeViews vs = {};
+    for (int v = 0; v < V; ++v) {
+        if (!mask_logits[v]) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_mask_merge: null logits of view %d", v);
+        vs.src[v] = mask_logits[v];
+        vs.mirror[v] = views[v].mirror;
+    }
+    hipLaunchKernelGGL(k_tta_mask_merge, dim3(mrcnn::cdiv((long long)D * S * S, NT)), dim3(NT), 0, (hipStream_t)stream, vs, V, D, S, Cm,
+                       label, prob);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrcnn_mask_paste_prob_f32(const float *prob, int D, int S, const float *bbox, int H, int W, unsigned char *out, void *stream) {
+    if (D < 0 || S <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7FFFFFFFLL)
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "mask_paste_prob: bad sizes");
+    if (D == 0) return 0;
+    if (!prob || !bbox || !out) return mrcnn::fail_arg(MRCNN_E_INVALID, "mask_paste_prob: null pointer");
+    if (D > 65535) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "mask_paste_prob: D = %d > 65535", D);
+    if (reinterpret_cast<uintptr_t>(bbox) & 15) return mrcnn::fail_arg(MRCNN_E_INVALID, "mask_paste_prob: bbox not 16-byte aligned");
+    hipLaunchKernelGGL(k_mask_paste_prob, dim3(std::min(mrcnn::cdiv((long long)H * W, 256), 1024), D), dim3(256), 0, (hipStream_t)stream,
+                       prob, S, bbox, H, W, out);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrcnn_tta_keypoint_merge_f32(const float *const *heat, const mrcnn_tta_view_t *views, int V, int D, int S, int Cp, int K,
+                                            const int32_t *perm, float *out, void *stream) {
+    if (int e = check_views("tta_keypoint_merge", views, V)) return e;
+    if (D < 0 || S <= 0 || K <= 0 || Cp < K || (long long)D * S * S * Cp > 0x7FFFFFFFLL)
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_keypoint_merge: bad sizes (D %d, S %d, Cp %d, K %d)", D, S, Cp, K);
+    if (K > MRCNN_TTA_KEYPOINTS_MAX) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "tta_keypoint_merge: K = %d > %d", K, MRCNN_TTA_KEYPOINTS_MAX);
+    KpViews vs = {};
+    bool any_mirror = false;
+    for (int v = 0; v < V; ++v) any_mirror |= views[v].mirror != 0;
+    if (any_mirror) {
+        if (!perm) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_keypoint_merge: a mirrored view needs the channel permutation");
+        bool seen[MRCNN_TTA_KEYPOINTS_MAX] = {};
+        for (int k = 0; k < K; ++k) {
+            if (perm[k] < 0 || perm[k] >= K || seen[perm[k]])
+                return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_keypoint_merge: perm is not a permutation of 0..%d (entry %d)", K - 1, k);
+            seen[perm[k]] = true;
+            vs.perm[k] = (unsigned char)perm[k];
+        }
+    }
+    if (D == 0) return 0;
+    if (!heat || !out) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_keypoint_merge: null pointer");
+    for (int v = 0; v < V; ++v) {
+        if (!heat[v]) return mrcnn::fail_arg(MRCNN_E_INVALID, "tta_keypoint_merge: null heat maps of view %d", v);
+        vs.src[v] = heat[v];
+        vs.mirror[v] = views[v].mirror;
+    }
+    hipLaunchKernelGGL(k_tta_keypoint_merge, dim3(mrcnn::cdiv((long long)D * S * S * Cp, NT)), dim3(NT), 0, (hipStream_t)stream, vs, V, D, S, Cp, K, out);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}

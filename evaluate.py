@@ -7,7 +7,10 @@
 --synthetic 0 evaluates every image of <anno-dir>/instances_<split><data-type>.json (COCOeval's default image set), the first
 --eval-images of them when given; --synthetic 1 the deterministic make_batch val split of train.py --eval-metric mask_coco.  Writes
 <out>/segm_results.json and <out>/bbox_results.json ({"image_id", "category_id", "segmentation": RLE / "bbox", "score"}; not with
---no-results) and <out>/metrics.json (all 12 stats per type), and prints COCOeval's summary lines.  Keypoint heads are scored by
+--no-results) and <out>/metrics.json (all 12 stats per type, and the test-time augmentation under "tta" when it is on), and prints
+COCOeval's summary lines.  --tta-sizes / --tta-hflip 1 score with test-time augmentation (MaskRCNN.use_test_augmentation):
+
+  python evaluate.py --weight result/model_90000.npz --tta-sizes 640 800 1000 --tta-hflip 1  Keypoint heads are scored by
 train_keypoints.py --eval-metric keypoint_coco.
 """
 import argparse
@@ -20,6 +23,8 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from train import tta_settings  # noqa: E402
 
 SYNTHETIC_VAL_IMAGES = 16           # train.py's synthetic val split of --eval-images 0
 
@@ -40,6 +45,11 @@ def build_parser():
     parser.add_argument('--image-size', type=int, nargs=2, default=[800, 800], help='--synthetic 1: image height and width')
     parser.add_argument('--score-thresh', type=float, default=None, help="overrides the 'evaluate' preset's score threshold (0.05)")
     parser.add_argument('--no-results', action='store_true', help='do not write the COCO results files')
+    parser.add_argument('--tta-sizes', type=int, nargs='+', default=None, metavar='N',
+                        help='test-time augmentation: run every image at these short sides and merge the views (off by default)')
+    parser.add_argument('--tta-hflip', type=int, default=0, choices=[0, 1],
+                        help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no --tta-sizes)')
+    parser.add_argument('--tta-max-size', type=int, default=None, help='long-side cap of the test-time views (default: the model\'s max_size)')
     parser.add_argument('--out', '-o', default='result_eval', help='Output directory')
     return parser
 
@@ -93,6 +103,9 @@ def run(args):
     from chainer_maskrcnn.evaluator import InstanceSegmentationCOCOEvaluator, split_coco_results
     check_args(args)
     model = build_model(args)
+    tta = tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, model.min_size)
+    if tta is not None:
+        model.use_test_augmentation(tta['sizes'], hflip=tta['hflip'], max_size=tta['max_size'])
     data = build_dataset(args, model.n_class - 1)
     results = None if args.no_results else []
     ev = InstanceSegmentationCOCOEvaluator(data, model, results=results)
@@ -104,7 +117,7 @@ def run(args):
             with open(os.path.join(args.out, name), 'w') as f:
                 json.dump(res, f)
     with open(os.path.join(args.out, 'metrics.json'), 'w') as f:
-        json.dump(ev.stats, f, indent=1)
+        json.dump(dict(ev.stats, tta=tta) if tta is not None else ev.stats, f, indent=1)
     for t in ('segm', 'bbox'):
         print(evaluations.format_coco_stats(ev.stats[t], t))
     return ev.stats

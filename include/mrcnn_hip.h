@@ -724,6 +724,49 @@ int mrcnn_image_resize_batch_u8_f32(const unsigned char *src, size_t src_bytes, 
 int mrcnn_mask_resize_batch_nearest_u8(const unsigned char *src, size_t src_bytes, const mrcnn_resize_desc_t *desc, int N, int G,
                                        unsigned char *dst, int dst_h, int dst_w, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Test-time augmentation (tta.hip; MaskRCNN.use_test_augmentation).  An image runs as V <= MRCNN_TTA_VIEWS_MAX views (short sides,
+ * optionally mirrored), one N = 1 forward each; these calls merge the views after the forward pass.
+ *   views (V) HOST array, read at the call (passed to the kernels by value): R = the view's candidates (decode), mirror 0 / 1, scale = the
+ *         view's resize factor ow / W (decode).  The merges read mirror only.
+ *   *const *: V HOST-side device pointers, one per view (the precedent of mrcnn_roi_align_fpn_fwd_f32's xs)
+ * image_resize_mirror: mrcnn_image_resize_f32 with mirror = 1 reading source column s as W-1-s: bit-identical to resizing img[..., ::-1].
+ * tta_detect_decode: the rows of all views concatenated in view order into cls_bbox (R,4) / prob (R,n_class), R = sum of views[v].R;
+ *   row i of view v = mrcnn_detect_decode_f32 of rois[v][i], box_out[v][i] with views[v].scale and the original (size_h, size_w);
+ *   a mirrored view's box is then mapped to (y1, size_w - x2, y2, size_w - x1).  rois[v] / box_out[v] may be NULL when R = 0.
+ * class_nms_ws: mrcnn_class_nms_f32 for R <= MRCNN_CLASS_NMS_WS_MAX candidates (same outputs, same keep lists), no host sync.
+ *   R <= 512 runs mrcnn_class_nms_f32 itself (ws unused, may be NULL); above, ws of mrcnn_class_nms_workspace_bytes(R, n_class) bytes,
+ *   256-byte aligned (the sorted candidates and the IoU bitmask of every class).  R > MRCNN_CLASS_NMS_WS_MAX: MRCNN_E_UNSUPPORTED.
+ * tta_mask_merge: prob (D,S,S) = (sum over views u, in order, of sigmoid(mask_logits[u][d, y, x_u, label[d]])) / V, float32,
+ *   x_u = S-1-x for a mirrored view; mask_logits[u] (D,S,S,Cm) NHWC as mrcnn_mask_paste_f32 takes them.
+ * mask_paste_prob: mrcnn_mask_paste_f32 from probabilities prob (D,S,S) instead of logits (bbox (D,4) 16-byte aligned).
+ * tta_keypoint_merge: out (D,S,S,Cp) = (sum over views u, in order, of heat[u][d, y, x_u, k_u]) / V, x_u as above, k_u = perm[k] for a
+ *   mirrored view and k < K, k otherwise.  perm: HOST array of K ints (a permutation of 0..K-1), needed when a view is mirrored.
+ * D == 0 and R == 0 are no-ops.  Errors, before any launch: MRCNN_E_INVALID for V outside 1..MRCNN_TTA_VIEWS_MAX, a mirror other than
+ * 0 / 1, bad sizes or scales, NULL pointers, a bad permutation, a misaligned workspace; MRCNN_E_WORKSPACE for a short or NULL workspace;
+ * MRCNN_E_UNSUPPORTED for R > MRCNN_CLASS_NMS_WS_MAX or K > MRCNN_TTA_KEYPOINTS_MAX.
+ * ---------------------------------------------------------------------------------------- */
+#define MRCNN_TTA_VIEWS_MAX 8
+#define MRCNN_TTA_KEYPOINTS_MAX 256
+#define MRCNN_CLASS_NMS_WS_MAX 4096
+typedef struct mrcnn_tta_view {
+    int R, mirror;
+    float scale;
+} mrcnn_tta_view_t;             /* 12 bytes */
+int mrcnn_image_resize_mirror_f32(const float *src, int C, int H, int W, float *dst, int oh, int ow, int dst_h, int dst_w, int mirror,
+                                  float div, void *stream);
+int mrcnn_tta_detect_decode_f32(const float *const *rois, const float *const *box_out, const mrcnn_tta_view_t *views, int V, int ld,
+                                int n_class, int loc0, const float *loc_mean4, const float *loc_std4, float size_h, float size_w,
+                                float *cls_bbox, float *prob, void *stream);
+size_t mrcnn_class_nms_workspace_bytes(int R, int n_class);
+int mrcnn_class_nms_ws_f32(const float *cls_bbox, const float *prob, int R, int n_class, int l_begin, int l_end, float score_thresh,
+                           float nms_thresh, int32_t *keep_idx, int32_t *keep_cnt, void *ws, size_t ws_bytes, void *stream);
+int mrcnn_tta_mask_merge_f32(const float *const *mask_logits, const mrcnn_tta_view_t *views, int V, int D, int S, int Cm,
+                             const int32_t *label, float *prob, void *stream);
+int mrcnn_mask_paste_prob_f32(const float *prob, int D, int S, const float *bbox, int H, int W, unsigned char *out, void *stream);
+int mrcnn_tta_keypoint_merge_f32(const float *const *heat, const mrcnn_tta_view_t *views, int V, int D, int S, int Cp, int K,
+                                 const int32_t *perm, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,14 @@ def build_parser(keypoints=False):
                         help='metric of --eval-interval: mask_voc = PASCAL VOC mask mAP (mask heads, InstanceSegmentationVOCEvaluator); '
                              'mask_coco = COCO mask and box AP over IoU .50:.95 (mask heads, InstanceSegmentationCOCOEvaluator); '
                              'keypoint_coco = COCO keypoint AP over OKS .50:.95 (keypoint heads, KeypointCOCOEvaluator)')
+    parser.add_argument('--eval-tta-sizes', type=int, nargs='+', default=None, metavar='N',
+                        help='test-time augmentation of the --eval-interval evaluator: every val image also runs at these short sides '
+                             '(MaskRCNN.use_test_augmentation); off by default')
+    parser.add_argument('--eval-tta-hflip', type=int, default=0, choices=[0, 1],
+                        help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no '
+                             '--eval-tta-sizes); keypoint heads swap their left / right channels')
+    parser.add_argument('--eval-tta-max-size', type=int, default=None,
+                        help='long-side cap of the test-time views (default: the model\'s max_size)')
     parser.add_argument('--hflip', type=int, default=0, choices=[0, 1],
                         help='1: mirror each training example with probability 0.5 (images, masks, boxes; keypoints with their left / right '
                              'channels swapped); --synthetic 0 only')
@@ -94,6 +102,17 @@ def build_parser(keypoints=False):
 def augment_settings(args):
     """The augmentation of a run as recorded in trainer_<it>.pt (NO_AUGMENT when off)."""
     return {'hflip': int(args.hflip), 'min_sizes': [int(s) for s in args.min_sizes] if args.min_sizes else None, 'seed': AUGMENT_SEED}
+
+
+def tta_settings(sizes, hflip, max_size, min_size):
+    """use_test_augmentation's arguments from the TTA flags (--tta-* of evaluate.py, --eval-tta-* here): None = off.  hflip without sizes
+    mirrors the model's own min_size."""
+    if not sizes and not hflip:
+        if max_size is not None:
+            raise ValueError('a test-time max size needs test-time sizes or the test-time flip')
+        return None
+    return {'sizes': [int(s) for s in sizes] if sizes else [int(min_size)], 'hflip': bool(hflip),
+            'max_size': None if max_size is None else int(max_size)}
 
 
 def _check_augment_args(args):
@@ -240,6 +259,8 @@ def run(args, keypoints=False):
         optimizer.load_state_dict(resume['optimizer'])
         first_it = resume['iteration'] + 1
     evaluator = _make_evaluator(args, faster_rcnn, labels, n_fg, K) if args.eval_interval > 0 else None
+    if evaluator is not None:
+        _use_eval_tta(args, faster_rcnn, evaluator)
     rtx = _Roctx() if args.profile else None
     t0 = time.time()
     t_eval = 0.0            # seconds spent in evaluation: not part of the training throughput
@@ -301,6 +322,26 @@ def run(args, keypoints=False):
         loader.close()
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def _use_eval_tta(args, faster_rcnn, evaluator):
+    """--eval-tta-*: test-time augmentation of the periodic evaluator's predictions.  A keypoint model's flip map comes from the val data's
+    names (_keypoint_flip_perm; COCO's 17 names for the synthetic split)."""
+    t = tta_settings(args.eval_tta_sizes, args.eval_tta_hflip, args.eval_tta_max_size, faster_rcnn.min_size)
+    if t is None:
+        return
+    perm = None
+    if faster_rcnn.head_arch == 'fpn_keypoint' and t['hflip']:
+        from chainer_maskrcnn.dataset import augment
+        data = getattr(evaluator.dataset, 'loader', None)
+        if args.synthetic or data is None:
+            names = augment.COCO_KEYPOINT_NAMES
+            if len(names) != faster_rcnn.head.n_keypoints:
+                raise ValueError('--eval-tta-hflip 1: %d keypoint names for %d keypoints' % (len(names), faster_rcnn.head.n_keypoints))
+            perm = augment.flip_permutation(names)
+        else:
+            perm = _keypoint_flip_perm(args, data)
+    faster_rcnn.use_test_augmentation(t['sizes'], hflip=t['hflip'], max_size=t['max_size'], keypoint_flip_perm=perm)
 
 
 def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
