@@ -82,6 +82,42 @@ def bn_infer_fwd(x, gamma, beta, mean, var, residual=None, relu=False, eps=2e-5)
     return y
 
 
+def bn_frozen_bwd(gy, gamma, var, yx=None, beta=None, mean=None, relu=0, want_gres=False, out=None, eps=2e-5):
+    """Backward of a frozen (inference-mode) BatchNorm: gx = dz * gamma / sqrt(var + eps); relu 0 / 1 (yx = y) / 2 (yx = x, needs beta
+    and mean).  out may be gy.  Returns (gx, gres or None)."""
+    _ck(gy, gamma, var, yx, beta, mean, out)
+    C = gy.shape[-1]
+    gx = torch.empty_like(gy) if out is None else out
+    gres = torch.empty_like(gy) if want_gres else None
+    check(lib().mrcnn_bn_frozen_bwd_f32(ptr(gy), ptr(yx), ptr(gamma), ptr(beta), ptr(mean), ptr(var), ptr(gx), ptr(gres),
+                                        gy.numel() // C, C, eps, int(relu), stream_ptr()))
+    return gx, gres
+
+
+def bn_infer_fwd_pair(xa, gamma_a, beta_a, mean_a, var_a, xb, gamma_b, beta_b, mean_b, var_b, eps=2e-5):
+    """relu(bn_a(xa) + bn_b(xb)) with running statistics: the bits of bn_infer_fwd(xb) then bn_infer_fwd(xa, residual, relu)."""
+    _ck(xa, gamma_a, beta_a, mean_a, var_a, xb, gamma_b, beta_b, mean_b, var_b)
+    if xa.shape != xb.shape:
+        raise ValueError('bn_infer_fwd_pair: xa %r and xb %r differ in shape' % (tuple(xa.shape), tuple(xb.shape)))
+    C = xa.shape[-1]
+    y = torch.empty_like(xa)
+    check(lib().mrcnn_bn_infer_fwd_pair_f32(ptr(xa), ptr(gamma_a), ptr(beta_a), ptr(mean_a), ptr(var_a), ptr(xb), ptr(gamma_b),
+                                            ptr(beta_b), ptr(mean_b), ptr(var_b), ptr(y), xa.numel() // C, C, eps, stream_ptr()))
+    return y
+
+
+def bn_frozen_bwd_pair(gy, y, gamma_a, var_a, gamma_b, var_b, out_a=None, eps=2e-5):
+    """Both input gradients of relu(bn_a(xa) + bn_b(xb)) (frozen layers) from one read of gy and of y (None: gy arrives masked).
+    out_a may be gy."""
+    _ck(gy, y, gamma_a, var_a, gamma_b, var_b, out_a)
+    C = gy.shape[-1]
+    gxa = torch.empty_like(gy) if out_a is None else out_a
+    gxb = torch.empty_like(gy)
+    check(lib().mrcnn_bn_frozen_bwd_pair_f32(ptr(gy), ptr(y), ptr(gamma_a), ptr(var_a), ptr(gamma_b), ptr(var_b), ptr(gxa), ptr(gxb),
+                                             gy.numel() // C, C, eps, stream_ptr()))
+    return gxa, gxb
+
+
 def relu_bwd(gy, y, out=None):
     _ck(gy, y)
     out = torch.empty_like(gy) if out is None else out
@@ -282,6 +318,14 @@ def random_keys_dev(shape, state):
 def sgd_momentum_wd(p, g, v, lr, momentum=0.9, weight_decay=5e-4):
     _ck(p, g, v)
     check(lib().mrcnn_sgd_momentum_wd_f32(ptr(p), ptr(g), ptr(v), p.numel(), lr, momentum, weight_decay, stream_ptr()))
+
+
+def sgd_momentum_wd_masked(p, g, v, offset, frozen_blocks, lr, momentum=0.9, weight_decay=5e-4):
+    """sgd_momentum_wd over a section (p, g, v: views starting at element ``offset`` of the flat buffers) that skips the 64-float blocks
+    whose bit is set in ``frozen_blocks`` (int32 words over the WHOLE flat buffer, ParamStore.frozen_block_mask)."""
+    _ck(p, g, v, frozen_blocks)
+    check(lib().mrcnn_sgd_momentum_wd_masked_f32(ptr(p), ptr(g), ptr(v), p.numel(), int(offset), ptr(frozen_blocks),
+                                                 frozen_blocks.numel() * 32, lr, momentum, weight_decay, stream_ptr()))
 
 
 # ---- losses -------------------------------------------------------------------------------------

@@ -69,13 +69,50 @@ class FeaturePyramidNetwork(object):
         self.lat_p3 = Conv(self.ps, p + 'lat_p3', 512 // d, fc, 1)
         self.lat_p2 = Conv(self.ps, p + 'lat_p2', 256 // d, fc, 1)
         self.anchor_scales = list(map(lambda x: x / float(self.anchor_base), self.anchor_sizes))
+        self.freeze_bn, self.freeze_at = False, 0
+
+    def set_freeze(self, bn=False, at=0):
+        """bn: every BatchNorm of the ResNet runs the training step on its running statistics with a constant affine.
+        at = k in 0..5: the stem (k >= 1) and the stages res2 .. res{k} are not trained - forward without a tape, no backward.
+        Returns the names of the parameters this leaves constant (for ParamStore.set_frozen)."""
+        at = int(at)
+        if not 0 <= at <= 5:
+            raise ValueError('freeze_at must be in 0..5 (0 = off, 1 = stem, k = stem + res2 .. res{k}), got %r' % (at,))
+        if at > 0 and not bn:
+            raise ValueError('freeze_at > 0 requires freeze_bn: a frozen prefix with batch-statistics BatchNorm is not implemented')
+        self.freeze_bn, self.freeze_at = bool(bn), at
+        self.bn1.frozen = bool(bn)
+        names = set()
+        for si, blocks in enumerate(self.stages):
+            for b in blocks:
+                b.trained = si + 2 > at
+                for n in b.norms():
+                    n.frozen = bool(bn)
+        if bn:
+            names.update(n for n in self.ps.offsets if '/resnet/' in n and (n.endswith('/gamma') or n.endswith('/beta')))
+        for pre in self.frozen_prefixes():
+            names.update(n for n in self.ps.offsets if n.startswith(pre + '/'))
+        return names
+
+    def frozen_prefixes(self):
+        """Name prefixes of the layers freeze_at leaves untrained."""
+        if self.freeze_at < 1:
+            return []
+        out = [self.conv1.name, self.bn1.name]
+        for si in range(min(self.freeze_at - 1, len(self.stages))):
+            out += [b.conv1.name.rsplit('/', 1)[0] for b in self.stages[si]]
+        return out
 
     def __call__(self, x):
         """x (N,H,W,4) NHWC.  Returns (p2, p3, p4, p5, p6) NHWC and keeps the tape for backward()."""
         t = {}
-        h, t['conv1'] = self.conv1.fwd(x)
+        stem_trained = self.freeze_at < 1
+        h, t['conv1'] = self.conv1.fwd(x, tape=stem_trained)
         h, t['bn1'] = self.bn1.fwd(h, relu=True)
-        t['pool_in'] = h
+        if stem_trained:
+            t['pool_in'] = h
+        else:
+            t['bn1'] = None
         h = ops.maxpool2x2_fwd(h)
         cs = []
         t['blocks'] = []
@@ -87,7 +124,8 @@ class FeaturePyramidNetwork(object):
         for si, blocks in enumerate(self.stages):
             for b in blocks:
                 h, ctx = b.fwd(h)
-                t['blocks'].append((b, ctx))
+                if b.trained:                   # (a block of the frozen prefix leaves no tape)
+                    t['blocks'].append((b, ctx))
             cs.append(h)
             if off_chain and si < 3:        # the stage's lateral, beside the stages that follow
                 side.wait_stream(main)
@@ -127,7 +165,14 @@ class FeaturePyramidNetwork(object):
             import torch
             main, ls = torch.cuda.current_stream(g_p2.device), _lateral_stream(g_p2.device)
 
-        def lateral_bwd(conv, ctx, g_m):
+        # freeze_at = k: the stages res2 .. res{k} take no gradient, so the 1x1 convolution that reads such a stage's output (lat_p2 for
+        # k >= 2, ..., toplayer for k = 5) computes its filter gradient only
+        k = self.freeze_at
+
+        def lateral_bwd(conv, ctx, g_m, stage):
+            if k >= stage:
+                conv.bwd(ctx, g_m, need_gx=False)
+                return None
             if not off_chain:
                 return conv.bwd(ctx, g_m, mask_gx=MASK_IN_PRODUCER)
             ls.wait_stream(main)                # g_m is complete on the main stream
@@ -136,29 +181,41 @@ class FeaturePyramidNetwork(object):
                 g_c = conv.bwd(ctx, g_m, mask_gx=MASK_IN_PRODUCER)
             g_c.record_stream(main)             # accumulated into by the next stage's first block, on the main stream
             return g_c
-        g_c2 = lateral_bwd(self.lat_p2, t['lat2'], g_m2)
+        g_c2 = lateral_bwd(self.lat_p2, t['lat2'], g_m2, 2)
         g_m3 = self.conv_p3.bwd(t['p3'], g_p3)
         ops.upsample2x_bwd(g_m3, gtop=g_p4)
-        g_c3 = lateral_bwd(self.lat_p3, t['lat3'], g_m3)
+        g_c3 = lateral_bwd(self.lat_p3, t['lat3'], g_m3, 3)
         g_m4 = self.conv_p4.bwd(t['p4'], g_p4)
         ops.upsample2x_bwd(g_m4, gtop=g_p5)
-        g_c4 = lateral_bwd(self.lat_p4, t['lat4'], g_m4)
-        g_c5 = self.toplayer.bwd(t['top'], g_p5, mask_gx=MASK_IN_PRODUCER)
+        g_c4 = lateral_bwd(self.lat_p4, t['lat4'], g_m4, 4)
+        g_c5 = self.toplayer.bwd(t['top'], g_p5, need_gx=k < 5, mask_gx=MASK_IN_PRODUCER)
         if progress:
             progress(self.toplayer.name)        # the FPN layers are registered after the ResNet
         # The gradient of c2..c4 is (lateral gradient) + (input gradient of the next stage): the next
         # stage's first block accumulates its input gradient into the lateral one (gx_acc).
         acc_for = {id(self.stages[k][0]): g for k, g in ((1, g_c2), (2, g_c3), (3, g_c4))}
         g = g_c5
-        first = t['blocks'][0][0]
+        first = t['blocks'][0][0] if t['blocks'] else None
         for b, ctx in reversed(t['blocks']):
             # every block's output gradient arrives masked (from the block after it, or from toplayer / the laterals above); its own
             # input gradient is masked for the block before it - except the first block, whose input is the max-pool output
-            if off_chain and id(b) in acc_for:
+            if off_chain and acc_for.get(id(b)) is not None:
                 main.wait_stream(ls)            # the lateral gradient this block accumulates into
-            g = b.bwd(ctx, g, gx_acc=acc_for.get(id(b)), gy_masked=MASK_IN_PRODUCER, mask_gx=MASK_IN_PRODUCER and b is not first)
+            if k >= 1 and b is first:           # the first trained block above the frozen prefix: parameter gradients only
+                g = b.bwd(ctx, g, gy_masked=MASK_IN_PRODUCER, need_gx=False)
+            else:
+                g = b.bwd(ctx, g, gx_acc=acc_for.get(id(b)), gy_masked=MASK_IN_PRODUCER, mask_gx=MASK_IN_PRODUCER and b is not first)
             if progress:
                 progress(b.conv1.name)
+        if k >= 1:
+            # nothing below is trained; every prefix is still reported, in backward order, so that the data-parallel buckets and the
+            # sectioned update close as without freezing (frozen parameters keep the zeros of their gradient slots)
+            if progress:
+                for blocks in reversed(self.stages[:k - 1]):
+                    for b in reversed(blocks):
+                        progress(b.conv1.name)
+            self.tape = None
+            return
         g = ops.maxpool2x2_bwd(t['pool_in'], g)
         g, _ = self.bn1.bwd(t['bn1'], g)
         self.conv1.bwd(t['conv1'], g, need_gx=False)

@@ -90,6 +90,26 @@ class MaskRCNN(object):
         self.tta = None                 # test-time augmentation, off (use_test_augmentation)
         self.device = torch.device(device)
         self.ps.materialise(self.device, seed)
+        self.freeze_state = (False, 0)
+
+    def freeze(self, bn=False, at=0):
+        """Fine-tuning recipe of the training step (off by default; inference is not affected).
+        bn: every BatchNorm of the FPN's ResNet is frozen - the step computes it from avg_mean / avg_var with a constant gamma / beta
+            (the bits of the inference layer), computes no gradient for them and updates neither them nor the running statistics.
+        at = k in 0..5: the stem (conv1, bn1) and the stages res2 .. res{k} are not trained: no tape, no backward pass, parameters and
+            momentum untouched by the optimizer (weight decay included).  k = 2 is the usual recipe; k = 5 trains FPN / RPN / heads only.
+            Requires bn.
+        ``freeze(False, 0)`` undoes it.  Call it before capturing a GraphedStep (an existing one re-captures by itself)."""
+        if not hasattr(self.extractor, 'set_freeze'):
+            if not bn and not at:
+                return self
+            raise ValueError('freeze() exists for the FPN ResNet backbone only')
+        names = self.extractor.set_freeze(bn, at)
+        self.ps.set_frozen(names)
+        for n in names:                 # a frozen parameter's gradient slot is never written again: it carries zeros (all-reduce included)
+            self.ps.g(n).zero_()
+        self.freeze_state = (bool(bn), int(at))
+        return self
 
     @property
     def n_class(self):

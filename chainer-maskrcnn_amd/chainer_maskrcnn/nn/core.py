@@ -106,6 +106,8 @@ class ParamStore(object):
         self.size = 0
         self.buffers = {}       # non-trainable state (BN running statistics)
         self._views = {}        # id(flat buffer) -> (flat buffer, {name: view})
+        self.frozen = frozenset()       # names the optimizer leaves alone (MaskRCNN.freeze) ...
+        self.frozen_mask = None         # ... and their 64-float blocks, one bit each, on the parameters' device (None: nothing frozen)
 
     def register(self, name, shape, init, trainable=True):
         if name in self.offsets:
@@ -131,6 +133,27 @@ class ParamStore(object):
         self.momentum = torch.zeros_like(self.params)
         self._views = {}            # the views of earlier flat buffers (and the buffers they keep alive) go with them
         return self
+
+    def frozen_block_mask(self, names):
+        """One bit per ALIGN-float block of the flat buffers (bit b of word b // 32 = block b; int32 words on the host): set for
+        the blocks of the parameters in ``names``.  Every parameter starts on a block boundary and owns whole blocks, its padding
+        included, so a block is either frozen or trainable."""
+        nblk = self.size // self.ALIGN
+        bits = np.zeros((pad_to(max(nblk, 1), 32),), bool)
+        for name in names:
+            o, shape = self.offsets[name]
+            bits[o // self.ALIGN:(o + pad_to(int(np.prod(shape)), self.ALIGN)) // self.ALIGN] = True
+        words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder='little').view('<u4').reshape(-1)
+        return torch.from_numpy(words.view(np.int32).copy())
+
+    def set_frozen(self, names):
+        """The optimizer updates every parameter except these (value, momentum and weight decay untouched); () = all trainable."""
+        names = frozenset(names)
+        for n in names:
+            if n not in self.offsets:
+                raise KeyError('no trainable parameter %s' % n)
+        self.frozen = names
+        self.frozen_mask = self.frozen_block_mask(names).to(self.params.device) if names else None
 
     def _view(self, flat, name):
         # (views are cached per flat buffer: ~250 parameter / gradient lookups per step were 1.6 ms of slicing)
@@ -204,12 +227,18 @@ class Conv(object):
     def b(self):
         return self.ps.p(self.name + '/b') if self.has_bias else None
 
-    def fwd(self, x, relu=None, bn_stats=False):
+    def fwd(self, x, relu=None, bn_stats=False, tape=True):
         """bn_stats: the output feeds a training-mode BatchNorm - where the geometry allows, the GEMM epilogue also leaves the
-        statistics partials in ``self.last_bn_part`` (None otherwise) and BatchNorm.fwd skips its statistics pass."""
+        statistics partials in ``self.last_bn_part`` (None otherwise) and BatchNorm.fwd skips its statistics pass.
+        tape=False: the layer is not trained (frozen backbone prefix) - nothing is kept for a backward pass, the context is None."""
         relu = self.relu if relu is None else relu
         self.last_bn_part = None
         hnn.LOGICAL = (self.cin, self.cout)
+        if not tape:
+            with _layer_tiles(self):
+                y = hnn.conv2d_fwd_raw(x, self.W, self.b, self.stride, self.pad, relu)
+            hnn.LOGICAL = None
+            return y, None
         if bn_stats and FUSE_BN_STATS and TRAIN and not relu and not self.has_bias:
             with _layer_tiles(self):
                 res = hnn.conv2d_fwd_bnstats_raw(x, self.W, self.stride, self.pad, keep_v=True)
@@ -297,10 +326,15 @@ class Conv(object):
 
 
 class BatchNorm(object):
-    """Training-mode BatchNormalization (batch statistics; eps 2e-5, decay 0.9 as in Chainer)."""
+    """Training-mode BatchNormalization (batch statistics; eps 2e-5, decay 0.9 as in Chainer).
+
+    ``frozen`` (per layer, set by MaskRCNN.freeze): the training step runs the layer on its running statistics with a constant
+    affine - the inference expression, bit for bit - and back-propagates through it as the per-channel scale it then is; no statistics,
+    no gradient of gamma / beta, no update of avg_mean / avg_var."""
 
     def __init__(self, ps, name, c):
         self.ps, self.name, self.c = ps, name, c
+        self.frozen = False
         ps.register(name + '/gamma', (c,), lambda rs: np.ones((c,), np.float32))
         ps.register(name + '/beta', (c,), lambda rs: np.zeros((c,), np.float32))
         ps.register(name + '/avg_mean', (c,), lambda rs: np.zeros((c,), np.float32), trainable=False)
@@ -312,6 +346,12 @@ class BatchNorm(object):
             y = ops.bn_infer_fwd(x, gamma, beta, self.ps.buffers[self.name + '/avg_mean'],
                                  self.ps.buffers[self.name + '/avg_var'], residual, relu)
             return y, None
+        if self.frozen:
+            y = ops.bn_infer_fwd(x, gamma, beta, self.ps.buffers[self.name + '/avg_mean'], self.ps.buffers[self.name + '/avg_var'],
+                                 residual, relu)
+            # the ReLU mask is read from y: the layer's output is alive until the backward pass anyway (it is the next convolution's
+            # operand), the convolution output x is not kept
+            return y, ('frozen', y if relu else None)
         if partials is not None and partials.shape[2] == x.shape[-1]:
             y, mean, invstd = ops.bn_train_fwd_stats(x, partials, gamma, beta, residual, relu, self.ps.buffers[self.name + '/avg_mean'],
                                                      self.ps.buffers[self.name + '/avg_var'])
@@ -322,9 +362,19 @@ class BatchNorm(object):
         # kept for (or read by) the backward pass
         return y, (x, y if (residual is not None or not relu) else None, mean, invstd, relu)
 
-    def bwd(self, ctx, gy, want_gres=False, gy_masked=False):
+    def scale_operands(self):
+        """(gamma, avg_var): what the frozen backward's per-channel scale gamma / sqrt(avg_var + eps) is made of."""
+        return self.ps.p(self.name + '/gamma'), self.ps.buffers[self.name + '/avg_var']
+
+    def bwd(self, ctx, gy, want_gres=False, gy_masked=False, in_place=False):
         """gy_masked: the producer of gy already zeroed it where this layer's ReLU output is <= 0 (its data-gradient epilogue
-        ran with mask_gx on the tensor this layer produced): no mask stream is read here and gres would be gy itself."""
+        ran with mask_gx on the tensor this layer produced): no mask stream is read here and gres would be gy itself.
+        in_place (frozen layers): gx overwrites gy."""
+        if ctx[0] == 'frozen':
+            y = None if gy_masked else ctx[1]
+            assert not (want_gres and y is None)
+            gamma, var = self.scale_operands()
+            return ops.bn_frozen_bwd(gy, gamma, var, yx=y, relu=0 if y is None else 1, want_gres=want_gres, out=gy if in_place else None)
         x, y, mean, invstd, relu = ctx
         if gy_masked:
             assert relu and not want_gres
@@ -359,6 +409,68 @@ class Bottleneck(object):
         if project:
             self.conv4 = Conv(ps, name + '/conv4', cin, cout, 1, stride, 0, bias=False, init=he(cin), in_backbone=True)
             self.bn4 = BatchNorm(ps, name + '/bn4', cout)
+        self.trained = True         # False: part of the frozen backbone prefix (MaskRCNN.freeze(at=...)) - forward only, no tape
+
+    def norms(self):
+        return [self.bn1, self.bn2, self.bn3] + ([self.bn4] if self.project else [])
+
+    def _fwd_frozen(self, x):
+        """Frozen BatchNorm (all of the block's layers): layer by layer on the running statistics, the projection pair in one apply.
+        Neither the composite call nor conv2's bn1-on-load path exists for it (both are built on batch statistics)."""
+        t = self.trained
+        h1, c1 = self.conv1.fwd(x, tape=t)
+        a1, b1 = self.bn1.fwd(h1, relu=True)
+        h2, c2 = self.conv2.fwd(a1, tape=t)
+        a2, b2 = self.bn2.fwd(h2, relu=True)
+        h3, c3 = self.conv3.fwd(a2, tape=t)
+        if self.project:
+            h4, c4 = self.conv4.fwd(x, tape=t)
+            ps, n3, n4 = self.bn3.ps, self.bn3.name, self.bn4.name
+            y = ops.bn_infer_fwd_pair(h3, ps.p(n3 + '/gamma'), ps.p(n3 + '/beta'), ps.buffers[n3 + '/avg_mean'], ps.buffers[n3 + '/avg_var'],
+                                      h4, ps.p(n4 + '/gamma'), ps.p(n4 + '/beta'), ps.buffers[n4 + '/avg_mean'], ps.buffers[n4 + '/avg_var'])
+            b3 = ('frozen', y)
+        else:
+            c4 = None
+            y, b3 = self.bn3.fwd(h3, relu=True, residual=x)
+        if not t:
+            return y, None
+        return y, ('frozen', c1, b1, c2, b2, c3, b3, c4)
+
+    def _bwd_frozen(self, ctx, gy, gx_acc, gy_masked, mask_gx, need_gx):
+        """The frozen block's backward: every BatchNorm is a per-channel scale.  bn2 / bn1 get their gradient with the ReLU mask
+        already applied by the convolution above them (mask_gx on its operand) and scale it in place."""
+        _, c1, b1, c2, b2, c3, b3, c4 = ctx
+        if self.project:
+            g3, v3 = self.bn3.scale_operands()
+            g4, v4 = self.bn4.scale_operands()
+            g_h3, g_h4 = ops.bn_frozen_bwd_pair(gy, None if gy_masked else b3[1], g3, v3, g4, v4)
+            g_r = None
+        elif gy_masked:
+            g_h3, _ = self.bn3.bwd(b3, gy, gy_masked=True)
+            g_r = gy
+        else:
+            g_h3, g_r = self.bn3.bwd(b3, gy, want_gres=True)
+        g_a2 = self.conv3.bwd(c3, g_h3, mask_gx=True)
+        g_h2, _ = self.bn2.bwd(b2, g_a2, gy_masked=True, in_place=True)
+        g_a1 = self.conv2.bwd(c2, g_h2, mask_gx=True)
+        g_h1, _ = self.bn1.bwd(b1, g_a1, gy_masked=True, in_place=True)
+        if not need_gx:         # the block below is frozen: filter gradients only
+            self.conv1.bwd(c1, g_h1, need_gx=False)
+            if self.project:
+                self.conv4.bwd(c4, g_h4, need_gx=False)
+            return None
+        if not self.project:
+            if gx_acc is not None:
+                g_r = ops.add(g_r, gx_acc, out=gx_acc)
+            return self.conv1.bwd(c1, g_h1, gx_acc=g_r, mask_gx=mask_gx)
+        if self.stride == 1:
+            gx = self.conv1.bwd(c1, g_h1, gx_acc=gx_acc)
+            return self.conv4.bwd(c4, g_h4, gx_acc=gx, mask_gx=mask_gx)
+        self.conv1.bwd(c1, g_h1, need_gx=False)
+        self.conv4.bwd(c4, g_h4, need_gx=False)
+        g_sub = self.conv1.bwd_data_sub(g_h1)
+        self.conv4.bwd_data_sub(g_h4, out=g_sub)
+        return ops.subsample_bwd(g_sub, tuple(c1[0].shape), self.stride, gx=gx_acc, relu_x=c1[0] if mask_gx else None)
 
     def _composite_ok(self, x):
         return (COMPOSITE_BLOCKS and TRAIN and FUSE_BN_STATS and x.is_cuda and hnn.PROFILE is None and FWD_TILE_RULE is None
@@ -439,6 +551,8 @@ class Bottleneck(object):
         return gy if gy_masked else g_r          # identity shortcut: accumulated into the shortcut gradient in place
 
     def fwd(self, x):
+        if TRAIN and self.bn1.frozen:
+            return self._fwd_frozen(x)
         if self._composite_ok(x):
             return self._fwd_composite(x)
         h1, c1 = self.conv1.fwd(x, bn_stats=True)
@@ -455,11 +569,15 @@ class Bottleneck(object):
         y, b3 = self.bn3.fwd(h3, relu=True, residual=r, partials=p3)
         return y, (c1, b1, c2, b2, c3, b3, c4, b4)
 
-    def bwd(self, ctx, gy, gx_acc=None, gy_masked=False, mask_gx=False):
-        """gy_masked: gy already carries this block's output ReLU mask (its producer ran with mask_gx on this block's output);
+    def bwd(self, ctx, gy, gx_acc=None, gy_masked=False, mask_gx=False, need_gx=True):
+        """need_gx=False (frozen blocks only: the first trained block above a frozen prefix): parameter gradients only, returns None.
+        gy_masked: gy already carries this block's output ReLU mask (its producer ran with mask_gx on this block's output);
         bn3's backward then reads two streams instead of three and writes no separate shortcut gradient (it IS gy).
         mask_gx: the block's input is itself a ReLU output (the previous block's): the returned gradient - the sum of all its
         contributions - is zeroed where that input is <= 0, in the epilogue of the kernel that writes it last."""
+        if ctx[0] == 'frozen':
+            return self._bwd_frozen(ctx, gy, gx_acc, gy_masked, mask_gx, need_gx)
+        assert need_gx, 'need_gx=False exists for blocks with frozen BatchNorm only'
         if ctx[0] == 'composite':
             return self._bwd_composite(ctx, gy, gx_acc, gy_masked, mask_gx)
         c1, b1, c2, b2, c3, b3, c4, b4 = ctx

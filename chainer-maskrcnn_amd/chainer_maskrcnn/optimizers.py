@@ -319,8 +319,17 @@ class MomentumSGD(object):
             if len(self._section_views) > 4096:         # (rebound flat buffers: do not keep the old ones alive through stale views)
                 self._section_views.clear()
             views = self._section_views[key] = (ps.params[start:end], ps.grads[start:end], ps.momentum[start:end])
-        ops.sgd_momentum_wd(views[0], views[1], views[2], self.lr, self.momentum, self.weight_decay)
+        self._sgd(views[0], views[1], views[2], start)
         self._updated_down_to = start
+
+    def _sgd(self, p, g, v, start):
+        """The fused update of the slice that starts at element ``start`` of the flat buffers; with frozen parameters
+        (ParamStore.set_frozen) the kernel that skips their blocks."""
+        mask = self.ps.frozen_mask
+        if mask is None:
+            ops.sgd_momentum_wd(p, g, v, self.lr, self.momentum, self.weight_decay)
+        else:
+            ops.sgd_momentum_wd_masked(p, g, v, start, mask, self.lr, self.momentum, self.weight_decay)
 
     def _sectioning(self, lossfun):
         """The synchronizer that walks the sections of this update, or None (plain single pass)."""
@@ -379,7 +388,7 @@ class MomentumSGD(object):
             sect.finish()
         rest = self.ps.params.numel() if self._updated_down_to is None else self._updated_down_to
         if rest > 0:        # everything (no sections), or what no section covered
-            ops.sgd_momentum_wd(self.ps.params[:rest], self.ps.grads[:rest], self.ps.momentum[:rest], self.lr, self.momentum, self.weight_decay)
+            self._sgd(self.ps.params[:rest], self.ps.grads[:rest], self.ps.momentum[:rest], 0)
         self.t += 1
         return loss
 
@@ -416,12 +425,17 @@ class GraphedStep(object):
         # the learning rate is a kernel argument baked into the captured launch: re-capture when it changes
         # (ExponentialShift('lr', 0.1), train.py:139-140)
         self._lr = self.optimizer.lr
+        self._freeze = self._freeze_state()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.optimizer.update(self.chain, *self.static, self.scale)
 
+    def _freeze_state(self):
+        # MaskRCNN.freeze changes which kernels the step launches: part of what a capture is valid for
+        return getattr(getattr(self.chain, 'faster_rcnn', None), 'freeze_state', None)
+
     def __call__(self, *batch):
-        if self.optimizer.lr != self._lr:
+        if self.optimizer.lr != self._lr or self._freeze_state() != self._freeze:
             torch.cuda.synchronize()
             self._capture()
         for dst, src in zip(self.static, batch):

@@ -767,6 +767,35 @@ int mrcnn_mask_paste_prob_f32(const float *prob, int D, int S, const float *bbox
 int mrcnn_tta_keypoint_merge_f32(const float *const *heat, const mrcnn_tta_view_t *views, int V, int D, int S, int Cp, int K,
                                  const int32_t *perm, float *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frozen BatchNorm in the training step (bn_frozen.hip; MaskRCNN.freeze).  A frozen layer is mrcnn_bn_infer_fwd_f32 inside the
+ * training step: gamma, beta, avg_mean, avg_var are constants, nothing is reduced, no workspace.  float32, NHWC (P rows of C
+ * channels), C % 4 == 0, every pointer 16-byte aligned.  With a[c] = gamma[c] * (1.0f / sqrtf(avg_var[c] + eps)):
+ * bn_frozen_bwd: dz = gy under the ReLU mask, gx = dz * a[c], gres (nullable, a buffer of its own) = dz.  relu: 0 no mask (also a gy
+ *   that arrives masked), 1 mask = (yx > 0) with yx the layer's output y, 2 mask recomputed from yx = the layer's input x by the
+ *   forward's expression gamma * ((x - avg_mean) * (1.0f / sqrtf(avg_var + eps))) + beta > 0 (BatchNorm + ReLU without a residual).
+ *   yx may be NULL for relu 0, beta / avg_mean for relu 0 and 1.  gx may be gy.
+ * bn_infer_fwd_pair: y = relu(bn_a(xa) + bn_b(xb)), the bits of mrcnn_bn_infer_fwd_f32(xb) followed by
+ *   mrcnn_bn_infer_fwd_f32(xa, residual = that, relu = 1) without the intermediate tensor.
+ * bn_frozen_bwd_pair: dz = y ? gy where y > 0 : gy (y NULL: gy arrives masked); gxa = dz * a_a[c], gxb = dz * a_b[c]: the bits of
+ *   two bn_frozen_bwd calls.  gxa or gxb may be gy; gxa != gxb.
+ * sgd_momentum_wd_masked: mrcnn_sgd_momentum_wd_f32 over n elements starting at element `offset` of the flat parameter buffer
+ *   (p, g, v point AT that element; the flat buffers are 16-byte aligned), skipping every 64-float block b of the flat buffer whose bit
+ *   (frozen_blocks[b / 32] >> (b % 32)) & 1 is set: such elements of p and v are neither read nor written.  n_blocks = blocks the mask
+ *   covers (>= ceil((offset + n) / 64)).  Trainable elements get the bits of the unmasked call.  n == 0 is a no-op.
+ * Errors, before any launch: MRCNN_E_INVALID for a NULL or misaligned pointer, P <= 0, C % 4 != 0, a relu outside 0..2, an aliased
+ * output that may not alias, a section outside the mask.
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_bn_frozen_bwd_f32(const float *gy, const float *yx, const float *gamma, const float *beta, const float *avg_mean,
+                            const float *avg_var, float *gx, float *gres, int P, int C, float eps, int relu, void *stream);
+int mrcnn_bn_infer_fwd_pair_f32(const float *xa, const float *gamma_a, const float *beta_a, const float *mean_a, const float *var_a,
+                                const float *xb, const float *gamma_b, const float *beta_b, const float *mean_b, const float *var_b,
+                                float *y, int P, int C, float eps, void *stream);
+int mrcnn_bn_frozen_bwd_pair_f32(const float *gy, const float *y, const float *gamma_a, const float *var_a, const float *gamma_b,
+                                 const float *var_b, float *gxa, float *gxb, int P, int C, float eps, void *stream);
+int mrcnn_sgd_momentum_wd_masked_f32(float *p, const float *g, float *v, size_t n, size_t offset, const uint32_t *frozen_blocks,
+                                     size_t n_blocks, float lr, float momentum, float weight_decay, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

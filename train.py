@@ -24,6 +24,7 @@ import torch  # noqa: E402
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
 AUGMENT_SEED = 5678                 # seed of the per-example augmentation decisions (dataset/augment.py), recorded in trainer_<it>.pt
+NO_FREEZE = {'bn': 0, 'at': 0}       # what a trainer state without the 'freeze' key was trained with
 NO_AUGMENT = {'hflip': 0, 'min_sizes': None, 'seed': AUGMENT_SEED}     # what a trainer state without the 'augment' key was trained with
 
 
@@ -96,7 +97,32 @@ def build_parser(keypoints=False):
     parser.add_argument('--min-sizes', type=int, nargs='+', default=None, metavar='N',
                         help='scale jitter: each training example\'s short side is drawn uniformly from these sizes (the long side stays '
                              'capped by the model\'s max_size); --synthetic 0 only.  Default: the model\'s min_size')
+    parser.add_argument('--freeze-bn', type=int, default=0, choices=[0, 1],
+                        help='1: the ResNet\'s BatchNorm layers are frozen in the training step - running statistics, constant gamma / beta '
+                             '(MaskRCNN.freeze); meant for a backbone imported with --resnet50-npz / --weight')
+    parser.add_argument('--freeze-at', type=int, default=0, choices=[0, 1, 2, 3, 4, 5],
+                        help='k: the stem and the stages res2 .. res{k} are not trained and take no backward pass (1: stem only, 2: the usual '
+                             'fine-tuning recipe, 5: the whole ResNet); needs --freeze-bn 1')
     return parser
+
+
+def freeze_settings(args):
+    """The freezing of a run as recorded in trainer_<it>.pt (NO_FREEZE when off); raises on a combination MaskRCNN.freeze refuses."""
+    bn, at = int(args.freeze_bn), int(args.freeze_at)
+    if not 0 <= at <= 5:
+        raise ValueError('--freeze-at must be in 0..5, got %d' % at)
+    if bn not in (0, 1):
+        raise ValueError('--freeze-bn must be 0 or 1, got %d' % bn)
+    if at > 0 and not bn:
+        raise ValueError('--freeze-at %d needs --freeze-bn 1 (a frozen prefix with batch-statistics BatchNorm is not implemented)' % at)
+    return {'bn': bn, 'at': at}
+
+
+def check_resume_freeze(resume, args, path=''):
+    """A resumed run freezes what its checkpoint froze (a state without the key was trained with everything trainable)."""
+    was, now = resume.get('freeze', NO_FREEZE), freeze_settings(args)
+    if was != now:
+        raise ValueError('--resume %s: the checkpoint was trained with freezing %r, this run asks for %r' % (path, was, now))
 
 
 def augment_settings(args):
@@ -162,6 +188,12 @@ def run(args, keypoints=False):
     if resume is not None and resume.get('augment', NO_AUGMENT) != augment_settings(args):
         raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
                          % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
+    freeze = freeze_settings(args)
+    if resume is not None:
+        check_resume_freeze(resume, args, args.resume)
+    if freeze['bn'] and not (args.weight or args.resnet50_npz or args.resume) and rank == 0:
+        print('warning: --freeze-bn 1 without --weight / --resnet50-npz / --resume freezes freshly initialised BatchNorm statistics '
+              '(mean 0, variance 1)')
     data = None
     if not args.synthetic:          # the training set (before any device work: a keypoint set's flip map is checked here)
         from chainer_maskrcnn.dataset.coco_dataset import COCOMaskLoader, COCOKeypointsLoader
@@ -222,6 +254,8 @@ def run(args, keypoints=False):
             print('ResNet-50 snapshot: %d arrays loaded from %s' % (n, args.resnet50_npz))
     if args.weight and os.path.exists(args.weight):
         load_npz(args.weight, faster_rcnn)
+    if freeze != NO_FREEZE:
+        faster_rcnn.freeze(bn=bool(freeze['bn']), at=freeze['at'])
     optimizer = MomentumSGD(lr=args.lr, momentum=0.9)
     optimizer.setup(model)
     optimizer.add_hook(WeightDecay(rate=0.0005))
@@ -316,7 +350,7 @@ def run(args, keypoints=False):
             if rank == 0:
                 save_npz(os.path.join(args.out, 'model_%d.npz' % it), faster_rcnn)      # snapshot_object, train.py:134-137
                 torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets,
-                            'augment': augment_settings(args)},
+                            'augment': augment_settings(args), 'freeze': freeze},
                            os.path.join(args.out, 'trainer_%d.pt' % it))
     if loader is not None:
         loader.close()
