@@ -328,6 +328,51 @@ def sgd_momentum_wd_masked(p, g, v, offset, frozen_blocks, lr, momentum=0.9, wei
                                                  frozen_blocks.numel() * 32, lr, momentum, weight_decay, stream_ptr()))
 
 
+# the optimizer's device-resident hyper block (include/mrcnn_hip.h: MRCNN_HYPER_*)
+HYPER_FLOATS, HYPER_LR, HYPER_A, HYPER_THRESHOLD, HYPER_SCALE, HYPER_NORM, HYPER_RATE, HYPER_SKIPPED = 8, 0, 1, 2, 3, 4, 5, 6
+
+
+def _mask_args(frozen_blocks):
+    return ptr(frozen_blocks), 0 if frozen_blocks is None else frozen_blocks.numel() * 32
+
+
+def grad_accumulate(acc, g, offset=0, frozen_blocks=None, first=False):
+    """acc = g (first) or acc += g over a section (views starting at element ``offset`` of the flat buffers); frozen blocks untouched."""
+    _ck(acc, g, frozen_blocks)
+    if acc.numel() != g.numel():
+        raise ValueError('grad_accumulate: acc and g differ in size')
+    mp, nb = _mask_args(frozen_blocks)
+    check(lib().mrcnn_grad_accumulate_f32(ptr(acc), ptr(g), g.numel(), int(offset), mp, nb, int(first), stream_ptr()))
+
+
+def grad_norm_workspace(n, device):
+    """A workspace of its own for grad_norm_hyper over n elements (the optimizer keeps one: its partial sums never share a buffer)."""
+    return torch.empty(max(int(lib().mrcnn_grad_norm_workspace_bytes(int(n))), 8), dtype=torch.uint8, device=device)
+
+
+def grad_norm_hyper(g, hyper, acc=None, offset=0, frozen_blocks=None, ws=None):
+    """The clipped-gradient scale of the WHOLE buffer into the hyper block: norm = sqrt(sum (acc + g)^2) * a in double, rate, scale
+    (include/mrcnn_hip.h).  Nothing comes back to the host.  ws: grad_norm_workspace (default: the stream's scratch buffer)."""
+    _ck(g, hyper, acc, frozen_blocks, ws)
+    if hyper.numel() < HYPER_FLOATS or (acc is not None and acc.numel() != g.numel()):
+        raise ValueError('grad_norm_hyper: hyper block too small, or acc and g differ in size')
+    if ws is None:
+        ws = workspace(lib().mrcnn_grad_norm_workspace_bytes(g.numel()), g.device)
+    mp, nb = _mask_args(frozen_blocks)
+    check(lib().mrcnn_grad_norm_hyper_f32(ptr(acc), ptr(g), g.numel(), int(offset), mp, nb, ptr(hyper), ptr(ws), ws.numel() * ws.element_size(),
+                                          stream_ptr()))
+
+
+def sgd_momentum_wd_hyper(p, g, v, hyper, acc=None, offset=0, frozen_blocks=None, momentum=0.9, weight_decay=5e-4):
+    """sgd_momentum_wd of gs = (acc + g) * scale with the learning rate and the scale read from the hyper block on the device."""
+    _ck(p, g, v, hyper, acc, frozen_blocks)
+    if hyper.numel() < HYPER_FLOATS or g.numel() != p.numel() or v.numel() != p.numel() or (acc is not None and acc.numel() != p.numel()):
+        raise ValueError('sgd_momentum_wd_hyper: hyper block too small, or the sections differ in size')
+    mp, nb = _mask_args(frozen_blocks)
+    check(lib().mrcnn_sgd_momentum_wd_hyper_f32(ptr(p), ptr(acc), ptr(g), ptr(v), p.numel(), int(offset), mp, nb, ptr(hyper), momentum,
+                                                weight_decay, stream_ptr()))
+
+
 # ---- losses -------------------------------------------------------------------------------------
 def _loss_ws(dev):
     return workspace(lib().mrcnn_loss_workspace_bytes(), dev)

@@ -85,6 +85,46 @@ class WeightDecay(object):
         self.rate = rate
 
 
+class GradientClipping(object):
+    """Clip the gradient by its global L2 norm: with ``norm`` over the threshold the gradient is multiplied by ``threshold / norm``.
+
+    The norm is that of the RAW effective gradient over the trainable parameters: summed over ranks and micro-batches, after averaging
+    where averaging is on (``--grad-average``, ``average_accumulated``), and BEFORE weight decay is added - unlike Chainer, where the
+    hooks run in the order they were added and a WeightDecay hook added first would enter the norm.  Frozen parameters do not count.
+    A non-finite norm skips the update (gradient taken as zero: momentum decays, weight decay acts) and is counted in
+    ``optimizer.skipped_updates``.  Everything happens on the device; nothing is read back."""
+
+    def __init__(self, threshold):
+        threshold = float(threshold)
+        if not threshold > 0.0:
+            raise ValueError('GradientClipping: the threshold must be positive, got %r' % (threshold,))
+        self.threshold = threshold
+
+
+class LRSchedule(object):
+    """Linear warmup and step drops: the learning rate of the 1-based update ``it`` is
+    ``base_lr * w(it) * gamma ** #{s in steps : s < it}`` with ``w(it) = f + (1 - f) * (it - 1) / W`` for ``it <= W`` and 1 behind it
+    (f = warmup_factor, W = warmup_iterations).  A function of ``it`` alone: a resumed run needs no stored learning rate."""
+
+    def __init__(self, base_lr, warmup_iterations=0, warmup_factor=1.0 / 3, steps=(), gamma=0.1):
+        if warmup_iterations < 0 or any(s <= 0 for s in steps):
+            raise ValueError('LRSchedule: warmup_iterations must be >= 0 and every step positive')
+        self.base_lr, self.warmup_iterations, self.warmup_factor = float(base_lr), int(warmup_iterations), float(warmup_factor)
+        self.steps, self.gamma = tuple(sorted(int(s) for s in steps)), float(gamma)
+
+    def lr_at(self, it):
+        if it < 1:
+            raise ValueError('LRSchedule.lr_at: updates are counted from 1')
+        W, f = self.warmup_iterations, self.warmup_factor
+        w = f + (1.0 - f) * (it - 1) / W if it <= W else 1.0
+        return self.base_lr * w * self.gamma ** sum(1 for s in self.steps if s < it)
+
+    def describe(self):
+        """What a trainer state records of it."""
+        return {'base_lr': self.base_lr, 'warmup_iterations': self.warmup_iterations, 'warmup_factor': self.warmup_factor,
+                'steps': list(self.steps), 'gamma': self.gamma}
+
+
 class GradientSynchronizer(object):
     """Bucketed all-reduce of the flat gradient buffer, overlapped with backward.
 
@@ -119,6 +159,9 @@ class GradientSynchronizer(object):
         # update of exactly those parameters (MomentumSGD.sectioned_update).  With a callback the buckets are also walked when there is
         # nothing to reduce (one rank): the update of a finished section then runs beside the rest of the backward pass.
         self.after_bucket = None
+        # before_bucket(start, end) (optional): called once per bucket, on the bucket's stream, in front of its all-reduce - the
+        # optimizer adds its accumulated micro-batch gradients there, so that an accumulated update costs one all-reduce per bucket
+        self.before_bucket = None
 
     def begin(self):
         self.next = 0
@@ -141,6 +184,8 @@ class GradientSynchronizer(object):
             from chainer_maskrcnn._hip import nn as hnn
             self.stream.wait_stream(hnn.side_stream(self.grads.device))   # ... on the main and on the weight-gradient stream
             with torch.cuda.stream(self.stream):
+                if self.before_bucket is not None:
+                    self.before_bucket(start, end)
                 if self.active:
                     ev = None
                     if self.timing:
@@ -153,13 +198,18 @@ class GradientSynchronizer(object):
                 if self.after_bucket is not None:
                     self.after_bucket(start, end)
         else:
+            if self.before_bucket is not None:
+                self.before_bucket(start, end)
             if self.active:
                 self._all_reduce(sl)
             if self.after_bucket is not None:
                 self.after_bucket(start, end)
 
+    def _walks(self):
+        return self.active or self.after_bucket is not None or self.before_bucket is not None
+
     def mark_ready(self, offset):
-        if not (self.active or self.after_bucket is not None):
+        if not self._walks():
             return
         while self.next < len(self.buckets) and self.buckets[self.next][0] >= offset:
             self._reduce(*self.buckets[self.next])
@@ -167,7 +217,7 @@ class GradientSynchronizer(object):
 
     def finish(self):
         """All buckets reduced (and updated, with a callback) and visible to the compute stream."""
-        if not (self.active or self.after_bucket is not None):
+        if not self._walks():
             return
         self.mark_ready(0)
         if self.stream is not None:
@@ -194,7 +244,8 @@ class GradientSynchronizer(object):
 class MomentumSGD(object):
     LOCAL_BUCKET_BYTES = 8 << 20        # sections of the one-rank sectioned update (the data-parallel path uses its all-reduce buckets)
 
-    def __init__(self, lr=0.01, momentum=0.9, high_priority_stream=None, sectioned_update=None):
+    def __init__(self, lr=0.01, momentum=0.9, high_priority_stream=None, sectioned_update=None, average_accumulated=False,
+                 device_lr=False):
         """high_priority_stream (default: on, MRCNN_STEP_STREAM_PRIORITY=0 turns it off): ``update(lossfun, ...)`` issues the
         step on a HIGH-priority HIP stream.  The step's main stream is the critical path (forward, data gradients); the
         weight-gradient and auxiliary streams only have to be done by the end of the step, and at equal priority their
@@ -208,8 +259,23 @@ class MomentumSGD(object):
         (tests/test_step_gpu.py).  Measured on configs[2], one process (tools/ab_step.py): 21.47 ms single pass, 21.52 ms with
         8-MB sections, 21.57 ms with 25-MB sections - the step is bound by the chip's throughput, the update's 0.9 GB
         cost the same HBM time beside the backward pass as behind it, so the single pass stays the default.  An exception raised
-        inside the backward pass leaves the sections already finished updated."""
+        inside the backward pass leaves the sections already finished updated.
+
+        average_accumulated: an update that consumed k micro-batches (``accumulate``) applies their mean instead of their sum.
+
+        device_lr: the update reads the learning rate from the optimizer's device-resident hyper block instead of taking it as a
+        kernel argument - same bits; a GraphedStep then follows a changing ``lr`` without capturing again.  A GradientClipping hook
+        and a pending accumulator use the hyper block whatever this says."""
         self.lr, self.momentum = lr, momentum
+        self.average_accumulated = bool(average_accumulated)
+        self.device_lr = bool(device_lr)
+        self.clip_threshold = 0.0           # GradientClipping hook (0: none)
+        self.pending = 0                    # micro-batches waiting in the accumulator
+        self._acc = None                    # the accumulator: one more flat buffer, allocated by the first accumulate()
+        self._hyper = None                  # device-resident hyper block (ops.HYPER_*), its views, and what the host last placed in it
+        self._hyper_views = None
+        self._placed = {}
+        self._norm_ws = None
         if sectioned_update is None:
             import os
             sectioned_update = os.environ.get('MRCNN_SECTIONED_UPDATE', '0') == '1'
@@ -245,8 +311,56 @@ class MomentumSGD(object):
     def add_hook(self, hook):
         if isinstance(hook, WeightDecay):
             self.weight_decay = hook.rate
+        elif isinstance(hook, GradientClipping):
+            self.clip_threshold = hook.threshold
         else:
-            raise TypeError('only WeightDecay hooks exist on this path (train.py:109)')
+            raise TypeError('only WeightDecay (train.py:109) and GradientClipping hooks exist on this path')
+
+    # ---- the device-resident hyper block ------------------------------------------------------------------------------
+    @property
+    def uses_hyper_block(self):
+        """The update reads lr and the gradient scale from the device (a clipping hook, device_lr, or a pending accumulator)."""
+        return self.device_lr or self.clip_threshold > 0.0 or self.pending > 0
+
+    def _hyper_block(self):
+        if self._hyper is None or self._hyper.device != self.ps.params.device:
+            h = self._hyper = torch.zeros(ops.HYPER_FLOATS, dtype=torch.float32, device=self.ps.params.device)
+            self._hyper_views = {k: h[i:i + 1] for k, i in (('lr', ops.HYPER_LR), ('a', ops.HYPER_A), ('threshold', ops.HYPER_THRESHOLD),
+                                                            ('scale', ops.HYPER_SCALE))}
+            self._hyper_views['norm'] = h[ops.HYPER_NORM]
+            self._hyper_views['skipped'] = h[ops.HYPER_SKIPPED:ops.HYPER_SKIPPED + 1].view(torch.int32)[0]
+            self._placed = {}
+        return self._hyper
+
+    def _place_hyper(self, k):
+        """lr, a (1 or 1/k) and the threshold into the hyper block - and scale = a when no norm kernel will write it.  One ``fill_``
+        (a kernel with a scalar argument, on the current stream: no staging buffer, no synchronisation) per value that CHANGED.
+        Never inside a stream capture: a captured fill would bake the value into the graph - GraphedStep places before it replays."""
+        self._hyper_block()
+        a = 1.0 / k if (self.average_accumulated and k > 1) else 1.0
+        want = {'lr': float(self.lr), 'a': a}
+        if self.clip_threshold > 0.0:
+            want['threshold'] = float(self.clip_threshold)
+        else:
+            want['scale'] = a
+        stale = {n: x for n, x in want.items() if self._placed.get(n) != x}
+        if not stale:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('MomentumSGD: the hyper block must be placed before the step is captured (%s changed)' % sorted(stale))
+        for n, x in stale.items():
+            self._hyper_views[n].fill_(x)
+            self._placed[n] = x
+
+    @property
+    def grad_norm(self):
+        """Device scalar: the gradient norm the last clipped update saw (``float()`` it to read - that synchronises)."""
+        return None if self._hyper is None else self._hyper_views['norm']
+
+    @property
+    def skipped_updates(self):
+        """Device int32 scalar: updates skipped because their gradient norm was not finite."""
+        return None if self._hyper is None else self._hyper_views['skipped']
 
     def enable_data_parallel(self, bucket_bytes=25 << 20, average=False, broadcast=True, sync_single_rank=False):
         """One process per GPU; every rank keeps a replica and applies the same update to the summed gradients.  The
@@ -271,10 +385,13 @@ class MomentumSGD(object):
     def state_dict(self):
         """Everything a bit-identical continuation needs: parameters, momentum, BatchNorm running statistics, the
         update count, the hyper-parameters and the device-resident sampler seeds of the train chain."""
+        if self.pending > 0:
+            raise RuntimeError('MomentumSGD.state_dict: %d accumulated micro-batch(es) are waiting for their update' % self.pending)
         ps = self.ps
         d = {'params': ps.params.detach().cpu(), 'momentum': ps.momentum.detach().cpu(),
              'buffers': {k: v.detach().cpu() for k, v in ps.buffers.items()},
-             't': self.t, 'lr': self.lr, 'sgd_momentum': self.momentum, 'weight_decay': self.weight_decay, 'samplers': {}}
+             't': self.t, 'lr': self.lr, 'sgd_momentum': self.momentum, 'weight_decay': self.weight_decay, 'samplers': {},
+             'clip_threshold': self.clip_threshold, 'average_accumulated': self.average_accumulated}
         for name in ('proposal_target_creator', 'anchor_target_creator'):
             c = getattr(self.target, name, None)
             if c is not None:
@@ -291,6 +408,9 @@ class MomentumSGD(object):
         for k, v in d['buffers'].items():
             ps.buffers[k].copy_(v)
         self.t, self.lr, self.momentum, self.weight_decay = d['t'], d['lr'], d['sgd_momentum'], d['weight_decay']
+        self.clip_threshold = d.get('clip_threshold', 0.0)              # (files from before these existed: both off)
+        self.average_accumulated = d.get('average_accumulated', False)
+        self.pending = 0
         for name, st in d.get('samplers', {}).items():
             c = getattr(self.target, name, None)
             if c is not None:
@@ -299,16 +419,49 @@ class MomentumSGD(object):
 
     def update(self, lossfun=None, *args, **kwds):
         """Chainer semantics: with ``lossfun`` -> loss = lossfun(*args); backward; update.  Without: update only."""
+        return self._on_step_stream(self._update, lossfun, *args, **kwds)
+
+    def accumulate(self, lossfun, *args, **kwds):
+        """One micro-batch of a larger update: forward and backward exactly as ``update(lossfun, ...)`` runs them, then the gradient is
+        added into the accumulator (csrc/optim.hip; the buffer is allocated by the first call).  Parameters, momentum and ``t`` do not
+        change and no collective is issued.  The next ``update(lossfun, ...)`` is the LAST micro-batch: it applies accumulator + its own
+        gradient in one pass and empties the accumulator; ``update()`` applies the accumulator alone.  Returns the loss."""
+        return self._on_step_stream(self._accumulate, lossfun, *args, **kwds)
+
+    def _on_step_stream(self, fn, lossfun, *args, **kwds):
         hi = self._step_stream() if lossfun is not None else None
         if hi is None:
-            return self._update(lossfun, *args, **kwds)
+            return fn(lossfun, *args, **kwds)
         cur = torch.cuda.current_stream(hi.device)
         if cur == hi:
-            return self._update(lossfun, *args, **kwds)
+            return fn(lossfun, *args, **kwds)
         hi.wait_stream(cur)                     # inputs produced on the caller's stream
         with torch.cuda.stream(hi):
-            loss = self._update(lossfun, *args, **kwds)
+            loss = fn(lossfun, *args, **kwds)
         cur.wait_stream(hi)                     # the caller's stream sees the updated parameters / loss (no host sync)
+        return loss
+
+    def _accumulate(self, lossfun, *args, **kwds):
+        if lossfun is None:
+            raise TypeError('MomentumSGD.accumulate needs the loss function')
+        ps = self.ps
+        if ps.params.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('MomentumSGD.accumulate: an accumulated update cannot be captured into a graph')
+        if self._acc is None or self._acc.shape != ps.grads.shape or self._acc.device != ps.grads.device:
+            if self.pending:
+                raise RuntimeError('MomentumSGD.accumulate: the gradient buffer changed under a pending accumulator')
+            self._acc = torch.empty_like(ps.grads)
+        # a data-parallel chain reports finished gradients to the synchronizer: not for a micro-batch that is only accumulated
+        hooked = self.sync is not None and getattr(lossfun, 'grad_ready_hook', None) is not None
+        if hooked:
+            hook, lossfun.grad_ready_hook = lossfun.grad_ready_hook, None
+        try:
+            loss = self._forward_backward(lossfun, *args, **kwds)
+        finally:
+            if hooked:
+                lossfun.grad_ready_hook = hook
+        ops.grad_accumulate(self._acc, ps.grads, 0, ps.frozen_mask, first=self.pending == 0)
+        self.pending += 1
         return loss
 
     def _sgd_section(self, start, end):
@@ -326,13 +479,17 @@ class MomentumSGD(object):
         """The fused update of the slice that starts at element ``start`` of the flat buffers; with frozen parameters
         (ParamStore.set_frozen) the kernel that skips their blocks."""
         mask = self.ps.frozen_mask
-        if mask is None:
+        if self.uses_hyper_block:           # (sections: device_lr alone - a clipping hook or an accumulator turn sectioning off)
+            ops.sgd_momentum_wd_hyper(p, g, v, self._hyper, None, start, mask, self.momentum, self.weight_decay)
+        elif mask is None:
             ops.sgd_momentum_wd(p, g, v, self.lr, self.momentum, self.weight_decay)
         else:
             ops.sgd_momentum_wd_masked(p, g, v, start, mask, self.lr, self.momentum, self.weight_decay)
 
     def _sectioning(self, lossfun):
         """The synchronizer that walks the sections of this update, or None (plain single pass)."""
+        if self.pending > 0 or self.clip_threshold > 0.0:
+            return None                                             # the norm needs the whole gradient
         if not self.sectioned_update or lossfun is None or not hasattr(lossfun, 'grad_ready_hook') or not self.ps.params.is_cuda:
             return None
         if torch.cuda.is_current_stream_capturing():
@@ -363,32 +520,77 @@ class MomentumSGD(object):
                     lossfun.grad_ready_hook = None
         return loss
 
+    def _forward_backward(self, lossfun, *args, **kwds):
+        """loss = lossfun(...); loss.backward() the way the step runs them (the chain is told that the backward pass follows)."""
+        if hasattr(lossfun, 'backward_follows'):    # the train chain may start branches of the backward pass inside its forward call
+            lossfun.backward_follows = True
+        try:
+            loss = lossfun(*args, **kwds)
+        finally:
+            if hasattr(lossfun, 'backward_follows'):
+                lossfun.backward_follows = False
+        if hasattr(lossfun, 'unit_upstream'):       # the train chain: d loss = 1 here, no gradient-scaling pass
+            lossfun.unit_upstream = True
+        try:
+            loss.backward()
+        finally:
+            if hasattr(lossfun, 'unit_upstream'):
+                lossfun.unit_upstream = False
+        return loss
+
+    def _add_accumulator(self, start, end):
+        """GradientSynchronizer.before_bucket of a data-parallel update that closes an accumulation: g[bucket] += acc[bucket]."""
+        ops.grad_accumulate(self.ps.grads[start:end], self._acc[start:end], start, self.ps.frozen_mask, first=False)
+
+    def _set_accumulator(self, start, end):
+        """... of ``update()`` without a loss function: the accumulator IS the gradient, g[bucket] = acc[bucket]."""
+        ops.grad_accumulate(self.ps.grads[start:end], self._acc[start:end], start, self.ps.frozen_mask, first=True)
+
     def _step(self, lossfun, sect, *args, **kwds):
         loss = None
-        if lossfun is not None:
-            if self.sync is not None:
+        ps = self.ps
+        pending = self.pending
+        k = pending + (1 if lossfun is not None else 0)         # micro-batches this update consumes
+        acc = self._acc if pending > 0 else None
+        if self.uses_hyper_block:
+            self._place_hyper(k)
+        if self.sync is not None and acc is not None:
+            # the ranks exchange accumulator + last gradient: added bucket by bucket in front of each all-reduce
+            self.sync.before_bucket = self._add_accumulator if lossfun is not None else self._set_accumulator
+            if lossfun is None:
                 self.sync.begin()
-            if hasattr(lossfun, 'backward_follows'):    # the train chain may start branches of the backward pass inside its forward call
-                lossfun.backward_follows = True
-            try:
-                loss = lossfun(*args, **kwds)
-            finally:
-                if hasattr(lossfun, 'backward_follows'):
-                    lossfun.backward_follows = False
-            if hasattr(lossfun, 'unit_upstream'):       # the train chain: d loss = 1 here, no gradient-scaling pass
-                lossfun.unit_upstream = True
-            try:
-                loss.backward()
-            finally:
-                if hasattr(lossfun, 'unit_upstream'):
-                    lossfun.unit_upstream = False
-        if self.sync is not None:
-            self.sync.finish()
-        elif sect is not None:
-            sect.finish()
-        rest = self.ps.params.numel() if self._updated_down_to is None else self._updated_down_to
-        if rest > 0:        # everything (no sections), or what no section covered
-            self._sgd(self.ps.params[:rest], self.ps.grads[:rest], self.ps.momentum[:rest], 0)
+        try:
+            if lossfun is not None:
+                if self.sync is not None:
+                    self.sync.begin()
+                loss = self._forward_backward(lossfun, *args, **kwds)
+            if self.sync is not None:
+                self.sync.finish()
+                if self.sync.before_bucket is not None:
+                    acc = None                                  # it is in the (reduced) gradient buffer now
+            elif sect is not None:
+                sect.finish()
+        finally:
+            if self.sync is not None:
+                self.sync.before_bucket = None
+        if not self.uses_hyper_block:
+            rest = ps.params.numel() if self._updated_down_to is None else self._updated_down_to
+            if rest > 0:        # everything (no sections), or what no section covered
+                self._sgd(ps.params[:rest], ps.grads[:rest], ps.momentum[:rest], 0)
+        else:
+            g = ps.grads
+            if lossfun is None and acc is not None:
+                g, acc = acc, None                              # update() after accumulate(): the accumulator alone
+            rest = ps.params.numel() if self._updated_down_to is None else self._updated_down_to
+            if self.clip_threshold > 0.0:
+                if self._norm_ws is None or self._norm_ws.device != g.device:
+                    self._norm_ws = ops.grad_norm_workspace(g.numel(), g.device)
+                ops.grad_norm_hyper(g, self._hyper, acc, 0, ps.frozen_mask, ws=self._norm_ws)
+                self._placed.pop('scale', None)                 # the device wrote it
+            if rest > 0:
+                ops.sgd_momentum_wd_hyper(ps.params[:rest], g[:rest], ps.momentum[:rest], self._hyper, None if acc is None else acc[:rest],
+                                          0, ps.frozen_mask, self.momentum, self.weight_decay)
+        self.pending = 0
         self.t += 1
         return loss
 
@@ -406,6 +608,8 @@ class GraphedStep(object):
     def __init__(self, optimizer, chain, example_batch, scale=1.0, warmup=3):
         if optimizer.sync is not None:
             raise RuntimeError('GraphedStep: data-parallel steps run eagerly')
+        if optimizer.pending > 0:
+            raise RuntimeError('GraphedStep: %d accumulated micro-batch(es) are pending - an accumulated update runs eagerly' % optimizer.pending)
         self.optimizer, self.chain, self.scale = optimizer, chain, scale
         # graph replay and the eager high-priority step stream do not mix: with that stream created in the process the replay
         # of the captured step measured 36.4 ms instead of 26.6 ms (ROCm 7.2); a graphed optimizer stays on normal priority
@@ -423,9 +627,13 @@ class GraphedStep(object):
 
     def _capture(self):
         # the learning rate is a kernel argument baked into the captured launch: re-capture when it changes
-        # (ExponentialShift('lr', 0.1), train.py:139-140)
+        # (ExponentialShift('lr', 0.1), train.py:139-140) - unless the update reads it from the optimizer's hyper block on the device:
+        # then the captured step holds no learning rate, clip threshold or scale at all and __call__ places them in front of the replay
         self._lr = self.optimizer.lr
+        self._hyper = self._hyper_state()
         self._freeze = self._freeze_state()
+        if self._hyper[0]:
+            self.optimizer._place_hyper(1)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.optimizer.update(self.chain, *self.static, self.scale)
@@ -434,10 +642,20 @@ class GraphedStep(object):
         # MaskRCNN.freeze changes which kernels the step launches: part of what a capture is valid for
         return getattr(getattr(self.chain, 'faster_rcnn', None), 'freeze_state', None)
 
+    def _hyper_state(self):
+        # which update kernels the step launches: plain, from the hyper block, with the norm in front
+        return (self.optimizer.uses_hyper_block, self.optimizer.clip_threshold > 0.0)
+
     def __call__(self, *batch):
-        if self.optimizer.lr != self._lr or self._freeze_state() != self._freeze:
+        opt = self.optimizer
+        if opt.pending > 0:
+            raise RuntimeError('GraphedStep: %d accumulated micro-batch(es) are pending - an accumulated update runs eagerly' % opt.pending)
+        hyper = self._hyper_state()
+        if (opt.lr != self._lr and not hyper[0]) or hyper != self._hyper or self._freeze_state() != self._freeze:
             torch.cuda.synchronize()
             self._capture()
+        if hyper[0]:
+            opt._place_hyper(1)             # lr / threshold that changed: a fill_ in front of the replay, not part of the graph
         for dst, src in zip(self.static, batch):
             if src is not dst:
                 dst.copy_(src, non_blocking=True)

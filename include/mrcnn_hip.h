@@ -796,6 +796,45 @@ int mrcnn_bn_frozen_bwd_pair_f32(const float *gy, const float *y, const float *g
 int mrcnn_sgd_momentum_wd_masked_f32(float *p, const float *g, float *v, size_t n, size_t offset, const uint32_t *frozen_blocks,
                                      size_t n_blocks, float lr, float momentum, float weight_decay, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Gradient accumulation, gradient-norm clipping and the update with a device-resident learning rate (optim.hip).  float32 streaming
+ * kernels over sections of the flat buffers, addressed like mrcnn_sgd_momentum_wd_masked_f32: n elements starting at element `offset`
+ * of the flat buffer, every data pointer points AT that element of a 16-byte aligned flat buffer; frozen_blocks is that function's
+ * mask (n_blocks >= ceil((offset + n) / 64)) or NULL = nothing frozen (n_blocks is then ignored); elements of frozen blocks are neither
+ * read nor written.  No host synchronisation, no atomics; the same input gives the same bits on every run.
+ *
+ * The hyper block is MRCNN_HYPER_FLOATS floats of device memory owned by the caller:
+ *   [MRCNN_HYPER_LR] learning rate, [MRCNN_HYPER_A] a = 1 or 1 / (number of micro-batches), [MRCNN_HYPER_THRESHOLD] clip threshold
+ *   (+inf: never clip) - placed by the caller; [MRCNN_HYPER_SCALE], [MRCNN_HYPER_NORM], [MRCNN_HYPER_RATE] - written by grad_norm_hyper
+ *   (a caller that takes no norm places scale = a itself); [MRCNN_HYPER_SKIPPED] a uint32 counter of skipped updates.
+ *
+ * grad_accumulate: acc = g (first != 0) or acc = acc + g.  acc != g.
+ * grad_norm_hyper: S = sum of (acc + g)^2 (acc NULL: g^2) over the trainable elements, every square and every partial sum in double,
+ *   combined in a fixed order (per-block partials in `workspace`, mrcnn_grad_norm_workspace_bytes(n) bytes, 8-byte aligned); then, on
+ *   the device, norm = (float)sqrt(S) * a; rate = norm > threshold ? threshold / norm : 1.0f; scale = a * rate.  A non-finite norm gives
+ *   rate = scale = 0 and increments the skipped counter.  The norm is taken over ONE section: pass the whole buffer.
+ * sgd_momentum_wd_hyper: ge = acc + g (acc NULL: g); gs = ge * scale; v = momentum * v - lr * (gs + wd * p); p += v, with lr and scale
+ *   read from the hyper block.  scale == 0 takes gs = 0 whatever ge holds (a skipped update: inf * 0 would be nan).  With scale == 1.0f
+ *   and acc NULL the bits of mrcnn_sgd_momentum_wd_f32 / _masked_f32.  n == 0 is a no-op (also for grad_accumulate).
+ * Errors, before any launch: MRCNN_E_INVALID for a NULL or misaligned pointer, a section outside the mask, a workspace too small.
+ * ---------------------------------------------------------------------------------------- */
+#define MRCNN_HYPER_FLOATS 8
+#define MRCNN_HYPER_LR 0
+#define MRCNN_HYPER_A 1
+#define MRCNN_HYPER_THRESHOLD 2
+#define MRCNN_HYPER_SCALE 3
+#define MRCNN_HYPER_NORM 4
+#define MRCNN_HYPER_RATE 5
+#define MRCNN_HYPER_SKIPPED 6
+int mrcnn_grad_accumulate_f32(float *acc, const float *g, size_t n, size_t offset, const uint32_t *frozen_blocks, size_t n_blocks,
+                              int first, void *stream);
+size_t mrcnn_grad_norm_workspace_bytes(size_t n);
+int mrcnn_grad_norm_hyper_f32(const float *acc, const float *g, size_t n, size_t offset, const uint32_t *frozen_blocks, size_t n_blocks,
+                              float *hyper, void *workspace, size_t workspace_bytes, void *stream);
+int mrcnn_sgd_momentum_wd_hyper_f32(float *p, const float *acc, const float *g, float *v, size_t n, size_t offset,
+                                    const uint32_t *frozen_blocks, size_t n_blocks, const float *hyper, float momentum, float weight_decay,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ import torch  # noqa: E402
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
 AUGMENT_SEED = 5678                 # seed of the per-example augmentation decisions (dataset/augment.py), recorded in trainer_<it>.pt
 NO_FREEZE = {'bn': 0, 'at': 0}       # what a trainer state without the 'freeze' key was trained with
+NO_OPTIM = {'accum_steps': 1, 'grad_clip': 0.0, 'schedule': None}      # what a trainer state without the 'optim' key was trained with
 NO_AUGMENT = {'hflip': 0, 'min_sizes': None, 'seed': AUGMENT_SEED}     # what a trainer state without the 'augment' key was trained with
 
 
@@ -103,7 +104,50 @@ def build_parser(keypoints=False):
     parser.add_argument('--freeze-at', type=int, default=0, choices=[0, 1, 2, 3, 4, 5],
                         help='k: the stem and the stages res2 .. res{k} are not trained and take no backward pass (1: stem only, 2: the usual '
                              'fine-tuning recipe, 5: the whole ResNet); needs --freeze-bn 1')
+    # train_keypoints.py spells its flags with underscores: it takes both spellings of these
+    both = (lambda name: (name.replace('-', '_').replace('__', '--', 1), name)) if keypoints else (lambda name: (name,))
+    parser.add_argument(*both('--accum-steps'), type=int, default=1, metavar='K',
+                        help='gradient accumulation: one iteration stays one optimizer update and consumes K batches (K-1 x accumulate, then '
+                             'update) - the step the reference takes with K workers of one batch each; images/sec counts all of them, the '
+                             'logged losses are those of the iteration\'s LAST micro-batch; --grad-average 1 also averages over K')
+    parser.add_argument(*both('--grad-clip'), type=float, default=0.0, metavar='T',
+                        help='clip the gradient to global L2 norm T (optimizers.GradientClipping: the raw summed / averaged gradient, before '
+                             'weight decay; a non-finite norm skips the update); logs main/grad_norm and skipped_updates.  0 = off')
+    parser.add_argument(*both('--warmup-iterations'), type=int, default=0, metavar='W',
+                        help='linear learning-rate warmup over the first W updates, from --warmup-factor x lr (optimizers.LRSchedule)')
+    parser.add_argument(*both('--warmup-factor'), type=float, default=1.0 / 3, metavar='F')
+    parser.add_argument(*both('--lr-steps'), type=int, nargs='+', default=None, metavar='S',
+                        help='lr x0.1 behind each of these iterations (e.g. 60000 80000 of 90000); not together with --lr-shift-interval')
     return parser
+
+
+def optim_settings(args):
+    """The optimizer-side recipe of a run as recorded in trainer_<it>.pt (NO_OPTIM when all off), with the LRSchedule it describes (or None);
+    raises on a refused combination."""
+    from chainer_maskrcnn.optimizers import LRSchedule
+    k, clip, W = int(args.accum_steps), float(args.grad_clip), int(args.warmup_iterations)
+    if k < 1:
+        raise ValueError('--accum-steps must be at least 1, got %d' % k)
+    if clip < 0 or clip != clip:
+        raise ValueError('--grad-clip must be positive (0 = off), got %r' % clip)
+    if W < 0:
+        raise ValueError('--warmup-iterations must not be negative, got %d' % W)
+    if args.lr_steps and args.lr_shift_interval:
+        raise ValueError('--lr-steps and --lr-shift-interval both schedule the learning-rate drops: give one of them')
+    schedule = None
+    if args.lr_steps or W > 0:
+        steps = args.lr_steps or ()
+        if args.lr_shift_interval:      # warmup in front of the periodic x0.1: the same drops, as a function of the iteration
+            steps = range(args.lr_shift_interval, args.iteration + 1, args.lr_shift_interval)
+        schedule = LRSchedule(args.lr, W, args.warmup_factor, steps)
+    return {'accum_steps': k, 'grad_clip': clip, 'schedule': None if schedule is None else schedule.describe()}, schedule
+
+
+def check_resume_optim(resume, args, path=''):
+    """A resumed run accumulates, clips and schedules as its checkpoint did (a state without the key: all off)."""
+    was, now = resume.get('optim', NO_OPTIM), optim_settings(args)[0]
+    if was != now:
+        raise ValueError('--resume %s: the checkpoint was trained with the optimizer recipe %r, this run asks for %r' % (path, was, now))
 
 
 def freeze_settings(args):
@@ -168,7 +212,7 @@ def _keypoint_flip_perm(args, data):
 def run(args, keypoints=False):
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss
-    from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay
+    from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay, GradientClipping
     from chainer_maskrcnn.utils.synthetic import make_batch
     world = int(os.environ.get('WORLD_SIZE', 1))
     rank = int(os.environ.get('RANK', 0))
@@ -191,6 +235,10 @@ def run(args, keypoints=False):
     freeze = freeze_settings(args)
     if resume is not None:
         check_resume_freeze(resume, args, args.resume)
+    optim, schedule = optim_settings(args)
+    if resume is not None:
+        check_resume_optim(resume, args, args.resume)
+    accum = optim['accum_steps']
     if freeze['bn'] and not (args.weight or args.resnet50_npz or args.resume) and rank == 0:
         print('warning: --freeze-bn 1 without --weight / --resnet50-npz / --resume freezes freshly initialised BatchNorm statistics '
               '(mean 0, variance 1)')
@@ -256,9 +304,11 @@ def run(args, keypoints=False):
         load_npz(args.weight, faster_rcnn)
     if freeze != NO_FREEZE:
         faster_rcnn.freeze(bn=bool(freeze['bn']), at=freeze['at'])
-    optimizer = MomentumSGD(lr=args.lr, momentum=0.9)
+    optimizer = MomentumSGD(lr=args.lr, momentum=0.9, average_accumulated=bool(args.grad_average))
     optimizer.setup(model)
     optimizer.add_hook(WeightDecay(rate=0.0005))
+    if optim['grad_clip'] > 0:
+        optimizer.add_hook(GradientClipping(optim['grad_clip']))
     if world > 1:
         optimizer.enable_data_parallel(average=bool(args.grad_average))
     bs = args.batch_size
@@ -298,17 +348,26 @@ def run(args, keypoints=False):
     rtx = _Roctx() if args.profile else None
     t0 = time.time()
     t_eval = 0.0            # seconds spent in evaluation: not part of the training throughput
-    for it in range(first_it, args.iteration + 1):
+    def next_batch(micro):
         if loader is not None:
             b = next(loader)
-            batch = [b[k] for k in ('imgs', 'bboxes', 'labels', 'keypoints' if keypoints else 'masks')]
             # every image keeps its own resize factor and its own size inside the padded batch (the reference runs batch 1
             # per process, so its img_size / scale are always those of THE image: fpn_maskrcnn_train_chain.py:60-70)
-            scale, sizes = b['scales'], b['sizes']
-        else:           # a small pool of device-resident synthetic batches, cycled (generating one per step is host-bound)
-            batch = pool[it % len(pool)]
-            scale, sizes = 1.0, None
-        if rtx is not None and args.profile[0] <= it <= args.profile[1]:
+            return [b[k] for k in ('imgs', 'bboxes', 'labels', 'keypoints' if keypoints else 'masks')], b['scales'], b['sizes']
+        # a small pool of device-resident synthetic batches, cycled (generating one per step is host-bound)
+        return pool[micro % len(pool)], 1.0, None
+
+    for it in range(first_it, args.iteration + 1):
+        if schedule is not None:
+            optimizer.lr = schedule.lr_at(it)
+        for j in range(accum - 1):      # --accum-steps: all but the last micro-batch of this update
+            batch, scale, sizes = next_batch((it - 1) * accum + j + 1)
+            optimizer.accumulate(model, *batch, scale, img_sizes=sizes)
+        batch, scale, sizes = next_batch(it * accum)
+        if rtx is not None and args.profile[0] <= it <= args.profile[1] and accum > 1:
+            with rtx.range('step %d' % it):         # (an update() without the loss function would apply the accumulator alone)
+                optimizer.update(model, *batch, scale, img_sizes=sizes)
+        elif rtx is not None and args.profile[0] <= it <= args.profile[1]:
             with rtx.range('step %d' % it):
                 with rtx.range('forward+backward'):
                     if optimizer.sync is not None:
@@ -330,11 +389,16 @@ def run(args, keypoints=False):
             t_eval += time.time() - te
         if it % args.log_interval == 0 or it == args.iteration or validation is not None:       # one device->host sync per log interval
             obs = {k: float(v) for k, v in model.observation.items()}
-            if any(not np.isfinite(v) for v in obs.values()):
+            # (with --grad-clip an update whose gradient is not finite has been skipped on the device: logged, not fatal)
+            if any(not np.isfinite(v) for v in obs.values()) and not optim['grad_clip'] > 0:
                 raise FloatingPointError('non-finite loss at iteration %d: %r' % (it, obs))
             entry = {'iteration': it, 'lr': optimizer.lr, 'elapsed_time': time.time() - t0,
-                     'images/sec': (it - first_it + 1) * bs * world / (time.time() - t0 - t_eval)}
+                     'images/sec': (it - first_it + 1) * accum * bs * world / (time.time() - t0 - t_eval)}
             entry.update({'main/' + k: v for k, v in obs.items()})
+            if optim['grad_clip'] > 0:
+                entry['main/grad_norm'] = float(optimizer.grad_norm)
+                if int(optimizer.skipped_updates):
+                    entry['skipped_updates'] = int(optimizer.skipped_updates)
             if validation is not None:
                 entry.update(validation)
             if rank == 0:
@@ -350,7 +414,7 @@ def run(args, keypoints=False):
             if rank == 0:
                 save_npz(os.path.join(args.out, 'model_%d.npz' % it), faster_rcnn)      # snapshot_object, train.py:134-137
                 torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets,
-                            'augment': augment_settings(args), 'freeze': freeze},
+                            'augment': augment_settings(args), 'freeze': freeze, 'optim': optim},
                            os.path.join(args.out, 'trainer_%d.pt' % it))
     if loader is not None:
         loader.close()
