@@ -849,3 +849,97 @@ def tta_keypoint_merge(heat, mirrors, K, perm=None):
     check(lib().mrcnn_tta_keypoint_merge_f32(ctypes.cast(p, ctypes.c_void_p), views.ctypes.data, V, D, S, Cp, K,
                                              pa.ctypes.data if pa is not None else None, ptr(out), stream_ptr()))
     return out
+
+
+# ---- rendering of detections (vis.hip) ------------------------------------------------------------------------------------------------
+# mrcnn_vis_prim_t of include/mrcnn_hip.h, one row per primitive; rgb = r | g << 8 | b << 16
+VIS_PRIM = np.dtype([(k, '<i4') for k in ('kind', 'x0', 'y0', 'x1', 'y1', 'p', 'rgb', 'a')])
+assert VIS_PRIM.itemsize == 32
+VIS_RECT, VIS_SEGMENT, VIS_DISC, VIS_GLYPH, VIS_FILL = range(5)
+VIS_DRAW_MASKS, VIS_DRAW_CONTOURS, VIS_DRAW_BOXES = 1, 2, 4
+VIS_MAX_SIDE, VIS_COORD_MIN, VIS_COORD_MAX, VIS_PARAM_MAX, VIS_GLYPH_SCALE_MAX, VIS_GLYPHS_MAX = 16384, -4096, 20479, 4096, 64, 256
+
+
+def check_vis_prims(prims):
+    """The primitive array as VIS_PRIM rows, every cap of include/mrcnn_hip.h checked on the host (the kernel cannot report a bad
+    descriptor; it would draw nothing for it).  ValueError names the first offending row."""
+    p = np.ascontiguousarray(prims)
+    if p.dtype != VIS_PRIM:
+        if p.dtype != np.int32 or p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError('vis primitives: a VIS_PRIM array or (P,8) int32 expected, got %s %s' % (p.dtype, p.shape))
+        p = p.view(VIS_PRIM).reshape(-1)
+    if p.ndim != 1:
+        raise ValueError('vis primitives: a flat VIS_PRIM array expected, got shape %s' % (p.shape,))
+    kind, two = p['kind'], np.isin(p['kind'], (VIS_RECT, VIS_SEGMENT, VIS_FILL))
+    p_min = np.select([kind == VIS_DISC, kind == VIS_FILL], [0, 0], 1)
+    p_max = np.where(kind == VIS_GLYPH, VIS_GLYPH_SCALE_MAX, VIS_PARAM_MAX)
+    bad = (kind < 0) | (kind > VIS_FILL) | (p['a'] < 0) | (p['a'] > 256) | (p['p'] < p_min) | (p['p'] > p_max)
+    bad |= (p['rgb'] < 0) | (p['rgb'] > 0xFFFFFF)
+    for k in ('x0', 'y0'):
+        bad |= (p[k] < VIS_COORD_MIN) | (p[k] > VIS_COORD_MAX)
+    for k in ('x1', 'y1'):
+        bad |= two & ((p[k] < VIS_COORD_MIN) | (p[k] > VIS_COORD_MAX))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError('vis primitives: row %d %s breaks a cap (coordinates %d..%d, p <= %d, glyph scale 1..%d, a 0..256, kind 0..4)'
+                         % (i, p[i], VIS_COORD_MIN, VIS_COORD_MAX, VIS_PARAM_MAX, VIS_GLYPH_SCALE_MAX))
+    return p
+
+
+def vis_render(img, masks=None, bbox=None, colors=None, order=None, mask_a256=128, box_thickness=1, flags=0, prims=None, font=None):
+    """img (3,H,W) float32 device tensor (RGB 0..255) -> (H,W,3) uint8 device tensor, drawn by mrcnn_vis_render_u8 (its contract: include/
+    mrcnn_hip.h).  masks (D,H,W) bool / uint8 and bbox (D,4) float32 on the device (None when not drawn), colors (D,3) uint8 (host array or
+    device tensor), order a host array of D instance indices (the drawing order; None: 0..D-1), prims a host VIS_PRIM array, font a host array of uint64 glyph bitmaps.  One launch; the only copies are the small
+    host->device uploads of colors, prims and font."""
+    _hip.require_cuda(img)
+    if img.dim() != 3 or img.shape[0] != 3 or img.dtype != f32:
+        raise ValueError('vis_render: a (3,H,W) float32 image expected, got %s %s' % (tuple(img.shape), img.dtype))
+    H, W = int(img.shape[1]), int(img.shape[2])
+    if H > VIS_MAX_SIDE or W > VIS_MAX_SIDE:
+        raise ValueError('vis_render: image %d x %d larger than %d a side' % (H, W, VIS_MAX_SIDE))
+    dev = img.device
+    img = img.contiguous()
+    D = 0
+    for name, t, tail in (('masks', masks, (H, W)), ('bbox', bbox, (4,)), ('colors', colors, (3,))):
+        if t is not None:
+            if tuple(t.shape[1:]) != tail or t.ndim != len(tail) + 1:
+                raise ValueError('vis_render: %s (D,%s) expected, got %s' % (name, ','.join(str(s) for s in tail), tuple(t.shape)))
+            D = max(D, int(t.shape[0]))
+    for name, t in (('masks', masks), ('bbox', bbox), ('colors', colors)):
+        if t is not None and int(t.shape[0]) != D:
+            raise ValueError('vis_render: %s has %d instances, another argument %d' % (name, int(t.shape[0]), D))
+    if D and colors is None:
+        raise ValueError('vis_render: colors (D,3) needed for %d instances' % D)
+    if masks is not None:
+        _hip.require_cuda(masks)
+        if masks.dtype not in (torch.bool, torch.uint8):
+            raise TypeError('vis_render: bool or uint8 masks expected, got %s' % masks.dtype)
+        masks = masks.contiguous().view(torch.uint8)
+    elif D and flags & (VIS_DRAW_MASKS | VIS_DRAW_CONTOURS):
+        raise ValueError('vis_render: masks needed to draw masks or contours')
+    if bbox is not None:
+        _hip.require_cuda(bbox)
+        bbox = bbox.to(f32).contiguous()
+    elif D and flags & VIS_DRAW_BOXES:
+        raise ValueError('vis_render: bbox needed to draw boxes')
+    if colors is not None:
+        if not isinstance(colors, torch.Tensor):
+            colors = torch.from_numpy(np.ascontiguousarray(colors, np.uint8))
+        if colors.dtype != torch.uint8:
+            raise TypeError('vis_render: uint8 colors expected, got %s' % colors.dtype)
+        colors = colors.to(dev).contiguous()
+    order_d = None
+    if order is not None and D:
+        o = np.ascontiguousarray(order, np.int32).reshape(-1)
+        if o.shape[0] != D or (o < 0).any() or (o >= D).any():
+            raise ValueError('vis_render: order must hold %d indices in 0..%d' % (D, D - 1))
+        order_d = torch.from_numpy(o).to(dev)
+    pr = check_vis_prims(prims) if prims is not None and len(prims) else None
+    prims_d = torch.from_numpy(pr.view(np.int32).reshape(-1, 8)).to(dev) if pr is not None else None
+    ft = np.ascontiguousarray(font, np.uint64).reshape(-1) if font is not None and len(font) else None
+    font_d = torch.from_numpy(ft.view(np.int64)).to(dev) if ft is not None else None
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    check(lib().mrcnn_vis_render_u8(ptr(img), H, W, ptr(masks), ptr(bbox), ptr(colors), ptr(order_d), D, int(mask_a256), int(box_thickness), int(flags),
+                                    ptr(prims_d), 0 if pr is None else int(pr.shape[0]), ptr(font_d), 0 if ft is None else int(ft.shape[0]),
+                                    ptr(out), stream_ptr()))
+    return out

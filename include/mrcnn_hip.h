@@ -835,6 +835,64 @@ int mrcnn_sgd_momentum_wd_hyper_f32(float *p, const float *acc, const float *g, 
                                     const uint32_t *frozen_blocks, size_t n_blocks, const float *hyper, float momentum, float weight_decay,
                                     void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rendering of detections (vis.hip; chainer_maskrcnn/vis.py, demo.py).  One launch turns an image and its
+ * detections into a picture on the device; integer arithmetic only, the same bytes on every run.
+ *   img (3,H,W) float32 RGB, values 0..255 as predict takes it; out (H,W,3) uint8 RGB, contiguous.
+ *   masks (D,H,W) bytes, any nonzero byte is a set pixel (rows may start at any byte offset); bbox (D,4) float32 (y1,x1,y2,x2);
+ *   colors (D,3) uint8; prims: n_prims descriptors in DEVICE memory, 16-byte aligned; font: n_glyphs uint64 in DEVICE memory, bit
+ *   5 * row + col of font[g] = pixel (row, col) of the 5 x 7 glyph g.
+ * Per pixel, painter's order:
+ *   c = min(255, max(0, floor(v + 0.5))) per channel (float32 arithmetic; NaN gives 0);
+ *   for d = order[0], .., order[D-1] (order: D int32 in DEVICE memory; NULL: d = 0..D-1; an index outside 0..D-1 draws nothing):
+ *                   MRCNN_VIS_DRAW_MASKS and mask[d] set: c = blend(c, colors[d], mask_a256);
+ *                   MRCNN_VIS_DRAW_CONTOURS and the pixel is set with a 4-neighbour that is unset or outside the image: c = colors[d];
+ *                   MRCNN_VIS_DRAW_BOXES and the pixel is on the outline (box_thickness) of the rectangle with the inclusive corners
+ *                   (top, left, bottom, right) = floor(bbox[d] + 0.5), each clamped to the coordinate range (NaN: its lower end):
+ *                   c = colors[d];
+ *   for every primitive in array order: the pixel is on it: c = blend(c, its rgb, its a).
+ *   blend(c, col, a) = (c * (256 - a) + col * a + 128) >> 8 per channel, a = round(alpha * 256) in [0, 256].
+ * Primitives (all fields int32; rgb = r | g << 8 | b << 16):
+ *   MRCNN_VIS_RECT     outline of the rectangle with inclusive corners (x0,y0)-(x1,y1), thickness p >= 1 growing inwards: a pixel of
+ *                      the rectangle with x < x0 + p or x > x1 - p or y < y0 + p or y > y1 - p;
+ *   MRCNN_VIS_SEGMENT  a = (x0,y0), b = (x1,y1), thickness p; with d = b - a, L = d.d, w = pixel - a, s = w.d, in int64:
+ *                      L == 0 or s <= 0: 4 |w|^2 <= p^2;  s >= L: 4 |pixel - b|^2 <= p^2;  otherwise 4 cross(w,d)^2 <= p^2 L;
+ *   MRCNN_VIS_DISC     |pixel - (x0,y0)|^2 <= p^2;
+ *   MRCNN_VIS_GLYPH    glyph x1 at scale p (1..MRCNN_VIS_GLYPH_SCALE_MAX), top-left (x0,y0): pixel (x,y) of the 5p x 7p cell is on
+ *                      when bit 5 * ((y - y0) / p) + (x - x0) / p of font[x1] is set; x1 outside 0..n_glyphs-1: the whole cell;
+ *   MRCNN_VIS_FILL     every pixel of the rectangle with inclusive corners (x0,y0)-(x1,y1).
+ * Everything is clipped to the image.  Caps: H, W <= MRCNN_VIS_MAX_SIDE; primitive coordinates and rounded box corners within
+ * MRCNN_VIS_COORD_MIN..MRCNN_VIS_COORD_MAX (the image and a margin of 4096 around it); p <= MRCNN_VIS_PARAM_MAX; a in 0..256.  With
+ * these no term of the segment rule exceeds 2^63.  A primitive that breaks a cap or has an unknown kind draws nothing (the host layer
+ * refuses it before the call).  D == 0, n_prims == 0 are valid; H * W == 0 is a no-op.  masks may be NULL when neither masks nor
+ * contours are drawn, bbox when boxes are not.
+ * Errors, before any launch: MRCNN_E_INVALID for H or W outside 0..MRCNN_VIS_MAX_SIDE, a negative D or n_prims, n_glyphs outside
+ * 0..MRCNN_VIS_GLYPHS_MAX, unknown flags, mask_a256 outside 0..256, box_thickness outside 1..MRCNN_VIS_PARAM_MAX, a NULL or
+ * misaligned pointer of a side that is used.
+ * ---------------------------------------------------------------------------------------- */
+#define MRCNN_VIS_MAX_SIDE 16384
+#define MRCNN_VIS_COORD_MIN (-4096)
+#define MRCNN_VIS_COORD_MAX 20479
+#define MRCNN_VIS_PARAM_MAX 4096
+#define MRCNN_VIS_GLYPH_W 5
+#define MRCNN_VIS_GLYPH_H 7
+#define MRCNN_VIS_GLYPH_SCALE_MAX 64
+#define MRCNN_VIS_GLYPHS_MAX 256
+#define MRCNN_VIS_DRAW_MASKS 1
+#define MRCNN_VIS_DRAW_CONTOURS 2
+#define MRCNN_VIS_DRAW_BOXES 4
+#define MRCNN_VIS_RECT 0
+#define MRCNN_VIS_SEGMENT 1
+#define MRCNN_VIS_DISC 2
+#define MRCNN_VIS_GLYPH 3
+#define MRCNN_VIS_FILL 4
+typedef struct mrcnn_vis_prim {
+    int32_t kind, x0, y0, x1, y1, p, rgb, a;
+} mrcnn_vis_prim_t;             /* 32 bytes */
+int mrcnn_vis_render_u8(const float *img, int H, int W, const unsigned char *masks, const float *bbox, const unsigned char *colors,
+                        const int32_t *order, int D, int mask_a256, int box_thickness, int flags, const mrcnn_vis_prim_t *prims, int n_prims,
+                        const unsigned long long *font, int n_glyphs, unsigned char *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
