@@ -8,6 +8,8 @@ combination the reference can actually train is backbone 'fpn' with head_arch 'f
 SURVEY.md section 8 f-4) construct like in the reference and run forward through ``forward_legacy``.
 ``predict`` / ``_suppress`` are SURVEY.md section 8f "next" rows.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -212,45 +214,60 @@ class MaskRCNN(object):
         oh, ow = self.prepare_size(H, W)
         return ops.image_resize_f32(img.to(self.device, torch.float32).contiguous(), oh, ow, 255.0)
 
+    @contextlib.contextmanager
+    def _inference_mode(self):
+        """``self.train`` and ``core.TRAIN`` off for the block, restored after it."""
+        from chainer_maskrcnn.nn import core
+        keep_train, keep_core = self.train, core.TRAIN
+        self.train, core.TRAIN = False, False
+        try:
+            yield
+        finally:
+            self.train, core.TRAIN = keep_train, keep_core
+
+    def _xy5(self, box, scale=None):
+        """Boxes (D,4) (y1,x1,y2,x2), times ``scale`` unless they are in the forward's frame already -> the branch's (D,5) RoIs
+        (0, x1, y1, x2, y2)."""
+        z = torch.zeros((box.shape[0], 1), device=self.device)
+        xy = box[:, [1, 0, 3, 2]]
+        return torch.cat((z, xy if scale is None else xy * scale), dim=1).contiguous()
+
+    def _detect_and_branch(self, img, branch):
+        """One image of ``predict`` / ``predict_keypoints`` (inference mode set by the caller): the detections and, with ``branch`` and
+        D > 0, the mask / keypoint branch on the kept boxes.  Returns (size, bbox (D,4) contiguous, label, score, m, mirrors): without
+        test-time augmentation m = the branch output (D,S,S,C) and mirrors = None; with it m = one such output per view and mirrors =
+        the views' mirror flags; m = None where the branch did not run."""
+        if getattr(self, 'tta', None) is not None:
+            size, bbox, label, score, level, view, views = self._detect_tta(img)
+            bbox = bbox.contiguous()
+            m = self._branch_per_view(bbox, level, view, views, size[1]) if branch and bbox.shape[0] > 0 else None
+            return size, bbox, label, score, m, [v[2] for v in views]
+        size, scale, bbox, label, score, level = self._detect(img)
+        bbox = bbox.contiguous()
+        m = None
+        if branch and bbox.shape[0] > 0:        # not through _branch_per_view: the one view's levels are the proposals' own
+            m = self.head.mask_branch(self.head.x, self._xy5(bbox, scale), level.to(torch.int32).contiguous(),
+                                      self.extractor.spatial_scales)
+        return size, bbox, label, score, m, None
+
     def predict(self, imgs):
         """maskrcnn.py:157-259: imgs = list of (3,H,W) float32 tensors (0..255).  Returns (masks, labels, scores) -
         lists with one entry per image: masks (D,H,W) bool, labels (D,) int32 in [0, n_fg_class-1], scores (D,) float32 -
         and keeps the boxes in ``self.last_bboxes``.  One device->host copy per image (the per-class keep counts)."""
-        from chainer_maskrcnn.nn import core
         masks, labels, scores, bboxes = [], [], [], []
-        keep_train, keep_core = self.train, core.TRAIN
-        self.train, core.TRAIN = False, False
-        try:
+        with self._inference_mode():
             for img in imgs:
-                if getattr(self, 'tta', None) is not None:
-                    size, bbox, label, score, level, view, views = self._detect_tta(img)
-                    D = bbox.shape[0]
-                    if D > 0 and self.predict_mask:
-                        m = self._branch_per_view(bbox, level, view, views, size[1])
-                        p = ops.tta_mask_merge(m, [v[2] for v in views], label.contiguous())
-                        mask = ops.mask_paste_prob(p, bbox.contiguous(), size).bool()
-                    else:
-                        mask = torch.zeros((D,) + size, dtype=torch.bool, device=self.device)
-                    masks.append(mask)
-                    labels.append(label)
-                    scores.append(score)
-                    bboxes.append(bbox)
-                    continue
-                size, scale, bbox, label, score, level = self._detect(img)
-                D = bbox.shape[0]
-                if D > 0 and self.predict_mask:
-                    xy5 = torch.cat((torch.zeros((D, 1), device=self.device), bbox[:, [1, 0, 3, 2]] * scale), dim=1).contiguous()
-                    m = self.head.mask_branch(self.head.x, xy5, level.to(torch.int32).contiguous(),
-                                              self.extractor.spatial_scales)
-                    mask = ops.mask_paste(m, label.contiguous(), bbox.contiguous(), size).bool()
+                size, bbox, label, score, m, mirrors = self._detect_and_branch(img, self.predict_mask)
+                if m is None:
+                    mask = torch.zeros((bbox.shape[0],) + size, dtype=torch.bool, device=self.device)
+                elif mirrors is None:
+                    mask = ops.mask_paste(m, label.contiguous(), bbox, size).bool()
                 else:
-                    mask = torch.zeros((D,) + size, dtype=torch.bool, device=self.device)
+                    mask = ops.mask_paste_prob(ops.tta_mask_merge(m, mirrors, label.contiguous()), bbox, size).bool()
                 masks.append(mask)
                 labels.append(label)
                 scores.append(score)
                 bboxes.append(bbox)
-        finally:
-            self.train, core.TRAIN = keep_train, keep_core
         self.last_bboxes = bboxes
         return masks, labels, scores
 
@@ -295,14 +312,12 @@ class MaskRCNN(object):
         """The mask / keypoint branch of every view on the final boxes bbox (D,4) (original image): mirrored into a mirrored view, scaled
         by the view's scale; a detection keeps its proposal's level in its own view and takes map_rois_to_fpn_levels of the box in every
         other view.  Returns the per-view branch outputs (D,S,S,C)."""
-        D = bbox.shape[0]
         out = []
         for u, (feats, scale, mirror) in enumerate(views):
             b = torch.stack((bbox[:, 0], W - bbox[:, 3], bbox[:, 2], W - bbox[:, 1]), dim=1) if mirror else bbox
             b = b * scale
             lv = torch.where(view == u, level, ops.map_rois_to_fpn_levels(b.contiguous()).clamp(0, len(feats) - 1))
-            xy5 = torch.cat((torch.zeros((D, 1), device=self.device), b[:, [1, 0, 3, 2]]), dim=1).contiguous()
-            out.append(self.head.mask_branch(feats, xy5, lv.to(torch.int32).contiguous(), self.extractor.spatial_scales))
+            out.append(self.head.mask_branch(feats, self._xy5(b), lv.to(torch.int32).contiguous(), self.extractor.spatial_scales))
         return out
 
     def predict_keypoints(self, imgs, return_heatmaps=False):
@@ -313,45 +328,27 @@ class MaskRCNN(object):
         rule, viewer.py:86-107), prob = the softmax over the cells at the argmax.  return_heatmaps=True appends the heat maps in the
         reference's format (maskrcnn.py:249: (D, K, 56*56), there with a fixed 20 for K).  Like ``predict``, one device->host copy
         per image (the per-class keep counts)."""
-        from chainer_maskrcnn.nn import core
         if self.head_arch != 'fpn_keypoint':
             raise ValueError('predict_keypoints needs a keypoint model (head_arch \'fpn_keypoint\'), this one has %r' % self.head_arch)
         K, S = self.head.n_keypoints, self.head.mask_size
         keypoints, labels, scores, bboxes, heatmaps = [], [], [], [], []
-        keep_train, keep_core = self.train, core.TRAIN
-        self.train, core.TRAIN = False, False
-        try:
+        with self._inference_mode():
             for img in imgs:
-                tta = getattr(self, 'tta', None) is not None
-                if tta:
-                    size, bbox, label, score, level, view, views = self._detect_tta(img)
-                else:
-                    size, scale, bbox, label, score, level = self._detect(img)
+                size, bbox, label, score, m, mirrors = self._detect_and_branch(img, True)
                 D = bbox.shape[0]
-                if D > 0 and tta:
-                    bbox = bbox.contiguous()
-                    hv = self._branch_per_view(bbox, level, view, views, size[1])
-                    m = ops.tta_keypoint_merge(hv, [v[2] for v in views], K, self.tta['keypoint_flip_perm'])
-                    kp = ops.keypoint_decode(m, bbox, K)
-                    if return_heatmaps:
-                        heatmaps.append(m[..., :K].permute(0, 3, 1, 2).reshape(D, K, S * S))
-                elif D > 0:
-                    bbox = bbox.contiguous()
-                    xy5 = torch.cat((torch.zeros((D, 1), device=self.device), bbox[:, [1, 0, 3, 2]] * scale), dim=1).contiguous()
-                    m = self.head.mask_branch(self.head.x, xy5, level.to(torch.int32).contiguous(), self.extractor.spatial_scales)
-                    kp = ops.keypoint_decode(m, bbox, K)
-                    if return_heatmaps:
-                        heatmaps.append(m[..., :K].permute(0, 3, 1, 2).reshape(D, K, S * S))
-                else:
+                if m is None:                   # D = 0
+                    m = torch.zeros((0, S, S, K), dtype=torch.float32, device=self.device)
                     kp = torch.zeros((0, K, 4), dtype=torch.float32, device=self.device)
-                    if return_heatmaps:
-                        heatmaps.append(torch.zeros((0, K, S * S), dtype=torch.float32, device=self.device))
+                else:
+                    if mirrors is not None:
+                        m = ops.tta_keypoint_merge(m, mirrors, K, self.tta['keypoint_flip_perm'])
+                    kp = ops.keypoint_decode(m, bbox, K)
                 keypoints.append(kp)
                 labels.append(label)
                 scores.append(score)
                 bboxes.append(bbox)
-        finally:
-            self.train, core.TRAIN = keep_train, keep_core
+                if return_heatmaps:
+                    heatmaps.append(m[..., :K].permute(0, 3, 1, 2).reshape(D, K, S * S))
         self.last_bboxes = bboxes
         if return_heatmaps:
             return keypoints, labels, scores, heatmaps

@@ -1,0 +1,109 @@
+// The arithmetic of the inference post-processing, stated once and shared by the single-view kernels of predict.hip
+// and the multi-view kernels of tta.hip, so one unmirrored view gives predict()'s bits by construction; rpn.hip takes orderable().
+// Float arithmetic follows oracle/predict.py operation for operation: no contraction, correctly rounded division.
+//   decode       chainer_maskrcnn/model/maskrcnn.py:178-205  (un-scale, loc2bbox, clip, softmax)
+//   candidates   maskrcnn.py:278-312  (_suppress: prob > score_thresh, score descending then index descending, ChainerCV NMS)
+//   paste        maskrcnn.py:231-246  (cv2.resize to the box, *255, truncate, > 127, paste)
+#pragma once
+#include <hip/hip_runtime.h>
+
+#pragma clang fp contract(off)
+
+typedef unsigned long long u64;
+
+constexpr int CN_CAP = 512;         // most RoIs of the all-in-LDS class NMS (k_class_nms); above it mrcnn_class_nms_ws_f32's workspace kernels
+
+__device__ __forceinline__ unsigned orderable(float f) {     // monotone float -> uint
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// One RoI (y1,x1,y2,x2) of the forward's scaled image and its box_out row o (n_class scores, then the class-agnostic loc at loc0):
+// the box in original-image pixels, clipped to size; softmax over the n_class scores into prob_row.
+__device__ __forceinline__ float4 detect_decode_row(const float *__restrict__ roi, const float *__restrict__ o, int n_class, int loc0,
+                                                    float scale, float4 mean, float4 stdv, float size_h, float size_w,
+                                                    float *__restrict__ prob_row) {
+    const float4 rr = *reinterpret_cast<const float4 *>(roi);
+    const float4 r = make_float4(rr.x / scale, rr.y / scale, rr.z / scale, rr.w / scale);         // roi = rois / scale (:178)
+    const float dy = o[loc0] * stdv.x + mean.x, dx = o[loc0 + 1] * stdv.y + mean.y;                // (:191-195)
+    const float dh = o[loc0 + 2] * stdv.z + mean.z, dw = o[loc0 + 3] * stdv.w + mean.w;
+    const float h = r.z - r.x, w = r.w - r.y;                                                      // loc2bbox (:196)
+    const float cy = r.x + 0.5f * h, cx = r.y + 0.5f * w;
+    const float ncy = dy * h + cy, ncx = dx * w + cx;
+    const float nh = expf(dh) * h, nw = expf(dw) * w;
+    float y1 = ncy - 0.5f * nh, x1 = ncx - 0.5f * nw, y2 = ncy + 0.5f * nh, x2 = ncx + 0.5f * nw;
+    y1 = fmaxf(fminf(y1, size_h), 0.f); y2 = fmaxf(fminf(y2, size_h), 0.f);                       // clip (:202-203)
+    x1 = fmaxf(fminf(x1, size_w), 0.f); x2 = fmaxf(fminf(x2, size_w), 0.f);
+    float m = -INFINITY;
+    for (int c = 0; c < n_class; ++c) m = fmaxf(m, o[c]);
+    float s = 0.f;
+    for (int c = 0; c < n_class; ++c) s += expf(o[c] - m);
+    for (int c = 0; c < n_class; ++c) prob_row[c] = expf(o[c] - m) / s;                            // F.softmax (:205)
+    return make_float4(y1, x1, y2, x2);
+}
+
+// NMS candidate i with class probability p: valid | orderable score << 31 | index, 0 when p <= score_thresh.  Descending key order is
+// (score descending, index descending), the oracle's pin of argsort()[::-1]; the zero keys come last.
+__device__ __forceinline__ u64 candidate_key(float p, float score_thresh, int i) {
+    return p > score_thresh ? (1ull << 63) | ((u64)orderable(p) << 31) | (u64)i : 0ull;
+}
+__device__ __forceinline__ int candidate_index(u64 key) { return (int)(key & 0x7FFFFFFFull); }
+
+// Bitonic sort, descending, of skey[0..P) in LDS (P a power of two) by a workgroup of T threads.  The keys are visible to the workgroup
+// on entry (a barrier after they were written) and the sorted keys are on return.
+template <int T>
+__device__ __forceinline__ void bitonic_sort_desc(u64 *skey, int P, int tid) {
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += T) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const u64 a = skey[i], b = skey[ixj];
+                    const bool up = (i & k) == 0;
+                    if ((a < b) == up) { skey[i] = b; skey[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// Box b (of area area_b, the product of its sides) suppresses box c: IoU = ai / ((area_b + area_c) - ai) >= thresh, the division
+// correctly rounded (ChainerCV's non_maximum_suppression).
+__device__ __forceinline__ bool nms_suppresses(float4 b, float area_b, float4 c, float thresh) {
+    const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y), bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
+    const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
+    const float ai = hgt * wid;
+    const float iou = ai / ((area_b + (c.z - c.x) * (c.w - c.y)) - ai);
+    return iou >= thresh;
+}
+
+// Mask paste of one detection (maskrcnn.py:231-246): the S x S map m(yy, xx) = tap(yy, xx) goes through cv2.resize(m, (w, h)), float
+// bilinear (half-pixel centres, edge clamp); *255 -> uint8 (truncate) -> > 127; pasted at (int(y1), int(x1)) of box b, clipped to the
+// H x W image o.  Grid-stride over the pixels along blockIdx.x with 256-thread workgroups.
+template <class Tap>
+__device__ __forceinline__ void mask_paste_box(float4 b, int S, int H, int W, unsigned char *__restrict__ o, Tap tap) {
+    const int mw = (int)(b.w - b.y), mh = (int)(b.z - b.x);
+    const int s0 = (int)b.x, t0 = (int)b.y;
+    const double sy = mh > 0 ? 1.0 / ((double)mh / (double)S) : 0.0, sx = mw > 0 ? 1.0 / ((double)mw / (double)S) : 0.0;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < H * W; p += gridDim.x * 256) {
+        const int y = p / W, x = p % W;
+        const int dy = y - s0, dx = x - t0;
+        unsigned char v = 0;
+        if (dy >= 0 && dy < mh && dx >= 0 && dx < mw) {
+            float fy = (float)(((double)dy + 0.5) * sy - 0.5), fx = (float)(((double)dx + 0.5) * sx - 0.5);
+            int iy = (int)floorf(fy), ix = (int)floorf(fx);
+            fy -= (float)iy; fx -= (float)ix;
+            if (iy < 0) { fy = 0.f; iy = 0; }
+            if (iy >= S - 1) { fy = 0.f; iy = S - 1; }
+            if (ix < 0) { fx = 0.f; ix = 0; }
+            if (ix >= S - 1) { fx = 0.f; ix = S - 1; }
+            const int iy1 = min(iy + 1, S - 1), ix1 = min(ix + 1, S - 1);
+            const float r0 = tap(iy, ix) * (1.0f - fx) + tap(iy, ix1) * fx;
+            const float r1 = tap(iy1, ix) * (1.0f - fx) + tap(iy1, ix1) * fx;
+            const float m = r0 * (1.0f - fy) + r1 * fy;
+            const int q = (int)(m * 255.0f);
+            v = (unsigned char)((q & 0xFF) > 127 ? 1 : 0);
+        }
+        o[p] = v;
+    }
+}

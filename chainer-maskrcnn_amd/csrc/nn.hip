@@ -837,7 +837,8 @@ __global__ __launch_bounds__(NT) void k_deconv_merge_bwd_w2(const float *__restr
 // in chainer_maskrcnn/dataset/transforms.py (bit-identical results: same float operations, no contraction):
 //   INTER_LINEAR  fx = (float)((dx + 0.5) * (src/dst) - 0.5), sx = floor(fx), clamped taps; horizontal then vertical
 //   INTER_NEAREST sx = min(floor(dx * (src/dst)), src - 1)
-// The taps (linear_tap, nearest_tap) live in resize_common.h, shared with the batched kernels of augment.hip.
+// The taps (linear_tap, nearest_tap) live in resize_common.h, shared with the batched kernels of augment.hip; the float32 kernel is
+// the one resize of inference, plain (MaskRCNN.prepare) and mirrored (the test-time views of tta.hip).
 // ---------------------------------------------------------------------------------------------
 // src (H,W,3) uint8 -> dst[c][y][x] (planes of dst_h x dst_w, written for y < oh, x < ow), values / div
 __global__ __launch_bounds__(NT) void k_image_resize_u8(const uint8_t *__restrict__ src, int H, int W, float *__restrict__ dst,
@@ -858,10 +859,11 @@ __global__ __launch_bounds__(NT) void k_image_resize_u8(const uint8_t *__restric
     }
 }
 
-// float32 planes: src (C,H,W) -> dst (C, dst_h, dst_w) written for y < oh, x < ow, values / div.  MaskRCNN.prepare
-// (maskrcnn.py:261-276) resizes the float32 CHW image with chainercv.transforms.resize = cv2.resize INTER_LINEAR.
-__global__ __launch_bounds__(NT) void k_image_resize_f32(const float *__restrict__ src, int C, int H, int W, float *__restrict__ dst,
-                                                         int oh, int ow, int dst_h, int dst_w, float div) {
+// float32 planes: src (C,H,W) -> dst (C, dst_h, dst_w) written for y < oh, x < ow, values / div; mirror = 1 reads source column s as
+// W-1-s (= resizing src[..., ::-1]).  MaskRCNN.prepare (maskrcnn.py:261-276) resizes the float32 CHW image with
+// chainercv.transforms.resize = cv2.resize INTER_LINEAR (mirror = 0); the test-time views (tta.hip) take both.
+__global__ __launch_bounds__(NT) void k_image_resize_mirror_f32(const float *__restrict__ src, int C, int H, int W, float *__restrict__ dst,
+                                                                int oh, int ow, int dst_h, int dst_w, int mirror, float div) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= oh * ow) return;
     const int y = i / ow, x = i - y * ow;
@@ -869,6 +871,7 @@ __global__ __launch_bounds__(NT) void k_image_resize_f32(const float *__restrict
     float a0, a1, b0, b1;
     linear_tap(x, ow, W, x0, x1, a0, a1);
     linear_tap(y, oh, H, y0, y1, b0, b1);
+    if (mirror) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
     for (int c = 0; c < C; ++c) {
         const float *r0 = src + ((size_t)c * H + y0) * W, *r1 = src + ((size_t)c * H + y1) * W;
         const float top = r0[x0] * a0 + r0[x1] * a1;
@@ -1323,8 +1326,20 @@ extern "C" int mrcnn_image_resize_f32(const float *src, int C, int H, int W, flo
                                       float div, void *stream) {
     if (int e = chk(src && dst, "image_resize_f32: null pointer")) return e;
     if (int e = chk(C > 0 && H > 0 && W > 0 && oh > 0 && ow > 0 && dst_h >= oh && dst_w >= ow, "image_resize_f32: bad sizes")) return e;
-    hipLaunchKernelGGL(k_image_resize_f32, dim3(mrcnn::cdiv(oh * ow, NT)), dim3(NT), 0, (hipStream_t)stream, src, C, H, W, dst,
-                       oh, ow, dst_h, dst_w, div);
+    hipLaunchKernelGGL(k_image_resize_mirror_f32, dim3(mrcnn::cdiv(oh * ow, NT)), dim3(NT), 0, (hipStream_t)stream, src, C, H, W, dst,
+                       oh, ow, dst_h, dst_w, 0, div);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrcnn_image_resize_mirror_f32(const float *src, int C, int H, int W, float *dst, int oh, int ow, int dst_h, int dst_w,
+                                             int mirror, float div, void *stream) {
+    if (!src || !dst) return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: null pointer");
+    if (C <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0 || dst_h < oh || dst_w < ow || (long long)oh * ow > 0x7FFFFFFFLL)
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: bad sizes");
+    if (mirror != 0 && mirror != 1) return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: mirror %d (0 or 1 expected)", mirror);
+    hipLaunchKernelGGL(k_image_resize_mirror_f32, dim3(mrcnn::cdiv((long long)oh * ow, NT)), dim3(NT), 0, (hipStream_t)stream, src, C, H, W,
+                       dst, oh, ow, dst_h, dst_w, mirror, div);
     MRCNN_LAUNCH_CHECK();
     return 0;
 }

@@ -14,12 +14,9 @@
 // index desc).  NMS keep lists are bit-exact given identical boxes.  All kernels are latency/HBM
 // bound; sizes at config 3: A = 261,888 anchors, n_pre = 12,000 (18 MB of bit masks), n_post = 2,000.
 #include "common.h"
-
-#pragma clang fp contract(off)
+#include "detect_common.h"          // orderable(); FP contraction off
 
 namespace {
-
-typedef unsigned long long u64;
 
 // ---- pack / unpack the RPN head output ---------------------------------------------------------
 // head (N, HW, Cp) NHWC with channels [0,4A) = loc (a*4+k), [4A,6A) = score (a*2+c).
@@ -103,11 +100,6 @@ __global__ __launch_bounds__(256) void k_rpn_unpack_levels(RpnLevels lv, const f
 }
 
 // ---- decode + clip + filter + sort key ---------------------------------------------------------
-__device__ __forceinline__ unsigned orderable(float f) {     // monotone float -> uint
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void k_decode(const float *__restrict__ locs, const float *__restrict__ scores,
                                                 const float *__restrict__ anchors, int N, int A, float img_h, float img_w,
                                                 float min_size, const float *__restrict__ per_image, float *__restrict__ boxes,

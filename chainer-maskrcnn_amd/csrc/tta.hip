@@ -1,41 +1,19 @@
 // Test-time augmentation (TTA) post-processing for gfx950 (MaskRCNN.use_test_augmentation): every image runs at
 // several short sides, optionally mirrored, one N = 1 forward per view; the kernels here merge the views after the forward pass.
-//   mirrored resize        the taps of resize_common.h; a mirrored view reads source column s as W-1-s (= resizing img[..., ::-1])
-//   multi-view decode      k_detect_decode's arithmetic per view (scale_v), mirrored views mapped back to (y1, W-x2, y2, W-x1)
+//   multi-view decode      detect_decode_row per view (scale_v), mirrored views mapped back to (y1, W-x2, y2, W-x1)
 //   union class NMS        R <= 4096 candidates: per class an LDS bitonic sort, an IoU bitmask in the caller's workspace, a one-wave sweep
-//   mask merge + paste     mean over the views of sigmoid(logit) at the mirrored column, then k_mask_paste's resize / threshold rule
+//   mask merge + paste     mean over the views of sigmoid(logit) at the mirrored column, then mask_paste_box's resize / threshold rule
 //   keypoint merge         mean over the views of the heat maps, mirrored column and left / right channels swapped
-// Float arithmetic restates predict.hip operation for operation (FP contraction off), so one unmirrored view gives predict()'s bits.
+// The decode row, the candidate key and sort, the suppression predicate and the paste pixel rule are detect_common.h's, the functions
+// predict.hip's single-view kernels call, so one unmirrored view gives predict()'s bits.  The views' mirrored resize is nn.hip's
+// k_image_resize_mirror_f32.
 #include "common.h"
-#include "resize_common.h"
-
-#pragma clang fp contract(off)
+#include "detect_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int NT = 256;
 constexpr int UNION_MAX = MRCNN_CLASS_NMS_WS_MAX;
-constexpr int LDS_NMS_CAP = 512;               // mrcnn_class_nms_f32's CN_CAP (predict.hip)
-
-// ---- mirrored float32 resize (k_image_resize_f32 of nn.hip with the mirrored source column) -------------------------------------------
-__global__ __launch_bounds__(NT) void k_image_resize_mirror_f32(const float *__restrict__ src, int C, int H, int W, float *__restrict__ dst,
-                                                                int oh, int ow, int dst_h, int dst_w, int mirror, float div) {
-    const int i = blockIdx.x * NT + threadIdx.x;
-    if (i >= oh * ow) return;
-    const int y = i / ow, x = i - y * ow;
-    int x0, x1, y0, y1;
-    float a0, a1, b0, b1;
-    linear_tap(x, ow, W, x0, x1, a0, a1);
-    linear_tap(y, oh, H, y0, y1, b0, b1);
-    if (mirror) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
-    for (int c = 0; c < C; ++c) {
-        const float *r0 = src + ((size_t)c * H + y0) * W, *r1 = src + ((size_t)c * H + y1) * W;
-        const float top = r0[x0] * a0 + r0[x1] * a1;
-        const float bot = r1[x0] * a0 + r1[x1] * a1;
-        dst[((size_t)c * dst_h + y) * dst_w + x] = (top * b0 + bot * b1) / div;
-    }
-}
 
 // ---- multi-view decode ------------------------------------------------------------------------------------------------------------------
 struct DecodeViews {
@@ -46,7 +24,7 @@ struct DecodeViews {
     float scale[MRCNN_TTA_VIEWS_MAX];
 };
 
-// One thread per union row: the arithmetic of k_detect_decode (predict.hip) with the row's view's scale, then the mirror back.
+// One thread per union row: detect_decode_row with the row's view's scale, then the mirror back.
 __global__ __launch_bounds__(NT) void k_tta_detect_decode(const DecodeViews vs, int V, int ld, int n_class, int loc0, float4 mean, float4 stdv,
                                                           float size_h, float size_w, float *__restrict__ cls_bbox, float *__restrict__ prob) {
     const int g = blockIdx.x * NT + threadIdx.x;
@@ -54,37 +32,13 @@ __global__ __launch_bounds__(NT) void k_tta_detect_decode(const DecodeViews vs, 
     int v = 0;
     while (g >= vs.off[v + 1]) ++v;
     const int i = g - vs.off[v];
-    const float scale = vs.scale[v];
-    const float4 rr = *reinterpret_cast<const float4 *>(vs.rois[v] + (size_t)i * 4);
-    const float4 r = make_float4(rr.x / scale, rr.y / scale, rr.z / scale, rr.w / scale);
-    const float *o = vs.box[v] + (size_t)i * ld;
-    const float dy = o[loc0] * stdv.x + mean.x, dx = o[loc0 + 1] * stdv.y + mean.y;
-    const float dh = o[loc0 + 2] * stdv.z + mean.z, dw = o[loc0 + 3] * stdv.w + mean.w;
-    const float h = r.z - r.x, w = r.w - r.y;
-    const float cy = r.x + 0.5f * h, cx = r.y + 0.5f * w;
-    const float ncy = dy * h + cy, ncx = dx * w + cx;
-    const float nh = expf(dh) * h, nw = expf(dw) * w;
-    float y1 = ncy - 0.5f * nh, x1 = ncx - 0.5f * nw, y2 = ncy + 0.5f * nh, x2 = ncx + 0.5f * nw;
-    y1 = fmaxf(fminf(y1, size_h), 0.f); y2 = fmaxf(fminf(y2, size_h), 0.f);
-    x1 = fmaxf(fminf(x1, size_w), 0.f); x2 = fmaxf(fminf(x2, size_w), 0.f);
-    if (vs.mirror[v]) {
-        const float m1 = size_w - x2, m2 = size_w - x1;
-        x1 = m1; x2 = m2;
-    }
-    *reinterpret_cast<float4 *>(cls_bbox + (size_t)g * 4) = make_float4(y1, x1, y2, x2);
-    float m = -INFINITY;
-    for (int c = 0; c < n_class; ++c) m = fmaxf(m, o[c]);
-    float s = 0.f;
-    for (int c = 0; c < n_class; ++c) s += expf(o[c] - m);
-    for (int c = 0; c < n_class; ++c) prob[(size_t)g * n_class + c] = expf(o[c] - m) / s;
+    float4 b = detect_decode_row(vs.rois[v] + (size_t)i * 4, vs.box[v] + (size_t)i * ld, n_class, loc0, vs.scale[v], mean, stdv, size_h,
+                                 size_w, prob + (size_t)g * n_class);
+    if (vs.mirror[v]) b = make_float4(b.x, size_w - b.w, b.z, size_w - b.y);
+    *reinterpret_cast<float4 *>(cls_bbox + (size_t)g * 4) = b;
 }
 
 // ---- union class NMS (R <= 4096) --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned orderable(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 struct UnionLayout {
     size_t sboxes, sidx, n_valid, mask, total;
     int nblk;
@@ -102,7 +56,7 @@ UnionLayout union_layout(int R, int n_class) {
     return L;
 }
 
-// One workgroup per class l: the keys of k_class_nms (prob > thresh; score descending, then index descending) bitonic-sorted in LDS over
+// One workgroup per class l: the candidate keys (prob > thresh; score descending, then index descending) bitonic-sorted in LDS over
 // P = pow2 >= R; the n candidates' boxes and indices in sort order go to the workspace.  Slot s = l - l_begin.
 constexpr int SORT_T = 1024;
 __global__ __launch_bounds__(SORT_T) void k_union_sort(const float *__restrict__ cls_bbox, const float *__restrict__ prob, int R, int P,
@@ -114,39 +68,24 @@ __global__ __launch_bounds__(SORT_T) void k_union_sort(const float *__restrict__
     if (tid == 0) s_n = 0;
     int mine = 0;
     for (int i = tid; i < P; i += SORT_T) {
-        u64 k = 0ull;
-        if (i < R) {
-            const float p = prob[(size_t)i * n_class + l];
-            if (p > score_thresh) { k = (1ull << 63) | ((u64)orderable(p) << 31) | (u64)i; ++mine; }
-        }
+        const u64 k = i < R ? candidate_key(prob[(size_t)i * n_class + l], score_thresh, i) : 0ull;
+        mine += k != 0ull;
         skey[i] = k;
     }
     __syncthreads();
     if (mine) atomicAdd(&s_n, mine);
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += SORT_T) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const u64 a = skey[i], b = skey[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a < b) == up) { skey[i] = b; skey[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort_desc<SORT_T>(skey, P, tid);
     const int n = s_n;
     for (int i = tid; i < n; i += SORT_T) {
-        const int idx = (int)(skey[i] & 0x7FFFFFFFull);
+        const int idx = candidate_index(skey[i]);
         sboxes[(size_t)s * R + i] = *reinterpret_cast<const float4 *>(cls_bbox + (size_t)idx * 4);
         sidx[(size_t)s * R + i] = idx;
     }
     if (tid == 0) n_valid[s] = n;
 }
 
-// mask[(s*R + i)*nblk + cb] bit j: sorted box i suppresses sorted box cb*64+j (> i), IoU >= thresh decided as k_class_nms does
-// (ai / u >= thresh, correctly rounded).  Grid (nblk, cdiv(nblk, 4), classes), 4 waves = 4 row blocks; only words cb >= rb are written,
-// the only ones the sweep reads.
+// mask[(s*R + i)*nblk + cb] bit j: sorted box i suppresses sorted box cb*64+j (> i) by nms_suppresses, as in k_class_nms.
+// Grid (nblk, cdiv(nblk, 4), classes), 4 waves = 4 row blocks; only words cb >= rb are written, the only ones the sweep reads.
 __global__ __launch_bounds__(256) void k_union_mask(const float4 *__restrict__ sboxes, const int32_t *__restrict__ n_valid, int R, int nblk,
                                                     float thresh, u64 *__restrict__ mask) {
     const int s = blockIdx.z, cb = blockIdx.x;
@@ -166,14 +105,8 @@ __global__ __launch_bounds__(256) void k_union_mask(const float4 *__restrict__ s
     const float area_i = (b.z - b.x) * (b.w - b.y);
     u64 bits = 0ull;
     const int jmax = min(64, n - cb * 64);
-    for (int j = 0; j < jmax; ++j) {
-        const float4 c = cbox[j];
-        const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y), bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
-        const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
-        const float ai = hgt * wid;
-        const float iou = ai / ((area_i + (c.z - c.x) * (c.w - c.y)) - ai);
-        if (iou >= thresh && cb * 64 + j > i) bits |= 1ull << j;
-    }
+    for (int j = 0; j < jmax; ++j)
+        if (nms_suppresses(b, area_i, cbox[j], thresh) && cb * 64 + j > i) bits |= 1ull << j;
     mask[((size_t)s * R + i) * nblk + cb] = bits;
 }
 
@@ -253,38 +186,13 @@ __global__ __launch_bounds__(NT) void k_tta_mask_merge(const MergeViews vs, int 
     prob[i] = acc / (float)V;
 }
 
-// k_mask_paste (predict.hip) reading the probabilities instead of sigmoid(logit)
+// Mask paste: mask_paste_box on the stored probabilities m = prob[d].
 __global__ __launch_bounds__(256) void k_mask_paste_prob(const float *__restrict__ prob, int S, const float *__restrict__ bbox, int H, int W,
                                                          unsigned char *__restrict__ out) {
     const int d = blockIdx.y;
-    const float4 b = *reinterpret_cast<const float4 *>(bbox + (size_t)d * 4);
-    const int mw = (int)(b.w - b.y), mh = (int)(b.z - b.x);
-    const int s0 = (int)b.x, t0 = (int)b.y;
-    unsigned char *o = out + (size_t)d * H * W;
     const float *pr = prob + (size_t)d * S * S;
-    const double sy = mh > 0 ? 1.0 / ((double)mh / (double)S) : 0.0, sx = mw > 0 ? 1.0 / ((double)mw / (double)S) : 0.0;
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < H * W; p += gridDim.x * 256) {
-        const int y = p / W, x = p % W;
-        const int dy = y - s0, dx = x - t0;
-        unsigned char v = 0;
-        if (dy >= 0 && dy < mh && dx >= 0 && dx < mw) {
-            float fy = (float)(((double)dy + 0.5) * sy - 0.5), fx = (float)(((double)dx + 0.5) * sx - 0.5);
-            int iy = (int)floorf(fy), ix = (int)floorf(fx);
-            fy -= (float)iy; fx -= (float)ix;
-            if (iy < 0) { fy = 0.f; iy = 0; }
-            if (iy >= S - 1) { fy = 0.f; iy = S - 1; }
-            if (ix < 0) { fx = 0.f; ix = 0; }
-            if (ix >= S - 1) { fx = 0.f; ix = S - 1; }
-            const int iy1 = min(iy + 1, S - 1), ix1 = min(ix + 1, S - 1);
-            auto pv = [&](int yy, int xx) { return pr[(size_t)yy * S + xx]; };
-            const float r0 = pv(iy, ix) * (1.0f - fx) + pv(iy, ix1) * fx;
-            const float r1 = pv(iy1, ix) * (1.0f - fx) + pv(iy1, ix1) * fx;
-            const float m = r0 * (1.0f - fy) + r1 * fy;
-            const int q = (int)(m * 255.0f);
-            v = (unsigned char)((q & 0xFF) > 127 ? 1 : 0);
-        }
-        o[p] = v;
-    }
+    mask_paste_box(*reinterpret_cast<const float4 *>(bbox + (size_t)d * 4), S, H, W, out + (size_t)d * H * W,
+                   [&](int yy, int xx) { return pr[(size_t)yy * S + xx]; });
 }
 
 // ---- keypoint heat-map merge ------------------------------------------------------------------------------------------------------------
@@ -323,18 +231,6 @@ int check_views(const char *who, const mrcnn_tta_view_t *views, int V) {
 
 }  // namespace
 
-extern "C" int mrcnn_image_resize_mirror_f32(const float *src, int C, int H, int W, float *dst, int oh, int ow, int dst_h, int dst_w,
-                                             int mirror, float div, void *stream) {
-    if (!src || !dst) return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: null pointer");
-    if (C <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0 || dst_h < oh || dst_w < ow || (long long)oh * ow > 0x7FFFFFFFLL)
-        return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: bad sizes");
-    if (mirror != 0 && mirror != 1) return mrcnn::fail_arg(MRCNN_E_INVALID, "image_resize_mirror: mirror %d (0 or 1 expected)", mirror);
-    hipLaunchKernelGGL(k_image_resize_mirror_f32, dim3(mrcnn::cdiv((long long)oh * ow, NT)), dim3(NT), 0, (hipStream_t)stream, src, C, H, W,
-                       dst, oh, ow, dst_h, dst_w, mirror, div);
-    MRCNN_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int mrcnn_tta_detect_decode_f32(const float *const *rois, const float *const *box_out, const mrcnn_tta_view_t *views, int V,
                                            int ld, int n_class, int loc0, const float *loc_mean4, const float *loc_std4, float size_h,
                                            float size_w, float *cls_bbox, float *prob, void *stream) {
@@ -367,7 +263,7 @@ extern "C" int mrcnn_tta_detect_decode_f32(const float *const *rois, const float
 }
 
 extern "C" size_t mrcnn_class_nms_workspace_bytes(int R, int n_class) {
-    if (R <= LDS_NMS_CAP || R > UNION_MAX || n_class <= 0) return 0;
+    if (R <= CN_CAP || R > UNION_MAX || n_class <= 0) return 0;
     return union_layout(R, n_class).total;
 }
 
@@ -377,7 +273,7 @@ extern "C" int mrcnn_class_nms_ws_f32(const float *cls_bbox, const float *prob, 
     if (!cls_bbox || !prob || !keep_idx || !keep_cnt || R <= 0 || n_class <= 0 || l_begin < 0 || l_end > n_class || l_begin > l_end)
         return mrcnn::fail_arg(MRCNN_E_INVALID, "class_nms_ws: bad arguments");
     if (R > UNION_MAX) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "class_nms_ws: %d RoIs > %d", R, UNION_MAX);
-    if (R <= LDS_NMS_CAP)           // the single-view kernel: one workgroup per class, everything in LDS
+    if (R <= CN_CAP)           // the single-view kernel: one workgroup per class, everything in LDS
         return mrcnn_class_nms_f32(cls_bbox, prob, R, n_class, l_begin, l_end, score_thresh, nms_thresh, keep_idx, keep_cnt, stream);
     const UnionLayout L = union_layout(R, n_class);
     if (!ws || ws_bytes < L.total)
