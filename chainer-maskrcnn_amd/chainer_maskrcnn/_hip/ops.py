@@ -798,6 +798,51 @@ def class_nms_ws(cls_bbox, prob, l_begin, l_end, score_thresh, nms_thresh):
     return keep_idx, keep_cnt
 
 
+SOFT_NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}       # MRCNN_SOFT_NMS_* of include/mrcnn_hip.h
+BOXPOST_MAX = 4096                                                # MRCNN_BOXPOST_MAX
+
+
+def class_soft_nms(cls_bbox, prob, l_begin, l_end, score_thresh, method, nms_thresh, sigma):
+    """Soft-NMS per class (mrcnn_class_soft_nms_f32) for up to 4096 candidates -> keep_idx (n_class,R) int32, keep_score
+    (n_class,R) float32 (the decayed scores, in selection order), keep_cnt (n_class,) int32.  method: 'hard' (class_nms's keep lists),
+    'linear' or 'gaussian'."""
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError('class_soft_nms: method must be one of %s, got %r' % (sorted(SOFT_NMS_METHODS), method))
+    _ck(cls_bbox, prob)
+    R, n_class = prob.shape
+    keep_idx = torch.full((n_class, max(R, 1)), -1, dtype=i32, device=prob.device)
+    keep_score = torch.zeros((n_class, max(R, 1)), dtype=torch.float32, device=prob.device)
+    keep_cnt = torch.zeros((n_class,), dtype=i32, device=prob.device)
+    if R > 0:
+        nb = lib().mrcnn_class_soft_nms_workspace_bytes(R, n_class)
+        ws = torch.empty((nb,), dtype=torch.uint8, device=prob.device) if nb else None
+        check(lib().mrcnn_class_soft_nms_f32(ptr(cls_bbox), ptr(prob), R, n_class, l_begin, l_end, float(score_thresh),
+                                             SOFT_NMS_METHODS[method], float(nms_thresh), float(sigma), ptr(keep_idx), ptr(keep_score),
+                                             ptr(keep_cnt), ptr(ws), nb, stream_ptr()))
+    return keep_idx, keep_score, keep_cnt
+
+
+def box_vote(cls_bbox, prob, l_begin, l_end, score_thresh, vote_thresh, keep_idx, keep_cnt, out=None):
+    """Box voting (mrcnn_box_vote_f32): keep_box (n_class,R,4) float32, row [l,k] = the prob-weighted mean of the boxes
+    of class l's candidates whose IoU with the kept box keep_idx[l,k] is >= vote_thresh, for k < keep_cnt[l]; the other rows are not
+    written (zeros, or what ``out`` held)."""
+    _ck(cls_bbox, prob, keep_idx, keep_cnt)
+    R, n_class = prob.shape
+    if tuple(keep_idx.shape) != (n_class, max(R, 1)) or tuple(keep_cnt.shape) != (n_class,) or keep_idx.dtype != i32 or keep_cnt.dtype != i32:
+        raise ValueError('box_vote: keep_idx (%d,%d) / keep_cnt (%d,) int32 expected, got %s %s / %s %s'
+                         % (n_class, max(R, 1), n_class, tuple(keep_idx.shape), keep_idx.dtype, tuple(keep_cnt.shape), keep_cnt.dtype))
+    if out is None:
+        out = torch.zeros((n_class, max(R, 1), 4), dtype=torch.float32, device=prob.device)
+    else:
+        _ck(out)
+        if tuple(out.shape) != (n_class, max(R, 1), 4) or out.dtype != torch.float32:
+            raise ValueError('box_vote: out (%d,%d,4) float32 expected, got %s %s' % (n_class, max(R, 1), tuple(out.shape), out.dtype))
+    if R > 0:
+        check(lib().mrcnn_box_vote_f32(ptr(cls_bbox), ptr(prob), R, n_class, l_begin, l_end, float(score_thresh), float(vote_thresh),
+                                       ptr(keep_idx), ptr(keep_cnt), ptr(out), stream_ptr()))
+    return out
+
+
 def tta_mask_merge(mask_logits, mirrors, label):
     """mask_logits: per view (D,S,S,Cm) NHWC; label (D,) int32.  Returns prob (D,S,S) float32 = the mean over the views, in order, of
     sigmoid(logit) of channel label[d], read at column S-1-x in a mirrored view."""

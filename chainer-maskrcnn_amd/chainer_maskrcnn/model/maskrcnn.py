@@ -22,6 +22,10 @@ from .head.fpn_roi_mask_head import FPNRoIMaskHead
 
 class MaskRCNN(object):
     feat_stride = 16
+    # box post-processing of _suppress, off until use_soft_nms / use_box_voting / use_max_detections set them on an instance
+    soft_nms = None                 # (method, sigma)
+    vote_thresh = None
+    max_detections = None
 
     def __init__(self, n_fg_class, n_keypoints=None, n_mask_convs=None, pretrained_model=None, min_size=600,
                  max_size=1000, ratios=[0.5, 1, 2], anchor_scales=[8], rpn_initialW=None, loc_initialW=None,
@@ -156,6 +160,42 @@ class MaskRCNN(object):
                                      % self.head.n_keypoints)
         self.tta = {'sizes': sizes, 'hflip': bool(hflip), 'max_size': None if max_size is None else int(max_size),
                     'keypoint_flip_perm': perm}
+
+    def use_soft_nms(self, method, sigma=0.5):
+        """Soft-NMS (Bodla et al. 2017; Detectron's TEST.SOFT_NMS) in place of the hard per-class NMS of ``predict`` /
+        ``predict_keypoints``: a kept box lowers the scores of the remaining boxes of its class - 'linear': times 1 - IoU where IoU >=
+        nms_thresh; 'gaussian': times exp(-IoU^2 / sigma) - and a box leaves when its score is no longer above score_thresh.  The
+        returned scores are the decayed ones.  ``None`` turns it off (the initial state)."""
+        if method is None:
+            self.soft_nms = None
+            return
+        if method not in ('linear', 'gaussian'):
+            raise ValueError("use_soft_nms: method must be None, 'linear' or 'gaussian', got %r" % (method,))
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.floating, np.integer)) or not float(sigma) > 0:
+            raise ValueError('use_soft_nms: sigma must be positive, got %r' % (sigma,))
+        self.soft_nms = (method, float(sigma))
+
+    def use_box_voting(self, vote_thresh):
+        """Box voting (Detectron's TEST.BBOX_VOTE, scoring method ID): the box of every kept detection becomes the
+        score-weighted mean of the boxes of all candidates of its class (prob > score_thresh, before the NMS) whose IoU with it is >=
+        ``vote_thresh`` (0 < vote_thresh <= 1; Detectron uses 0.8).  Scores do not change.  ``None`` turns it off (the initial state)."""
+        if vote_thresh is None:
+            self.vote_thresh = None
+            return
+        if isinstance(vote_thresh, bool) or not isinstance(vote_thresh, (int, float, np.floating, np.integer)) \
+                or not 0 < float(vote_thresh) <= 1:
+            raise ValueError('use_box_voting: vote_thresh must lie in (0, 1], got %r' % (vote_thresh,))
+        self.vote_thresh = float(vote_thresh)
+
+    def use_max_detections(self, n):
+        """At most ``n`` detections per image (Detectron's TEST.DETECTIONS_PER_IM): the n highest scores over all classes, ties to the
+        earlier row, kept in their order, before the mask / keypoint branch runs.  ``None`` turns it off (the initial state)."""
+        if n is None:
+            self.max_detections = None
+            return
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError('use_max_detections: an integer >= 1 or None expected, got %r' % (n,))
+        self.max_detections = int(n)
 
     def test_views(self, H, W):
         """The test-time views of an H x W image: [(oh, ow, mirror)] in view order (``prepare_size``'s rule with min_size = s)."""
@@ -360,6 +400,9 @@ class MaskRCNN(object):
         descending score order; results concatenated over classes, labels l-1.  With ``view`` (the test-time views' union, up to 4096
         candidates) the selection runs through class_nms_ws and the kept rows of ``view`` are returned last."""
         l_end = self.n_class - 1 if self.predict_mask else self.n_class
+        soft, vote, cap = self.soft_nms, self.vote_thresh, self.max_detections
+        if soft is not None or vote is not None or cap is not None:
+            return self._suppress_boxpost(cls_bbox, prob, levels, view, l_end, soft, vote, cap)
         nms = ops.class_nms if view is None else ops.class_nms_ws
         keep_idx, keep_cnt = nms(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
         cnt = keep_cnt.cpu().tolist()                   # the one host sync of predict()
@@ -375,6 +418,44 @@ class MaskRCNN(object):
         sel = torch.cat(sel).long()
         lab = torch.cat(lab)
         out = (cls_bbox[sel], lab, prob[sel, (lab + 1).long()], levels[sel])
+        return out if view is None else out + (view[sel],)
+
+    def _suppress_boxpost(self, cls_bbox, prob, levels, view, l_end, soft, vote, cap):
+        """``_suppress`` with Soft-NMS, box voting or the detection cap on: the selection through class_soft_nms (its
+        decayed scores are the returned ones) or the hard NMS, the kept boxes through box_vote, then the ``cap`` highest scores (ties
+        to the earlier row) in their order.  level / view stay those of the kept proposal; still one host sync (the keep counts)."""
+        dev = prob.device
+        keep_score = keep_box = None
+        if soft is not None:
+            keep_idx, keep_score, keep_cnt = ops.class_soft_nms(cls_bbox, prob, 1, l_end, self.score_thresh, soft[0], self.nms_thresh, soft[1])
+        else:
+            nms = ops.class_nms if view is None else ops.class_nms_ws
+            keep_idx, keep_cnt = nms(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
+        if vote is not None:
+            keep_box = ops.box_vote(cls_bbox, prob, 1, l_end, self.score_thresh, vote, keep_idx, keep_cnt)
+        cnt = keep_cnt.cpu().tolist()                   # the one host sync of predict()
+        sel, lab, sc, bb = [], [], [], []
+        for l in range(1, l_end):
+            if cnt[l]:
+                sel.append(keep_idx[l, :cnt[l]])
+                lab.append(torch.full((cnt[l],), l - 1, dtype=torch.int32, device=dev))
+                if keep_score is not None:
+                    sc.append(keep_score[l, :cnt[l]])
+                if keep_box is not None:
+                    bb.append(keep_box[l, :cnt[l]])
+        if not sel:
+            z = torch.zeros((0,), dtype=torch.long, device=dev)
+            out = (cls_bbox[z], z.to(torch.int32), prob[z, 0], levels[z])
+            return out if view is None else out + (view[z],)
+        sel = torch.cat(sel).long()
+        lab = torch.cat(lab)
+        score = torch.cat(sc) if keep_score is not None else prob[sel, (lab + 1).long()]
+        bbox = torch.cat(bb) if keep_box is not None else cls_bbox[sel]
+        if cap is not None and sel.shape[0] > cap:
+            top = torch.sort(score, descending=True, stable=True)[1][:cap]
+            top = torch.sort(top)[0]
+            sel, lab, score, bbox = sel[top], lab[top], score[top], bbox[top]
+        out = (bbox, lab, score, levels[sel])
         return out if view is None else out + (view[sel],)
 
     def prepare_size(self, H, W):

@@ -4,6 +4,7 @@
 //   decode       chainer_maskrcnn/model/maskrcnn.py:178-205  (un-scale, loc2bbox, clip, softmax)
 //   candidates   maskrcnn.py:278-312  (_suppress: prob > score_thresh, score descending then index descending, ChainerCV NMS)
 //   paste        maskrcnn.py:231-246  (cv2.resize to the box, *255, truncate, > 127, paste)
+// and the rules of Soft-NMS and box voting (boxpost.hip): the IoU as a value and the score weight.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,26 @@ __device__ __forceinline__ bool nms_suppresses(float4 b, float area_b, float4 c,
     const float ai = hgt * wid;
     const float iou = ai / ((area_b + (c.z - c.x) * (c.w - c.y)) - ai);
     return iou >= thresh;
+}
+
+// The IoU of nms_suppresses as a value: box b (of area area_b, the product of its sides) against box c, the division correctly rounded.
+// Two zero-area boxes give NaN; the callers' comparisons are written so that NaN has no effect.
+__device__ __forceinline__ float box_iou(float4 b, float area_b, float4 c) {
+    const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y), bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
+    const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
+    const float ai = hgt * wid;
+    return ai / ((area_b + (c.z - c.x) * (c.w - c.y)) - ai);
+}
+
+// The weight a selected box puts on the score of a remaining candidate of its class at this IoU (Soft-NMS, Bodla et al. 2017; method =
+// SOFT_NMS_*, the values of the public header's MRCNN_SOFT_NMS_*): hard 0 at iou >= nms_thresh; linear 1 - iou at iou >= nms_thresh; gaussian expf(-(iou * iou) / sigma) at iou > 0;
+// 1 otherwise (a NaN IoU included).
+enum { SOFT_NMS_HARD = 0, SOFT_NMS_LINEAR = 1, SOFT_NMS_GAUSSIAN = 2 };
+
+__device__ __forceinline__ float soft_nms_weight(int method, float iou, float nms_thresh, float sigma) {
+    if (method == SOFT_NMS_GAUSSIAN) return iou > 0.f ? expf(-(iou * iou) / sigma) : 1.0f;
+    if (iou >= nms_thresh) return method == SOFT_NMS_LINEAR ? 1.0f - iou : 0.0f;
+    return 1.0f;
 }
 
 // Mask paste of one detection (maskrcnn.py:231-246): the S x S map m(yy, xx) = tap(yy, xx) goes through cv2.resize(m, (w, h)), float

@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from evaluate import tta_settings  # noqa: E402
+from evaluate import add_boxpost_flags, boxpost_settings, tta_settings, use_boxpost  # noqa: E402
 
 IMAGE_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
 SYNTHETIC_FIRST_SEED = 2000003      # far from the seeds of the synthetic training pool and of the synthetic val split
@@ -58,6 +58,7 @@ def build_parser():
     parser.add_argument('--tta-hflip', type=int, default=0, choices=[0, 1],
                         help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no --tta-sizes)')
     parser.add_argument('--tta-max-size', type=int, default=None, help='long-side cap of the test-time views (default: the model\'s max_size)')
+    add_boxpost_flags(parser)
     parser.add_argument('--json', type=int, default=0, choices=[0, 1], help='1: also write <stem>.json per image')
     parser.add_argument('--image-size', type=int, nargs=2, default=[480, 640], help='--synthetic: image height and width')
     return parser
@@ -116,6 +117,7 @@ def check_args(args):
     if args.tta_sizes and any(s <= 0 for s in args.tta_sizes):
         raise ValueError('--tta-sizes: every size must be positive, got %s' % (args.tta_sizes,))
     tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, 1)      # a max size without views
+    boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
     return collect_inputs(args.inputs)
 
 
@@ -216,6 +218,7 @@ def run(args):
     if args.score_thresh is not None:
         model.score_thresh = args.score_thresh
     keypoints = model.head_arch == 'fpn_keypoint'
+    use_boxpost(model, boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections))
     tta = tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, model.min_size)
     if tta is not None:
         perm = None

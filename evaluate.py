@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from train import tta_settings  # noqa: E402
+from train import add_boxpost_flags, boxpost_settings, tta_settings, use_boxpost  # noqa: E402
 
 SYNTHETIC_VAL_IMAGES = 16           # train.py's synthetic val split of --eval-images 0
 
@@ -50,6 +50,7 @@ def build_parser():
     parser.add_argument('--tta-hflip', type=int, default=0, choices=[0, 1],
                         help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no --tta-sizes)')
     parser.add_argument('--tta-max-size', type=int, default=None, help='long-side cap of the test-time views (default: the model\'s max_size)')
+    add_boxpost_flags(parser)
     parser.add_argument('--out', '-o', default='result_eval', help='Output directory')
     return parser
 
@@ -60,6 +61,7 @@ def check_args(args):
     world = int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
         raise ValueError('evaluate.py runs in a single process; with %d ranks it is not supported' % world)
+    return boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
 
 
 def label_names(args):
@@ -101,8 +103,9 @@ def run(args):
     """Evaluates and writes the files; returns {'segm': 12 stats, 'bbox': 12 stats}."""
     from chainer_maskrcnn import evaluations
     from chainer_maskrcnn.evaluator import InstanceSegmentationCOCOEvaluator, split_coco_results
-    check_args(args)
+    boxpost = check_args(args)
     model = build_model(args)
+    use_boxpost(model, boxpost)
     tta = tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, model.min_size)
     if tta is not None:
         model.use_test_augmentation(tta['sizes'], hflip=tta['hflip'], max_size=tta['max_size'])
@@ -117,7 +120,8 @@ def run(args):
             with open(os.path.join(args.out, name), 'w') as f:
                 json.dump(res, f)
     with open(os.path.join(args.out, 'metrics.json'), 'w') as f:
-        json.dump(dict(ev.stats, tta=tta) if tta is not None else ev.stats, f, indent=1)
+        extra = {k: v for k, v in (('tta', tta), ('boxpost', boxpost)) if v is not None}
+        json.dump(dict(ev.stats, **extra) if extra else ev.stats, f, indent=1)
     for t in ('segm', 'bbox'):
         print(evaluations.format_coco_stats(ev.stats[t], t))
     return ev.stats

@@ -893,6 +893,40 @@ int mrcnn_vis_render_u8(const float *img, int H, int W, const unsigned char *mas
                         const int32_t *order, int D, int mask_a256, int box_thickness, int flags, const mrcnn_vis_prim_t *prims, int n_prims,
                         const unsigned long long *font, int n_glyphs, unsigned char *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Soft-NMS and box voting (boxpost.hip; MaskRCNN.use_soft_nms / use_box_voting).  Detectron's TEST.SOFT_NMS and
+ * TEST.BBOX_VOTE on the outputs of mrcnn_detect_decode_f32 / mrcnn_tta_detect_decode_f32: cls_bbox (R,4), prob (R,n_class), classes
+ * l in [l_begin, l_end), float32 throughout, no contraction, correctly rounded divisions.  iou(b, c) = ai / ((area_b + area_c) - ai), the
+ * expression of mrcnn_class_nms_f32.  A row i is a candidate of class l when prob[i,l] > score_thresh.
+ * class_soft_nms: per class, with the working scores s_i = prob[i,l] of its candidates: while a candidate remains, take m = the largest
+ *   (s, i) (score descending, then index descending); keep_idx[l][cnt] = m, keep_score[l][cnt] = s_m; remove m; every remaining c gets
+ *   s_c = s_c * w(iou(box_m, box_c)) and is removed unless s_c > score_thresh.  w by method: MRCNN_SOFT_NMS_HARD 0 at iou >= nms_thresh
+ *   (the keep lists of mrcnn_class_nms_f32, scores unchanged); MRCNN_SOFT_NMS_LINEAR 1 - iou at iou >= nms_thresh; MRCNN_SOFT_NMS_GAUSSIAN
+ *   expf(-(iou * iou) / sigma) at iou > 0; 1 otherwise (a NaN iou included).  keep_idx (n_class,R) int32, keep_score (n_class,R) float32,
+ *   keep_cnt (n_class) int32 (0 outside [l_begin, l_end)); rows >= keep_cnt[l] are left unwritten.  0 < R <= MRCNN_BOXPOST_MAX.  A class
+ *   with up to MRCNN_SOFT_NMS_LDS_MAX candidates runs in LDS; R above that needs ws of mrcnn_class_soft_nms_workspace_bytes(R, n_class)
+ *   bytes, 16-byte aligned (otherwise ws is unused and may be NULL).  One launch, no host synchronisation.
+ * box_vote: for every kept detection k < keep_cnt[l] of class l, with b = cls_bbox[keep_idx[l][k]]: over the candidates c of the class with
+ *   iou(b, box_c) >= vote_thresh, keep_box[l][k] = (sum of prob[c,l] * box_c) / (sum of prob[c,l]) per coordinate (Detectron's scoring
+ *   method ID: scores are not changed); b itself when no candidate qualifies (a zero-area b).  Fixed summation order, no atomics: the
+ *   same bits on every run.  keep_box (n_class,R,4) float32, 16-byte aligned; rows >= keep_cnt[l] are left unwritten.
+ * Errors, before any launch: MRCNN_E_INVALID for a NULL pointer, R <= 0, n_class <= 0, an l range outside [0, n_class], an unknown
+ * method, sigma <= 0, a vote_thresh outside (0, 1], a negative score_thresh of box_vote (its weights must be positive), a misaligned
+ * pointer; MRCNN_E_UNSUPPORTED for R > MRCNN_BOXPOST_MAX; MRCNN_E_WORKSPACE
+ * for a short or NULL workspace.
+ * ---------------------------------------------------------------------------------------- */
+#define MRCNN_BOXPOST_MAX 4096
+#define MRCNN_SOFT_NMS_LDS_MAX 2048
+#define MRCNN_SOFT_NMS_HARD 0
+#define MRCNN_SOFT_NMS_LINEAR 1
+#define MRCNN_SOFT_NMS_GAUSSIAN 2
+size_t mrcnn_class_soft_nms_workspace_bytes(int R, int n_class);
+int mrcnn_class_soft_nms_f32(const float *cls_bbox, const float *prob, int R, int n_class, int l_begin, int l_end, float score_thresh,
+                             int method, float nms_thresh, float sigma, int32_t *keep_idx, float *keep_score, int32_t *keep_cnt,
+                             void *ws, size_t ws_bytes, void *stream);
+int mrcnn_box_vote_f32(const float *cls_bbox, const float *prob, int R, int n_class, int l_begin, int l_end, float score_thresh,
+                       float vote_thresh, const int32_t *keep_idx, const int32_t *keep_cnt, float *keep_box, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

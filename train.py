@@ -23,6 +23,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
+DEFAULT_SOFT_NMS_SIGMA = 0.5        # --soft-nms-sigma / --eval-soft-nms-sigma when not given (Detectron's TEST.SOFT_NMS.SIGMA)
 AUGMENT_SEED = 5678                 # seed of the per-example augmentation decisions (dataset/augment.py), recorded in trainer_<it>.pt
 NO_FREEZE = {'bn': 0, 'at': 0}       # what a trainer state without the 'freeze' key was trained with
 NO_OPTIM = {'accum_steps': 1, 'grad_clip': 0.0, 'schedule': None}      # what a trainer state without the 'optim' key was trained with
@@ -92,6 +93,7 @@ def build_parser(keypoints=False):
                              '--eval-tta-sizes); keypoint heads swap their left / right channels')
     parser.add_argument('--eval-tta-max-size', type=int, default=None,
                         help='long-side cap of the test-time views (default: the model\'s max_size)')
+    add_boxpost_flags(parser, '--eval-')
     parser.add_argument('--hflip', type=int, default=0, choices=[0, 1],
                         help='1: mirror each training example with probability 0.5 (images, masks, boxes; keypoints with their left / right '
                              'channels swapped); --synthetic 0 only')
@@ -185,6 +187,60 @@ def tta_settings(sizes, hflip, max_size, min_size):
             'max_size': None if max_size is None else int(max_size)}
 
 
+def add_boxpost_flags(parser, prefix='--'):
+    """--soft-nms / --soft-nms-sigma / --box-vote-thresh / --max-detections of evaluate.py and demo.py; with the prefix '--eval-' the
+    flags of the periodic evaluator here."""
+    parser.add_argument(prefix + 'soft-nms', default='off', choices=['off', 'linear', 'gaussian'],
+                        help='Soft-NMS in place of the hard per-class NMS (MaskRCNN.use_soft_nms): a kept box lowers the scores of the '
+                             'boxes it overlaps instead of deleting them; off by default')
+    parser.add_argument(prefix + 'soft-nms-sigma', type=float, default=None, metavar='S',
+                        help='sigma of %ssoft-nms gaussian (default %s)' % (prefix, DEFAULT_SOFT_NMS_SIGMA))
+    parser.add_argument(prefix + 'box-vote-thresh', type=float, default=0.0, metavar='T',
+                        help='box voting (MaskRCNN.use_box_voting): every kept box becomes the score-weighted mean of the candidates of '
+                             'its class with IoU >= T (Detectron: 0.8); 0 = off')
+    parser.add_argument(prefix + 'max-detections', type=int, default=0, metavar='N',
+                        help='keep the N highest-scoring detections of an image (MaskRCNN.use_max_detections; Detectron: 100); 0 = off')
+
+
+def boxpost_settings(soft_nms, sigma, vote_thresh, max_detections, prefix='--'):
+    """The arguments of use_soft_nms / use_box_voting / use_max_detections from the flags (evaluate.py, demo.py; --eval-* here): None = all
+    off, else {'soft_nms': None | 'linear' | 'gaussian', 'sigma', 'vote_thresh': None | T, 'max_detections': None | N}.  ValueError for
+    a value the model would refuse."""
+    if soft_nms not in ('off', 'linear', 'gaussian'):
+        raise ValueError('%ssoft-nms must be off, linear or gaussian, got %r' % (prefix, soft_nms))
+    if sigma is not None and soft_nms != 'gaussian':
+        raise ValueError('%ssoft-nms-sigma belongs to %ssoft-nms gaussian' % (prefix, prefix))
+    if sigma is not None and not sigma > 0:
+        raise ValueError('%ssoft-nms-sigma must be positive, got %r' % (prefix, sigma))
+    if not 0 <= vote_thresh <= 1:
+        raise ValueError('%sbox-vote-thresh must lie in (0, 1] (0 = off), got %r' % (prefix, vote_thresh))
+    if max_detections < 0:
+        raise ValueError('%smax-detections must not be negative (0 = off), got %r' % (prefix, max_detections))
+    if soft_nms == 'off' and not vote_thresh and not max_detections:
+        return None
+    return {'soft_nms': None if soft_nms == 'off' else soft_nms, 'sigma': float(sigma) if sigma is not None else DEFAULT_SOFT_NMS_SIGMA,
+            'vote_thresh': float(vote_thresh) if vote_thresh else None, 'max_detections': int(max_detections) if max_detections else None}
+
+
+def use_boxpost(model, settings):
+    """Applies boxpost_settings' result (None: nothing) to the model."""
+    if settings is None:
+        return
+    model.use_soft_nms(settings['soft_nms'], settings['sigma'])
+    model.use_box_voting(settings['vote_thresh'])
+    model.use_max_detections(settings['max_detections'])
+
+
+def _eval_boxpost_settings(args):
+    """--eval-soft-nms / --eval-soft-nms-sigma / --eval-box-vote-thresh / --eval-max-detections: they act on the periodic evaluator's
+    predictions, so they are refused without one."""
+    b = boxpost_settings(args.eval_soft_nms, args.eval_soft_nms_sigma, args.eval_box_vote_thresh, args.eval_max_detections, '--eval-')
+    if b is not None and args.eval_interval <= 0:
+        raise ValueError('--eval-soft-nms / --eval-box-vote-thresh / --eval-max-detections change the predictions of the periodic '
+                         'evaluator: they need --eval-interval > 0')
+    return b
+
+
 def _check_augment_args(args):
     if (args.hflip or args.min_sizes) and args.synthetic:
         raise ValueError('--hflip / --min-sizes augment the dataset loader (--synthetic 0); the synthetic batches (--synthetic 1) are not '
@@ -228,6 +284,7 @@ def run(args, keypoints=False):
         raise ValueError('--eval-interval: evaluation runs in single-process training only; with %d ranks it is not supported '
                          '(the reference\'s multi-GPU branch has no test iterator either, train.py:117-121, and would fail there)' % world)
     _check_augment_args(args)
+    eval_boxpost = _eval_boxpost_settings(args)
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
     if resume is not None and resume.get('augment', NO_AUGMENT) != augment_settings(args):
         raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
@@ -345,6 +402,7 @@ def run(args, keypoints=False):
     evaluator = _make_evaluator(args, faster_rcnn, labels, n_fg, K) if args.eval_interval > 0 else None
     if evaluator is not None:
         _use_eval_tta(args, faster_rcnn, evaluator)
+        use_boxpost(faster_rcnn, eval_boxpost)
     rtx = _Roctx() if args.profile else None
     t0 = time.time()
     t_eval = 0.0            # seconds spent in evaluation: not part of the training throughput
