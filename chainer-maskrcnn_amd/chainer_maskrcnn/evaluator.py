@@ -15,6 +15,8 @@ Mask heads, COCO's metric: ``InstanceSegmentationCOCOEvaluator``, mask and box A
 'segm' / 'bbox'), from the same device counts; optionally it writes COCO results entries, the masks run-length encoded on the device
 (``mask_rle_encode``).
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -47,14 +49,81 @@ class TransformedDataset(object):
         return self.transform(self.dataset[i])
 
 
-class InstanceSegmentationVOCEvaluator(object):
+def image_tensor(img):
+    """An example's image (array or tensor, 0..255) as the float32 tensor ``predict`` / ``predict_keypoints`` take."""
+    return img.to(torch.float32) if isinstance(img, torch.Tensor) else torch.as_tensor(np.asarray(img, dtype=np.float32))
+
+
+def device_tensor(a, device):
+    """Ground truth (array or tensor) on the device."""
+    return a.to(device) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def copy_to_host(*parts):
+    """int32 / float32 device tensors -> NumPy arrays of their shapes and dtypes through ONE device->host copy (none when every part is
+    empty): concatenated as 32-bit words on the device, split by lengths on the host."""
+    if any(p.dtype not in (torch.int32, torch.float32) for p in parts):
+        raise TypeError('copy_to_host: int32 / float32 tensors expected, got %s' % ', '.join(str(p.dtype) for p in parts))
+    dtypes = [np.float32 if p.dtype == torch.float32 else np.int32 for p in parts]
+    if not any(p.numel() for p in parts):
+        return [np.zeros(tuple(p.shape), dtype=t) for p, t in zip(parts, dtypes)]
+    words = torch.cat([p.reshape(-1).view(torch.int32) for p in parts]).cpu().numpy()
+    words = np.split(words, np.cumsum([p.numel() for p in parts])[:-1])
+    return [w.view(t).reshape(tuple(p.shape)) for w, p, t in zip(words, parts, dtypes)]
+
+
+@contextlib.contextmanager
+def training_state_kept(target):
+    """``target.train``, ``core.TRAIN`` and the train flags a forward leaves on ``target.rpn`` / ``target.head`` (where the target has
+    them) are, after the block, what they were before it - also when the block raises."""
+    from chainer_maskrcnn.nn import core
+    parts = [p for p in (getattr(target, 'rpn', None), getattr(target, 'head', None)) if hasattr(p, 'train')]
+    keep = (target.train, core.TRAIN, [p.train for p in parts])
+    try:
+        yield
+    finally:
+        target.train, core.TRAIN = keep[0], keep[1]
+        for p, t in zip(parts, keep[2]):
+            p.train = t
+
+
+class _Evaluator(object):
+    """The loop of the three evaluators: every example of ``dataset`` through ``_add_example`` into a fresh ``_accumulator()``, without
+    autograd and with the target's training state restored afterwards, then ``_report`` of what was accumulated."""
+
+    default_name = 'validation'
+
+    def evaluate(self):
+        acc = self._accumulator()
+        with training_state_kept(self.target), torch.no_grad():
+            for i in range(len(self.dataset)):
+                self._add_example(acc, self.dataset[i])
+        return self._report(acc)
+
+
+class _SyntheticSplit(object):
+    """A deterministic synthetic val split: example i is ``_example`` of utils/synthetic.make_batch(first_seed + i, 1, H, W, G=G,
+    **batch_kwargs), one image per seed.  Seeds start at ``first_seed``, far from the seeds of train.py's synthetic training pool."""
+
+    def __init__(self, n_images, H, W, G, first_seed, **batch_kwargs):
+        self.n, self.H, self.W, self.G, self.first_seed, self.batch_kwargs = n_images, H, W, G, first_seed, batch_kwargs
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        from chainer_maskrcnn.utils.synthetic import make_batch
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        return self._example(make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, **self.batch_kwargs), i)
+
+
+class InstanceSegmentationVOCEvaluator(_Evaluator):
     """PASCAL VOC mAP of ``target.predict`` over ``dataset``, whose examples are (img (3,H,W) 0..255, gt_masks (G,H,W), gt_labels (G,))
     or the same with (G,) difficult flags appended.  ``evaluate()`` returns {'main/map': float, 'main/ap/<label_names[l]>': float};
     a trainer writes them with the prefix 'validation/' (the reference's keys, e.g. 'validation/main/map').
 
     ``target``'s preset (score / NMS thresholds) is used as it is, and its training state is restored afterwards."""
-
-    default_name = 'validation'
 
     def __init__(self, dataset, target, iou_thresh=0.5, use_07_metric=False, label_names=None):
         self.dataset = dataset
@@ -63,22 +132,10 @@ class InstanceSegmentationVOCEvaluator(object):
         self.use_07_metric = use_07_metric
         self.label_names = label_names
 
-    def evaluate(self):
-        from chainer_maskrcnn.nn import core
-        target = self.target
-        rpn, head = getattr(target, 'rpn', None), getattr(target, 'head', None)
-        keep = (target.train, core.TRAIN, getattr(rpn, 'train', None), getattr(head, 'train', None))
-        acc = evaluations.VOCMatchAccumulator()
-        try:
-            with torch.no_grad():
-                for i in range(len(self.dataset)):
-                    self._add_example(acc, self.dataset[i])
-        finally:
-            target.train, core.TRAIN = keep[0], keep[1]
-            if keep[2] is not None:
-                rpn.train = keep[2]
-            if keep[3] is not None:
-                head.train = keep[3]
+    def _accumulator(self):
+        return evaluations.VOCMatchAccumulator()
+
+    def _report(self, acc):
         prec, rec = acc.prec_rec()
         ap = evaluations.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
         report = {'main/map': evaluations.nanmean(ap)}
@@ -91,41 +148,28 @@ class InstanceSegmentationVOCEvaluator(object):
         img, gt_mask, gt_label = example[:3]
         gt_difficult = np.asarray(example[3], dtype=bool) if len(example) > 3 and example[3] is not None else None
         dev = self.target.device
-        img = torch.as_tensor(np.asarray(img, dtype=np.float32)) if not isinstance(img, torch.Tensor) else img.to(torch.float32)
-        masks, labels, scores = self.target.predict([img])
+        masks, labels, scores = self.target.predict([image_tensor(img)])
         mask, label, score = masks[0], labels[0].to(torch.int32), scores[0].to(torch.float32)
         gt_label = np.asarray(gt_label.cpu() if isinstance(gt_label, torch.Tensor) else gt_label, dtype=np.int32).reshape(-1)
         D, G = int(label.shape[0]), int(gt_label.shape[0])
-        parts = [label, score.view(torch.int32)]
         if D and G:
-            gm = gt_mask.to(dev) if isinstance(gt_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_mask)).to(dev)
-            inter, area_a, area_b = ops.mask_iou_counts(mask, gm, label, torch.from_numpy(gt_label).to(dev))
-            parts += [inter.reshape(-1), area_a, area_b]
-        host = torch.cat(parts).cpu().numpy() if D else np.zeros((0,), dtype=np.int32)      # the one copy of this image
-        pred_label, pred_score = host[:D], host[D:2 * D].view(np.float32)
-        if D and G:
-            o = 2 * D
-            iou = evaluations.iou_from_counts(host[o:o + D * G].reshape(D, G), host[o + D * G:o + D * G + D], host[o + D * G + D:])
+            overlap = ops.mask_iou_counts(mask, device_tensor(gt_mask, dev), label, torch.from_numpy(gt_label).to(dev))
+            pred_label, pred_score, inter, area_a, area_b = copy_to_host(label, score, *overlap)      # the one copy of this image
+            iou = evaluations.iou_from_counts(inter, area_a, area_b)
         else:
+            pred_label, pred_score = copy_to_host(label, score)
             iou = np.zeros((D, G), dtype=np.float64)
         acc.add_image(iou, pred_label, pred_score, gt_label, gt_difficult, self.iou_thresh)
 
 
-class SyntheticEvalDataset(object):
-    """Deterministic synthetic val split (utils/synthetic.make_batch, one image per seed): examples (img 0..255, masks, labels).
-    Seeds start at ``first_seed``, far from the seeds of train.py's synthetic training pool."""
+class SyntheticEvalDataset(_SyntheticSplit):
+    """Deterministic synthetic val split (_SyntheticSplit): examples (img 0..255, masks, labels)."""
 
     def __init__(self, n_images, H, W, n_fg_class=80, G=8, first_seed=1000003):
-        self.n, self.H, self.W, self.n_fg_class, self.G, self.first_seed = n_images, H, W, n_fg_class, G, first_seed
+        super().__init__(n_images, H, W, G, first_seed, n_fg_class=n_fg_class)
+        self.n_fg_class = n_fg_class
 
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        from chainer_maskrcnn.utils.synthetic import make_batch
-        if not 0 <= i < self.n:
-            raise IndexError(i)
-        b = make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, n_fg_class=self.n_fg_class)
+    def _example(self, b, i):
         return b['imgs'][0] * 255, b['masks'][0], b['labels'][0]
 
 
@@ -155,7 +199,7 @@ class COCOKeypointEvalDataset(object):
         return coco_keypoint_example(self.loader, i)
 
 
-class KeypointCOCOEvaluator(object):
+class KeypointCOCOEvaluator(_Evaluator):
     """COCO keypoint AP (pycocotools COCOeval, iouType='keypoints'; evaluations.COCOKeypointMatchAccumulator) of
     ``target.predict_keypoints`` over ``dataset``, whose examples are (img (3,H,W) 0..255, gt_kp (G,K,3) (y,x,v), gt_area (G,),
     gt_crowd (G,), gt_bbox_xywh (G,4)).  ``evaluate()`` returns {'main/map' (AP at OKS .50:.95), 'main/ap50', 'main/ap75',
@@ -164,8 +208,6 @@ class KeypointCOCOEvaluator(object):
     Per image: ``predict_keypoints``, then ONE device->host copy of the scores and the (y, x) of the (up to) 20 best-scored
     detections; OKS in float64 and the matching on the host.  sigmas default to COCO's 17; other K need explicit sigmas.
     ``target``'s preset is used as it is, and its training state is restored afterwards."""
-
-    default_name = 'validation'
 
     def __init__(self, dataset, target, sigmas=None):
         K = getattr(getattr(target, 'head', None), 'n_keypoints', None)
@@ -176,30 +218,17 @@ class KeypointCOCOEvaluator(object):
         self.target = target
         self.sigmas = None if sigmas is None else np.asarray(sigmas, dtype=np.float64)
 
-    def evaluate(self):
-        from chainer_maskrcnn.nn import core
-        target = self.target
-        rpn, head = getattr(target, 'rpn', None), getattr(target, 'head', None)
-        keep = (target.train, core.TRAIN, getattr(rpn, 'train', None), getattr(head, 'train', None))
-        acc = evaluations.COCOKeypointMatchAccumulator()
-        try:
-            with torch.no_grad():
-                for i in range(len(self.dataset)):
-                    self._add_example(acc, self.dataset[i])
-        finally:
-            target.train, core.TRAIN = keep[0], keep[1]
-            if keep[2] is not None:
-                rpn.train = keep[2]
-            if keep[3] is not None:
-                head.train = keep[3]
+    def _accumulator(self):
+        return evaluations.COCOKeypointMatchAccumulator()
+
+    def _report(self, acc):
         s = acc.summarize()
         return {'main/map': s['AP'], 'main/ap50': s['AP50'], 'main/ap75': s['AP75'], 'main/ap_medium': s['APm'],
                 'main/ap_large': s['APl'], 'main/ar': s['AR']}
 
     def _add_example(self, acc, example):
         img, gt_kp, gt_area, gt_crowd, gt_bbox = example[:5]
-        img = torch.as_tensor(np.asarray(img, dtype=np.float32)) if not isinstance(img, torch.Tensor) else img.to(torch.float32)
-        keypoints, _, scores = self.target.predict_keypoints([img])
+        keypoints, _, scores = self.target.predict_keypoints([image_tensor(img)])
         kp, score = keypoints[0], scores[0].to(torch.float32)
         D, K = int(kp.shape[0]), int(kp.shape[1])
         n = min(D, acc.max_dets)
@@ -212,22 +241,15 @@ class KeypointCOCOEvaluator(object):
         evaluations.add_keypoint_image(acc, dt_yx, dt_score, gt_kp, gt_area, gt_crowd, gt_bbox, self.sigmas)
 
 
-class SyntheticKeypointEvalDataset(object):
-    """Deterministic synthetic keypoint val split (utils/synthetic.make_batch with n_fg_class=1, n_keypoints=K, one image per seed):
-    examples (img 0..255, gt_kp (G,K,3) (y,x,v=2), gt_area, gt_crowd (zeros), gt_bbox_xywh).  gt_area is the box area h * w, a
-    stand-in for COCO's segmentation area.  Seeds start at ``first_seed``, far from the seeds of train.py's synthetic training pool."""
+class SyntheticKeypointEvalDataset(_SyntheticSplit):
+    """Deterministic synthetic keypoint val split (_SyntheticSplit with n_fg_class=1, n_keypoints=K): examples (img 0..255, gt_kp (G,K,3)
+    (y,x,v=2), gt_area, gt_crowd (zeros), gt_bbox_xywh).  gt_area is the box area h * w, a stand-in for COCO's segmentation area."""
 
     def __init__(self, n_images, H, W, n_keypoints=17, G=8, first_seed=1000003):
-        self.n, self.H, self.W, self.K, self.G, self.first_seed = n_images, H, W, n_keypoints, G, first_seed
+        super().__init__(n_images, H, W, G, first_seed, n_fg_class=1, n_keypoints=n_keypoints)
+        self.K = n_keypoints
 
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        from chainer_maskrcnn.utils.synthetic import make_batch
-        if not 0 <= i < self.n:
-            raise IndexError(i)
-        b = make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, n_fg_class=1, n_keypoints=self.K)
+    def _example(self, b, i):
         box = b['bboxes'][0].astype(np.float64)
         h, w = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
         xywh = np.stack([box[:, 1], box[:, 0], w, h], axis=1)
@@ -239,7 +261,7 @@ _COCO_KEYS = (('map', 'AP'), ('ap50', 'AP50'), ('ap75', 'AP75'), ('ap_small', 'A
               ('ar', 'AR100'))
 
 
-class InstanceSegmentationCOCOEvaluator(object):
+class InstanceSegmentationCOCOEvaluator(_Evaluator):
     """COCO mask and box AP (pycocotools COCOeval, iouType 'segm' / 'bbox'; evaluations.COCOInstanceMatchAccumulator) of
     ``target.predict`` over ``dataset``, whose examples are (img (3,H,W) 0..255, gt_masks (G,H,W), gt_labels (G,), gt_area (G,),
     gt_crowd (G,), gt_bbox_xywh (G,4), image_id) - COCOInstanceEvalDataset, SyntheticCOCOEvalDataset.  ``cat_ids[label]`` is a
@@ -257,8 +279,6 @@ class InstanceSegmentationCOCOEvaluator(object):
     (split_coco_results makes the two results files).  No mask is kept on the host.  ``target``'s preset is used as it is, and its
     training state is restored afterwards."""
 
-    default_name = 'validation'
-
     def __init__(self, dataset, target, label_names=None, cat_ids=None, iou_types=('segm', 'bbox'), results=None):
         if not iou_types or any(t not in ('segm', 'bbox') for t in iou_types):
             raise ValueError("InstanceSegmentationCOCOEvaluator: iou_types from ('segm', 'bbox'), got %r" % (iou_types,))
@@ -274,22 +294,10 @@ class InstanceSegmentationCOCOEvaluator(object):
         label = np.asarray(label, dtype=np.int64)
         return label if self.cat_ids is None else np.asarray(self.cat_ids, dtype=np.int64)[label]
 
-    def evaluate(self):
-        from chainer_maskrcnn.nn import core
-        target = self.target
-        rpn, head = getattr(target, 'rpn', None), getattr(target, 'head', None)
-        keep = (target.train, core.TRAIN, getattr(rpn, 'train', None), getattr(head, 'train', None))
-        accs = {t: evaluations.COCOInstanceMatchAccumulator() for t in self.iou_types}
-        try:
-            with torch.no_grad():
-                for i in range(len(self.dataset)):
-                    self._add_example(accs, self.dataset[i])
-        finally:
-            target.train, core.TRAIN = keep[0], keep[1]
-            if keep[2] is not None:
-                rpn.train = keep[2]
-            if keep[3] is not None:
-                head.train = keep[3]
+    def _accumulator(self):
+        return {t: evaluations.COCOInstanceMatchAccumulator() for t in self.iou_types}
+
+    def _report(self, accs):
         report = {}
         for t, acc in accs.items():
             pr = acc.precision_recall()
@@ -305,8 +313,7 @@ class InstanceSegmentationCOCOEvaluator(object):
     def _add_example(self, accs, example):
         img, gt_mask, gt_label, gt_area, gt_crowd, gt_bbox, image_id = example[:7]
         dev = self.target.device
-        img = torch.as_tensor(np.asarray(img, dtype=np.float32)) if not isinstance(img, torch.Tensor) else img.to(torch.float32)
-        masks, labels, scores = self.target.predict([img])
+        masks, labels, scores = self.target.predict([image_tensor(img)])
         mask, label, score = masks[0], labels[0].to(torch.int32).contiguous(), scores[0].to(torch.float32).contiguous()
         gt_label = np.asarray(gt_label.cpu() if isinstance(gt_label, torch.Tensor) else gt_label, dtype=np.int32).reshape(-1)
         gt_crowd = np.asarray(gt_crowd, dtype=bool).reshape(-1)
@@ -315,17 +322,9 @@ class InstanceSegmentationCOCOEvaluator(object):
         H, W = int(mask.shape[1]), int(mask.shape[2])
         if D:
             bbox = self.target.last_bboxes[0].to(torch.float32).contiguous()
-            gm = gt_mask.to(dev) if isinstance(gt_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_mask)).to(dev)
-            gm = gm.reshape(G, H, W)
-            inter, area_dt, area_gt = ops.mask_iou_counts(mask, gm, label, torch.from_numpy(gt_label).to(dev))
-            host = torch.cat((label, score.view(torch.int32), bbox.view(torch.int32).reshape(-1), inter.reshape(-1), area_dt,
-                              area_gt)).cpu().numpy()                      # the one copy of this image
-            o = 2 * D
-            dt_label, dt_score = host[:D], host[D:o].view(np.float32)
-            yx = host[o:o + 4 * D].view(np.float32).reshape(D, 4).astype(np.float64)
-            o += 4 * D
-            inter_h = host[o:o + D * G].reshape(D, G)
-            area_dt_h, area_gt_h = host[o + D * G:o + D * G + D], host[o + D * G + D:]
+            overlap = ops.mask_iou_counts(mask, device_tensor(gt_mask, dev).reshape(G, H, W), label, torch.from_numpy(gt_label).to(dev))
+            dt_label, dt_score, yx, inter_h, area_dt_h, area_gt_h = copy_to_host(label, score, bbox, *overlap)     # the one copy of this image
+            yx = yx.astype(np.float64)
             xywh = np.stack([yx[:, 1], yx[:, 0], yx[:, 3] - yx[:, 1], yx[:, 2] - yx[:, 0]], axis=1)
         else:
             dt_label, dt_score = np.zeros((0,), np.int32), np.zeros((0,), np.float32)
@@ -340,8 +339,7 @@ class InstanceSegmentationCOCOEvaluator(object):
         if self.results is not None and D:
             from chainer_maskrcnn.dataset.coco_api import rle_to_strings
             offsets, counts, _ = ops.mask_rle_encode(mask)
-            rle = torch.cat((offsets, counts)).cpu().numpy()                   # the second copy: the run lengths
-            strings = rle_to_strings(rle[:D + 1], rle[D + 1:])
+            strings = rle_to_strings(*copy_to_host(offsets, counts))           # the second copy: the run lengths
             for d in range(D):
                 self.results.append({'image_id': int(image_id), 'category_id': int(dt_cat[d]),
                                      'segmentation': {'size': [H, W], 'counts': strings[d]},
@@ -356,23 +354,16 @@ def split_coco_results(results):
     return segm, bbox
 
 
-class SyntheticCOCOEvalDataset(object):
-    """SyntheticEvalDataset with COCO's annotation fields (utils/synthetic.make_batch, one image per seed): examples (img 0..255, masks,
-    labels, area = each mask's pixel count, iscrowd (none), bbox_xywh from make_batch's boxes, image_id = the seed index).  Category
-    ids are the labels.  Seeds start at ``first_seed``, far from the seeds of train.py's synthetic training pool."""
+class SyntheticCOCOEvalDataset(_SyntheticSplit):
+    """SyntheticEvalDataset with COCO's annotation fields: examples (img 0..255, masks, labels, area = each mask's pixel count, iscrowd
+    (none), bbox_xywh from make_batch's boxes, image_id = the seed index).  Category ids are the labels."""
 
     def __init__(self, n_images, H, W, n_fg_class=80, G=8, first_seed=1000003):
-        self.n, self.H, self.W, self.n_fg_class, self.G, self.first_seed = n_images, H, W, n_fg_class, G, first_seed
+        super().__init__(n_images, H, W, G, first_seed, n_fg_class=n_fg_class)
+        self.n_fg_class = n_fg_class
         self.cat_ids = list(range(n_fg_class))
 
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        from chainer_maskrcnn.utils.synthetic import make_batch
-        if not 0 <= i < self.n:
-            raise IndexError(i)
-        b = make_batch(self.first_seed + i, 1, self.H, self.W, G=self.G, n_fg_class=self.n_fg_class)
+    def _example(self, b, i):
         masks, box = b['masks'][0], b['bboxes'][0].astype(np.float64)
         xywh = np.stack([box[:, 1], box[:, 0], box[:, 3] - box[:, 1], box[:, 2] - box[:, 0]], axis=1)
         area = (masks != 0).reshape(len(masks), -1).sum(axis=1).astype(np.float64)

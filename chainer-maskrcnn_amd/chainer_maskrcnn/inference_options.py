@@ -1,0 +1,134 @@
+"""The inference options of the entry scripts, stated once: the test-time augmentation and box post-processing flags of evaluate.py and
+demo.py (train.py declares them with the prefix '--eval-' for its periodic evaluator), what they turn into on a model, the label file and
+the model a checkpoint is scored or drawn with.  Importing this module needs neither a device nor the training script."""
+import os
+
+DEFAULT_SOFT_NMS_SIGMA = 0.5        # --soft-nms-sigma when not given (Detectron's TEST.SOFT_NMS.SIGMA)
+
+
+# ---- test-time augmentation (MaskRCNN.use_test_augmentation) ------------------------------------------------------------
+def add_tta_flags(parser, prefix='--'):
+    """--tta-sizes / --tta-hflip / --tta-max-size of evaluate.py and demo.py; with the prefix '--eval-' the flags of train.py's periodic
+    evaluator."""
+    parser.add_argument(prefix + 'tta-sizes', type=int, nargs='+', default=None, metavar='N',
+                        help='test-time augmentation (MaskRCNN.use_test_augmentation): run every image at these short sides and merge '
+                             'the views; off by default')
+    parser.add_argument(prefix + 'tta-hflip', type=int, default=0, choices=[0, 1],
+                        help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no %stta-sizes); '
+                             'keypoint heads swap their left / right channels' % prefix)
+    parser.add_argument(prefix + 'tta-max-size', type=int, default=None,
+                        help='long-side cap of the test-time views (default: the model\'s max_size)')
+
+
+def tta_settings(sizes, hflip, max_size, min_size):
+    """use_test_augmentation's arguments from the TTA flags (--tta-* of evaluate.py, --eval-tta-* of train.py): None = off.  hflip without
+    sizes mirrors the model's own min_size."""
+    if not sizes and not hflip:
+        if max_size is not None:
+            raise ValueError('a test-time max size needs test-time sizes or the test-time flip')
+        return None
+    return {'sizes': [int(s) for s in sizes] if sizes else [int(min_size)], 'hflip': bool(hflip),
+            'max_size': None if max_size is None else int(max_size)}
+
+
+def use_tta(model, settings, keypoint_names=None, prefix='--'):
+    """Applies tta_settings' result (None: nothing) to the model.  A keypoint head with hflip swaps its left / right channels by the flip
+    permutation of ``keypoint_names`` (default: COCO's 17 names); ValueError, naming the flag ``prefix``tta-hflip, when they are not the
+    head's keypoints or do not pair."""
+    if settings is None:
+        return
+    perm = None
+    if model.head_arch == 'fpn_keypoint' and settings['hflip']:
+        from chainer_maskrcnn.dataset import augment
+        names = augment.COCO_KEYPOINT_NAMES if keypoint_names is None else keypoint_names
+        if len(names) != model.head.n_keypoints:
+            raise ValueError('%stta-hflip 1: %d keypoint names for %d keypoints' % (prefix, len(names), model.head.n_keypoints))
+        try:
+            perm = augment.flip_permutation(names)
+        except ValueError as e:
+            raise ValueError('%stta-hflip 1: this keypoint dataset has no complete left / right flip map (%s)' % (prefix, e))
+    model.use_test_augmentation(settings['sizes'], hflip=settings['hflip'], max_size=settings['max_size'], keypoint_flip_perm=perm)
+
+
+# ---- box post-processing (MaskRCNN.use_soft_nms / use_box_voting / use_max_detections) ----------------------------------
+def add_boxpost_flags(parser, prefix='--'):
+    """--soft-nms / --soft-nms-sigma / --box-vote-thresh / --max-detections of evaluate.py and demo.py; with the prefix '--eval-' the
+    flags of train.py's periodic evaluator."""
+    parser.add_argument(prefix + 'soft-nms', default='off', choices=['off', 'linear', 'gaussian'],
+                        help='Soft-NMS in place of the hard per-class NMS (MaskRCNN.use_soft_nms): a kept box lowers the scores of the '
+                             'boxes it overlaps instead of deleting them; off by default')
+    parser.add_argument(prefix + 'soft-nms-sigma', type=float, default=None, metavar='S',
+                        help='sigma of %ssoft-nms gaussian (default %s)' % (prefix, DEFAULT_SOFT_NMS_SIGMA))
+    parser.add_argument(prefix + 'box-vote-thresh', type=float, default=0.0, metavar='T',
+                        help='box voting (MaskRCNN.use_box_voting): every kept box becomes the score-weighted mean of the candidates of '
+                             'its class with IoU >= T (Detectron: 0.8); 0 = off')
+    parser.add_argument(prefix + 'max-detections', type=int, default=0, metavar='N',
+                        help='keep the N highest-scoring detections of an image (MaskRCNN.use_max_detections; Detectron: 100); 0 = off')
+
+
+def boxpost_settings(soft_nms, sigma, vote_thresh, max_detections, prefix='--'):
+    """The arguments of use_soft_nms / use_box_voting / use_max_detections from the flags (evaluate.py, demo.py; --eval-* of train.py):
+    None = all off, else {'soft_nms': None | 'linear' | 'gaussian', 'sigma', 'vote_thresh': None | T, 'max_detections': None | N}.
+    ValueError for a value the model would refuse."""
+    if soft_nms not in ('off', 'linear', 'gaussian'):
+        raise ValueError('%ssoft-nms must be off, linear or gaussian, got %r' % (prefix, soft_nms))
+    if sigma is not None and soft_nms != 'gaussian':
+        raise ValueError('%ssoft-nms-sigma belongs to %ssoft-nms gaussian' % (prefix, prefix))
+    if sigma is not None and not sigma > 0:
+        raise ValueError('%ssoft-nms-sigma must be positive, got %r' % (prefix, sigma))
+    if not 0 <= vote_thresh <= 1:
+        raise ValueError('%sbox-vote-thresh must lie in (0, 1] (0 = off), got %r' % (prefix, vote_thresh))
+    if max_detections < 0:
+        raise ValueError('%smax-detections must not be negative (0 = off), got %r' % (prefix, max_detections))
+    if soft_nms == 'off' and not vote_thresh and not max_detections:
+        return None
+    return {'soft_nms': None if soft_nms == 'off' else soft_nms, 'sigma': float(sigma) if sigma is not None else DEFAULT_SOFT_NMS_SIGMA,
+            'vote_thresh': float(vote_thresh) if vote_thresh else None, 'max_detections': int(max_detections) if max_detections else None}
+
+
+def use_boxpost(model, settings):
+    """Applies boxpost_settings' result (None: nothing) to the model."""
+    if settings is None:
+        return
+    model.use_soft_nms(settings['soft_nms'], settings['sigma'])
+    model.use_box_voting(settings['vote_thresh'])
+    model.use_max_detections(settings['max_detections'])
+
+
+# ---- labels and the model -----------------------------------------------------------------------------------------------------------------
+def read_labels(label_file):
+    """The category names of --label_file (None when the file does not exist: every category)."""
+    if not os.path.exists(label_file):
+        return None
+    with open(label_file) as f:
+        return f.read().strip().split('\n')
+
+
+def use_score_preset(model, preset, score_thresh=None):
+    """``preset`` ('visualize' / 'evaluate') on the model, its score threshold overridden by --score-thresh when given."""
+    model.use_preset(preset)
+    if score_thresh is not None:
+        model.score_thresh = score_thresh
+
+
+def build_inference_model(args, preset=None):
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --label_file with --weight loaded (keys missing from the file keep their
+    initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
+    17 keypoints; a mask head has one class per label (80 without a label file)."""
+    import torch
+    from chainer_maskrcnn.model.maskrcnn import MaskRCNN
+    from chainer_maskrcnn.utils import chainer_npz
+    dev = torch.device('cuda', args.gpu)
+    torch.cuda.set_device(dev)
+    if args.head_arch == 'fpn_keypoint':
+        model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev)
+    else:
+        labels = read_labels(args.label_file)
+        model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev)
+    if args.weight:
+        if not os.path.exists(args.weight):
+            raise FileNotFoundError('--weight %s does not exist' % args.weight)
+        chainer_npz.load_npz(args.weight, model, strict=False)
+    if preset is not None:
+        use_score_preset(model, preset, args.score_thresh)
+    return model

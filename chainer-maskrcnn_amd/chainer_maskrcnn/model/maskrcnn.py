@@ -277,7 +277,7 @@ class MaskRCNN(object):
         D > 0, the mask / keypoint branch on the kept boxes.  Returns (size, bbox (D,4) contiguous, label, score, m, mirrors): without
         test-time augmentation m = the branch output (D,S,S,C) and mirrors = None; with it m = one such output per view and mirrors =
         the views' mirror flags; m = None where the branch did not run."""
-        if getattr(self, 'tta', None) is not None:
+        if self.tta is not None:
             size, bbox, label, score, level, view, views = self._detect_tta(img)
             bbox = bbox.contiguous()
             m = self._branch_per_view(bbox, level, view, views, size[1]) if branch and bbox.shape[0] > 0 else None
@@ -397,65 +397,41 @@ class MaskRCNN(object):
     def _suppress(self, cls_bbox, prob, levels, view=None):
         """maskrcnn.py:278-312 on the device: for every foreground class l (skipping the LAST class when masks are
         predicted - the reference's off-by-one guard, :288-291): prob[:, l] > score_thresh, NMS(nms_thresh) in
-        descending score order; results concatenated over classes, labels l-1.  With ``view`` (the test-time views' union, up to 4096
-        candidates) the selection runs through class_nms_ws and the kept rows of ``view`` are returned last."""
+        descending score order; results concatenated over classes, labels l-1.  Returns (bbox, label, score, level) of the kept
+        rows, and with ``view`` (the test-time views' union, up to 4096 candidates) the kept rows of ``view`` last.
+
+        Optional stages, none of which launches anything when off: with ``soft_nms`` the selection runs through
+        class_soft_nms and its decayed scores are the returned ones; with ``vote_thresh`` the kept boxes go through box_vote; with
+        ``max_detections`` the cap highest scores (ties to the earlier row) stay, in their order.  level / view are always those of
+        the kept proposal.  One host sync: the keep counts."""
+        dev = prob.device
         l_end = self.n_class - 1 if self.predict_mask else self.n_class
         soft, vote, cap = self.soft_nms, self.vote_thresh, self.max_detections
-        if soft is not None or vote is not None or cap is not None:
-            return self._suppress_boxpost(cls_bbox, prob, levels, view, l_end, soft, vote, cap)
-        nms = ops.class_nms if view is None else ops.class_nms_ws
-        keep_idx, keep_cnt = nms(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
-        cnt = keep_cnt.cpu().tolist()                   # the one host sync of predict()
-        sel, lab = [], []
-        for l in range(1, l_end):
-            if cnt[l]:
-                sel.append(keep_idx[l, :cnt[l]])
-                lab.append(torch.full((cnt[l],), l - 1, dtype=torch.int32, device=prob.device))
-        if not sel:
-            z = torch.zeros((0,), dtype=torch.long, device=prob.device)
-            out = (cls_bbox[z], z.to(torch.int32), prob[z, 0], levels[z])
-            return out if view is None else out + (view[z],)
-        sel = torch.cat(sel).long()
-        lab = torch.cat(lab)
-        out = (cls_bbox[sel], lab, prob[sel, (lab + 1).long()], levels[sel])
-        return out if view is None else out + (view[sel],)
-
-    def _suppress_boxpost(self, cls_bbox, prob, levels, view, l_end, soft, vote, cap):
-        """``_suppress`` with Soft-NMS, box voting or the detection cap on: the selection through class_soft_nms (its
-        decayed scores are the returned ones) or the hard NMS, the kept boxes through box_vote, then the ``cap`` highest scores (ties
-        to the earlier row) in their order.  level / view stay those of the kept proposal; still one host sync (the keep counts)."""
-        dev = prob.device
         keep_score = keep_box = None
         if soft is not None:
             keep_idx, keep_score, keep_cnt = ops.class_soft_nms(cls_bbox, prob, 1, l_end, self.score_thresh, soft[0], self.nms_thresh, soft[1])
-        else:
-            nms = ops.class_nms if view is None else ops.class_nms_ws
-            keep_idx, keep_cnt = nms(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
+        else:                                           # (up to 512 rows class_nms_ws runs class_nms's kernel and takes no workspace)
+            keep_idx, keep_cnt = ops.class_nms_ws(cls_bbox, prob, 1, l_end, self.score_thresh, self.nms_thresh)
         if vote is not None:
             keep_box = ops.box_vote(cls_bbox, prob, 1, l_end, self.score_thresh, vote, keep_idx, keep_cnt)
         cnt = keep_cnt.cpu().tolist()                   # the one host sync of predict()
-        sel, lab, sc, bb = [], [], [], []
-        for l in range(1, l_end):
-            if cnt[l]:
-                sel.append(keep_idx[l, :cnt[l]])
-                lab.append(torch.full((cnt[l],), l - 1, dtype=torch.int32, device=dev))
-                if keep_score is not None:
-                    sc.append(keep_score[l, :cnt[l]])
-                if keep_box is not None:
-                    bb.append(keep_box[l, :cnt[l]])
-        if not sel:
-            z = torch.zeros((0,), dtype=torch.long, device=dev)
-            out = (cls_bbox[z], z.to(torch.int32), prob[z, 0], levels[z])
-            return out if view is None else out + (view[z],)
-        sel = torch.cat(sel).long()
-        lab = torch.cat(lab)
-        score = torch.cat(sc) if keep_score is not None else prob[sel, (lab + 1).long()]
-        bbox = torch.cat(bb) if keep_box is not None else cls_bbox[sel]
-        if cap is not None and sel.shape[0] > cap:
-            top = torch.sort(score, descending=True, stable=True)[1][:cap]
-            top = torch.sort(top)[0]
-            sel, lab, score, bbox = sel[top], lab[top], score[top], bbox[top]
-        out = (bbox, lab, score, levels[sel])
+        kept = [l for l in range(1, l_end) if cnt[l]]
+        if not kept:
+            sel = torch.zeros((0,), dtype=torch.long, device=dev)
+            out = (cls_bbox[sel], sel.to(torch.int32), prob[sel, 0])
+        else:
+            rows = lambda t: torch.cat([t[l, :cnt[l]] for l in kept])       # the kept entries of a per-class (n_class, R, ...) output
+            lab = [torch.full((cnt[l],), l - 1, dtype=torch.int32, device=dev) for l in kept]
+            sel = rows(keep_idx).long()
+            lab = torch.cat(lab)
+            bbox = cls_bbox[sel] if keep_box is None else rows(keep_box)
+            score = prob[sel, (lab + 1).long()] if keep_score is None else rows(keep_score)
+            if cap is not None and sel.shape[0] > cap:
+                top = torch.sort(score, descending=True, stable=True)[1][:cap]
+                top = torch.sort(top)[0]
+                sel, lab, score, bbox = sel[top], lab[top], score[top], bbox[top]
+            out = (bbox, lab, score)
+        out += (levels[sel],)
         return out if view is None else out + (view[sel],)
 
     def prepare_size(self, H, W):

@@ -25,7 +25,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from evaluate import add_boxpost_flags, boxpost_settings, tta_settings, use_boxpost  # noqa: E402
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_tta_flags, boxpost_settings, build_inference_model,  # noqa: E402
+                                                read_labels, tta_settings, use_boxpost, use_score_preset, use_tta)
 
 IMAGE_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
 SYNTHETIC_FIRST_SEED = 2000003      # far from the seeds of the synthetic training pool and of the synthetic val split
@@ -53,11 +54,7 @@ def build_parser():
     parser.add_argument('--no-contours', action='store_true')
     parser.add_argument('--kp-thresh', type=float, default=None,
                         help='keypoint heads: the heat-map logit from which a keypoint is drawn (%s)' % DEFAULT_KP_THRESH)
-    parser.add_argument('--tta-sizes', type=int, nargs='+', default=None, metavar='N',
-                        help='test-time augmentation: run every image at these short sides and merge the views (off by default)')
-    parser.add_argument('--tta-hflip', type=int, default=0, choices=[0, 1],
-                        help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no --tta-sizes)')
-    parser.add_argument('--tta-max-size', type=int, default=None, help='long-side cap of the test-time views (default: the model\'s max_size)')
+    add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--json', type=int, default=0, choices=[0, 1], help='1: also write <stem>.json per image')
     parser.add_argument('--image-size', type=int, nargs=2, default=[480, 640], help='--synthetic: image height and width')
@@ -121,30 +118,10 @@ def check_args(args):
     return collect_inputs(args.inputs)
 
 
-def label_names(args):
-    if os.path.exists(args.label_file):
-        with open(args.label_file) as f:
-            return f.read().strip().split('\n')
-    return None
-
-
 def build_model(args):
-    """MaskRCNN of the flags with --weight loaded and the 'visualize' preset (score threshold overridden by --score-thresh); a keypoint
-    head is COCO's: one class, 17 keypoints.  Tests replace this function to draw with a reduced network."""
-    from chainer_maskrcnn.model.maskrcnn import MaskRCNN
-    from train import load_npz
-    dev = torch.device('cuda', args.gpu)
-    torch.cuda.set_device(dev)
-    if args.head_arch == 'fpn_keypoint':
-        model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev)
-    else:
-        labels = label_names(args)
-        model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev)
-    if args.weight:
-        if not os.path.exists(args.weight):
-            raise FileNotFoundError('--weight %s does not exist' % args.weight)
-        load_npz(args.weight, model)
-    return model
+    """MaskRCNN of the flags with --weight loaded; a keypoint head is COCO's: one class, 17 keypoints.  run() sets the 'visualize' preset
+    on what this returns.  Tests replace this function to draw with a reduced network."""
+    return build_inference_model(args)
 
 
 def images(args, files):
@@ -214,19 +191,10 @@ def run(args):
     from PIL import Image
     files = check_args(args)
     model = build_model(args)
-    model.use_preset('visualize')
-    if args.score_thresh is not None:
-        model.score_thresh = args.score_thresh
-    keypoints = model.head_arch == 'fpn_keypoint'
+    use_score_preset(model, 'visualize', args.score_thresh)
     use_boxpost(model, boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections))
-    tta = tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, model.min_size)
-    if tta is not None:
-        perm = None
-        if keypoints and tta['hflip']:
-            from chainer_maskrcnn.dataset import augment
-            perm = augment.flip_permutation(augment.COCO_KEYPOINT_NAMES)
-        model.use_test_augmentation(tta['sizes'], hflip=tta['hflip'], max_size=tta['max_size'], keypoint_flip_perm=perm)
-    names = ['person'] if keypoints else label_names(args)
+    use_tta(model, tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, model.min_size))
+    names = ['person'] if model.head_arch == 'fpn_keypoint' else read_labels(args.label_file)
     os.makedirs(args.out, exist_ok=True)
     written = []
     with torch.no_grad():

@@ -22,9 +22,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 sys.path.insert(0, ROOT)
 
-import torch  # noqa: E402
-
-from train import add_boxpost_flags, boxpost_settings, tta_settings, use_boxpost  # noqa: E402
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_tta_flags, boxpost_settings, build_inference_model,  # noqa: E402
+                                                read_labels, tta_settings, use_boxpost, use_tta)
 
 SYNTHETIC_VAL_IMAGES = 16           # train.py's synthetic val split of --eval-images 0
 
@@ -45,11 +44,7 @@ def build_parser():
     parser.add_argument('--image-size', type=int, nargs=2, default=[800, 800], help='--synthetic 1: image height and width')
     parser.add_argument('--score-thresh', type=float, default=None, help="overrides the 'evaluate' preset's score threshold (0.05)")
     parser.add_argument('--no-results', action='store_true', help='do not write the COCO results files')
-    parser.add_argument('--tta-sizes', type=int, nargs='+', default=None, metavar='N',
-                        help='test-time augmentation: run every image at these short sides and merge the views (off by default)')
-    parser.add_argument('--tta-hflip', type=int, default=0, choices=[0, 1],
-                        help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no --tta-sizes)')
-    parser.add_argument('--tta-max-size', type=int, default=None, help='long-side cap of the test-time views (default: the model\'s max_size)')
+    add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--out', '-o', default='result_eval', help='Output directory')
     return parser
@@ -64,29 +59,9 @@ def check_args(args):
     return boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
 
 
-def label_names(args):
-    if os.path.exists(args.label_file):
-        with open(args.label_file) as f:
-            return f.read().strip().split('\n')
-    return None
-
-
 def build_model(args):
     """MaskRCNN of the flags, with --weight loaded and the 'evaluate' preset (score threshold overridden by --score-thresh)."""
-    from chainer_maskrcnn.model.maskrcnn import MaskRCNN
-    from train import load_npz
-    labels = label_names(args)
-    dev = torch.device('cuda', args.gpu)
-    torch.cuda.set_device(dev)
-    model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev)
-    if args.weight:
-        if not os.path.exists(args.weight):
-            raise FileNotFoundError('--weight %s does not exist' % args.weight)
-        load_npz(args.weight, model)
-    model.use_preset('evaluate')
-    if args.score_thresh is not None:
-        model.score_thresh = args.score_thresh
-    return model
+    return build_inference_model(args, 'evaluate')
 
 
 def build_dataset(args, n_fg_class):
@@ -96,7 +71,7 @@ def build_dataset(args, n_fg_class):
         return SyntheticCOCOEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_fg_class=n_fg_class)
     from chainer_maskrcnn.dataset.coco_dataset import COCOInstanceEvalDataset
     return COCOInstanceEvalDataset(anno_dir=args.anno_dir, img_dir=args.img_dir, split=args.split, data_type=args.data_type,
-                                   category_filter=label_names(args), n=args.eval_images or None)
+                                   category_filter=read_labels(args.label_file), n=args.eval_images or None)
 
 
 def run(args):
@@ -107,8 +82,7 @@ def run(args):
     model = build_model(args)
     use_boxpost(model, boxpost)
     tta = tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, model.min_size)
-    if tta is not None:
-        model.use_test_augmentation(tta['sizes'], hflip=tta['hflip'], max_size=tta['max_size'])
+    use_tta(model, tta)
     data = build_dataset(args, model.n_class - 1)
     results = None if args.no_results else []
     ev = InstanceSegmentationCOCOEvaluator(data, model, results=results)

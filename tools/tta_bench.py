@@ -28,8 +28,8 @@ def _model(args):
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     m = MaskRCNN(n_fg_class=80, device='cuda:0', seed=args.seed)
     if args.weight:
-        from train import load_npz
-        load_npz(args.weight, m)
+        from chainer_maskrcnn.utils.chainer_npz import load_npz
+        load_npz(args.weight, m, strict=False)
     m.use_preset('evaluate')
     return m
 

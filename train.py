@@ -22,8 +22,11 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_tta_flags, boxpost_settings, read_labels, tta_settings,  # noqa: E402,F401
+                                                use_boxpost, use_tta)
+from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
+
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
-DEFAULT_SOFT_NMS_SIGMA = 0.5        # --soft-nms-sigma / --eval-soft-nms-sigma when not given (Detectron's TEST.SOFT_NMS.SIGMA)
 AUGMENT_SEED = 5678                 # seed of the per-example augmentation decisions (dataset/augment.py), recorded in trainer_<it>.pt
 NO_FREEZE = {'bn': 0, 'at': 0}       # what a trainer state without the 'freeze' key was trained with
 NO_OPTIM = {'accum_steps': 1, 'grad_clip': 0.0, 'schedule': None}      # what a trainer state without the 'optim' key was trained with
@@ -85,14 +88,7 @@ def build_parser(keypoints=False):
                         help='metric of --eval-interval: mask_voc = PASCAL VOC mask mAP (mask heads, InstanceSegmentationVOCEvaluator); '
                              'mask_coco = COCO mask and box AP over IoU .50:.95 (mask heads, InstanceSegmentationCOCOEvaluator); '
                              'keypoint_coco = COCO keypoint AP over OKS .50:.95 (keypoint heads, KeypointCOCOEvaluator)')
-    parser.add_argument('--eval-tta-sizes', type=int, nargs='+', default=None, metavar='N',
-                        help='test-time augmentation of the --eval-interval evaluator: every val image also runs at these short sides '
-                             '(MaskRCNN.use_test_augmentation); off by default')
-    parser.add_argument('--eval-tta-hflip', type=int, default=0, choices=[0, 1],
-                        help='1: test-time augmentation adds the mirrored view of every size (the model\'s min_size when no '
-                             '--eval-tta-sizes); keypoint heads swap their left / right channels')
-    parser.add_argument('--eval-tta-max-size', type=int, default=None,
-                        help='long-side cap of the test-time views (default: the model\'s max_size)')
+    add_tta_flags(parser, '--eval-')
     add_boxpost_flags(parser, '--eval-')
     parser.add_argument('--hflip', type=int, default=0, choices=[0, 1],
                         help='1: mirror each training example with probability 0.5 (images, masks, boxes; keypoints with their left / right '
@@ -176,61 +172,6 @@ def augment_settings(args):
     return {'hflip': int(args.hflip), 'min_sizes': [int(s) for s in args.min_sizes] if args.min_sizes else None, 'seed': AUGMENT_SEED}
 
 
-def tta_settings(sizes, hflip, max_size, min_size):
-    """use_test_augmentation's arguments from the TTA flags (--tta-* of evaluate.py, --eval-tta-* here): None = off.  hflip without sizes
-    mirrors the model's own min_size."""
-    if not sizes and not hflip:
-        if max_size is not None:
-            raise ValueError('a test-time max size needs test-time sizes or the test-time flip')
-        return None
-    return {'sizes': [int(s) for s in sizes] if sizes else [int(min_size)], 'hflip': bool(hflip),
-            'max_size': None if max_size is None else int(max_size)}
-
-
-def add_boxpost_flags(parser, prefix='--'):
-    """--soft-nms / --soft-nms-sigma / --box-vote-thresh / --max-detections of evaluate.py and demo.py; with the prefix '--eval-' the
-    flags of the periodic evaluator here."""
-    parser.add_argument(prefix + 'soft-nms', default='off', choices=['off', 'linear', 'gaussian'],
-                        help='Soft-NMS in place of the hard per-class NMS (MaskRCNN.use_soft_nms): a kept box lowers the scores of the '
-                             'boxes it overlaps instead of deleting them; off by default')
-    parser.add_argument(prefix + 'soft-nms-sigma', type=float, default=None, metavar='S',
-                        help='sigma of %ssoft-nms gaussian (default %s)' % (prefix, DEFAULT_SOFT_NMS_SIGMA))
-    parser.add_argument(prefix + 'box-vote-thresh', type=float, default=0.0, metavar='T',
-                        help='box voting (MaskRCNN.use_box_voting): every kept box becomes the score-weighted mean of the candidates of '
-                             'its class with IoU >= T (Detectron: 0.8); 0 = off')
-    parser.add_argument(prefix + 'max-detections', type=int, default=0, metavar='N',
-                        help='keep the N highest-scoring detections of an image (MaskRCNN.use_max_detections; Detectron: 100); 0 = off')
-
-
-def boxpost_settings(soft_nms, sigma, vote_thresh, max_detections, prefix='--'):
-    """The arguments of use_soft_nms / use_box_voting / use_max_detections from the flags (evaluate.py, demo.py; --eval-* here): None = all
-    off, else {'soft_nms': None | 'linear' | 'gaussian', 'sigma', 'vote_thresh': None | T, 'max_detections': None | N}.  ValueError for
-    a value the model would refuse."""
-    if soft_nms not in ('off', 'linear', 'gaussian'):
-        raise ValueError('%ssoft-nms must be off, linear or gaussian, got %r' % (prefix, soft_nms))
-    if sigma is not None and soft_nms != 'gaussian':
-        raise ValueError('%ssoft-nms-sigma belongs to %ssoft-nms gaussian' % (prefix, prefix))
-    if sigma is not None and not sigma > 0:
-        raise ValueError('%ssoft-nms-sigma must be positive, got %r' % (prefix, sigma))
-    if not 0 <= vote_thresh <= 1:
-        raise ValueError('%sbox-vote-thresh must lie in (0, 1] (0 = off), got %r' % (prefix, vote_thresh))
-    if max_detections < 0:
-        raise ValueError('%smax-detections must not be negative (0 = off), got %r' % (prefix, max_detections))
-    if soft_nms == 'off' and not vote_thresh and not max_detections:
-        return None
-    return {'soft_nms': None if soft_nms == 'off' else soft_nms, 'sigma': float(sigma) if sigma is not None else DEFAULT_SOFT_NMS_SIGMA,
-            'vote_thresh': float(vote_thresh) if vote_thresh else None, 'max_detections': int(max_detections) if max_detections else None}
-
-
-def use_boxpost(model, settings):
-    """Applies boxpost_settings' result (None: nothing) to the model."""
-    if settings is None:
-        return
-    model.use_soft_nms(settings['soft_nms'], settings['sigma'])
-    model.use_box_voting(settings['vote_thresh'])
-    model.use_max_detections(settings['max_detections'])
-
-
 def _eval_boxpost_settings(args):
     """--eval-soft-nms / --eval-soft-nms-sigma / --eval-box-vote-thresh / --eval-max-detections: they act on the periodic evaluator's
     predictions, so they are refused without one."""
@@ -249,14 +190,19 @@ def _check_augment_args(args):
         raise ValueError('--min-sizes: every size must be positive, got %s' % args.min_sizes)
 
 
-def _keypoint_flip_perm(args, data):
-    """The flip map of a keypoint dataset: COCO's names from the annotation file's person category (COCO's 17 names when the file has
-    none), the depth dataset's 20 joints.  ValueError when the names do not pair completely."""
+def _keypoint_names(args, data):
+    """The keypoint names of a keypoint dataset: COCO's from the annotation file's person category (COCO's 17 names when the file has
+    none), the depth dataset's 20 joints."""
     from chainer_maskrcnn.dataset import augment
     if args.dataset == 'depth':
-        names = augment.DEPTH_KEYPOINT_NAMES
-    else:
-        names = data.coco.cats.get(1, {}).get('keypoints') or augment.COCO_KEYPOINT_NAMES
+        return augment.DEPTH_KEYPOINT_NAMES
+    return data.coco.cats.get(1, {}).get('keypoints') or augment.COCO_KEYPOINT_NAMES
+
+
+def _keypoint_flip_perm(args, data):
+    """The flip map of a keypoint dataset's names.  ValueError when the names do not pair completely."""
+    from chainer_maskrcnn.dataset import augment
+    names = _keypoint_names(args, data)
     if len(names) != data.n_keypoints:
         raise ValueError('--hflip 1: %d keypoint names for %d keypoints' % (len(names), data.n_keypoints))
     try:
@@ -309,7 +255,7 @@ def run(args, keypoints=False):
             data = COCOKeypointsLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type)
         else:
             data = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type,
-                                  category_filter=_read_labels(args.label_file))
+                                  category_filter=read_labels(args.label_file))
     augment = None
     if args.hflip or args.min_sizes:
         from chainer_maskrcnn.dataset.augment import Augment
@@ -333,6 +279,7 @@ def run(args, keypoints=False):
         init_process_group('nccl')
     if keypoints:
         n_fg, K = 1, 20 if args.dataset == 'depth' else 17          # DepthDataset.n_keypoints / COCOKeypointsLoader.n_keypoints
+        labels = None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, n_keypoints=K, backbone=args.backbone, head_arch=args.head_arch, n_mask_convs=args.n_mask_convs,
                                min_size=args.min_size, max_size=args.max_size, device=dev)
         loss_fun = calc_keypoint_loss
@@ -341,16 +288,10 @@ def run(args, keypoints=False):
             loss_fun.fused_kind = calc_keypoint_loss.fused_kind
         model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=loss_fun, binary_mask=False, gemm_arithmetic=args.gemm_arithmetic)
     else:
-        n_fg, K = 80, None
-        if os.path.exists(args.label_file):
-            with open(args.label_file) as f:
-                n_fg = len(f.read().strip().split('\n'))
+        labels = read_labels(args.label_file)
+        n_fg, K = len(labels) if labels else 80, None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev)
         model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic)
-    labels = None
-    if not keypoints and os.path.exists(args.label_file):
-        with open(args.label_file) as f:
-            labels = f.read().strip().split('\n')
     faster_rcnn.use_preset('evaluate')
     if args.resnet50_npz:           # ImageNet initialisation of the bottom-up pathway (before --weight, which may override it)
         from chainer_maskrcnn.utils import chainer_npz
@@ -482,22 +423,12 @@ def run(args, keypoints=False):
 
 def _use_eval_tta(args, faster_rcnn, evaluator):
     """--eval-tta-*: test-time augmentation of the periodic evaluator's predictions.  A keypoint model's flip map comes from the val data's
-    names (_keypoint_flip_perm; COCO's 17 names for the synthetic split)."""
-    t = tta_settings(args.eval_tta_sizes, args.eval_tta_hflip, args.eval_tta_max_size, faster_rcnn.min_size)
-    if t is None:
-        return
-    perm = None
-    if faster_rcnn.head_arch == 'fpn_keypoint' and t['hflip']:
-        from chainer_maskrcnn.dataset import augment
-        data = getattr(evaluator.dataset, 'loader', None)
-        if args.synthetic or data is None:
-            names = augment.COCO_KEYPOINT_NAMES
-            if len(names) != faster_rcnn.head.n_keypoints:
-                raise ValueError('--eval-tta-hflip 1: %d keypoint names for %d keypoints' % (len(names), faster_rcnn.head.n_keypoints))
-            perm = augment.flip_permutation(names)
-        else:
-            perm = _keypoint_flip_perm(args, data)
-    faster_rcnn.use_test_augmentation(t['sizes'], hflip=t['hflip'], max_size=t['max_size'], keypoint_flip_perm=perm)
+    names (_keypoint_names; COCO's 17 names for the synthetic split)."""
+    names = None
+    data = getattr(evaluator.dataset, 'loader', None)
+    if faster_rcnn.head_arch == 'fpn_keypoint' and not args.synthetic and data is not None:
+        names = _keypoint_names(args, data)
+    use_tta(faster_rcnn, tta_settings(args.eval_tta_sizes, args.eval_tta_hflip, args.eval_tta_max_size, faster_rcnn.min_size), names, '--eval-')
 
 
 def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
@@ -534,14 +465,6 @@ def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
         val = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type, category_filter=labels)
         data = TransformedDataset(val, coco_mask_example, n=args.eval_images or None)
     return InstanceSegmentationVOCEvaluator(data, faster_rcnn, label_names=labels)
-
-
-def _read_labels(label_file):
-    """The category names of --label_file (None when the file does not exist: every category)."""
-    if not os.path.exists(label_file):
-        return None
-    with open(label_file) as f:
-        return f.read().strip().split('\n')
 
 
 def _all_rank_tickets(ticket, world, dev):
@@ -586,18 +509,6 @@ class _Roctx(object):
             def __exit__(self_, *a):
                 rtx.lib.roctxRangePop()
         return _R()
-
-
-def save_npz(path, faster_rcnn):
-    """Chainer-NPZ key names and array layouts (chainer_maskrcnn/utils/chainer_npz.py), like snapshot_object."""
-    from chainer_maskrcnn.utils import chainer_npz
-    chainer_npz.save_npz(path, faster_rcnn)
-
-
-def load_npz(path, faster_rcnn):
-    """strict=False like train.py:99-101: keys present in the file are loaded, the rest keep their initial values."""
-    from chainer_maskrcnn.utils import chainer_npz
-    return chainer_npz.load_npz(path, faster_rcnn, strict=False)
 
 
 def main():
