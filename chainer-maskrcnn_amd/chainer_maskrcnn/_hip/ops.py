@@ -296,6 +296,70 @@ def mask_resize_batch_u8(src, desc, G, dst_h, dst_w):
     return out
 
 
+# ---- large-scale jitter: the same resizes through a crop window (augment.hip; DESIGN.md §3.17) ---------------------------------------
+# mrcnn_crop_desc_t of include/mrcnn_hip.h
+CROP_DESC = np.dtype(RESIZE_DESC.descr + [('y0', '<i4'), ('x0', '<i4'), ('ch', '<i4'), ('cw', '<i4')])
+assert CROP_DESC.itemsize == 48
+
+
+def crop_descs(rows):
+    """[(src_offset, H, W, oh, ow, flip, count, y0, x0, ch, cw)] -> the host descriptor table the crop kernels take."""
+    return np.array([tuple(int(v) for v in r) for r in rows], CROP_DESC)
+
+
+def _crop_src(name, src):
+    _ck(src)
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError('%s: src must be a 1-D uint8 tensor' % name)
+    return ptr(src) if src.numel() else ptr(None)
+
+
+def image_resize_crop_batch_u8(src, desc, dst_h, dst_w, div=255.0):
+    """image_resize_batch_u8 through each example's crop window (desc: crop_descs(...)): the window of the virtual oh x ow resize at the
+    top-left of the (N,3,dst_h,dst_w) canvas, zero elsewhere.  One launch."""
+    sp = _crop_src('image_resize_crop_batch_u8', src)
+    desc = np.ascontiguousarray(desc, CROP_DESC)
+    out = _empty((len(desc), 3, dst_h, dst_w), src.device)
+    check(lib().mrcnn_image_resize_crop_batch_u8_f32(sp, src.numel(), desc.ctypes.data, len(desc), ptr(out), dst_h, dst_w, float(div),
+                                                     stream_ptr()))
+    return out
+
+
+def mask_crop_boxes_u8(src, desc, labels_in, G, dst_h, dst_w):
+    """What the crop leaves of each instance, without writing a plane.  src: each example's (count,H,W) masks packed at
+    desc['src_offset']; labels_in (N,Gin) int32.  Returns (bboxes (N,G,4) float32, labels (N,G) int32, gather (N,G) int32): per example
+    the instances with a pixel inside the window first, in their order, with the tight box of their cropped mask; behind them zero
+    boxes, label -1 and gather -1.  One fill and two launches, no host synchronisation."""
+    sp = _crop_src('mask_crop_boxes_u8', src)
+    _ck(labels_in)
+    desc = np.ascontiguousarray(desc, CROP_DESC)
+    N = len(desc)
+    if labels_in.dtype != i32 or labels_in.dim() != 2 or labels_in.shape[0] != N or not labels_in.is_contiguous():
+        raise ValueError('mask_crop_boxes_u8: labels_in must be a contiguous (N,Gin) int32 tensor')
+    Gin = labels_in.shape[1]
+    bboxes, labels, gather = _empty((N, G, 4), src.device), _empty((N, G), src.device, i32), _empty((N, G), src.device, i32)
+    ws = _empty((N, Gin, 4), src.device, i32)
+    check(lib().mrcnn_mask_crop_boxes_u8(sp, src.numel(), desc.ctypes.data, N, Gin, G, dst_h, dst_w, ptr(labels_in), ptr(bboxes),
+                                         ptr(labels), ptr(gather), ptr(ws), stream_ptr()))
+    return bboxes, labels, gather
+
+
+def mask_resize_crop_batch_u8(src, desc, gather, dst_h, dst_w):
+    """mask_resize_batch_u8 through each example's crop window, output plane j reading source instance gather[n, j] (mask_crop_boxes_u8's
+    table; -1: a zero plane).  Returns the (N,G,dst_h,dst_w) uint8 batch.  One launch."""
+    sp = _crop_src('mask_resize_crop_batch_u8', src)
+    _ck(gather)
+    desc = np.ascontiguousarray(desc, CROP_DESC)
+    N = len(desc)
+    if gather.dtype != i32 or gather.dim() != 2 or gather.shape[0] != N or not gather.is_contiguous():
+        raise ValueError('mask_resize_crop_batch_u8: gather must be a contiguous (N,G) int32 tensor')
+    G = gather.shape[1]
+    out = torch.empty((N, G, dst_h, dst_w), dtype=torch.uint8, device=src.device)
+    check(lib().mrcnn_mask_resize_crop_batch_nearest_u8(sp, src.numel(), desc.ctypes.data, N, G, ptr(gather), ptr(out), dst_h, dst_w,
+                                                        stream_ptr()))
+    return out
+
+
 def random_keys(shape, seed, device):
     """uint32 sampler keys stored in an int32 tensor."""
     out = _empty(shape, device, i32)

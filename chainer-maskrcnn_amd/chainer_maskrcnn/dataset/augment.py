@@ -11,6 +11,12 @@ Conventions (the augmented example is ``Transform(hflip(example))`` with the dra
                 boxes         (y1, x1, y2, x2) -> (y1, W - x2, y2, W - x1)       (continuous, chainercv.transforms.flip_bbox)
                 keypoints     (x, y, v) with v > 0: x -> W - 1 - x (pixel indices, Detectron's flip_keypoints); v == 0 entries keep
                               their coordinates; then the channels are permuted by the flip map (left <-> right).
+  LSJ         large-scale jitter (``Augment(lsj_size=S)``): after the flip the example is resized VIRTUALLY by a random
+              factor (``lsj_geometry``: to oh x ow, the longer side S * s, s uniform in ``lsj_scale``) and the window of rows
+              y0 .. y0+ch-1, columns x0 .. x0+cw-1 of that resize, at most S x S, lands at the top-left of an S x S canvas; the rest is
+              zero.  scale = oh / H as ever, the example's size is (ch, cw).  Mask instances whose cropped mask has no pixel left are
+              dropped and the others get the tight box (ymin, xmin, ymax + 1, xmax + 1) of their cropped mask; keypoint instances get
+              their box shifted and clipped to the window (dropped when nothing is left), keypoints outside the window get v = 0.
   flip map    from the keypoint names: left_* <-> right_* (COCO), *Left <-> *Right (the depth dataset); names without a side map to
               themselves.  A side without its partner is an error: coordinates are never flipped without swapping the channels.
 """
@@ -27,9 +33,10 @@ DEPTH_KEYPOINT_NAMES = ('SpineBase', 'SpineMid', 'Neck', 'Head', 'ShoulderLeft',
                         'ElbowRight', 'WristRight', 'HandRight', 'HipLeft', 'KneeLeft', 'AnkleLeft', 'FootLeft', 'HipRight', 'KneeRight',
                         'AnkleRight', 'FootRight')
 
-# per-example parameters a transform takes: flip (bool), min_size (int or None = the transform's own), keypoint_perm (flip map or None)
-AugmentParams = collections.namedtuple('AugmentParams', ['flip', 'min_size', 'keypoint_perm'])
-AugmentParams.__new__.__defaults__ = (None,)
+# per-example parameters a transform takes: flip (bool), min_size (int or None = the transform's own), keypoint_perm (flip map or None),
+# lsj (None, or (S, s, u_y, u_x): canvas size and the three draws of decide_lsj - the geometry follows from the source size, lsj_geometry)
+AugmentParams = collections.namedtuple('AugmentParams', ['flip', 'min_size', 'keypoint_perm', 'lsj'])
+AugmentParams.__new__.__defaults__ = (None, None)
 
 
 def _partner(name):
@@ -70,6 +77,55 @@ def decide(seed, rank, ticket, p, min_sizes=None):
     flip = bool(rng.random() < p)
     min_size = int(min_sizes[int(rng.integers(len(min_sizes)))]) if min_sizes else None
     return flip, min_size
+
+
+def decide_lsj(seed, rank, ticket, p, scale_range):
+    """(flip, s, u_y, u_x) of the example at ``ticket`` of ``rank``'s sequence under large-scale jitter: a pure function of its arguments.
+    The first draw is ``decide``'s flip draw; then s uniform in [lo, hi] and the window position u_y, u_x uniform in [0, 1)."""
+    lo, hi = float(scale_range[0]), float(scale_range[1])
+    rng = np.random.default_rng([int(seed), int(rank), int(ticket)])
+    flip = bool(rng.random() < p)
+    s = lo + (hi - lo) * float(rng.random())
+    return flip, s, float(rng.random()), float(rng.random())
+
+
+def lsj_geometry(H, W, S, s, u_y, u_x):
+    """(oh, ow, y0, x0, ch, cw): an H x W source is resized virtually to oh x ow (its longer side to S * s) and the ch x cw window at
+    (y0, x0) of that resize, at most S x S, is what the example keeps."""
+    r = min(S * s / H, S * s / W)
+    oh, ow = max(1, int(H * r + 0.5)), max(1, int(W * r + 0.5))
+    ch, cw = min(oh, S), min(ow, S)
+    y0, x0 = min(int(u_y * (oh - ch + 1)), oh - ch), min(int(u_x * (ow - cw + 1)), ow - cw)
+    return oh, ow, y0, x0, ch, cw
+
+
+def tight_boxes(masks):
+    """(G,h,w) masks -> ((G,4) float32 boxes (ymin, xmin, ymax + 1, xmax + 1) of the non-zero pixels, (G,) bool: has a pixel).  The box of
+    an empty mask is zero."""
+    masks = np.asarray(masks)
+    boxes = np.zeros((masks.shape[0], 4), np.float32)
+    keep = np.zeros((masks.shape[0],), bool)
+    for g, m in enumerate(masks):
+        ys, xs = np.flatnonzero(m.any(1)), np.flatnonzero(m.any(0))
+        if len(ys):
+            boxes[g], keep[g] = (ys[0], xs[0], ys[-1] + 1, xs[-1] + 1), True
+    return boxes, keep
+
+
+def crop_boxes_keypoints(bbox, kp, y0, x0, ch, cw):
+    """The LSJ rule of keypoint examples, on resized coordinates: bbox (G,4) (y1,x1,y2,x2) and kp (G,K,(y,x,v)) shifted by (-y0, -x0), the
+    boxes clipped to [0, ch] x [0, cw]; instances whose clipped box has no height or width are dropped; a keypoint with v > 0 outside
+    [0, ch) x [0, cw) gets v = 0 and keeps its shifted coordinates.  Returns (bbox, kp, keep (G,) bool) of the kept rows."""
+    bbox = np.array(bbox, np.float32).reshape(-1, 4) - np.array([y0, x0, y0, x0], np.float32)
+    bbox[:, 0::2] = np.clip(bbox[:, 0::2], 0, ch)
+    bbox[:, 1::2] = np.clip(bbox[:, 1::2], 0, cw)
+    keep = (bbox[:, 2] - bbox[:, 0] > 0) & (bbox[:, 3] - bbox[:, 1] > 0)
+    kp = np.array(kp, np.float32)
+    kp[:, :, 0] -= np.float32(y0)
+    kp[:, :, 1] -= np.float32(x0)
+    inside = (kp[:, :, 0] >= 0) & (kp[:, :, 0] < ch) & (kp[:, :, 1] >= 0) & (kp[:, :, 1] < cw)
+    kp[:, :, 2] = np.where((kp[:, :, 2] > 0) & ~inside, 0, kp[:, :, 2])
+    return bbox[keep], kp[keep], keep
 
 
 def flip_bbox(bbox, W):
@@ -114,9 +170,10 @@ def hflip(example, keypoint_perm=None):
 
 class Augment(object):
     """The augmentation of a training run: flip probability, the short sides to draw from (None: the transform's own min_size), the
-    seed, and for keypoint data the flip map.  ``params(rank, ticket)`` gives an example's AugmentParams."""
+    seed, and for keypoint data the flip map; ``lsj_size`` = S turns large-scale jitter on (an S x S canvas, the scale drawn from
+    ``lsj_scale``; not together with min_sizes - two different resize rules).  ``params(rank, ticket)`` gives an example's AugmentParams."""
 
-    def __init__(self, hflip_prob=0.0, min_sizes=None, seed=0, keypoint_perm=None):
+    def __init__(self, hflip_prob=0.0, min_sizes=None, seed=0, keypoint_perm=None, lsj_size=None, lsj_scale=(0.1, 2.0)):
         if not 0.0 <= float(hflip_prob) <= 1.0:
             raise ValueError('hflip_prob must lie in [0, 1], got %r' % hflip_prob)
         if min_sizes is not None:
@@ -125,7 +182,19 @@ class Augment(object):
                 raise ValueError('min_sizes must be a non-empty list of positive sizes, got %r' % (min_sizes,))
         self.hflip_prob, self.min_sizes, self.seed = float(hflip_prob), min_sizes, int(seed)
         self.keypoint_perm = None if keypoint_perm is None else np.asarray(keypoint_perm, np.int64)
+        self.lsj_size, self.lsj_scale = None, (float(lsj_scale[0]), float(lsj_scale[1]))
+        if lsj_size:
+            if min_sizes is not None:
+                raise ValueError('min_sizes and lsj_size are two different resize rules: give one of them')
+            if int(lsj_size) <= 0 or int(lsj_size) % 64:
+                raise ValueError('lsj_size must be a positive multiple of 64, got %r' % (lsj_size,))
+            if not 0 < self.lsj_scale[0] <= self.lsj_scale[1]:
+                raise ValueError('lsj_scale must be 0 < lo <= hi, got %r' % (lsj_scale,))
+            self.lsj_size = int(lsj_size)
 
     def params(self, rank, ticket):
+        if self.lsj_size:
+            flip, s, u_y, u_x = decide_lsj(self.seed, rank, ticket, self.hflip_prob, self.lsj_scale)
+            return AugmentParams(flip, None, self.keypoint_perm, (self.lsj_size, s, u_y, u_x))
         flip, min_size = decide(self.seed, rank, ticket, self.hflip_prob, self.min_sizes)
         return AugmentParams(flip, min_size, self.keypoint_perm)

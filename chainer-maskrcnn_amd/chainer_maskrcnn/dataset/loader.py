@@ -9,7 +9,9 @@ batch at PCIe 5 rates) overlaps the previous step.  Batch layout = ``utils.synth
   labels (N,G) i32 with -1 on padded rows, masks (N,G,H,W) u8  |  keypoints (N,G,K,3) f32.
 Augmentation (``augment=dataset.augment.Augment``, off by default): every example's (flip, min_size) follows from its ticket and goes
 to the transform; on the device path the batch's raw images and masks are then uploaded packed and resized, mirrored where drawn, by
-one launch per tensor (csrc/augment.hip).
+one launch per tensor (csrc/augment.hip).  With large-scale jitter (``Augment(lsj_size=S)``) every batch is an S x S
+canvas; on the device path the crop kernels write it, and for mask data the boxes, the drop of instances the crop removed and the
+packing of the kept ones are device work on the loader's stream - ``bboxes`` and ``labels`` are then device outputs and nothing waits.
 """
 import queue
 import threading
@@ -17,15 +19,17 @@ import threading
 import numpy as np
 
 
-def collate(examples, max_gt=None, keypoints=False, size_multiple=64):
+def collate(examples, max_gt=None, keypoints=False, size_multiple=64, canvas=None):
     """examples: outputs of Transform / KeypointTransform.  G = max_gt or the largest instance count in the batch
     (extra instances are dropped, missing ones padded with label -1).  H, W are rounded up to ``size_multiple`` (the
-    coarsest pyramid level has stride 64)."""
+    coarsest pyramid level has stride 64); ``canvas`` = S (large-scale jitter): H = W = S whatever the examples' sizes."""
     N = len(examples)
     G = max_gt or max(1, max(e[1].shape[0] for e in examples))
     H = max(e[0].shape[1] for e in examples)
     W = max(e[0].shape[2] for e in examples)
     H, W = -(-H // size_multiple) * size_multiple, -(-W // size_multiple) * size_multiple
+    if canvas:
+        H = W = int(canvas)
     out = {'imgs': np.zeros((N, 3, H, W), np.float32), 'bboxes': np.zeros((N, G, 4), np.float32),
            'labels': np.full((N, G), -1, np.int32), 'scales': np.zeros((N,), np.float32),
            'sizes': np.zeros((N, 2), np.float32)}      # each image's own (h, w) inside the zero-padded batch tensor
@@ -100,15 +104,21 @@ class _PinnedRing(object):
         return out, [int(o) for o in offsets[:-1]]
 
 
+_EMPTY = object()       # large-scale jitter: an example whose annotations were empty BEFORE augmentation (skip_empty)
+
+
 class BatchLoader(object):
     """Endless iterator of device batches.  ``rank``/``world`` shard the (seeded, per-epoch) permutation.  ``augment``: a
-    dataset.augment.Augment; the transform is then called as transform(example, augment.params(rank, ticket))."""
+    dataset.augment.Augment; the transform is then called as transform(example, augment.params(rank, ticket)).  With large-scale jitter
+    ``skip_empty`` is judged on the annotations before augmentation: an image whose instances all leave the crop window stays in the
+    batch, with no instance."""
 
     def __init__(self, dataset, transform, batch_size=1, shuffle=True, seed=0, rank=0, world=1, num_workers=4,
                  prefetch=4, max_gt=None, keypoints=False, device=None, skip_empty=True, start_ticket=0, augment=None):
         self.dataset, self.transform, self.augment = dataset, transform, augment
         self.bs, self.shuffle, self.seed, self.rank, self.world = batch_size, shuffle, seed, rank, world
         self.max_gt, self.keypoints, self.device, self.skip_empty = max_gt, keypoints, device, skip_empty
+        self._lsj = getattr(augment, 'lsj_size', None)       # the canvas size S, or None
         self._idx = queue.Queue(maxsize=prefetch * batch_size * 2)
         self._out = {}
         self._cv = threading.Condition()
@@ -156,6 +166,9 @@ class BatchLoader(object):
             try:
                 if self.augment is None:
                     ex = self.transform(self.dataset[i])
+                elif self._lsj:
+                    raw = self.dataset[i]
+                    ex = _EMPTY if self.skip_empty and len(raw[1]) == 0 else self.transform(raw, self.augment.params(self.rank, ticket))
                 else:
                     ex = self.transform(self.dataset[i], self.augment.params(self.rank, ticket))
             except Exception as e:                           # surfaced in the consumer thread
@@ -174,7 +187,9 @@ class BatchLoader(object):
                 self._cv.notify_all()
             if isinstance(ex, Exception):
                 raise ex
-            if self.skip_empty and ex[1].shape[0] == 0:      # images whose annotations were all filtered out (:93-96)
+            if ex is _EMPTY:
+                continue
+            if self.skip_empty and not self._lsj and ex[1].shape[0] == 0:      # images whose annotations were all filtered out (:93-96)
                 continue
             return ex
 
@@ -193,9 +208,12 @@ class BatchLoader(object):
         dev = torch.device(self.device)
         exs = [self._next_example() for _ in range(self.bs)]
         N = len(exs)
-        G = self.max_gt or max(1, max(e[1].shape[0] for e in exs))
+        # (large-scale jitter: mask examples bring no boxes - the device computes them - so the instances are counted by their labels)
+        G = self.max_gt or max(1, max(e[2 if self._lsj else 1].shape[0] for e in exs))
         H = -(-max(e[5][0] for e in exs) // 64) * 64
         W = -(-max(e[5][1] for e in exs) // 64) * 64
+        if self._lsj:
+            H = W = self._lsj
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=dev)
         bboxes = np.zeros((N, G, 4), np.float32)
@@ -205,12 +223,15 @@ class BatchLoader(object):
         slot = self._ring.next_slot()
         with torch.cuda.stream(self._stream):
             st = self._stream.cuda_stream
-            if self.augment is not None:
+            dev_bboxes = dev_labels = None
+            if self._lsj:
+                imgs, extra, keep, dev_bboxes, dev_labels = self._resize_lsj(exs, slot, G, H, W, dev, bboxes, labels, scales, sizes)
+            elif self.augment is not None:
                 imgs, extra, keep = self._resize_packed(exs, slot, G, H, W, dev, bboxes, labels, scales, sizes)
             else:
                 imgs, extra, keep = self._resize_each(exs, slot, G, H, W, dev, st, bboxes, labels, scales, sizes)
-            out = {'imgs': imgs, 'bboxes': self._ring.upload(slot, 'bboxes', bboxes, dev),
-                   'labels': self._ring.upload(slot, 'labels', labels, dev),
+            out = {'imgs': imgs, 'bboxes': self._ring.upload(slot, 'bboxes', bboxes, dev) if dev_bboxes is None else dev_bboxes,
+                   'labels': self._ring.upload(slot, 'labels', labels, dev) if dev_labels is None else dev_labels,
                    'keypoints' if self.keypoints else 'masks': extra, 'scales': scales, 'sizes': sizes}
             slot['event'] = torch.cuda.Event()
             slot['event'].record(self._stream)
@@ -270,10 +291,47 @@ class BatchLoader(object):
             keep.append(m)
         return imgs, extra, keep
 
+    def _resize_lsj(self, exs, slot, G, H, W, dev, bboxes, labels, scales, sizes):
+        """Large-scale jitter (RawTransform outputs carry the geometry as an 8th item): the packed uploads of _resize_packed, then the crop
+        kernels write the S x S canvas.  Keypoint examples bring their boxes and keypoints from the host; for mask examples the device
+        decides which instances the crop keeps, computes their tight boxes and packs them first - boxes, labels and planes alike - so
+        the returned device boxes and labels replace the host arrays.  Nothing here waits for the device."""
+        import torch
+        from chainer_maskrcnn._hip import ops
+        N = len(exs)
+        for i, e in enumerate(exs):
+            scales[i], sizes[i] = e[4], e[5]
+        raw, offs = self._ring.upload_packed(slot, 'imgs', [e[0] for e in exs], dev)
+        imgs = ops.image_resize_crop_batch_u8(raw, self._crop_descs(offs, [e[0].shape[:2] for e in exs], [0] * N, exs), H, W, 255.0)
+        keep = [raw]
+        if self.keypoints:
+            extra = torch.zeros((N, G, exs[0][3].shape[1], 3), dtype=torch.float32, device=dev)
+            for i, e in enumerate(exs):
+                g = min(G, e[1].shape[0])
+                bboxes[i, :g], labels[i, :g] = e[1][:g], e[2][:g]
+                if g > 0:
+                    extra[i, :g] = self._ring.upload(slot, 'kp%d' % i, e[3][:g], dev)
+            return imgs, extra, keep, None, None
+        counts = [e[3].shape[0] for e in exs]
+        labels_in = np.full((N, max(1, max(counts))), -1, np.int32)
+        for i, e in enumerate(exs):
+            labels_in[i, :counts[i]] = e[2]
+        m, moffs = self._ring.upload_packed(slot, 'masks', [e[3] for e in exs], dev)
+        mdesc = self._crop_descs(moffs, [e[3].shape[1:] for e in exs], counts, exs)
+        lab = self._ring.upload(slot, 'labels_in', labels_in, dev)
+        dev_bboxes, dev_labels, gather = ops.mask_crop_boxes_u8(m, mdesc, lab, G, H, W)
+        extra = ops.mask_resize_crop_batch_u8(m, mdesc, gather, H, W)
+        return imgs, extra, keep + [m, lab, gather], dev_bboxes, dev_labels
+
+    @staticmethod
+    def _crop_descs(offs, src_hw, counts, exs):
+        from chainer_maskrcnn._hip import ops
+        return ops.crop_descs([(o, hw[0], hw[1], e[7][0], e[7][1], e[6], c) + tuple(e[7][2:]) for o, hw, c, e in zip(offs, src_hw, counts, exs)])
+
     def __next__(self):
         if getattr(self.transform, 'out_size', None) is not None and self.device is not None and str(self.device).startswith('cuda'):
             return self._next_device_batch()
-        batch = collate([self._next_example() for _ in range(self.bs)], self.max_gt, self.keypoints)
+        batch = collate([self._next_example() for _ in range(self.bs)], self.max_gt, self.keypoints, canvas=self._lsj)
         if self.device is None:
             return batch
         import torch

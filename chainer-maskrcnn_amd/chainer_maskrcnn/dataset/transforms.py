@@ -10,7 +10,7 @@ coordinate rules (parity unpinned; the float path is checked against the indepen
 """
 import numpy as np
 
-from chainer_maskrcnn.dataset.augment import flip_bbox, flip_keypoints, hflip
+from chainer_maskrcnn.dataset.augment import crop_boxes_keypoints, flip_bbox, flip_keypoints, hflip, lsj_geometry, tight_boxes
 
 F = np.float32
 
@@ -72,19 +72,39 @@ def prepare(img, min_size=600, max_size=1000):
     return resize_linear(img, (int(H * scale), int(W * scale))) / F(255)
 
 
+def _lsj_image(img, aug):
+    """Large-scale jitter of an (already mirrored) image (C,H,W): (the ch x cw window of its oh x ow resize, / 255; the geometry)."""
+    _, H, W = img.shape
+    geo = lsj_geometry(H, W, *aug.lsj)
+    oh, ow, y0, x0, ch, cw = geo
+    return np.ascontiguousarray((resize_linear(img, (oh, ow)) / F(255))[:, y0:y0 + ch, x0:x0 + cw]), geo
+
+
 class Transform(object):
     """train.py:21-37.  in: (img, bbox, label, masks list) -> (img, bbox, label, masks (G,oH,oW) uint8, scale).
     aug (dataset.augment.AugmentParams, optional): the example is mirrored first (augment.hflip) when aug.flip, and resized to
-    aug.min_size when that is given."""
+    aug.min_size when that is given.  With aug.lsj (large-scale jitter) image and masks are the crop window of the
+    mirrored example's virtual resize, instances without a pixel left are dropped and the boxes are the cropped masks' tight boxes."""
 
     def __init__(self, faster_rcnn):
         self.min_size, self.max_size = faster_rcnn.min_size, faster_rcnn.max_size
+
+    def _lsj(self, in_data, aug):
+        img, _, label, label_img = in_data
+        H = img.shape[1]
+        img, (oh, ow, y0, x0, ch, cw) = _lsj_image(img, aug)
+        masks = [resize_nearest(np.asarray(im), (oh, ow))[y0:y0 + ch, x0:x0 + cw] for im in label_img]
+        masks = np.stack(masks).astype(np.uint8) if masks else np.zeros((0, ch, cw), np.uint8)
+        bbox, keep = tight_boxes(masks)
+        return img, bbox[keep], np.asarray(label, np.int32)[keep], np.ascontiguousarray(masks[keep]), oh / H
 
     def __call__(self, in_data, aug=None):
         min_size = self.min_size
         if aug is not None:
             in_data = hflip(in_data) if aug.flip else in_data
             min_size = aug.min_size or min_size
+            if aug.lsj is not None:
+                return self._lsj(in_data, aug)
         img, bbox, label, label_img = in_data
         _, H, W = img.shape
         img = prepare(img, min_size, self.max_size)
@@ -99,16 +119,28 @@ class Transform(object):
 
 class KeypointTransform(object):
     """train_keypoints.py:51-68.  in: (img, bbox, keypoints (G,17,(x,y,v))) -> (img, bbox, label = 0, kp (G,17,(y,x,v)), scale).
-    aug: as Transform; a flip needs aug.keypoint_perm."""
+    aug: as Transform; a flip needs aug.keypoint_perm.  With aug.lsj the boxes and keypoints follow augment.crop_boxes_keypoints."""
 
     def __init__(self, faster_rcnn):
         self.min_size, self.max_size = faster_rcnn.min_size, faster_rcnn.max_size
+
+    def _lsj(self, in_data, aug):
+        img, bbox, keypoints = in_data
+        _, H, W = img.shape
+        img, (oh, ow, y0, x0, ch, cw) = _lsj_image(img, aug)
+        scale = oh / H
+        keypoints = keypoints.astype(np.float32)
+        kp = np.concatenate([keypoints[:, :, [1, 0]] * scale, keypoints[:, :, 2, None]], axis=2)
+        bbox, kp, _ = crop_boxes_keypoints(resize_bbox(bbox, (H, W), (oh, ow)), kp, y0, x0, ch, cw)
+        return img, bbox, np.zeros(bbox.shape[0], dtype=np.int32), kp, scale
 
     def __call__(self, in_data, aug=None):
         min_size = self.min_size
         if aug is not None:
             in_data = hflip(in_data, aug.keypoint_perm) if aug.flip else in_data
             min_size = aug.min_size or min_size
+            if aug.lsj is not None:
+                return self._lsj(in_data, aug)
         img, bbox, keypoints = in_data
         _, H, W = img.shape
         img = prepare(img, min_size, self.max_size)
@@ -128,7 +160,10 @@ class RawTransform(object):
     (img_u8 (H,W,3), bbox, label, masks_u8 (G,H,W) | keypoints, scale, (oH,oW)).
     aug (dataset.augment.AugmentParams, optional): (oH,oW) follow aug.min_size when given; with aug.flip the boxes and keypoints are
     mirrored here, while the image and masks stay as decoded - they are mirrored by the batched resize kernels, which read the 7th item
-    of the output, the flip flag (returned whenever aug is given)."""
+    of the output, the flip flag (returned whenever aug is given).
+    With aug.lsj (large-scale jitter) the 6th item is the window size (ch,cw) and an 8th item carries the geometry (oh,ow,y0,x0,ch,cw) of
+    augment.lsj_geometry for the crop kernels.  Keypoint examples get their boxes and keypoints here (augment.crop_boxes_keypoints); mask
+    examples return bbox = None, every raw mask and label: which instances survive the crop, and their boxes, is decided on the device."""
 
     def __init__(self, faster_rcnn, keypoints=False):
         self.min_size, self.max_size, self.keypoints = faster_rcnn.min_size, faster_rcnn.max_size, keypoints
@@ -139,7 +174,25 @@ class RawTransform(object):
             scale = self.max_size / max(H, W)
         return int(H * scale), int(W * scale)
 
+    def _lsj(self, in_data, aug):
+        _, H, W = in_data[0].shape
+        flip = bool(aug.flip)
+        geo = lsj_geometry(H, W, *aug.lsj)
+        oh, ow, y0, x0, ch, cw = geo
+        scale = oh / H
+        img_u8 = np.ascontiguousarray(in_data[0].transpose(1, 2, 0)).astype(np.uint8)
+        if self.keypoints:
+            keypoints = (flip_keypoints(in_data[2], W, aug.keypoint_perm) if flip else in_data[2]).astype(np.float32)
+            kp = np.concatenate([keypoints[:, :, [1, 0]] * scale, keypoints[:, :, 2, None]], axis=2)
+            bbox = resize_bbox(flip_bbox(in_data[1], W) if flip else in_data[1], (H, W), (oh, ow))
+            bbox, kp, _ = crop_boxes_keypoints(bbox, kp, y0, x0, ch, cw)
+            return img_u8, bbox, np.zeros(bbox.shape[0], dtype=np.int32), kp, scale, (ch, cw), int(flip), geo
+        masks = np.stack([np.asarray(m, np.uint8) for m in in_data[3]]) if len(in_data[3]) else np.zeros((0, H, W), np.uint8)
+        return img_u8, None, np.asarray(in_data[2], np.int32), masks, scale, (ch, cw), int(flip), geo
+
     def __call__(self, in_data, aug=None):
+        if aug is not None and aug.lsj is not None:
+            return self._lsj(in_data, aug)
         img = in_data[0]
         _, H, W = img.shape
         flip = bool(aug is not None and aug.flip)

@@ -725,6 +725,38 @@ int mrcnn_mask_resize_batch_nearest_u8(const unsigned char *src, size_t src_byte
                                        unsigned char *dst, int dst_h, int dst_w, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Large-scale jitter (augment.hip; dataset/augment.py lsj_geometry): the batched resizes above with a crop window.  The
+ * example is resized VIRTUALLY to oh x ow (either may exceed the canvas) and the window of rows y0 .. y0+ch-1, columns x0 .. x0+cw-1 of
+ * that resize lands at the top-left of the dst_h x dst_w canvas: output (y, x), y < ch, x < cw, is what the kernels above give at
+ * (y + y0, x + x0) of an oh x ow resize (same taps, flip = mirrored source column), everything else in the canvas is zero.
+ *   mrcnn_image_resize_crop_batch_u8_f32     the image writer: dst (N,3,dst_h,dst_w) float32.  One launch.
+ *   mrcnn_mask_crop_boxes_u8                 what the crop leaves of each instance, without writing a plane: src holds each example's
+ *       (count,H,W) masks, count <= Gin; labels_in (N,Gin) int32.  An instance is KEPT when its cropped nearest-neighbour resize has a
+ *       non-zero pixel.  Per example the kept instances, in their order, fill output rows 0, 1, ... (kept instances past row G-1 are
+ *       dropped): bboxes (N,G,4) float32 = the tight box (ymin, xmin, ymax + 1, xmax + 1) of the cropped mask in canvas coordinates,
+ *       labels (N,G) int32 = the instance's labels_in entry, gather (N,G) int32 = its index among the example's source instances; the
+ *       rows behind them are (0,0,0,0), -1, -1.  ws: (N,Gin,4) int32 scratch, 16-byte aligned, filled by the call.  One fill and two
+ *       launches on `stream`; integer maxima only - exact, the same for every schedule.
+ *   mrcnn_mask_resize_crop_batch_nearest_u8  the mask writer: dst (N,G,dst_h,dst_w) uint8; output plane j of example n reads source
+ *       instance gather[n][j] (DEVICE, (N,G) int32); an entry of -1, or outside the example's count, gives a zero plane.  One launch.
+ * Errors, before any launch: MRCNN_E_INVALID for everything the calls above refuse (with the window, not oh x ow, held against the
+ * canvas), ch > dst_h, cw > dst_w, y0 + ch > oh, x0 + cw > ow, a negative offset, an empty window, a NULL labels_in / bboxes / labels /
+ * gather / ws, a misaligned bboxes / ws.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mrcnn_crop_desc {
+    long long src_offset;
+    int H, W, oh, ow, flip, count;
+    int y0, x0, ch, cw;
+} mrcnn_crop_desc_t;            /* 48 bytes */
+int mrcnn_image_resize_crop_batch_u8_f32(const unsigned char *src, size_t src_bytes, const mrcnn_crop_desc_t *desc, int N, float *dst,
+                                         int dst_h, int dst_w, float div, void *stream);
+int mrcnn_mask_crop_boxes_u8(const unsigned char *src, size_t src_bytes, const mrcnn_crop_desc_t *desc, int N, int Gin, int G, int dst_h,
+                             int dst_w, const int32_t *labels_in, float *bboxes, int32_t *labels, int32_t *gather, int32_t *ws,
+                             void *stream);
+int mrcnn_mask_resize_crop_batch_nearest_u8(const unsigned char *src, size_t src_bytes, const mrcnn_crop_desc_t *desc, int N, int G,
+                                            const int32_t *gather, unsigned char *dst, int dst_h, int dst_w, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Test-time augmentation (tta.hip; MaskRCNN.use_test_augmentation).  An image runs as V <= MRCNN_TTA_VIEWS_MAX views (short sides,
  * optionally mirrored), one N = 1 forward each; these calls merge the views after the forward pass.
  *   views (V) HOST array, read at the call (passed to the kernels by value): R = the view's candidates (decode), mirror 0 / 1, scale = the

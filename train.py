@@ -116,6 +116,12 @@ def build_parser(keypoints=False):
     parser.add_argument(*both('--warmup-factor'), type=float, default=1.0 / 3, metavar='F')
     parser.add_argument(*both('--lr-steps'), type=int, nargs='+', default=None, metavar='S',
                         help='lr x0.1 behind each of these iterations (e.g. 60000 80000 of 90000); not together with --lr-shift-interval')
+    parser.add_argument(*both('--lsj-size'), type=int, default=0, metavar='S',
+                        help='large-scale jitter: every example is resized by a random factor (its longer side to S x a scale drawn from '
+                             '--lsj-scale), cropped to at most S x S at a random position and padded to an S x S canvas - every batch has '
+                             'that one shape; S a multiple of 64; --synthetic 0 only, not with --min-sizes.  0 = off')
+    parser.add_argument(*both('--lsj-scale'), type=float, nargs=2, default=[0.1, 2.0], metavar=('LO', 'HI'),
+                        help='the scale range of --lsj-size')
     return parser
 
 
@@ -169,7 +175,10 @@ def check_resume_freeze(resume, args, path=''):
 
 def augment_settings(args):
     """The augmentation of a run as recorded in trainer_<it>.pt (NO_AUGMENT when off)."""
-    return {'hflip': int(args.hflip), 'min_sizes': [int(s) for s in args.min_sizes] if args.min_sizes else None, 'seed': AUGMENT_SEED}
+    settings = {'hflip': int(args.hflip), 'min_sizes': [int(s) for s in args.min_sizes] if args.min_sizes else None, 'seed': AUGMENT_SEED}
+    if args.lsj_size:
+        settings['lsj'] = {'size': int(args.lsj_size), 'scale': [float(v) for v in args.lsj_scale]}
+    return settings
 
 
 def _eval_boxpost_settings(args):
@@ -188,6 +197,21 @@ def _check_augment_args(args):
                          'augmented')
     if args.min_sizes and any(s <= 0 for s in args.min_sizes):
         raise ValueError('--min-sizes: every size must be positive, got %s' % args.min_sizes)
+    if not args.lsj_size:
+        return
+    lo, hi = args.lsj_scale
+    if args.lsj_size < 0 or args.lsj_size % 64:
+        raise ValueError('--lsj-size must be a positive multiple of 64 (the coarsest pyramid stride), got %d' % args.lsj_size)
+    if not lo > 0:
+        raise ValueError('--lsj-scale: LO must be positive, got %r' % lo)
+    if lo > hi:
+        raise ValueError('--lsj-scale: LO must not exceed HI, got %r > %r' % (lo, hi))
+    if args.synthetic:
+        raise ValueError('--lsj-size augments the dataset loader (--synthetic 0); the synthetic batches (--synthetic 1) are not augmented')
+    if args.min_sizes:
+        raise ValueError('--min-sizes and --lsj-size are two different resize rules: give one of them')
+    if getattr(args, 'dataset', 'coco') == 'depth':
+        raise ValueError('--lsj-size: --dataset depth is transformed on the host only and has no large-scale jitter')
 
 
 def _keypoint_names(args, data):
@@ -257,10 +281,11 @@ def run(args, keypoints=False):
             data = COCOMaskLoader(anno_dir=args.anno_dir, img_dir=args.img_dir, data_type=args.data_type,
                                   category_filter=read_labels(args.label_file))
     augment = None
-    if args.hflip or args.min_sizes:
+    if args.hflip or args.min_sizes or args.lsj_size:
         from chainer_maskrcnn.dataset.augment import Augment
         augment = Augment(hflip_prob=0.5 if args.hflip else 0.0, min_sizes=args.min_sizes, seed=AUGMENT_SEED,
-                          keypoint_perm=_keypoint_flip_perm(args, data) if keypoints and args.hflip else None)
+                          keypoint_perm=_keypoint_flip_perm(args, data) if keypoints and args.hflip else None,
+                          lsj_size=args.lsj_size or None, lsj_scale=args.lsj_scale)
     local = int(os.environ.get('LOCAL_RANK', args.gpu))
     ndev = max(1, torch.cuda.device_count())
     lws = int(os.environ.get('LOCAL_WORLD_SIZE', 1))
