@@ -58,15 +58,16 @@ def bn_train_fwd_stats(x, part, gamma, beta, residual=None, relu=False, running_
     return y, mean, invstd
 
 
-def bn_train_bwd(gy, x, y, gamma, mean, invstd, relu=False, want_gres=False, beta=None):
-    """y None + beta given (BN + ReLU without residual): the ReLU mask is recomputed from x."""
-    _ck(gy, x, y, gamma, mean, invstd, beta)
+def bn_train_bwd(gy, x, y, gamma, mean, invstd, relu=False, want_gres=False, beta=None, gg=None, gb=None):
+    """y None + beta given (BN + ReLU without residual): the ReLU mask is recomputed from x.  gg / gb: where the gradients of gamma /
+    beta are written (the flat gradient buffer's views); allocated when not given."""
+    _ck(gy, x, y, gamma, mean, invstd, beta, gg, gb)
     C = x.shape[-1]
     P = x.numel() // C
     gx = torch.empty_like(x)
     gres = torch.empty_like(x) if want_gres else None
-    gg = _empty((C,), x.device)
-    gb = _empty((C,), x.device)
+    gg = _empty((C,), x.device) if gg is None else gg
+    gb = _empty((C,), x.device) if gb is None else gb
     ws = workspace(lib().mrcnn_bn_workspace_bytes(P, C), x.device)
     check(lib().mrcnn_bn_train_bwd_f32(ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(gx), ptr(gres),
                                        ptr(gg), ptr(gb), P, C, int(relu), ptr(ws), ws.numel(), stream_ptr()))

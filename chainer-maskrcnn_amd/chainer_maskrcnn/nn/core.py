@@ -342,13 +342,11 @@ class BatchNorm(object):
 
     def fwd(self, x, relu=False, residual=None, partials=None):
         gamma, beta = self.ps.p(self.name + '/gamma'), self.ps.p(self.name + '/beta')
-        if not TRAIN:
-            y = ops.bn_infer_fwd(x, gamma, beta, self.ps.buffers[self.name + '/avg_mean'],
-                                 self.ps.buffers[self.name + '/avg_var'], residual, relu)
-            return y, None
-        if self.frozen:
+        if not TRAIN or self.frozen:
             y = ops.bn_infer_fwd(x, gamma, beta, self.ps.buffers[self.name + '/avg_mean'], self.ps.buffers[self.name + '/avg_var'],
                                  residual, relu)
+            if not TRAIN:
+                return y, None
             # the ReLU mask is read from y: the layer's output is alive until the backward pass anyway (it is the next convolution's
             # operand), the convolution output x is not kept
             return y, ('frozen', y if relu else None)
@@ -379,17 +377,10 @@ class BatchNorm(object):
         if gy_masked:
             assert relu and not want_gres
             relu, y = False, None
-        from chainer_maskrcnn._hip import lib, check, ptr, stream_ptr
-        C = self.c
-        P = x.numel() // C
-        gx = torch.empty_like(x)
-        gres = torch.empty_like(x) if want_gres else None
-        ws = hnn.workspace(lib().mrcnn_bn_workspace_bytes(P, C), x.device)
-        check(lib().mrcnn_bn_train_bwd_f32(ptr(gy), ptr(x), ptr(y), ptr(self.ps.p(self.name + '/gamma')),
-                                           ptr(self.ps.p(self.name + '/beta')), ptr(mean),
-                                           ptr(invstd), ptr(gx), ptr(gres), ptr(self.ps.g(self.name + '/gamma')),
-                                           ptr(self.ps.g(self.name + '/beta')), P, C, int(relu), ptr(ws), ws.numel(),
-                                           stream_ptr()))
+        # the parameter gradients go straight into the flat gradient buffer
+        gx, gres, _, _ = ops.bn_train_bwd(gy, x, y, self.ps.p(self.name + '/gamma'), mean, invstd, relu, want_gres,
+                                          beta=self.ps.p(self.name + '/beta'), gg=self.ps.g(self.name + '/gamma'),
+                                          gb=self.ps.g(self.name + '/beta'))
         return gx, gres
 
 

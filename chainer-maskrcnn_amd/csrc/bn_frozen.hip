@@ -16,43 +16,14 @@
 // (The stride is at most 4096 * 256 and a thread's first element lies below it: those two remainders are 32-bit; the 64-bit remainder of
 // the per-element path is ~150 instructions of software division, as everywhere in nn.hip's grid-stride kernels.)
 #include "common.h"
+#include "bn_common.h"
 #include <algorithm>
 
 namespace {
 
 constexpr int NT = 256;
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-// streamed-once read (the last reader of a big tensor in its pass): non-temporal, as in nn.hip
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4s(const float *p) {
-    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-
 inline int ew_grid(size_t n4) { return (int)std::min<size_t>((n4 + NT - 1) / NT, 256 * 16); }
-
-// 1 / sqrt(avg_var + eps) of four channels: k_bn_infer's sub-expression
-__device__ __forceinline__ float4 inv_std4(const float *var, int c, float eps) {
-    const float4 va = ld4(var + c);
-    return make_float4(1.0f / sqrtf(va.x + eps), 1.0f / sqrtf(va.y + eps), 1.0f / sqrtf(va.z + eps), 1.0f / sqrtf(va.w + eps));
-}
-// a = gamma * (1 / sqrt(avg_var + eps))
-__device__ __forceinline__ float4 scale4(const float *gamma, const float *var, int c, float eps) {
-    const float4 g = ld4(gamma + c), s = inv_std4(var, c, eps);
-    return make_float4(g.x * s.x, g.y * s.y, g.z * s.z, g.w * s.w);
-}
-__device__ __forceinline__ float4 mask4(float4 g, float4 y) {
-    g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f; g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
-    return g;
-}
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-// gamma * ((x - mean) * inv) + beta: k_bn_infer's value before residual / ReLU
-__device__ __forceinline__ float4 affine4(float4 v, float4 g, float4 m, float4 s, float4 b) {
-    return make_float4(g.x * ((v.x - m.x) * s.x) + b.x, g.y * ((v.y - m.y) * s.y) + b.y, g.z * ((v.z - m.z) * s.z) + b.z,
-                       g.w * ((v.w - m.w) * s.w) + b.w);
-}
 
 // MODE 0: dz = gy.  1: dz = gy where y > 0 (yx = y).  2: dz = gy where the forward's y, recomputed from yx = x, is > 0.
 // gx may be gy (every element is read before it is written, by the same thread).
@@ -67,15 +38,16 @@ __global__ __launch_bounds__(NT) void k_bn_frozen_bwd(const float *gy, const flo
     const bool fixed = ((unsigned)stride % (unsigned)C4) == 0;         // grid-uniform
     float4 a, s, g_, m, b;
     auto coef = [&](int c) {
-        a = scale4(gamma, var, c, eps);
-        if (MODE == 2) { s = inv_std4(var, c, eps); g_ = ld4(gamma + c); m = ld4(mean + c); b = ld4(beta + c); }
+        g_ = ld4(gamma + c);
+        a = bn_scale4(g_, ld4(var + c), eps);
+        if (MODE == 2) { s = bn_inv_std4(ld4(var + c), eps); m = ld4(mean + c); b = ld4(beta + c); }
     };
     if (fixed) coef((int)((unsigned)i % (unsigned)C4) * 4);
     for (; i < n4; i += stride) {
         if (!fixed) coef((int)(i % C4) * 4);
         float4 g = ld4s(gy + i * 4);
-        if (MODE == 1) g = mask4(g, ld4s(yx + i * 4));
-        if (MODE == 2) g = mask4(g, affine4(ld4s(yx + i * 4), g_, m, s, b));
+        if (MODE == 1) g = relu_mask4(g, ld4s(yx + i * 4));
+        if (MODE == 2) g = relu_mask4(g, bn_affine4(ld4s(yx + i * 4), g_, m, s, b));
         st4(gx + i * 4, mul4(g, a));
         if (gres) st4(gres + i * 4, g);
     }
@@ -94,18 +66,15 @@ __global__ __launch_bounds__(NT) void k_bn_infer_pair(const float *__restrict__ 
     const bool fixed = ((unsigned)stride % (unsigned)C4) == 0;
     float4 ga, ba, ma, sa, gb, bb, mb, sb;
     auto coef = [&](int c) {
-        ga = ld4(gamma_a + c); ba = ld4(beta_a + c); ma = ld4(mean_a + c); sa = inv_std4(var_a, c, eps);
-        gb = ld4(gamma_b + c); bb = ld4(beta_b + c); mb = ld4(mean_b + c); sb = inv_std4(var_b, c, eps);
+        ga = ld4(gamma_a + c); ba = ld4(beta_a + c); ma = ld4(mean_a + c); sa = bn_inv_std4(ld4(var_a + c), eps);
+        gb = ld4(gamma_b + c); bb = ld4(beta_b + c); mb = ld4(mean_b + c); sb = bn_inv_std4(ld4(var_b + c), eps);
     };
     if (fixed) coef((int)((unsigned)i % (unsigned)C4) * 4);
     for (; i < n4; i += stride) {
         if (!fixed) coef((int)(i % C4) * 4);
         const float4 va = ld4s(xa + i * 4), vb = ld4s(xb + i * 4);
-        const float4 r = affine4(vb, gb, mb, sb, bb);
-        float4 o = affine4(va, ga, ma, sa, ba);
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-        st4(y + i * 4, o);
+        const float4 r = bn_affine4(vb, gb, mb, sb, bb);
+        st4(y + i * 4, relu4(add4(bn_affine4(va, ga, ma, sa, ba), r)));
     }
 }
 
@@ -119,12 +88,12 @@ __global__ __launch_bounds__(NT) void k_bn_frozen_bwd_pair(const float *gy, cons
     if (i >= n4) return;
     const bool fixed = ((unsigned)stride % (unsigned)C4) == 0;
     float4 aa, ab;
-    auto coef = [&](int c) { aa = scale4(gamma_a, var_a, c, eps); ab = scale4(gamma_b, var_b, c, eps); };
+    auto coef = [&](int c) { aa = bn_scale4(ld4(gamma_a + c), ld4(var_a + c), eps); ab = bn_scale4(ld4(gamma_b + c), ld4(var_b + c), eps); };
     if (fixed) coef((int)((unsigned)i % (unsigned)C4) * 4);
     for (; i < n4; i += stride) {
         if (!fixed) coef((int)(i % C4) * 4);
         float4 g = ld4s(gy + i * 4);
-        if (y) g = mask4(g, ld4s(y + i * 4));
+        if (y) g = relu_mask4(g, ld4s(y + i * 4));
         st4(gxa + i * 4, mul4(g, aa));
         st4(gxb + i * 4, mul4(g, ab));
     }

@@ -1,4 +1,4 @@
-// Shared host-side helpers of libmrcnn_hip.so (gfx950 only).
+// Shared host-side helpers and the float4 load / store helpers of libmrcnn_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -38,6 +38,17 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 }  // namespace mrcnn
 
 constexpr int kWave = 64;  // gfx950 wavefront
+
+// float4 access of the streaming kernels (16 B per lane); pointers are 16-byte aligned
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+// streamed-once read (the LAST reader of a big tensor in its pass): non-temporal, does not displace lines other kernels re-read
+typedef float nt_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4s(const float *p) {
+    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 
 namespace mrcnn {
 // Hand-written selection / sorting of unsigned 64-bit keys (sort.hip; no library): segments = images.

@@ -25,6 +25,7 @@
 // ("tail split"); all partial sums go to slabs that are added in fixed order (bit-reproducible results).
 // Epilogue: 32x32 accumulator tiles are transposed through per-wave LDS tiles and stored as float4.
 #include "common.h"
+#include "bn_common.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -74,7 +75,6 @@ struct ConvP {
 
 __device__ __forceinline__ float4 ldg4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 // read-once stream (split-K slabs, the Winograd GEMM's output M): non-temporal, does not displace lines other kernels re-read
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg4s(const float *p) {
     const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
     return make_float4(v.x, v.y, v.z, v.w);
@@ -1454,9 +1454,10 @@ __device__ __forceinline__ void v4bufst(__amdgpu_buffer_rsrc_t rs, unsigned voff
     __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff, soff, 0);
 }
 // (r6) The layer's input may be relu(BatchNorm(x)) of a training-mode BatchNorm whose statistics are final: the transform then applies
-// gamma * ((x - mean) * invstd) + beta and the ReLU to every tap as it loads it - the expression of nn.hip's k_bn_apply, so the values
-// are the bits that kernel would have written - and the normalised activation never crosses HBM (conv -> bn -> relu -> conv 3x3 of a
-// ResNet bottleneck: extractor/feature_pyramid_network.py:48-66).  A tap outside the image stays the zero of the padding.
+// gamma * ((x - mean) * invstd) + beta and the ReLU to every tap as it loads it - bn_common.h's bn_affine1 and relu1, which nn.hip's
+// k_bn_apply calls too, so the values are the bits that kernel would have written - and the normalised activation never crosses HBM
+// (conv -> bn -> relu -> conv 3x3 of a ResNet bottleneck: extractor/feature_pyramid_network.py:48-66).  A tap outside the image stays
+// the zero of the padding.
 struct InBN { const float *gamma, *beta, *mean, *invstd; };
 template <int M_>
 __device__ __forceinline__ void wino_input_body(const float *__restrict__ x, float *__restrict__ V, int N, int H, int W, int C,
@@ -1521,9 +1522,9 @@ __device__ __forceinline__ void wino_input_body(const float *__restrict__ x, flo
             for (int rr = 0; rr < A_; ++rr) {
                 const bool in = !(rowo[rr] == OOB || colo[q] == OOB);
                 const V4 v = d[rr];
-                V4 o;
-                o.x = fmaxf(bg.x * ((v.x - bm.x) * bs.x) + bb.x, 0.f); o.y = fmaxf(bg.y * ((v.y - bm.y) * bs.y) + bb.y, 0.f);
-                o.z = fmaxf(bg.z * ((v.z - bm.z) * bs.z) + bb.z, 0.f); o.w = fmaxf(bg.w * ((v.w - bm.w) * bs.w) + bb.w, 0.f);
+                V4 o;           // member by member: passing V4 through a 4-wide function changes how the transform is vectorised
+                o.x = relu1(bn_affine1(v.x, bg.x, bm.x, bs.x, bb.x)); o.y = relu1(bn_affine1(v.y, bg.y, bm.y, bs.y, bb.y));
+                o.z = relu1(bn_affine1(v.z, bg.z, bm.z, bs.z, bb.z)); o.w = relu1(bn_affine1(v.w, bg.w, bm.w, bs.w, bb.w));
                 d[rr] = in ? o : v4zero();
             }
         }

@@ -13,21 +13,12 @@
 // all reductions are two-stage with a fixed summation order (bit-reproducible, no float atomics).
 // Roofline: HBM; algorithmic bytes are stated per kernel.
 #include "common.h"
+#include "bn_common.h"
 #include "resize_common.h"
 
 namespace {
 
 constexpr int NT = 256;
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-// streamed-once read (the LAST reader of a big tensor in its pass): non-temporal, does not displace lines other kernels re-read
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4s(const float *p) {
-    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 
 // (n, h, w, c) of element i of an (N, Hd, Wd, C4) float4 grid.  32-bit unsigned arithmetic whenever the grid has fewer than 2^32
 // elements (always, in practice): the size_t divisions this replaces compile to ~100 instructions of software division EACH
@@ -247,6 +238,21 @@ void launch_stats_final(hipStream_t st, const float *x, const float *part, int n
         hipLaunchKernelGGL(k_bn_stats_final<4>, dim3(mrcnn::cdiv(C, 16)), dim3(FIN_THREADS), 0, st, x, part, nblk, P, C, eps, decay, shifted, mean,
                            invstd, run_mean, run_var);
 }
+// Statistics of one training-mode BatchNorm: from the partial rows (part, rows) the producing convolution left behind, or, part == nullptr,
+// from a pass of its own over x through ws (which the caller has checked against mrcnn_bn_workspace_bytes()).
+int launch_bn_stats(hipStream_t st, const float *x, const float *part, int rows, int P, int C, float eps, float decay, void *ws, float *mean,
+                    float *invstd, float *run_mean, float *run_var) {
+    if (part) {
+        launch_stats_final(st, x, part, rows, P, C, eps, decay, 0, mean, invstd, run_mean, run_var);
+    } else {
+        const RedPlan r = red_plan(P, C);
+        hipLaunchKernelGGL(k_bn_stats_partial, dim3(r.nblk), dim3(NT), 0, st, x, P, C, r.G, r.RPI, r.rows_per_blk, (float *)ws);
+        MRCNN_LAUNCH_CHECK();
+        launch_stats_final(st, x, (const float *)ws, r.nblk, P, C, eps, decay, 1, mean, invstd, run_mean, run_var);
+    }
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
 
 // y = gamma*(x-mean)*invstd + beta (+ residual) (ReLU).  Bytes: 4*P*C*(2 or 3).
 __global__ __launch_bounds__(NT) void k_bn_apply(const float *__restrict__ x, const float *__restrict__ gamma,
@@ -256,16 +262,9 @@ __global__ __launch_bounds__(NT) void k_bn_apply(const float *__restrict__ x, co
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
         const int c = (int)(i % C4) * 4;
         const float4 v = ld4s(x + i * 4), g = ld4(gamma + c), b = ld4(beta + c), m = ld4(mean + c), s = ld4(invstd + c);
-        float4 o;
-        o.x = g.x * ((v.x - m.x) * s.x) + b.x;
-        o.y = g.y * ((v.y - m.y) * s.y) + b.y;
-        o.z = g.z * ((v.z - m.z) * s.z) + b.z;
-        o.w = g.w * ((v.w - m.w) * s.w) + b.w;
-        if (res) {
-            const float4 r = ld4s(res + i * 4);
-            o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        }
-        if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+        float4 o = bn_affine4(v, g, m, s, b);
+        if (res) o = add4(o, ld4s(res + i * 4));
+        if (relu) o = relu4(o);
         st4(y + i * 4, o);
     }
 }
@@ -278,16 +277,9 @@ __global__ __launch_bounds__(NT) void k_bn_infer(const float *__restrict__ x, co
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
         const int c = (int)(i % C4) * 4;
         const float4 v = ld4(x + i * 4), g = ld4(gamma + c), b = ld4(beta + c), m = ld4(mean + c), va = ld4(var + c);
-        float4 o;
-        o.x = g.x * ((v.x - m.x) * (1.0f / sqrtf(va.x + eps))) + b.x;
-        o.y = g.y * ((v.y - m.y) * (1.0f / sqrtf(va.y + eps))) + b.y;
-        o.z = g.z * ((v.z - m.z) * (1.0f / sqrtf(va.z + eps))) + b.z;
-        o.w = g.w * ((v.w - m.w) * (1.0f / sqrtf(va.w + eps))) + b.w;
-        if (res) {
-            const float4 r = ld4(res + i * 4);
-            o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        }
-        if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+        float4 o = bn_affine4(v, g, m, bn_inv_std4(va, eps), b);
+        if (res) o = add4(o, ld4(res + i * 4));
+        if (relu) o = relu4(o);
         st4(y + i * 4, o);
     }
 }
@@ -309,17 +301,9 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_partial(const float *__restrict__
         const float4 ga = relu == 2 ? ld4(gamma + cg * 4) : f4(0.f), be = relu == 2 ? ld4(beta + cg * 4) : f4(0.f);
         float4 a = f4(0.f), b = f4(0.f);
         auto acc = [&](float4 g, const float4 v, float4 yy) {
-            if (relu == 2) {
-                yy.x = ga.x * ((v.x - m.x) * s.x) + be.x; yy.y = ga.y * ((v.y - m.y) * s.y) + be.y;
-                yy.z = ga.z * ((v.z - m.z) * s.z) + be.z; yy.w = ga.w * ((v.w - m.w) * s.w) + be.w;
-            }
-            if (relu) {
-                g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-                g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
-            }
-            a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
-            b.x = fmaf(g.x, (v.x - m.x) * s.x, b.x); b.y = fmaf(g.y, (v.y - m.y) * s.y, b.y);
-            b.z = fmaf(g.z, (v.z - m.z) * s.z, b.z); b.w = fmaf(g.w, (v.w - m.w) * s.w, b.w);
+            if (relu == 2) yy = bn_affine4(v, ga, m, s, be);
+            if (relu) g = relu_mask4(g, yy);
+            bn_bwd_acc4(g, v, m, s, a, b);
         };
         const float *yr = relu == 1 ? y : gy;             // only mode 1 reads the third stream
         int r = r0 + rr;
@@ -342,8 +326,7 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_partial(const float *__restrict__
         if (rr == 0) {
             for (int k = 1; k < RPI; ++k) {
                 const float4 p = s1[k * G + cg0], q = s2[k * G + cg0];
-                a.x += p.x; a.y += p.y; a.z += p.z; a.w += p.w;
-                b.x += q.x; b.y += q.y; b.z += q.z; b.w += q.w;
+                a = add4(a, p); b = add4(b, q);
             }
             st4(part + ((size_t)blockIdx.x * 2 * C) + cg * 4, a);
             st4(part + ((size_t)blockIdx.x * 2 * C) + C + cg * 4, b);
@@ -381,22 +364,11 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply(const float *__restrict__ g
         const float4 ga = ld4(gamma + c), m = ld4(mean + c), s = ld4(invstd + c), gb = ld4(gbeta + c), gg = ld4(ggamma + c);
         if (relu) {
             float4 yy;
-            if (relu == 2) {
-                const float4 be = ld4(beta + c);
-                yy.x = ga.x * ((v.x - m.x) * s.x) + be.x; yy.y = ga.y * ((v.y - m.y) * s.y) + be.y;
-                yy.z = ga.z * ((v.z - m.z) * s.z) + be.z; yy.w = ga.w * ((v.w - m.w) * s.w) + be.w;
-            } else {
-                yy = ld4s(y + i * 4);
-            }
-            g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-            g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
+            if (relu == 2) yy = bn_affine4(v, ga, m, s, ld4(beta + c));
+            else yy = ld4s(y + i * 4);
+            g = relu_mask4(g, yy);
         }
-        float4 o;
-        o.x = ga.x * s.x * (g.x - gb.x * invP - ((v.x - m.x) * s.x) * (gg.x * invP));
-        o.y = ga.y * s.y * (g.y - gb.y * invP - ((v.y - m.y) * s.y) * (gg.y * invP));
-        o.z = ga.z * s.z * (g.z - gb.z * invP - ((v.z - m.z) * s.z) * (gg.z * invP));
-        o.w = ga.w * s.w * (g.w - gb.w * invP - ((v.w - m.w) * s.w) * (gg.w * invP));
-        st4(gx + i * 4, o);
+        st4(gx + i * 4, bn_bwd_dx4(g, v, ga, m, s, gb, gg, invP));
         if (gres) st4(gres + i * 4, g);
     }
 }
@@ -406,8 +378,8 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply(const float *__restrict__ g
 // shortcut's BatchNorm output r crosses HBM twice in the forward pass (written by its apply kernel, read as the residual) and the masked
 // gradient g_r three times in the backward pass (written beside g_h3, read by both kernels of the shortcut's BatchNorm backward):
 // 5 x 252 MB per step at 2 x 1024^2.  The pair kernels read the two pre-BatchNorm tensors side by side and never materialise r / g_r.
-// Every value is computed by the expressions of the single-layer kernels in the same order (r first, then o = bn_a + r; the same row
-// blocks, the same order of the partial sums): the results are the same bits as the layer-by-layer sequence.
+// Every value is computed by the functions the single-layer kernels call (bn_common.h), in the same order (r first, then o = bn_a + r;
+// the same row blocks, the same order of the partial sums): the results are the same bits as the layer-by-layer sequence.
 __global__ __launch_bounds__(NT) void k_bn_apply2(const float *__restrict__ xa, const float *__restrict__ gamma_a, const float *__restrict__ beta_a,
                                                   const float *__restrict__ mean_a, const float *__restrict__ invstd_a,
                                                   const float *__restrict__ xb, const float *__restrict__ gamma_b, const float *__restrict__ beta_b,
@@ -418,14 +390,8 @@ __global__ __launch_bounds__(NT) void k_bn_apply2(const float *__restrict__ xa, 
         const float4 va = ld4s(xa + i * 4), vb = ld4s(xb + i * 4);
         const float4 ga = ld4(gamma_a + c), ba = ld4(beta_a + c), ma = ld4(mean_a + c), sa = ld4(invstd_a + c);
         const float4 gb = ld4(gamma_b + c), bb = ld4(beta_b + c), mb = ld4(mean_b + c), sb = ld4(invstd_b + c);
-        float4 r, o;
-        r.x = gb.x * ((vb.x - mb.x) * sb.x) + bb.x; r.y = gb.y * ((vb.y - mb.y) * sb.y) + bb.y;
-        r.z = gb.z * ((vb.z - mb.z) * sb.z) + bb.z; r.w = gb.w * ((vb.w - mb.w) * sb.w) + bb.w;
-        o.x = ga.x * ((va.x - ma.x) * sa.x) + ba.x; o.y = ga.y * ((va.y - ma.y) * sa.y) + ba.y;
-        o.z = ga.z * ((va.z - ma.z) * sa.z) + ba.z; o.w = ga.w * ((va.w - ma.w) * sa.w) + ba.w;
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-        st4(y + i * 4, o);
+        const float4 r = bn_affine4(vb, gb, mb, sb, bb);
+        st4(y + i * 4, relu4(add4(bn_affine4(va, ga, ma, sa, ba), r)));
     }
 }
 
@@ -443,15 +409,9 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_partial2(const float *__restrict_
         const float4 ma = ld4(mean_a + cg * 4), sa = ld4(invstd_a + cg * 4), mb = ld4(mean_b + cg * 4), sb = ld4(invstd_b + cg * 4);
         float4 a = f4(0.f), b = f4(0.f), c = f4(0.f);
         auto acc = [&](float4 g, const float4 va, const float4 vb, const float4 yy) {
-            if (y) {
-                g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-                g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
-            }
-            a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
-            b.x = fmaf(g.x, (va.x - ma.x) * sa.x, b.x); b.y = fmaf(g.y, (va.y - ma.y) * sa.y, b.y);
-            b.z = fmaf(g.z, (va.z - ma.z) * sa.z, b.z); b.w = fmaf(g.w, (va.w - ma.w) * sa.w, b.w);
-            c.x = fmaf(g.x, (vb.x - mb.x) * sb.x, c.x); c.y = fmaf(g.y, (vb.y - mb.y) * sb.y, c.y);
-            c.z = fmaf(g.z, (vb.z - mb.z) * sb.z, c.z); c.w = fmaf(g.w, (vb.w - mb.w) * sb.w, c.w);
+            if (y) g = relu_mask4(g, yy);
+            bn_bwd_acc4(g, va, ma, sa, a, b);
+            c = bn_dot4(g, vb, mb, sb, c);
         };
         const float *yr = y ? y : gy;
         int r = r0 + rr;
@@ -473,9 +433,7 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_partial2(const float *__restrict_
         if (rr == 0) {
             for (int k = 1; k < RPI; ++k) {
                 const float4 p = s1[k * G + cg0], q = s2[k * G + cg0], u = s3[k * G + cg0];
-                a.x += p.x; a.y += p.y; a.z += p.z; a.w += p.w;
-                b.x += q.x; b.y += q.y; b.z += q.z; b.w += q.w;
-                c.x += u.x; c.y += u.y; c.z += u.z; c.w += u.w;
+                a = add4(a, p); b = add4(b, q); c = add4(c, u);
             }
             st4(part + ((size_t)blockIdx.x * 3 * C) + cg * 4, a);
             st4(part + ((size_t)blockIdx.x * 3 * C) + C + cg * 4, b);
@@ -499,6 +457,12 @@ __global__ __launch_bounds__(FIN_THREADS) void k_bn_bwd_final2(const float *__re
     gbeta_a[c] = (float)a; ggamma_a[c] = (float)b;
     gbeta_b[c] = (float)a2; ggamma_b[c] = (float)b2;
 }
+void launch_bwd_final2(hipStream_t st, const float *part, int nblk, int C, float *gbeta_a, float *ggamma_a, float *gbeta_b, float *ggamma_b) {
+    if (g_fin_quads == 1)
+        hipLaunchKernelGGL(k_bn_bwd_final2<1>, dim3(mrcnn::cdiv(C, 4)), dim3(FIN_THREADS), 0, st, part, nblk, C, gbeta_a, ggamma_a, gbeta_b, ggamma_b);
+    else
+        hipLaunchKernelGGL(k_bn_bwd_final2<4>, dim3(mrcnn::cdiv(C, 16)), dim3(FIN_THREADS), 0, st, part, nblk, C, gbeta_a, ggamma_a, gbeta_b, ggamma_b);
+}
 
 __global__ __launch_bounds__(NT) void k_bn_bwd_apply2(const float *__restrict__ gy, const float *__restrict__ y, const float *__restrict__ xa,
                                                       const float *__restrict__ xb, const float *__restrict__ gamma_a,
@@ -512,28 +476,14 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply2(const float *__restrict__ 
         const int c = (int)(i % C4) * 4;
         float4 g = ld4s(gy + i * 4);
         const float4 va = ld4s(xa + i * 4), vb = ld4s(xb + i * 4);
-        if (y) {
-            const float4 yy = ld4s(y + i * 4);
-            g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-            g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
-        }
+        if (y) g = relu_mask4(g, ld4s(y + i * 4));
         {
             const float4 ga = ld4(gamma_a + c), m = ld4(mean_a + c), s = ld4(invstd_a + c), gb = ld4(gbeta_a + c), gg = ld4(ggamma_a + c);
-            float4 o;
-            o.x = ga.x * s.x * (g.x - gb.x * invP - ((va.x - m.x) * s.x) * (gg.x * invP));
-            o.y = ga.y * s.y * (g.y - gb.y * invP - ((va.y - m.y) * s.y) * (gg.y * invP));
-            o.z = ga.z * s.z * (g.z - gb.z * invP - ((va.z - m.z) * s.z) * (gg.z * invP));
-            o.w = ga.w * s.w * (g.w - gb.w * invP - ((va.w - m.w) * s.w) * (gg.w * invP));
-            st4(gxa + i * 4, o);
+            st4(gxa + i * 4, bn_bwd_dx4(g, va, ga, m, s, gb, gg, invP));
         }
         {
             const float4 ga = ld4(gamma_b + c), m = ld4(mean_b + c), s = ld4(invstd_b + c), gb = ld4(gbeta_b + c), gg = ld4(ggamma_b + c);
-            float4 o;
-            o.x = ga.x * s.x * (g.x - gb.x * invP - ((vb.x - m.x) * s.x) * (gg.x * invP));
-            o.y = ga.y * s.y * (g.y - gb.y * invP - ((vb.y - m.y) * s.y) * (gg.y * invP));
-            o.z = ga.z * s.z * (g.z - gb.z * invP - ((vb.z - m.z) * s.z) * (gg.z * invP));
-            o.w = ga.w * s.w * (g.w - gb.w * invP - ((vb.w - m.w) * s.w) * (gg.w * invP));
-            st4(gxb + i * 4, o);
+            st4(gxb + i * 4, bn_bwd_dx4(g, vb, ga, m, s, gb, gg, invP));
         }
     }
 }
@@ -541,19 +491,14 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply2(const float *__restrict__ 
 __global__ __launch_bounds__(NT) void k_relu_bwd(const float *__restrict__ gy, const float *__restrict__ y,
                                                  float *__restrict__ gx, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
-        float4 g = ld4(gy + i * 4);
-        const float4 yy = ld4(y + i * 4);
-        g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-        g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
-        st4(gx + i * 4, g);
+        st4(gx + i * 4, relu_mask4(ld4(gy + i * 4), ld4(y + i * 4)));
     }
 }
 
 __global__ __launch_bounds__(NT) void k_add(const float *__restrict__ a, const float *__restrict__ b,
                                             float *__restrict__ o, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
-        const float4 p = ld4(a + i * 4), q = ld4(b + i * 4);
-        st4(o + i * 4, make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w));
+        st4(o + i * 4, add4(ld4(a + i * 4), ld4(b + i * 4)));
     }
 }
 
@@ -621,8 +566,7 @@ __global__ __launch_bounds__(NT) void k_global_avg_pool(const float *__restrict_
 
 __global__ __launch_bounds__(NT) void k_relu_fwd(const float *__restrict__ x, float *__restrict__ y, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
-        const float4 v = ld4(x + i * 4);
-        st4(y + i * 4, make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)));
+        st4(y + i * 4, relu4(ld4(x + i * 4)));
     }
 }
 
@@ -1049,11 +993,7 @@ extern "C" int mrcnn_bn_train_fwd_f32(const float *x, const float *gamma, const 
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0, "bn_train_fwd: need P>0, C%4==0")) return e;
     if (ws_bytes < mrcnn_bn_workspace_bytes(P, C)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const RedPlan r = red_plan(P, C);
-    hipLaunchKernelGGL(k_bn_stats_partial, dim3(r.nblk), dim3(NT), 0, st, x, P, C, r.G, r.RPI, r.rows_per_blk, (float *)ws);
-    MRCNN_LAUNCH_CHECK();
-    launch_stats_final(st, x, (const float *)ws, r.nblk, P, C, eps, decay, 1, save_mean, save_invstd, running_mean, running_var);
-    MRCNN_LAUNCH_CHECK();
+    if (int e = launch_bn_stats(st, x, nullptr, 0, P, C, eps, decay, ws, save_mean, save_invstd, running_mean, running_var)) return e;
     const size_t n4 = (size_t)P * C / 4;
     hipLaunchKernelGGL(k_bn_apply, dim3(ew_grid(n4)), dim3(NT), 0, st, x, gamma, beta, save_mean, save_invstd, residual, y,
                        n4, C / 4, relu);
@@ -1071,8 +1011,7 @@ extern "C" int mrcnn_bn_train_fwd_stats_f32(const float *x, const float *part, i
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0 && rows > 0, "bn_train_fwd_stats: need P>0, C%4==0, rows>0")) return e;
     hipStream_t st = (hipStream_t)stream;
     if (!(g_bn_debug_skip & 2))
-    launch_stats_final(st, x, part, rows, P, C, eps, decay, 0, save_mean, save_invstd, running_mean, running_var);
-    MRCNN_LAUNCH_CHECK();
+        if (int e = launch_bn_stats(st, x, part, rows, P, C, eps, decay, nullptr, save_mean, save_invstd, running_mean, running_var)) return e;
     const size_t n4 = (size_t)P * C / 4;
     hipLaunchKernelGGL(k_bn_apply, dim3(ew_grid(n4)), dim3(NT), 0, st, x, gamma, beta, save_mean, save_invstd, residual, y, n4, C / 4, relu);
     MRCNN_LAUNCH_CHECK();
@@ -1109,18 +1048,8 @@ extern "C" int mrcnn_bn_train_stats_f32(const float *x, const float *part, int r
                                         float *running_var, int P, int C, float eps, float decay, void *ws, size_t ws_bytes, void *stream) {
     if (int e = chk(x && save_mean && save_invstd, "bn_train_stats: null pointer")) return e;
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0 && rows >= 0 && (rows == 0) == (part == nullptr), "bn_train_stats: need P>0, C%4==0, part / rows together")) return e;
-    hipStream_t st = (hipStream_t)stream;
-    if (part) {
-        launch_stats_final(st, x, part, rows, P, C, eps, decay, 0, save_mean, save_invstd, running_mean, running_var);
-    } else {
-        if (!ws || ws_bytes < mrcnn_bn_workspace_bytes(P, C)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_stats: workspace too small");
-        const RedPlan r = red_plan(P, C);
-        hipLaunchKernelGGL(k_bn_stats_partial, dim3(r.nblk), dim3(NT), 0, st, x, P, C, r.G, r.RPI, r.rows_per_blk, (float *)ws);
-        MRCNN_LAUNCH_CHECK();
-        launch_stats_final(st, x, (const float *)ws, r.nblk, P, C, eps, decay, 1, save_mean, save_invstd, running_mean, running_var);
-    }
-    MRCNN_LAUNCH_CHECK();
-    return 0;
+    if (!part && (!ws || ws_bytes < mrcnn_bn_workspace_bytes(P, C))) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_stats: workspace too small");
+    return launch_bn_stats((hipStream_t)stream, x, part, rows, P, C, eps, decay, ws, save_mean, save_invstd, running_mean, running_var);
 }
 
 extern "C" size_t mrcnn_bn_pair_workspace_bytes(int P, int C) {
@@ -1142,19 +1071,8 @@ extern "C" int mrcnn_bn_train_fwd_pair_f32(const float *xa, const float *part_a,
     if ((!part_a || !part_b) && (!ws || ws_bytes < mrcnn_bn_workspace_bytes(P, C)))
         return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_fwd_pair: a statistics pass needs mrcnn_bn_workspace_bytes() of workspace");
     hipStream_t st = (hipStream_t)stream;
-    const RedPlan r = red_plan(P, C);
-    auto stats = [&](const float *x, const float *part, int rows, float *mean, float *invstd, float *rm, float *rv) {
-        if (part) {
-            launch_stats_final(st, x, part, rows, P, C, eps, decay, 0, mean, invstd, rm, rv);
-        } else {
-            hipLaunchKernelGGL(k_bn_stats_partial, dim3(r.nblk), dim3(NT), 0, st, x, P, C, r.G, r.RPI, r.rows_per_blk, (float *)ws);
-            launch_stats_final(st, x, (const float *)ws, r.nblk, P, C, eps, decay, 1, mean, invstd, rm, rv);
-        }
-    };
-    stats(xb, part_b, rows_b, mean_b, invstd_b, run_mean_b, run_var_b);
-    MRCNN_LAUNCH_CHECK();
-    stats(xa, part_a, rows_a, mean_a, invstd_a, run_mean_a, run_var_a);
-    MRCNN_LAUNCH_CHECK();
+    if (int e = launch_bn_stats(st, xb, part_b, rows_b, P, C, eps, decay, ws, mean_b, invstd_b, run_mean_b, run_var_b)) return e;
+    if (int e = launch_bn_stats(st, xa, part_a, rows_a, P, C, eps, decay, ws, mean_a, invstd_a, run_mean_a, run_var_a)) return e;
     const size_t n4 = (size_t)P * C / 4;
     hipLaunchKernelGGL(k_bn_apply2, dim3(ew_grid(n4)), dim3(NT), 0, st, xa, gamma_a, beta_a, mean_a, invstd_a, xb, gamma_b, beta_b, mean_b, invstd_b, y,
                        n4, C / 4);
@@ -1176,10 +1094,7 @@ extern "C" int mrcnn_bn_train_bwd_pair_f32(const float *gy, const float *y, cons
     hipLaunchKernelGGL(k_bn_bwd_partial2, dim3(r.nblk), dim3(NT), 0, st, gy, y, xa, xb, mean_a, invstd_a, mean_b, invstd_b, P, C, r.G, r.RPI,
                        r.rows_per_blk, (float *)ws);
     MRCNN_LAUNCH_CHECK();
-    if (g_fin_quads == 1)
-        hipLaunchKernelGGL(k_bn_bwd_final2<1>, dim3(mrcnn::cdiv(C, 4)), dim3(FIN_THREADS), 0, st, (const float *)ws, r.nblk, C, gbeta_a, ggamma_a, gbeta_b, ggamma_b);
-    else
-        hipLaunchKernelGGL(k_bn_bwd_final2<4>, dim3(mrcnn::cdiv(C, 16)), dim3(FIN_THREADS), 0, st, (const float *)ws, r.nblk, C, gbeta_a, ggamma_a, gbeta_b, ggamma_b);
+    launch_bwd_final2(st, (const float *)ws, r.nblk, C, gbeta_a, ggamma_a, gbeta_b, ggamma_b);
     MRCNN_LAUNCH_CHECK();
     const size_t n4 = (size_t)P * C / 4;
     hipLaunchKernelGGL(k_bn_bwd_apply2, dim3(ew_grid(n4)), dim3(NT), 0, st, gy, y, xa, xb, gamma_a, mean_a, invstd_a, gbeta_a, ggamma_a, gamma_b, mean_b,

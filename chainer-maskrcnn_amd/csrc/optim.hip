@@ -26,9 +26,6 @@ constexpr int NORM_BLOCKS = 256 * 16;   // the most partial sums a norm leaves: 
 constexpr int HYPER_LR = MRCNN_HYPER_LR, HYPER_A = MRCNN_HYPER_A, HYPER_THRESHOLD = MRCNN_HYPER_THRESHOLD, HYPER_SCALE = MRCNN_HYPER_SCALE,
               HYPER_NORM = MRCNN_HYPER_NORM, HYPER_RATE = MRCNN_HYPER_RATE, HYPER_SKIPPED = MRCNN_HYPER_SKIPPED;
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-
 inline int ew_grid(size_t n4) { return (int)std::min<size_t>((n4 + NT - 1) / NT, 256 * 16); }
 inline int norm_grid(size_t n) { return (int)std::min<size_t>((std::max<size_t>(n / 4, 1) + NT - 1) / NT, NORM_BLOCKS); }
 

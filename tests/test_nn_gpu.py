@@ -17,7 +17,9 @@ def _rel(got, ref):
     return (got.double().cpu() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-6)
 
 
-@pytest.mark.parametrize('shape', [(2, 9, 7, 64), (1, 5, 6, 256), (2, 3, 3, 2048), (1, 31, 17, 8), (3, 40, 40, 128)])
+# (1, 129, 128, 256): 1,056,768 float4 groups, the first size with C = 256 and W = 128 above the 4096 * 256 groups one pass of the
+# element-wise kernels' grid covers - their grid-stride loops run a second iteration
+@pytest.mark.parametrize('shape', [(2, 9, 7, 64), (1, 5, 6, 256), (2, 3, 3, 2048), (1, 31, 17, 8), (3, 40, 40, 128), (1, 129, 128, 256)])
 @pytest.mark.parametrize('relu,res', [(False, False), (True, False), (True, True)])
 def test_bn_train_fwd_bwd(shape, relu, res):
     g = torch.Generator().manual_seed(sum(shape))
@@ -306,7 +308,8 @@ def test_composite_bottleneck_equals_the_per_layer_path(case, flags):
     assert float(out[0][2].abs().max()) > 0 and float(out[0][1].abs().max()) > 0
 
 
-@pytest.mark.parametrize('P,C', [(4096, 64), (2 * 33 * 41, 256), (2048, 2048)])
+# (2064, 2048): 1,056,768 float4 groups - the grid-stride loops of k_bn_apply2 / k_bn_bwd_apply2 wrap ((2048, 2048) is exactly one pass)
+@pytest.mark.parametrize('P,C', [(4096, 64), (2 * 33 * 41, 256), (2048, 2048), (2064, 2048)])
 @pytest.mark.parametrize('masked', [False, True], ids=['mask_from_y', 'gy_arrives_masked'])
 def test_bn_pair_kernels_equal_the_layer_by_layer_sequence(P, C, masked):
     """(ABI v10) relu(BN_a(xa) + BN_b(xb)) in one apply kernel and both backward passes from one read of gy (nn.hip k_bn_apply2,
