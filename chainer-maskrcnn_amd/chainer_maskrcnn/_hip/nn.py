@@ -94,6 +94,21 @@ def conv_out(n, k, s, p):
     return (n + 2 * p - k) // s + 1
 
 
+CONV_PLAN_FIELDS = ('path', 'bm', 'bn', 'ksplit', 'tail_ks', 'wino_m', 'smallc', 'arithmetic', 'plane_gemm')
+CONV_PATHS = ('direct', 'split_k', 'tail_split', 'winograd')       # values of 'path'
+
+
+def conv_plan(pass_, x_shape, w_shape, stride, pad):
+    """What the entry point of pass_ (0 forward, 1 backward-data, 2 backward-filter) would launch for this layer under the settings in
+    force (mrcnn_conv2d_plan_query: read-only, no launch): a dict of CONV_PLAN_FIELDS.  Raises where the entry point would decline."""
+    import ctypes
+    N, H, W, Cin = x_shape
+    Cout, KH, KW, _ = w_shape
+    out = (ctypes.c_int * len(CONV_PLAN_FIELDS))()
+    check(lib().mrcnn_conv2d_plan_query(int(pass_), N, H, W, Cin, Cout, KH, KW, stride, pad, out, len(CONV_PLAN_FIELDS)))
+    return dict(zip(CONV_PLAN_FIELDS, out))
+
+
 def conv2d_fwd_raw(x, w, b, stride, pad, relu, keep_v=False):
     """keep_v: returns (y, v) - v = the Winograd-transformed input of layers that take that path (else None), for the
     filter-gradient call of the same layer (conv2d_bwd_filter_raw(..., wino_v=v))."""

@@ -895,10 +895,19 @@ int g_debug_skip = 0;
 int g_split_mode[3] = {0, 0, 0};        // per pass (forward, backward-data, backward-filter): 0 float32, 1 bf16 planes, 2 half planes
 thread_local int g_cur_pass = 0;        // set by the entry points around their launches (PASS_*)
 
+// The tile and the operand arithmetic launch_conv really uses for a planned tile (also read by mrcnn_conv2d_plan_query): the image
+// layer has fixed tiles and only float32-MFMA instantiations, whatever split mode is set.
+template <int MODE>
+TileChoice launch_tile(const ConvP &p, TileChoice t) {
+    if (p.smallc) return (MODE == MODE_FWD) ? TileChoice{128, 64} : TileChoice{64, 128};
+    return t;
+}
+int launch_arithmetic(const ConvP &p, int pass) { return p.smallc ? 0 : g_split_mode[pass]; }
+
 template <int MODE>
 void launch_conv(ConvP &p, int zdim, TileChoice t, hipStream_t st) {
     // zdim: BWD_FILTER taps * ksplit; FWD / BWD_DATA ksplit
-    if (p.smallc) t = (MODE == MODE_FWD) ? TileChoice{128, 64} : TileChoice{64, 128};   // image layer: fixed tiles
+    t = launch_tile<MODE>(p, t);
     p.tiles_m = mrcnn::cdiv(p.M, t.bm);
     p.tiles_n = mrcnn::cdiv(p.Ng, t.bn);
     const int tiles = p.tiles_m * p.tiles_n;
@@ -917,7 +926,7 @@ void launch_conv(ConvP &p, int zdim, TileChoice t, hipStream_t st) {
         return;
     }
     {   // exploratory opt-in: three-term split operands; the planes' type per PASS of the calling entry point
-        const int split = g_split_mode[g_cur_pass];
+        const int split = launch_arithmetic(p, g_cur_pass);
         // (Sending the emulated launches with 64 x 64 / 128 x 64 / 64 x 128 tiles - MFMA-busy 0.12 - 0.24 - to the float32-MFMA kernel was
         // measured in round 5, same-process A/B on the step: 21.72 ms emulated everywhere against 21.84 - 21.91 ms with any subset on float32.)
         if (split == 1) {
@@ -1130,6 +1139,17 @@ ConvP make_p(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
     return p;
 }
 
+// GEMM view of the direct launches (entry points and mrcnn_conv2d_plan_query): rows M, columns Ng; the data passes return their K steps.
+int fwd_gemm(ConvP &p) {
+    p.M = p.N * p.Ho * p.Wo; p.Ng = p.Cout;
+    return p.smallc ? (p.KH * p.KW + 7) / 8 : p.KH * p.KW * (p.Cin / BK);
+}
+int bwd_data_gemm(ConvP &p) {
+    p.M = p.N * p.H * p.W; p.Ng = p.Cin;
+    return p.KH * p.KW * (p.Cout / BK);
+}
+void bwd_filter_gemm(ConvP &p) { p.M = p.Cout; p.Ng = p.smallc ? p.KH * p.KW * 4 : p.Cin; }
+
 // split-K plan for backward-filter: enough workgroups to fill 256 CUs a few times over.
 TileChoice filter_tile(const ConvP &p) {
     TileChoice t;
@@ -1190,18 +1210,20 @@ size_t tail_ws_bytes(const ConvP &p, const TileChoice &t) {
     return p.tail_ks ? (size_t)(tiles - p.tail_full) * p.tail_ks * t.bm * t.bn * sizeof(float) : 0;
 }
 
+// data_plan as the workspace at hand allows it (also read by mrcnn_conv2d_plan_query)
 template <int MODE>
-int run_data_conv(ConvP &p, int nsteps, long long ldc, void *ws, size_t ws_bytes, hipStream_t st) {
+TileChoice data_launch_plan(ConvP &p, int nsteps, long long ldc, bool have_ws, size_t ws_bytes) {
     TileChoice t;
     data_plan<MODE>(p, t, nsteps);
-    if (p.ksplit > 1) {
-        if (!ws || ws_bytes < data_ws_bytes(p, ldc)) { p.ksplit = 1; p.kchunk = nsteps; }      // no workspace: unsplit
-        else p.slab = (float *)ws;
-    }
-    if (p.tail_ks) {
-        if (!ws || ws_bytes < tail_ws_bytes(p, t)) p.tail_ks = 0;                              // no workspace: no tail split
-        else p.slab = (float *)ws;
-    }
+    if (p.ksplit > 1 && (!have_ws || ws_bytes < data_ws_bytes(p, ldc))) { p.ksplit = 1; p.kchunk = nsteps; }      // no workspace: unsplit
+    if (p.tail_ks && (!have_ws || ws_bytes < tail_ws_bytes(p, t))) p.tail_ks = 0;                                 // no workspace: no tail split
+    return t;
+}
+
+template <int MODE>
+int run_data_conv(ConvP &p, int nsteps, long long ldc, void *ws, size_t ws_bytes, hipStream_t st) {
+    const TileChoice t = data_launch_plan<MODE>(p, nsteps, ldc, ws != nullptr, ws_bytes);
+    if (p.ksplit > 1 || p.tail_ks) p.slab = (float *)ws;
     launch_conv<MODE>(p, p.ksplit, t, st);
     MRCNN_LAUNCH_CHECK();
     if (p.tail_ks) {
@@ -1903,11 +1925,17 @@ bool pg_big_g_ok(const WinoGeom &g, int Cin, int Cout) {
 // ksplit / kchunk: the split-K plan of the launch the layer takes by default (the plane GEMM when `big`); ks32 / kc32: the plan tuned for
 // k_conv_igemm's 128 x 128 tiles, taken when the call arrives with a cached float32 W (WINOGRAD_SHARED_GY_TRANSFORM) - ADVICE r4
 struct WinoFLayout { size_t v, w, slabs, du, total; WinoGeom g; int ksplit, kchunk; int big; int ks32, kc32; };
+// the batched filter-gradient GEMM of the Winograd path as k_conv_igemm sees it: a 1x1 layer over Tp "pixels" per transform point
+ConvP wino_filter_p(const WinoGeom &g, int Cin, int Cout) {
+    ConvP p = make_p(1, 1, (int)g.Tp, Cin, Cout, 1, 1, 1, 0);
+    p.wbatch_rows = (int)g.Tp; p.wbatch_n = g.nk;
+    bwd_filter_gemm(p);
+    return p;
+}
 WinoFLayout wino_filter_layout(int N, int H, int W, int Cin, int Cout) {
     WinoFLayout L;
     L.g = wino_geom(N, H, W, PASS_BWD_FILTER);
-    ConvP p = make_p(1, 1, (int)L.g.Tp, Cin, Cout, 1, 1, 1, 0);
-    p.wbatch_rows = (int)L.g.Tp; p.wbatch_n = L.g.nk;
+    ConvP p = wino_filter_p(L.g, Cin, Cout);
     filter_plan(p, L.ksplit, L.kchunk);
     L.ks32 = L.ksplit; L.kc32 = L.kchunk;
     L.big = pg_big_g_ok(L.g, Cin, Cout) ? 1 : 0;
@@ -1967,12 +1995,10 @@ int wino_bwd_filter(const float *x, const float *gy, float *gw, int N, int H, in
         WINO_LAUNCH(k_wino_filter_grad, g, dim3(mrcnn::cdiv(Cout * Cin, 256)), dU, gw, Cout, Cin, accumulate, 1);
         return 0;
     }
-    ConvP p = make_p(1, 1, (int)g.Tp, Cin, Cout, 1, 1, 1, 0);
-    p.wbatch_rows = (int)g.Tp; p.wbatch_n = g.nk;
+    ConvP p = wino_filter_p(g, Cin, Cout);
     p.ksplit = L.ks32; p.kchunk = L.kc32;
     p.a = w_cached ? w_cached : Wt; p.b = V; p.c = p.ksplit > 1 ? slabs : dU;
     p.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cout * 4); p.bytes_b = (unsigned)((size_t)g.nk * g.Tp * Cin * 4);
-    p.M = Cout; p.Ng = Cin;
     launch_conv<MODE_BWD_FILTER>(p, g.nk * p.ksplit, filter_tile(p), st);
     MRCNN_LAUNCH_CHECK();
     if (p.ksplit > 1) {     // a separate, fully parallel slab sum: folding it into k_wino_filter_grad (Cout*Cin threads only) was
@@ -1997,6 +2023,15 @@ bool pg_big_ok(int pass, const WinoGeom &g, int K, int Nn) {
     const long long rounds = (tiles + g_cus() - 1) / g_cus();
     if (tiles * 10 < rounds * g_cus() * 8) return false;
     return tiles >= g_pg_min_tiles && (long long)g.nk * g.Tp * K * 4 < (1ll << 32) && (long long)g.nk * Nn * K * 6 < (1ll << 32);
+}
+
+// the batched GEMM of the Winograd forward / backward-data path as k_conv_igemm sees it: a 1x1 "convolution" over nk*Tp pixels, weight
+// matrix selected by the row block; returns its K steps
+int wino_gemm_p(ConvP &p, const WinoGeom &g, int Cin, int Cout) {
+    p = make_p(1, 1, (int)(g.nk * g.Tp), Cin, Cout, 1, 1, 1, 0);
+    p.M = (int)(g.nk * g.Tp); p.Ng = Cout;
+    p.wbatch_rows = (int)g.Tp; p.wbatch_n = g.nk;
+    return Cin / BK;
 }
 
 // in (N,H,W,Cin) -> out (N,H,W,Cout); w is always the layer's (Cout_layer,3,3,Cin_layer) weight tensor: transposed selects
@@ -2046,15 +2081,30 @@ int wino_conv(const float *in, const float *w, float *out, int N, int H, int W, 
                     accumulate, relu_x, bn_part);
         return 0;
     }
-    // batched GEMM: 1x1 "convolution" over nk*Tp pixels, weight matrix selected by the row block
-    ConvP p = make_p(1, 1, (int)(g.nk * g.Tp), Cin, Cout, 1, 1, 1, 0);
+    ConvP p;
+    const int nsteps = wino_gemm_p(p, g, Cin, Cout);
     p.a = V; p.b = U; p.c = Mb;
     p.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cin * 4); p.bytes_b = (unsigned)((size_t)g.nk * Cout * Cin * 4);
-    p.M = (int)(g.nk * g.Tp); p.Ng = Cout;
-    p.wbatch_rows = (int)g.Tp; p.wbatch_n = g.nk;
-    if (int e = run_data_conv<MODE_FWD>(p, Cin / BK, Cout, base + L.inner, ws_bytes - L.inner, st)) return e;
+    if (int e = run_data_conv<MODE_FWD>(p, nsteps, Cout, base + L.inner, ws_bytes - L.inner, st)) return e;
     WINO_LAUNCH_OUT(g, dim3((unsigned)((nout + 255) / 256)), Mb, out, N, H, W, Cout, g.th, g.tw, g.T, g.Tp, bias, relu,
                 accumulate, relu_x, bn_part);
+    return 0;
+}
+
+// Whether the forward / backward-data entry point takes the Winograd path with this workspace (entry points and
+// mrcnn_conv2d_plan_query).  Cin / Cout are the LAYER's: backward-data runs the pipeline from Cout to Cin channels.
+bool fwd_takes_wino(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool have_ws, size_t ws_bytes) {
+    return wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD) && have_ws && ws_bytes >= wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD);
+}
+bool bwd_data_takes_wino(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool have_ws, size_t ws_bytes) {
+    return wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, PASS_BWD_DATA) && have_ws && ws_bytes >= wino_ws_bytes(N, H, W, Cout, Cin, PASS_BWD_DATA);
+}
+// what the backward-data entry point declines after check_conv
+int check_bwd_data(int Cin, int stride) {
+    if (stride != 1)
+        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: stride %d (only 1; strided 1x1 convs are "
+                                                    "handled by the host as a subsample + stride-1 conv)", stride);
+    if (Cin == 4) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: Cin == 4 (image layer) has no data gradient");
     return 0;
 }
 
@@ -2213,6 +2263,68 @@ extern "C" long long mrcnn_conv2d_executed_macs(int N, int H, int W, int Cin, in
     return (long long)N * Ho * Wo * KH * KW * (Cin == 4 ? 4 : Cin) * Cout;
 }
 
+extern "C" int mrcnn_conv2d_plan_query(int pass, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int *out, int n_out) {
+    // what the entry point of `pass` would launch for this geometry under the settings in force, with the workspace its size query asks
+    // for: every decision below is made by the function the entry point itself calls; nothing is launched, no setting is touched
+    enum { F_PATH, F_BM, F_BN, F_KSPLIT, F_TAIL_KS, F_WINO_M, F_SMALLC, F_ARITH, F_PLANE_GEMM, F_COUNT };
+    if (!out || n_out < F_COUNT) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d_plan_query: out must hold %d ints", (int)F_COUNT);
+    if (pass < PASS_FWD || pass > PASS_BWD_FILTER) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d_plan_query: pass %d (0 forward, 1 backward-data, 2 backward-filter)", pass);
+    if (int e = check_conv(out, out, out, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
+    if (pass == PASS_BWD_DATA) if (int e = check_bwd_data(Cin, stride)) return e;
+    for (int i = 0; i < F_COUNT; ++i) out[i] = 0;
+    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
+    TileChoice t{0, 0};
+    auto data_fields = [&](const ConvP &q) {       // a forward-kind launch planned by data_launch_plan
+        out[F_PATH] = q.tail_ks ? 2 : q.ksplit > 1 ? 1 : 0;
+        out[F_KSPLIT] = q.ksplit; out[F_TAIL_KS] = q.tail_ks;
+    };
+    if (pass == PASS_BWD_FILTER) {
+        if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_BWD_FILTER)) {
+            const WinoFLayout L = wino_filter_layout(N, H, W, Cin, Cout);        // (no cached transform of gy: the call as the wrappers make it)
+            p = wino_filter_p(L.g, Cin, Cout);
+            out[F_PATH] = 3; out[F_WINO_M] = L.g.m; out[F_PLANE_GEMM] = L.big;
+            out[F_KSPLIT] = L.big ? L.ksplit : L.ks32;
+            t = L.big ? TileChoice{PGB_BM, PGB_BN} : launch_tile<MODE_BWD_FILTER>(p, filter_tile(p));
+        } else {
+            filter_plan(p, p.ksplit, p.kchunk);
+            bwd_filter_gemm(p);
+            t = launch_tile<MODE_BWD_FILTER>(p, filter_tile(p));
+            out[F_PATH] = p.ksplit > 1 ? 1 : 0; out[F_KSPLIT] = p.ksplit;
+        }
+    } else {
+        const bool fwd = pass == PASS_FWD;
+        const size_t ws_bytes = mrcnn_conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad);
+        const bool have_ws = ws_bytes > 0;
+        const bool wino = fwd ? fwd_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, have_ws, ws_bytes)
+                              : bwd_data_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, have_ws, ws_bytes);
+        if (wino) {
+            const int ci = fwd ? Cin : Cout, co = fwd ? Cout : Cin;              // the pipeline's channels (wino_conv's Cin, Cout)
+            const WinoLayout L = wino_layout(N, H, W, ci, co, pass);
+            out[F_PATH] = 3; out[F_WINO_M] = L.g.m;
+            if (pg_big_ok(pass, L.g, ci, co)) {
+                out[F_PLANE_GEMM] = 1; out[F_KSPLIT] = 1;
+                t = TileChoice{PGB_BM, PGB_BN};
+            } else {
+                const int nsteps = wino_gemm_p(p, L.g, ci, co);
+                t = launch_tile<MODE_FWD>(p, data_launch_plan<MODE_FWD>(p, nsteps, co, true, ws_bytes - L.inner));
+                out[F_KSPLIT] = p.ksplit; out[F_TAIL_KS] = p.tail_ks;
+            }
+        } else if (fwd) {
+            const int nsteps = fwd_gemm(p);
+            t = launch_tile<MODE_FWD>(p, data_launch_plan<MODE_FWD>(p, nsteps, Cout, have_ws, ws_bytes));
+            data_fields(p);
+        } else {
+            const int nsteps = bwd_data_gemm(p);
+            t = launch_tile<MODE_BWD_DATA>(p, data_launch_plan<MODE_BWD_DATA>(p, nsteps, Cin, have_ws, ws_bytes));
+            data_fields(p);
+        }
+    }
+    out[F_BM] = t.bm; out[F_BN] = t.bn;
+    out[F_SMALLC] = p.smallc ? 1 : 0;
+    out[F_ARITH] = launch_arithmetic(p, pass);
+    return 0;
+}
+
 extern "C" size_t mrcnn_conv2d_winograd_v_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return 0;
     if (!wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD)) return 0;
@@ -2225,13 +2337,12 @@ extern "C" int mrcnn_conv2d_fwd_f32(const float *x, const float *w, const float 
                                     float *wino_v, void *ws, size_t ws_bytes, void *stream) {
     g_cur_pass = 0;
     if (int e = check_conv(x, w, y, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD) && ws && ws_bytes >= wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD))
+    if (fwd_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, ws != nullptr, ws_bytes))
         return wino_conv(x, w, y, N, H, W, Cin, Cout, false, bias, relu, 0, nullptr, ws, ws_bytes, (hipStream_t)stream, wino_v);
     ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
     p.a = x; p.b = w; p.c = y; p.bias = bias; p.relu = relu;
     p.bytes_a = (unsigned)((size_t)N * H * W * Cin * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
-    p.M = N * p.Ho * p.Wo; p.Ng = Cout;
-    const int nsteps = p.smallc ? (KH * KW + 7) / 8 : KH * KW * (Cin / BK);
+    const int nsteps = fwd_gemm(p);
     return run_data_conv<MODE_FWD>(p, nsteps, Cout, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -2348,21 +2459,18 @@ extern "C" int mrcnn_conv2d_bwd_data_f32(const float *gy, const float *w, float 
                                          size_t ws_bytes, void *stream) {
     g_cur_pass = 1;
     if (int e = check_conv(gy, w, gx, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    if (stride != 1)
-        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: stride %d (only 1; strided 1x1 convs are "
-                                                    "handled by the host as a subsample + stride-1 conv)", stride);
+    if (int e = check_bwd_data(Cin, stride)) return e;
     ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
-    if (Cin == 4) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: Cin == 4 (image layer) has no data gradient");
     // relu_x with accumulate: every path (direct epilogue, split-K / tail-split sums, Winograd output transform) adds the old value
     // first and masks the TOTAL - the ReLU backward of the tensor gx is the gradient of, applied where its last contribution lands
-    if (wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, PASS_BWD_DATA) && ws && ws_bytes >= wino_ws_bytes(N, H, W, Cout, Cin, PASS_BWD_DATA))
+    if (bwd_data_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, ws != nullptr, ws_bytes))
         return wino_conv(gy, w, gx, N, H, W, Cout, Cin, true, nullptr, 0, accumulate, relu_x, ws, ws_bytes, (hipStream_t)stream, nullptr,
                          wino_w, wino_w ? gbias : nullptr, gbias_accumulate);
     if (wino_w || gbias) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: wino_w / gbias only on the Winograd path (mrcnn_conv2d_winograd_w_bytes() > 0)");
     p.a = gy; p.b = w; p.c = gx; p.accumulate = accumulate; p.relu_x = relu_x;
     p.bytes_a = (unsigned)((size_t)N * p.Ho * p.Wo * Cout * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
-    p.M = N * H * W; p.Ng = Cin;
-    return run_data_conv<MODE_BWD_DATA>(p, KH * KW * (Cout / BK), Cin, ws, ws_bytes, (hipStream_t)stream);
+    const int nsteps = bwd_data_gemm(p);
+    return run_data_conv<MODE_BWD_DATA>(p, nsteps, Cin, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" size_t mrcnn_conv2d_bwd_filter_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW,
@@ -2424,7 +2532,7 @@ extern "C" int mrcnn_conv2d_bwd_filter_f32(const float *x, const float *gy, floa
     const bool use_slabs = p.ksplit > 1 || accumulate;
     p.a = gy; p.b = x; p.c = use_slabs ? slabs : gw;
     p.bytes_a = (unsigned)((size_t)N * p.Ho * p.Wo * Cout * 4); p.bytes_b = (unsigned)((size_t)N * H * W * Cin * 4);
-    p.M = Cout; p.Ng = p.smallc ? KH * KW * 4 : Cin;
+    bwd_filter_gemm(p);
     launch_conv<MODE_BWD_FILTER>(p, (p.smallc ? 1 : KH * KW) * p.ksplit, filter_tile(p), st);
     MRCNN_LAUNCH_CHECK();
     if (use_slabs) {

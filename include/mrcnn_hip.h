@@ -235,6 +235,20 @@ int mrcnn_conv2d_get_winograd_pass_tiles(int *tiles3);
 int mrcnn_conv2d_set_split_operands(int fwd, int bwd_data, int bwd_filter);
 /* The three modes in force (forward, backward-data, backward-filter), for callers that bracket a call with their own setting. */
 int mrcnn_conv2d_get_split_operands(int *modes3);
+/* Read-only plan query (tests, measurement): what the entry point of `pass` (0 forward, 1 backward-data, 2 backward-filter) would launch for
+ * this geometry under the settings in force, given the workspace its size query asks for.  Computed by the dispatcher's own functions;
+ * launches nothing, changes no setting.  Writes MRCNN_CONV_PLAN_FIELDS ints to out (n_out >= that):
+ *   [0] path        0 un-split direct, 1 split-K, 2 tail split, 3 Winograd
+ *   [1] bm, [2] bn  tile of the GEMM launch (256 x 256: the persistent plane GEMM)
+ *   [3] ksplit      split count over K of that launch (backward-filter: the filter plan's)
+ *   [4] tail_ks     tail-split factor (0 = none)
+ *   [5] wino_m      0, 2 or 4
+ *   [6] smallc      1 for the 4-channel image layer
+ *   [7] arithmetic  the operand mode the launch really uses: 0 for the image layer whatever is set, else the pass's split mode
+ *   [8] plane_gemm  1 when the batched Winograd GEMM goes to the persistent plane-GEMM kernels
+ * Geometries the entry point declines (backward-data with stride > 1 or on the image layer, unpadded channels) return its error code. */
+#define MRCNN_CONV_PLAN_FIELDS 9
+int mrcnn_conv2d_plan_query(int pass, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int *out, int n_out);
 /* Measurement knob (tools/gemm_only_profile.py): workgroups per CU the tile choice and the forward / backward-data split-K plan aim
  * for (default 2), the HALF rounds of workgroup slots the filter-gradient split-K fills (default 2 = one round), and a forced forward /
  * backward-data tile (0 = the planner's choice, 1 = 128x64, 2 = 64x64). */

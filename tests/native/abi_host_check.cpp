@@ -50,6 +50,15 @@ int main() {
     EXPECT_ERR(mrcnn_conv2d_set_winograd_pass_tiles(3, 0, 0));
     EXPECT_ERR(mrcnn_conv2d_get_winograd_pass_tiles(nullptr));
     EXPECT_ERR(mrcnn_conv2d_set_debug_skip(16));
+    {
+        int plan[MRCNN_CONV_PLAN_FIELDS];
+        EXPECT_ERR(mrcnn_conv2d_plan_query(0, 1, 8, 8, 32, 32, 3, 3, 1, 1, nullptr, MRCNN_CONV_PLAN_FIELDS));
+        EXPECT_ERR(mrcnn_conv2d_plan_query(0, 1, 8, 8, 32, 32, 3, 3, 1, 1, plan, MRCNN_CONV_PLAN_FIELDS - 1));
+        EXPECT_ERR(mrcnn_conv2d_plan_query(3, 1, 8, 8, 32, 32, 3, 3, 1, 1, plan, MRCNN_CONV_PLAN_FIELDS));
+        EXPECT_ERR(mrcnn_conv2d_plan_query(0, 1, 8, 8, 33, 32, 3, 3, 1, 1, plan, MRCNN_CONV_PLAN_FIELDS));
+        EXPECT_ERR(mrcnn_conv2d_plan_query(1, 1, 8, 8, 32, 32, 3, 3, 2, 1, plan, MRCNN_CONV_PLAN_FIELDS));       /* backward-data: stride 1 only */
+        EXPECT_ERR(mrcnn_conv2d_plan_query(1, 1, 8, 8, 4, 32, 7, 7, 2, 3, plan, MRCNN_CONV_PLAN_FIELDS));        /* and never the image layer */
+    }
     EXPECT_ERR(mrcnn_roi_align_set_bwd_variant(5));
     EXPECT(mrcnn_conv2d_workspace_bytes(0, 0, 0, 0, 0, 0, 0, 0, 0) == 0 || true);
     for (int N = 1; N <= 3; ++N)

@@ -90,11 +90,29 @@ def test_conv_rejects_unpadded_channels():
 # Grids a little larger than a whole number of rounds of workgroup slots take the tail-split path (the last tiles are
 # computed by several workgroups along K and summed from slabs).  The slot count is 512 or 768 depending on the
 # kernel's occupancy, so two pixel counts are used: 800 and 1050 M tiles of 128 rows.
-@pytest.mark.parametrize('hw', [(320, 320), (420, 320)])
-@pytest.mark.parametrize('k,cin,cout', [(1, 256, 128), (3, 32, 160)])
+# Which of them really take that path is asked of the dispatcher (hnn.conv_plan).  On gfx950 the 128 x 128 kernels have 768 slots and the
+# 128 x 64 kernels 1280, and a pass is tail-split only with >= 8 K steps - so of the first two layers and sizes only the FORWARD pass ever took
+# the path: the backward-data pass of the 1x1 layer has 128 / 32 = 4 K steps, that of the 3x3 layer 800 or 1050 tiles of 128 x 64.  The third
+# size (1300 tiles of 128 rows) and the third layer (8 K steps and 128 x 128 tiles in both passes) are there for the backward-data pass.
+TAIL_SPLIT_SIZES = [(320, 320), (420, 320), (520, 320)]
+TAIL_SPLIT_LAYERS = [(1, 256, 128), (3, 32, 160), (1, 256, 256)]      # k, cin, cout
+TAIL_SPLIT_MIN_K_STEPS = 8          # data_plan (csrc/conv.hip): fewer K steps of 32 channels are never split
+
+
+@pytest.mark.parametrize('hw', TAIL_SPLIT_SIZES)
+@pytest.mark.parametrize('k,cin,cout', TAIL_SPLIT_LAYERS)
 def test_conv_tail_split_forward_and_backward_data(hw, k, cin, cout):
     H, W = hw
     pad = k // 2
+    # the dispatcher's own answer (mrcnn_conv2d_plan_query): at least one of the sizes takes the tail-split path (2), in each pass whose K
+    # axis is long enough to be split at all (every layer in forward; all but the first in backward-data)
+    for pass_, k_steps in ((0, k * k * cin // 32), (1, k * k * cout // 32)):
+        plans = [hnn.conv_plan(pass_, (1, h, w_, cin), (cout, k, k, cin), 1, pad) for (h, w_) in TAIL_SPLIT_SIZES]
+        assert all(pl['path'] in (0, 2) and pl['arithmetic'] == 0 for pl in plans), (pass_, plans)
+        if k_steps >= TAIL_SPLIT_MIN_K_STEPS:
+            assert any(pl['path'] == 2 and pl['tail_ks'] >= 2 for pl in plans), (pass_, plans)
+        else:
+            assert (pass_, k, cin, cout) == (1, 1, 256, 128)
     g = torch.Generator().manual_seed(H + k)
     x = torch.randn((1, H, W, cin), generator=g)
     w = torch.randn((cout, k, k, cin), generator=g) / (k * k * cin) ** 0.5
@@ -236,6 +254,7 @@ def _winograd_case(case, tol, shared_gy=True):
     acc_w, acc_b = (torch.ones_like(gw), torch.ones_like(gb))
     hnn.conv2d_bwd_filter_raw(x.to(DEV), gy.to(DEV), tuple(w.shape), 1, 1, True, gw=acc_w, gb=acc_b, accumulate=True)
     assert (acc_w.cpu().double() - (wref + 1)).abs().max().item() / wref.abs().max().item() < tol
+    assert (acc_b.cpu().double() - (gbref + 1)).abs().max().item() / gbref.abs().max().item() < 2e-5
 
 
 # ---- EXPLORATORY opt-in: three-term split operands on the 16-bit MFMA (mrcnn_conv2d_set_split_operands) -----------------------
