@@ -407,3 +407,21 @@ def test_convolution_with_batchnorm_relu_on_load_equals_the_materialised_sequenc
             assert torch.equal(gw, gw_ref)
     finally:
         check(lib.mrcnn_conv2d_set_split_operands(*keep))
+
+
+@pytest.mark.parametrize('seed', [0, 12345, 2 ** 63 - 1])
+@pytest.mark.parametrize('n', [1, 257, 1048577])
+def test_random_keys_dev_is_splitmix64_and_advances_its_state(n, seed):
+    """Draw k = 0, 1, 2 from one device seed state is the splitmix64 stream of (seed + k * 0xD1B54A32D192ED03) mod 2^64 - what
+    ops.random_keys gives for that seed - and the state holds the advanced value afterwards; 1048577 keys wrap the grid-stride loop, the
+    seed 2^63 - 1 wraps the advance (the int64 state is read back modulo 2^64)."""
+    from tests import loss_reference as ref
+    dev = torch.device(DEV)
+    state = ops.seed_state(seed, dev)
+    assert state.item() == seed
+    for k in range(3):
+        s = (seed + k * ref.SEED_ADVANCE) % 2 ** 64
+        got = ops.random_keys_dev((n,), state).cpu().numpy().view(np.uint32)
+        np.testing.assert_array_equal(got, ref.splitmix_keys(s, n))
+        np.testing.assert_array_equal(got, ops.random_keys((n,), s, dev).cpu().numpy().view(np.uint32))
+    assert state.item() % 2 ** 64 == (seed + 3 * ref.SEED_ADVANCE) % 2 ** 64

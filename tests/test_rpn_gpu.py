@@ -206,3 +206,103 @@ def test_pack_unpack_roundtrip():
     gh = ops.rpn_unpack_grad(locs, scores, (N, H, W, Cp), A, 11).cpu().numpy()
     np.testing.assert_array_equal(gh[..., :18], head[..., :18])
     assert np.all(gh[..., 18:] == 0)
+
+
+# ---- the one-launch pack / unpack of all pyramid levels (what the training step launches) and softmax2 -------------------------------
+def _levels_reference(heads, A):
+    """The NumPy statement of test_pack_unpack_roundtrip per level, concatenated over the levels (level order = anchor order)."""
+    N = heads[0].shape[0]
+    locs = np.concatenate([h[..., :4 * A].reshape(N, -1, 4) for h in heads], 1)
+    scores = np.concatenate([h[..., 4 * A:6 * A].reshape(N, -1, 2) for h in heads], 1)
+    return locs, scores
+
+
+# L = 1, 5 and 8 (the most the launch takes) levels, a last level of one position, N = 1 and 2, channel counts that are padded
+# (6A < Cp) and exactly full (Cp = 12 = 6A); the last case has N x positions x A = 1,053,366 items for the pack and N x positions x Cp / 2 =
+# 3,511,220 for the unpack, both above the 4096 blocks x 256 threads of one pass of their launches: the grid-stride loops wrap
+LEVEL_CASES = [(2, 3, 32, [(8, 10), (4, 5), (2, 3), (1, 2), (1, 1)]),
+               (1, 3, 20, [(5, 7)]),
+               (2, 2, 12, [(9, 7), (5, 4), (3, 3), (2, 2), (2, 1), (1, 3), (1, 2), (1, 1)]),
+               (1, 1, 8, [(6, 5), (3, 3), (2, 1), (1, 1), (1, 1)]),
+               (1, 1, 8, [(1, 1)]),
+               (2, 3, 20, [(418, 420), (1, 1)])]
+
+
+@pytest.mark.parametrize('N,A,Cp,shapes', LEVEL_CASES, ids=['N%d-A%d-Cp%d-L%d' % (n, a, c, len(s)) for n, a, c, s in LEVEL_CASES])
+def test_pack_levels_and_unpack_grad_levels_bit_exact(N, A, Cp, shapes):
+    import ctypes
+    from chainer_maskrcnn._hip import check, lib, ptr, stream_ptr
+    rs = np.random.RandomState(N + A + Cp + len(shapes))
+    heads = [rs.standard_normal((N, h, w, Cp)).astype(np.float32) for h, w in shapes]
+    L, offs = len(shapes), np.cumsum([0] + [h * w * A for h, w in shapes])
+    Atot = int(offs[-1])
+    want_l, want_s = _levels_reference(heads, A)
+    hd = [torch.from_numpy(h).to(DEV) for h in heads]
+    nan = float('nan')
+    locs, scores = torch.full((N, Atot, 4), nan, device=DEV), torch.full((N, Atot, 2), nan, device=DEV)
+    ops.rpn_pack_levels(hd, A, locs, scores)
+    np.testing.assert_array_equal(locs.cpu().numpy(), want_l)
+    np.testing.assert_array_equal(scores.cpu().numpy(), want_s)
+    locs1, scores1 = torch.full((N, Atot, 4), nan, device=DEV), torch.full((N, Atot, 2), nan, device=DEV)
+    for l in range(L):
+        ops.rpn_pack(hd[l], A, locs1, scores1, int(offs[l]))
+    assert torch.equal(locs1, locs) and torch.equal(scores1, scores)
+    # the backward: gradients of locs / scores back into one NaN-filled head gradient per level; the padded channels 6A..Cp-1 come back zero
+    glocs = rs.standard_normal((N, Atot, 4)).astype(np.float32)
+    gscores = rs.standard_normal((N, Atot, 2)).astype(np.float32)
+    gl, gs = torch.from_numpy(glocs).to(DEV), torch.from_numpy(gscores).to(DEV)
+    gheads = [torch.full((N, h, w, Cp), nan, device=DEV) for h, w in shapes]
+    ptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in gheads])
+    hws = (ctypes.c_int * L)(*[h * w for h, w in shapes])
+    check(lib().mrcnn_rpn_unpack_grad_levels_f32(ptr(gl), ptr(gs), ptrs, hws, L, N, Cp, A, Atot, stream_ptr()))
+    for l, (h, w) in enumerate(shapes):
+        got = gheads[l].cpu().numpy()
+        assert not np.isnan(got).any()
+        np.testing.assert_array_equal(got[..., :4 * A], glocs[:, offs[l]:offs[l + 1]].reshape(N, h, w, 4 * A))
+        np.testing.assert_array_equal(got[..., 4 * A:6 * A], gscores[:, offs[l]:offs[l + 1]].reshape(N, h, w, 2 * A))
+        assert np.all(got[..., 6 * A:] == 0)
+        assert torch.equal(ops.rpn_unpack_grad(gl, gs, (N, h, w, Cp), A, int(offs[l])), gheads[l])
+    for g1, g2 in zip(ops.rpn_unpack_grad_levels(gl, gs, [(N, h, w, Cp) for h, w in shapes], A), gheads):
+        assert torch.equal(g1, g2)
+    # and the round trip: unpacking the packed values restores the heads' first 6A channels
+    for l, g in enumerate(ops.rpn_unpack_grad_levels(locs, scores, [(N, h, w, Cp) for h, w in shapes], A)):
+        np.testing.assert_array_equal(g.cpu().numpy()[..., :6 * A], heads[l][..., :6 * A])
+
+
+def _softmax2_float32(x):
+    """The kernel's arithmetic in NumPy float32 (the oracle whose own error sets rtol, tests/loss_judge.py)."""
+    x = np.asarray(x, np.float32)
+    e = np.exp(x - x.max(-1, keepdims=True))
+    return e / (e[..., :1] + e[..., 1:])
+
+
+@pytest.mark.parametrize('M', [1, 257, 2 * 23025])
+def test_softmax2_float64(M):
+    """(M,2) scores -> probabilities against float64 element by element (|got - want| <= rtol |want| + FLT_MIN, rtol = 4 x max(the float32
+    NumPy arithmetic's own ratio, 4 eps32)); pairs a naive exp would overflow on, equal pairs, zeros; every pair sums to 1 within 2 eps32."""
+    from tests import loss_reference as ref
+    from tests.loss_judge import EPS32, ratio, rtol_from
+    rs = np.random.RandomState(M)
+    x = (rs.standard_normal((M, 2)) * 5).astype(np.float32)
+    if M == 1:
+        x[0] = [90, -90]
+    else:
+        x[:5] = [[90, -90], [-90, 90], [3.25, 3.25], [0, 0], [-77.5, -77.5]]
+    got = ops.softmax2(torch.from_numpy(x).to(DEV)).cpu().numpy()
+    want = ref.softmax2(x)
+    rtol, r = rtol_from(_softmax2_float32(x), want), ratio(got, want)
+    print('LOSSRATIO k_softmax2 %.2f eps32 (bound %.2f eps32)' % (r / EPS32, rtol / EPS32))
+    assert r <= rtol, (r / EPS32, rtol / EPS32)
+    assert np.all(np.abs(got.astype(np.float64).sum(-1) - 1.0) <= 2 * EPS32)
+    if M > 1:
+        np.testing.assert_array_equal(got[:5], np.array([[1, 0], [0, 1], [0.5, 0.5], [0.5, 0.5], [0.5, 0.5]], np.float32))
+
+
+def test_softmax2_foreground_probability_is_monotone_in_the_logit_difference():
+    """The proposal sort orders by the foreground probability: across a sorted ramp of b - a it never decreases, whether a stays at 0 or
+    the pair is (-d/2, d/2) (d a multiple of 1/8: every value and every difference is exact in float32)."""
+    d = np.arange(-240, 241, dtype=np.float32) / 8
+    x = np.concatenate([np.stack([np.zeros_like(d), d], 1), np.stack([-d / 2, d / 2], 1)])
+    p = ops.softmax2(torch.from_numpy(x).to(DEV)).cpu().numpy()[:, 1].reshape(2, -1)
+    assert np.all(np.diff(p, axis=1) >= 0) and p[0, 0] < 1e-12 and p[0, -1] == 1 and p[0, 240] == 0.5
+    assert np.all(np.diff(p[:, 180:301], axis=1) > 0)              # |d| <= 7.5: neighbours 1/8 apart differ by far more than an ulp

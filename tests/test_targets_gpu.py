@@ -283,3 +283,19 @@ def test_anchor_target_per_image_sizes_equal_separate_calls():
         np.testing.assert_allclose(loc[i].cpu().numpy(), wl, rtol=1e-5, atol=1e-5)
     padded = ops.anchor_target(_t(anchors), _t(gt), _t(n_gt), (192, 256), keys=_t(keys.view(np.int32)))[1]
     assert not np.array_equal(padded[1].cpu().numpy(), label[1].cpu().numpy())
+
+
+@pytest.mark.parametrize('N', [1, 3])
+@pytest.mark.parametrize('G', [1, 63, 64, 65, 200])
+def test_count_valid_labels_exact(N, G):
+    """n_gt = (labels >= 0).sum(1): one wave per image, G below, at and above the wave width; -1 rows interleaved with valid ones (not
+    only trailing), label 0 counts, a row of nothing but -1 gives 0."""
+    rs = np.random.RandomState(N + G)
+    labels = rs.randint(-1, 4, (N, G)).astype(np.int32)
+    labels[0, 0] = 0
+    if G > 1:
+        labels[0, -1], labels[0, G // 2] = 2, -1
+    for lab in (labels, np.concatenate([labels[:-1], np.full((1, G), -1, np.int32)])):
+        got = ops.count_valid_labels(_t(lab)).cpu().numpy()
+        assert got.dtype == np.int32
+        np.testing.assert_array_equal(got, (lab >= 0).sum(1))
