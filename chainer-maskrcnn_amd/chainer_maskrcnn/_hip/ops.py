@@ -361,6 +361,41 @@ def mask_resize_crop_batch_u8(src, desc, gather, dst_h, dst_w):
     return out
 
 
+# ---- Simple Copy-Paste on a large-scale-jitter batch (copy_paste.hip) ----------------------------------------------
+def copy_paste(imgs, masks, labels, gather, sel, receive, G_out):
+    """dataset.augment.copy_paste_batch on the device.  imgs (N,3,H,W) float32, masks (N,G,H,W) uint8, labels (N,G) int32 and gather
+    (N,G) int32 as the LSJ stage leaves them (gather: the original instance index of each row), sel (N,Gin) uint8 (original instance i
+    of example n is offered), receive (N,) uint8 (example n takes the offer of its partner (n + 1) % N).  Returns new tensors
+    (imgs, masks (N,G_out,H,W), bboxes (N,G_out,4) float32, labels (N,G_out) int32); the inputs are only read.  One fill and four
+    launches on the current stream, no host synchronisation."""
+    _ck(imgs, masks, labels, gather, sel, receive)
+    if imgs.dtype != f32 or imgs.dim() != 4 or imgs.shape[1] != 3:
+        raise ValueError('copy_paste: imgs must be a contiguous (N,3,H,W) float32 tensor')
+    N, _, H, W = imgs.shape
+    if masks.dtype != torch.uint8 or masks.dim() != 4 or masks.shape[0] != N or tuple(masks.shape[2:]) != (H, W):
+        raise ValueError('copy_paste: masks must be a contiguous (N,G,H,W) uint8 tensor of the images\' size')
+    G = masks.shape[1]
+    for name, t in (('labels', labels), ('gather', gather)):
+        if t.dtype != i32 or tuple(t.shape) != (N, G):
+            raise ValueError('copy_paste: %s must be a contiguous (N,G) int32 tensor' % name)
+    if sel.dtype != torch.uint8 or sel.dim() != 2 or sel.shape[0] != N:
+        raise ValueError('copy_paste: sel must be a contiguous (N,Gin) uint8 tensor')
+    if receive.dtype != torch.uint8 or tuple(receive.shape) != (N,):
+        raise ValueError('copy_paste: receive must be a contiguous (N,) uint8 tensor')
+    Gin, G_out, dev = sel.shape[1], int(G_out), imgs.device
+    if not 1 <= G_out <= 65535:         # (before anything is allocated or launched; the entry point refuses it as well)
+        raise ValueError('copy_paste: G_out = %d outside 1..65535' % G_out)
+    out_imgs, alpha = _empty((N, 3, H, W), dev), _empty((N, H, W), dev, torch.uint8)
+    check(lib().mrcnn_copy_paste_image_f32(ptr(imgs), ptr(masks), ptr(labels), ptr(gather), ptr(sel), ptr(receive), N, G, Gin, H, W,
+                                           ptr(out_imgs), ptr(alpha), stream_ptr()))
+    out_masks = _empty((N, G_out, H, W), dev, torch.uint8)
+    bboxes, out_labels, source = _empty((N, G_out, 4), dev), _empty((N, G_out), dev, i32), _empty((N, G_out), dev, i32)
+    ws = _empty((N, 2 * G, 4), dev, i32)
+    check(lib().mrcnn_copy_paste_masks_u8(ptr(masks), ptr(alpha), ptr(labels), ptr(gather), ptr(sel), ptr(receive), N, G, Gin, G_out, H, W,
+                                          ptr(out_masks), ptr(bboxes), ptr(out_labels), ptr(source), ptr(ws), stream_ptr()))
+    return out_imgs, out_masks, bboxes, out_labels
+
+
 def random_keys(shape, seed, device):
     """uint32 sampler keys stored in an int32 tensor."""
     out = _empty(shape, device, i32)

@@ -17,6 +17,14 @@ Conventions (the augmented example is ``Transform(hflip(example))`` with the dra
               zero.  scale = oh / H as ever, the example's size is (ch, cw).  Mask instances whose cropped mask has no pixel left are
               dropped and the others get the tight box (ymin, xmin, ymax + 1, xmax + 1) of their cropped mask; keypoint instances get
               their box shifted and clipped to the window (dropped when nothing is left), keypoints outside the window get v = 0.
+  Copy-Paste  Simple Copy-Paste (``Augment(copy_paste_prob=P)``, on top of LSJ, mask examples, batches of N >= 2): after
+              flip and LSJ example n of a batch receives from its partner p = (n + 1) % N.  ``decide_copy_paste`` draws, from a stream
+              of its own, whether the example receives (as a target) and which of its annotated instances it offers (as a source, keyed
+              by the original instance index, before any crop).  ``AugmentParams.copy_paste`` carries (seed, rank, ticket, P); the
+              transform, which knows the raw instance count, calls ``decide_copy_paste`` with it.  ``copy_paste_batch`` is the rule, in
+              NumPy: the host path, and the oracle of the device path (csrc/copy_paste.hip).  The partner's offered rows are pasted over
+              the image (exact selection, no blending); n's own masks lose the covered pixels, every row gets the tight box of what is
+              left of its mask, rows without a pixel are dropped; the survivors come first, then the pasted rows.
   flip map    from the keypoint names: left_* <-> right_* (COCO), *Left <-> *Right (the depth dataset); names without a side map to
               themselves.  A side without its partner is an error: coordinates are never flipped without swapping the channels.
 """
@@ -34,9 +42,10 @@ DEPTH_KEYPOINT_NAMES = ('SpineBase', 'SpineMid', 'Neck', 'Head', 'ShoulderLeft',
                         'AnkleRight', 'FootRight')
 
 # per-example parameters a transform takes: flip (bool), min_size (int or None = the transform's own), keypoint_perm (flip map or None),
-# lsj (None, or (S, s, u_y, u_x): canvas size and the three draws of decide_lsj - the geometry follows from the source size, lsj_geometry)
-AugmentParams = collections.namedtuple('AugmentParams', ['flip', 'min_size', 'keypoint_perm', 'lsj'])
-AugmentParams.__new__.__defaults__ = (None, None)
+# lsj (None, or (S, s, u_y, u_x): canvas size and the three draws of decide_lsj - the geometry follows from the source size, lsj_geometry),
+# copy_paste (None, or (seed, rank, ticket, prob): the arguments of decide_copy_paste but the instance count, which the transform knows)
+AugmentParams = collections.namedtuple('AugmentParams', ['flip', 'min_size', 'keypoint_perm', 'lsj', 'copy_paste'])
+AugmentParams.__new__.__defaults__ = (None, None, None)
 
 
 def _partner(name):
@@ -87,6 +96,56 @@ def decide_lsj(seed, rank, ticket, p, scale_range):
     flip = bool(rng.random() < p)
     s = lo + (hi - lo) * float(rng.random())
     return flip, s, float(rng.random()), float(rng.random())
+
+
+def decide_copy_paste(seed, rank, ticket, prob, n_inst):
+    """(receive, sel) of the example at ``ticket`` of ``rank``'s sequence under Copy-Paste: a pure function of its arguments, drawn from
+    a stream of its own (``decide`` / ``decide_lsj`` draw from [seed, rank, ticket]).  receive: the example, as a target, takes its
+    partner's offer (the first draw < prob); sel (n_inst,) bool: which of its annotated instances it offers as a source (one draw each,
+    < 0.5), by original instance index."""
+    rng = np.random.default_rng([int(seed), int(rank), int(ticket), 1])
+    receive = bool(rng.random() < prob)
+    return receive, rng.random(int(n_inst)) < 0.5
+
+
+def copy_paste_batch(batch, receive, offers, max_gt=None):
+    """Simple Copy-Paste on a collated canvas batch (``loader.collate(canvas=S)`` of LSJ'd mask examples): a new batch, the given one is
+    only read.  receive (N,): is example n a target; offers: per example, which of its batch rows it offers as a source (bool per row, in
+    row order; missing entries count as not offered).  Example n's partner is p = (n + 1) % N.
+      pick    the partner's valid rows (label >= 0) that are offered when receive[n], else none; alpha = OR of masks[p, j] != 0 over pick
+      image   where(alpha, imgs[p], imgs[n])
+      rows    n's valid rows as mask & ~alpha with their labels, then the picked rows unchanged with the partner's labels; those with a
+              pixel left, in that order, are packed first with the tight box of their mask (``tight_boxes``); the first G_out stay
+      G_out   max_gt, or the largest number of kept rows in the batch (at least 1); behind the kept rows: label -1, zero box, zero plane
+      sizes   the elementwise max of n's and p's when receive[n]; scales are unchanged"""
+    imgs, masks, labels = np.asarray(batch['imgs']), np.asarray(batch['masks']), np.asarray(batch['labels'])
+    N, G = labels.shape
+    if N < 2:
+        raise ValueError('copy_paste_batch: a batch of at least 2 examples expected (an example receives from its neighbour), got %d' % N)
+    rows, out_imgs = [], imgs.copy()
+    sizes = np.array(batch['sizes'], copy=True)
+    for n in range(N):
+        p = (n + 1) % N
+        offer = np.zeros((G,), bool)
+        o = np.asarray(offers[p], bool).reshape(-1)[:G]
+        offer[:len(o)] = o
+        pick = np.flatnonzero((labels[p] >= 0) & offer) if receive[n] else np.zeros((0,), np.int64)
+        alpha = (masks[p, pick] != 0).any(0) if len(pick) else np.zeros(masks.shape[2:], bool)
+        out_imgs[n] = np.where(alpha, imgs[p], imgs[n])
+        own = np.flatnonzero(labels[n] >= 0)
+        cand = np.concatenate([np.where(alpha, 0, masks[n, own]).astype(masks.dtype), masks[p, pick]])
+        boxes, keep = tight_boxes(cand)
+        rows.append((cand[keep], boxes[keep], np.concatenate([labels[n, own], labels[p, pick]])[keep]))
+        if receive[n]:
+            sizes[n] = np.maximum(batch['sizes'][n], batch['sizes'][p])
+    G_out = max_gt or max(1, max(len(r[2]) for r in rows))
+    out = dict(batch)
+    out.update(imgs=out_imgs, sizes=sizes, masks=np.zeros((N, G_out) + masks.shape[2:], masks.dtype),
+               bboxes=np.zeros((N, G_out, 4), np.float32), labels=np.full((N, G_out), -1, np.int32))
+    for n, (m, b, l) in enumerate(rows):
+        g = min(G_out, len(l))
+        out['masks'][n, :g], out['bboxes'][n, :g], out['labels'][n, :g] = m[:g], b[:g], l[:g]
+    return out
 
 
 def lsj_geometry(H, W, S, s, u_y, u_x):
@@ -171,9 +230,11 @@ def hflip(example, keypoint_perm=None):
 class Augment(object):
     """The augmentation of a training run: flip probability, the short sides to draw from (None: the transform's own min_size), the
     seed, and for keypoint data the flip map; ``lsj_size`` = S turns large-scale jitter on (an S x S canvas, the scale drawn from
-    ``lsj_scale``; not together with min_sizes - two different resize rules).  ``params(rank, ticket)`` gives an example's AugmentParams."""
+    ``lsj_scale``; not together with min_sizes - two different resize rules); ``copy_paste_prob`` = P in (0, 1] turns Copy-Paste on (with
+    lsj_size only; 0 = off).  ``params(rank, ticket)`` gives an example's AugmentParams."""
 
-    def __init__(self, hflip_prob=0.0, min_sizes=None, seed=0, keypoint_perm=None, lsj_size=None, lsj_scale=(0.1, 2.0)):
+    def __init__(self, hflip_prob=0.0, min_sizes=None, seed=0, keypoint_perm=None, lsj_size=None, lsj_scale=(0.1, 2.0),
+                 copy_paste_prob=0.0):
         if not 0.0 <= float(hflip_prob) <= 1.0:
             raise ValueError('hflip_prob must lie in [0, 1], got %r' % hflip_prob)
         if min_sizes is not None:
@@ -191,10 +252,20 @@ class Augment(object):
             if not 0 < self.lsj_scale[0] <= self.lsj_scale[1]:
                 raise ValueError('lsj_scale must be 0 < lo <= hi, got %r' % (lsj_scale,))
             self.lsj_size = int(lsj_size)
+        self.copy_paste_prob = 0.0
+        if copy_paste_prob:
+            if not 0.0 < float(copy_paste_prob) <= 1.0:
+                raise ValueError('copy_paste_prob must lie in (0, 1] (0 = off), got %r' % (copy_paste_prob,))
+            if not self.lsj_size:
+                raise ValueError('copy_paste_prob needs lsj_size: Copy-Paste composes two large-scale-jittered canvases')
+            if keypoint_perm is not None:
+                raise ValueError('copy_paste_prob: Copy-Paste is defined for mask examples, not for keypoint data')
+            self.copy_paste_prob = float(copy_paste_prob)
 
     def params(self, rank, ticket):
         if self.lsj_size:
             flip, s, u_y, u_x = decide_lsj(self.seed, rank, ticket, self.hflip_prob, self.lsj_scale)
-            return AugmentParams(flip, None, self.keypoint_perm, (self.lsj_size, s, u_y, u_x))
+            cp = (self.seed, int(rank), int(ticket), self.copy_paste_prob) if self.copy_paste_prob else None
+            return AugmentParams(flip, None, self.keypoint_perm, (self.lsj_size, s, u_y, u_x), cp)
         flip, min_size = decide(self.seed, rank, ticket, self.hflip_prob, self.min_sizes)
         return AugmentParams(flip, min_size, self.keypoint_perm)

@@ -12,6 +12,8 @@ to the transform; on the device path the batch's raw images and masks are then u
 one launch per tensor (csrc/augment.hip).  With large-scale jitter (``Augment(lsj_size=S)``) every batch is an S x S
 canvas; on the device path the crop kernels write it, and for mask data the boxes, the drop of instances the crop removed and the
 packing of the kept ones are device work on the loader's stream - ``bboxes`` and ``labels`` are then device outputs and nothing waits.
+Copy-Paste (``Augment(copy_paste_prob=P)``) composes each LSJ'd example with its batch neighbour: on the host path
+``augment.copy_paste_batch`` after ``collate``, on the device path csrc/copy_paste.hip behind the LSJ launches, again without a wait.
 """
 import queue
 import threading
@@ -119,6 +121,12 @@ class BatchLoader(object):
         self.bs, self.shuffle, self.seed, self.rank, self.world = batch_size, shuffle, seed, rank, world
         self.max_gt, self.keypoints, self.device, self.skip_empty = max_gt, keypoints, device, skip_empty
         self._lsj = getattr(augment, 'lsj_size', None)       # the canvas size S, or None
+        self._cp = bool(getattr(augment, 'copy_paste_prob', 0.0))
+        if self._cp and (keypoints or getattr(transform, 'keypoints', False)):
+            raise ValueError('Copy-Paste (copy_paste_prob) is defined for mask examples, not for keypoint data')
+        if self._cp and batch_size < 2:
+            raise ValueError('Copy-Paste (copy_paste_prob) pastes from the neighbouring example of the batch: batch_size >= 2 expected, '
+                             'got %d' % batch_size)
         self._idx = queue.Queue(maxsize=prefetch * batch_size * 2)
         self._out = {}
         self._cv = threading.Condition()
@@ -321,7 +329,22 @@ class BatchLoader(object):
         lab = self._ring.upload(slot, 'labels_in', labels_in, dev)
         dev_bboxes, dev_labels, gather = ops.mask_crop_boxes_u8(m, mdesc, lab, G, H, W)
         extra = ops.mask_resize_crop_batch_u8(m, mdesc, gather, H, W)
-        return imgs, extra, keep + [m, lab, gather], dev_bboxes, dev_labels
+        keep += [m, lab, gather]
+        if self._cp:
+            # Copy-Paste: the decisions travel with the examples (RawTransform's 9th item); sel is keyed by the original instance index,
+            # which the gather table holds, so nothing here needs the kept counts.  Without max_gt the output has room for every
+            # instance an example and its partner had before the crop
+            receive = np.array([e[8][0] for e in exs], np.uint8)
+            sel = np.zeros(labels_in.shape, np.uint8)
+            for i, e in enumerate(exs):
+                sel[i, :counts[i]] = e[8][1]
+                if receive[i]:
+                    sizes[i] = np.maximum(e[5], exs[(i + 1) % N][5])
+            G_out = self.max_gt or max(1, max(counts[i] + counts[(i + 1) % N] for i in range(N)))
+            sel_d, receive_d = self._ring.upload(slot, 'cp_sel', sel, dev), self._ring.upload(slot, 'cp_receive', receive, dev)
+            keep += [imgs, extra, dev_bboxes, dev_labels, sel_d, receive_d]
+            imgs, extra, dev_bboxes, dev_labels = ops.copy_paste(imgs, extra, dev_labels, gather, sel_d, receive_d, G_out)
+        return imgs, extra, keep, dev_bboxes, dev_labels
 
     @staticmethod
     def _crop_descs(offs, src_hw, counts, exs):
@@ -331,7 +354,11 @@ class BatchLoader(object):
     def __next__(self):
         if getattr(self.transform, 'out_size', None) is not None and self.device is not None and str(self.device).startswith('cuda'):
             return self._next_device_batch()
-        batch = collate([self._next_example() for _ in range(self.bs)], self.max_gt, self.keypoints, canvas=self._lsj)
+        exs = [self._next_example() for _ in range(self.bs)]
+        batch = collate([e[:5] for e in exs], self.max_gt, self.keypoints, canvas=self._lsj)
+        if self._cp:        # (Transform's 6th and 7th items: receive, and which kept rows are offered)
+            from chainer_maskrcnn.dataset.augment import copy_paste_batch
+            batch = copy_paste_batch(batch, [e[5] for e in exs], [e[6] for e in exs], self.max_gt)
         if self.device is None:
             return batch
         import torch

@@ -10,7 +10,8 @@ coordinate rules (parity unpinned; the float path is checked against the indepen
 """
 import numpy as np
 
-from chainer_maskrcnn.dataset.augment import crop_boxes_keypoints, flip_bbox, flip_keypoints, hflip, lsj_geometry, tight_boxes
+from chainer_maskrcnn.dataset.augment import (crop_boxes_keypoints, decide_copy_paste, flip_bbox, flip_keypoints, hflip, lsj_geometry,
+                                              tight_boxes)
 
 F = np.float32
 
@@ -84,7 +85,10 @@ class Transform(object):
     """train.py:21-37.  in: (img, bbox, label, masks list) -> (img, bbox, label, masks (G,oH,oW) uint8, scale).
     aug (dataset.augment.AugmentParams, optional): the example is mirrored first (augment.hflip) when aug.flip, and resized to
     aug.min_size when that is given.  With aug.lsj (large-scale jitter) image and masks are the crop window of the
-    mirrored example's virtual resize, instances without a pixel left are dropped and the boxes are the cropped masks' tight boxes."""
+    mirrored example's virtual resize, instances without a pixel left are dropped and the boxes are the cropped masks' tight boxes.
+    With aug.copy_paste (Copy-Paste) two more items follow the scale: receive (bool: the example takes its batch
+    partner's offer) and offered (bool per kept row: the row is offered to the example's receiver) - ``augment.decide_copy_paste`` for the
+    example's annotated instances, the offer carried through the crop; ``BatchLoader`` applies them after collating."""
 
     def __init__(self, faster_rcnn):
         self.min_size, self.max_size = faster_rcnn.min_size, faster_rcnn.max_size
@@ -96,7 +100,11 @@ class Transform(object):
         masks = [resize_nearest(np.asarray(im), (oh, ow))[y0:y0 + ch, x0:x0 + cw] for im in label_img]
         masks = np.stack(masks).astype(np.uint8) if masks else np.zeros((0, ch, cw), np.uint8)
         bbox, keep = tight_boxes(masks)
-        return img, bbox[keep], np.asarray(label, np.int32)[keep], np.ascontiguousarray(masks[keep]), oh / H
+        out = img, bbox[keep], np.asarray(label, np.int32)[keep], np.ascontiguousarray(masks[keep]), oh / H
+        if aug.copy_paste is not None:
+            receive, sel = decide_copy_paste(*aug.copy_paste, n_inst=len(keep))
+            out += (receive, sel[keep])
+        return out
 
     def __call__(self, in_data, aug=None):
         min_size = self.min_size
@@ -163,7 +171,9 @@ class RawTransform(object):
     of the output, the flip flag (returned whenever aug is given).
     With aug.lsj (large-scale jitter) the 6th item is the window size (ch,cw) and an 8th item carries the geometry (oh,ow,y0,x0,ch,cw) of
     augment.lsj_geometry for the crop kernels.  Keypoint examples get their boxes and keypoints here (augment.crop_boxes_keypoints); mask
-    examples return bbox = None, every raw mask and label: which instances survive the crop, and their boxes, is decided on the device."""
+    examples return bbox = None, every raw mask and label: which instances survive the crop, and their boxes, is decided on the device.
+    With aug.copy_paste a mask example carries a 9th item (receive, sel): ``augment.decide_copy_paste`` for its annotated instances, sel
+    by original instance index - the device looks the offer of a kept row up through the crop's gather table."""
 
     def __init__(self, faster_rcnn, keypoints=False):
         self.min_size, self.max_size, self.keypoints = faster_rcnn.min_size, faster_rcnn.max_size, keypoints
@@ -188,7 +198,10 @@ class RawTransform(object):
             bbox, kp, _ = crop_boxes_keypoints(bbox, kp, y0, x0, ch, cw)
             return img_u8, bbox, np.zeros(bbox.shape[0], dtype=np.int32), kp, scale, (ch, cw), int(flip), geo
         masks = np.stack([np.asarray(m, np.uint8) for m in in_data[3]]) if len(in_data[3]) else np.zeros((0, H, W), np.uint8)
-        return img_u8, None, np.asarray(in_data[2], np.int32), masks, scale, (ch, cw), int(flip), geo
+        out = img_u8, None, np.asarray(in_data[2], np.int32), masks, scale, (ch, cw), int(flip), geo
+        if aug.copy_paste is not None:
+            out += (decide_copy_paste(*aug.copy_paste, n_inst=masks.shape[0]),)
+        return out
 
     def __call__(self, in_data, aug=None):
         if aug is not None and aug.lsj is not None:

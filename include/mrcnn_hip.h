@@ -771,6 +771,30 @@ int mrcnn_mask_resize_crop_batch_nearest_u8(const unsigned char *src, size_t src
                                             const int32_t *gather, unsigned char *dst, int dst_h, int dst_w, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Simple Copy-Paste on a large-scale-jitter batch (copy_paste.hip; dataset/augment.py copy_paste_batch is the rule).
+ * Inputs, all DEVICE, the pre-paste batch - nothing is updated in place: imgs (N,3,H,W) float32, masks (N,G,H,W) uint8, labels (N,G)
+ * int32 (-1: no instance), gather (N,G) int32 (the ORIGINAL instance index of each row, mrcnn_mask_crop_boxes_u8's table), sel (N,Gin)
+ * uint8 (is original instance i of example n offered as a source), receive (N) uint8 (is example n a target).  Example n's partner is
+ * p = (n + 1) % N; with receive[n] its rows j with labels[p][j] >= 0, 0 <= gather[p][j] < Gin and sel[p][gather[p][j]] != 0 are pasted.
+ *   mrcnn_copy_paste_image_f32  alpha (N,H,W) uint8 = 0xFF where a pasted row of the partner is non-zero, 0 elsewhere;
+ *       out_imgs[n] = alpha[n] ? imgs[p] : imgs[n] on the 3 channels.  One launch.
+ *   mrcnn_copy_paste_masks_u8   the candidates of example n are its own rows r with labels[n][r] >= 0, as masks[n][r] where alpha[n] is 0,
+ *       then the pasted rows of the partner, unchanged.  Those with a pixel left, in that order, fill output rows 0, 1, ... (those past row
+ *       G_out - 1 are dropped): out_masks (N,G_out,H,W) uint8, bboxes (N,G_out,4) float32 = the tight box (ymin, xmin, ymax + 1, xmax + 1),
+ *       labels_out (N,G_out) int32, source (N,G_out) int32 = r for an own row, G + j for a partner row; the rows behind them are a zero
+ *       plane, (0,0,0,0), -1, -1.  alpha: the plane of mrcnn_copy_paste_image_f32 for the same inputs.  ws: (N,2G,4) int32 scratch, filled
+ *       by the call.  One fill and three launches on `stream`; integer maxima only - exact, the same for every schedule.
+ * Errors, before any launch: MRCNN_E_INVALID for a NULL pointer, N outside 2..MRCNN_RESIZE_BATCH_MAX, G / Gin / G_out outside 1..65535,
+ * H or W not positive or H * (W + 15) past INT_MAX, out_imgs / alpha / out_masks / bboxes / ws not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_copy_paste_image_f32(const float *imgs, const unsigned char *masks, const int32_t *labels, const int32_t *gather,
+                               const unsigned char *sel, const unsigned char *receive, int N, int G, int Gin, int H, int W,
+                               float *out_imgs, unsigned char *alpha, void *stream);
+int mrcnn_copy_paste_masks_u8(const unsigned char *masks, const unsigned char *alpha, const int32_t *labels, const int32_t *gather,
+                              const unsigned char *sel, const unsigned char *receive, int N, int G, int Gin, int G_out, int H, int W,
+                              unsigned char *out_masks, float *bboxes, int32_t *labels_out, int32_t *source, int32_t *ws, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Test-time augmentation (tta.hip; MaskRCNN.use_test_augmentation).  An image runs as V <= MRCNN_TTA_VIEWS_MAX views (short sides,
  * optionally mirrored), one N = 1 forward each; these calls merge the views after the forward pass.
  *   views (V) HOST array, read at the call (passed to the kernels by value): R = the view's candidates (decode), mirror 0 / 1, scale = the

@@ -122,6 +122,10 @@ def build_parser(keypoints=False):
                              'that one shape; S a multiple of 64; --synthetic 0 only, not with --min-sizes.  0 = off')
     parser.add_argument(*both('--lsj-scale'), type=float, nargs=2, default=[0.1, 2.0], metavar=('LO', 'HI'),
                         help='the scale range of --lsj-size')
+    parser.add_argument(*both('--copy-paste'), type=float, default=0.0, metavar='P',
+                        help='Simple Copy-Paste on top of --lsj-size: with probability P an example receives a random half of the instances '
+                             'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
+                             'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
     return parser
 
 
@@ -178,6 +182,8 @@ def augment_settings(args):
     settings = {'hflip': int(args.hflip), 'min_sizes': [int(s) for s in args.min_sizes] if args.min_sizes else None, 'seed': AUGMENT_SEED}
     if args.lsj_size:
         settings['lsj'] = {'size': int(args.lsj_size), 'scale': [float(v) for v in args.lsj_scale]}
+    if args.copy_paste:
+        settings['copy_paste'] = float(args.copy_paste)
     return settings
 
 
@@ -191,7 +197,23 @@ def _eval_boxpost_settings(args):
     return b
 
 
-def _check_augment_args(args):
+def _check_copy_paste_args(args, keypoints):
+    p = args.copy_paste
+    if not 0.0 < p <= 1.0:
+        raise ValueError('--copy-paste: the probability must lie in (0, 1] (0 = off), got %r' % p)
+    if keypoints:
+        raise ValueError('--copy-paste pastes instance masks: it is defined for mask heads, not for keypoint data (train_keypoints.py)')
+    if args.synthetic:
+        raise ValueError('--copy-paste augments the dataset loader (--synthetic 0); the synthetic batches (--synthetic 1) are not augmented')
+    if not args.lsj_size:
+        raise ValueError('--copy-paste composes two large-scale-jittered canvases: it needs --lsj-size')
+    if args.batch_size < 2:
+        raise ValueError('--copy-paste pastes from the next example of the batch: it needs --batch-size >= 2, got %d' % args.batch_size)
+
+
+def _check_augment_args(args, keypoints=False):
+    if args.copy_paste:
+        _check_copy_paste_args(args, keypoints)
     if (args.hflip or args.min_sizes) and args.synthetic:
         raise ValueError('--hflip / --min-sizes augment the dataset loader (--synthetic 0); the synthetic batches (--synthetic 1) are not '
                          'augmented')
@@ -253,7 +275,7 @@ def run(args, keypoints=False):
     if args.eval_interval > 0 and world > 1:
         raise ValueError('--eval-interval: evaluation runs in single-process training only; with %d ranks it is not supported '
                          '(the reference\'s multi-GPU branch has no test iterator either, train.py:117-121, and would fail there)' % world)
-    _check_augment_args(args)
+    _check_augment_args(args, keypoints)
     eval_boxpost = _eval_boxpost_settings(args)
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
     if resume is not None and resume.get('augment', NO_AUGMENT) != augment_settings(args):
@@ -285,7 +307,7 @@ def run(args, keypoints=False):
         from chainer_maskrcnn.dataset.augment import Augment
         augment = Augment(hflip_prob=0.5 if args.hflip else 0.0, min_sizes=args.min_sizes, seed=AUGMENT_SEED,
                           keypoint_perm=_keypoint_flip_perm(args, data) if keypoints and args.hflip else None,
-                          lsj_size=args.lsj_size or None, lsj_scale=args.lsj_scale)
+                          lsj_size=args.lsj_size or None, lsj_scale=args.lsj_scale, copy_paste_prob=args.copy_paste)
     local = int(os.environ.get('LOCAL_RANK', args.gpu))
     ndev = max(1, torch.cuda.device_count())
     lws = int(os.environ.get('LOCAL_WORLD_SIZE', 1))
