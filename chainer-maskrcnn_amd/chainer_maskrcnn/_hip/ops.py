@@ -119,6 +119,52 @@ def bn_frozen_bwd_pair(gy, y, gamma_a, var_a, gamma_b, var_b, out_a=None, eps=2e
     return gxa, gxb
 
 
+# ---- group norm (RoI heads; csrc/groupnorm.hip) ---------------------------------------------------
+GN_PATHS = ('register', 'generic')      # values of group_norm_plan's path
+
+
+def group_norm_plan(R, H, W, C, Cp, G):
+    """(path, backward workspace bytes) of mrcnn_group_norm_plan: host arithmetic, no device.  Raises on an invalid geometry."""
+    path, nb = ctypes.c_int(-1), ctypes.c_size_t(0)
+    check(lib().mrcnn_group_norm_plan(int(R), int(H), int(W), int(C), int(Cp), int(G), ctypes.byref(path), ctypes.byref(nb)))
+    return path.value, nb.value
+
+
+def group_norm_fwd(x, gamma, beta, C, G, relu=False, want_stats=True, eps=1e-5):
+    """x (R,H,W,Cp) NHWC with C logical channels in G groups.  Returns (y, mean, rstd); mean / rstd (R,G) are None unless want_stats."""
+    _ck(x, gamma, beta)
+    R, H, W, Cp = x.shape
+    y = torch.empty_like(x)
+    mean = _empty((R, G), x.device) if want_stats else None
+    rstd = _empty((R, G), x.device) if want_stats else None
+    check(lib().mrcnn_group_norm_fwd_f32(ptr(x), ptr(gamma), ptr(beta), R, H, W, int(C), Cp, int(G), eps, int(bool(relu)), ptr(y),
+                                         ptr(mean), ptr(rstd), stream_ptr()))
+    return y, mean, rstd
+
+
+def group_norm_bwd(gy, x, gamma, beta, mean, rstd, C, G, relu=False, gg=None, gb=None, accumulate_params=False):
+    """relu: recompute the ReLU mask from x (False: gy arrives masked, or the layer has no ReLU).  gg / gb: where the gradients of gamma /
+    beta are written, or added with accumulate_params (the flat gradient buffer's views); allocated when not given.  Returns (gx, gg, gb)."""
+    _ck(gy, x, gamma, beta, mean, rstd, gg, gb)
+    R, H, W, Cp = x.shape
+    if tuple(gy.shape) != tuple(x.shape):
+        raise ValueError('group_norm_bwd: gy %r and x %r differ in shape' % (tuple(gy.shape), tuple(x.shape)))
+    if (gg is None or gb is None) and accumulate_params:
+        raise ValueError('group_norm_bwd: accumulate_params needs gg and gb')
+    gx = torch.empty_like(x)
+    gg = _empty((Cp,), x.device) if gg is None else gg
+    gb = _empty((Cp,), x.device) if gb is None else gb
+    _, nb = group_norm_plan(R, H, W, C, Cp, G)
+    if R == 0 and not accumulate_params:        # the library launches nothing for an empty batch: the sums over no sample are zeros
+        gg.zero_()
+        gb.zero_()
+    ws = workspace(nb, x.device)
+    check(lib().mrcnn_group_norm_bwd_f32(ptr(gy), ptr(x), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), R, H, W, int(C), Cp, int(G),
+                                         int(bool(relu)), ptr(gx), ptr(gg), ptr(gb), int(bool(accumulate_params)), ptr(ws), ws.numel(),
+                                         stream_ptr()))
+    return gx, gg, gb
+
+
 def relu_bwd(gy, y, out=None):
     _ck(gy, y)
     out = torch.empty_like(gy) if out is None else out

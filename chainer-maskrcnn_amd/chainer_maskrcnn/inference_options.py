@@ -95,6 +95,27 @@ def use_boxpost(model, settings):
     model.use_max_detections(settings['max_detections'])
 
 
+# ---- head normalisation -------------------------------------------------------------------------------------------------------------------
+def add_head_norm_flags(parser, both=lambda name: (name,)):
+    """--head-norm / --gn-groups (train.py, train_keypoints.py - which takes both spellings through ``both`` -, evaluate.py, demo.py)."""
+    parser.add_argument(*both('--head-norm'), default='none', choices=['none', 'gn'],
+                        help='gn: GroupNorm behind conv1 and every mask / keypoint convolution of the FPN heads (MaskRCNN head_norm; '
+                             'Detectron\'s *_gn heads), for long schedules from scratch; a checkpoint is evaluated with the value it was '
+                             'trained with')
+    parser.add_argument(*both('--gn-groups'), type=int, default=32, metavar='G', help='groups of --head-norm gn; must divide the head\'s 256 channels')
+
+
+def head_norm_settings(head_norm, gn_groups, head_arch):
+    """The MaskRCNN arguments {'head_norm': None | 'gn', 'gn_groups': G} of the flags; ValueError for a combination the model refuses."""
+    if head_norm not in ('none', 'gn'):
+        raise ValueError('--head-norm must be none or gn, got %r' % (head_norm,))
+    if head_norm == 'gn' and head_arch in ('res5', 'light'):
+        raise ValueError('--head-norm gn exists for --head-arch fpn and fpn_keypoint, not %s' % head_arch)
+    if gn_groups < 1 or (head_norm == 'gn' and 256 % gn_groups != 0):
+        raise ValueError('--gn-groups must be a positive divisor of the head\'s 256 channels, got %r' % (gn_groups,))
+    return {'head_norm': None if head_norm == 'none' else head_norm, 'gn_groups': int(gn_groups)}
+
+
 # ---- labels and the model -----------------------------------------------------------------------------------------------------------------
 def read_labels(label_file):
     """The category names of --label_file (None when the file does not exist: every category)."""
@@ -112,19 +133,20 @@ def use_score_preset(model, preset, score_thresh=None):
 
 
 def build_inference_model(args, preset=None):
-    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --label_file with --weight loaded (keys missing from the file keep their
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --gn-groups / --label_file with --weight loaded (keys missing from the file keep their
     initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
     17 keypoints; a mask head has one class per label (80 without a label file)."""
     import torch
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     from chainer_maskrcnn.utils import chainer_npz
+    norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
     dev = torch.device('cuda', args.gpu)
     torch.cuda.set_device(dev)
     if args.head_arch == 'fpn_keypoint':
-        model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev)
+        model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev, **norm)
     else:
         labels = read_labels(args.label_file)
-        model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev)
+        model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev, **norm)
     if args.weight:
         if not os.path.exists(args.weight):
             raise FileNotFoundError('--weight %s does not exist' % args.weight)

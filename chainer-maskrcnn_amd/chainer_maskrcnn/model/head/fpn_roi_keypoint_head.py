@@ -17,9 +17,11 @@ class FPNRoIKeypointHead(FPNRoIMaskHead):
     mask_size = 56
 
     def __init__(self, n_class, n_keypoints, roi_size_box, roi_size_mask, n_mask_convs=8, loc_initialW=None,
-                 score_initialW=None, mask_initialW=None, ps=None, prefix='head', in_channels=256, fc_channels=1024):
+                 score_initialW=None, mask_initialW=None, ps=None, prefix='head', in_channels=256, fc_channels=1024, norm=None,
+                 gn_groups=32):
         super().__init__(n_class, roi_size_box, roi_size_mask, loc_initialW=loc_initialW, score_initialW=score_initialW,
                          mask_initialW=mask_initialW, ps=ps, prefix=prefix, in_channels=in_channels,
                          fc_channels=fc_channels, n_mask_convs=n_mask_convs, mask_out_channels=n_keypoints,
-                         upsample2x=True, mask_conv_names=['mask_convs/%d' % i for i in range(n_mask_convs)])
+                         upsample2x=True, mask_conv_names=['mask_convs/%d' % i for i in range(n_mask_convs)], norm=norm,
+                         gn_groups=gn_groups)
         self.n_keypoints = n_keypoints

@@ -17,7 +17,7 @@ import torch
 from chainer_maskrcnn import _hip
 from chainer_maskrcnn._hip import lib, check, ptr, stream_ptr, ops
 from chainer_maskrcnn._hip.nn import workspace
-from chainer_maskrcnn.nn.core import Conv, ParamStore, normal, pad_to
+from chainer_maskrcnn.nn.core import Conv, GroupNorm, ParamStore, normal, pad_to
 
 
 def _level_args(xs, scales):
@@ -119,12 +119,22 @@ class FPNRoIMaskHead(object):
 
     def __init__(self, n_class, roi_size_box, roi_size_mask, loc_initialW=None, score_initialW=None,
                  mask_initialW=None, ps=None, prefix='head', in_channels=256, fc_channels=1024,
-                 n_mask_convs=4, mask_out_channels=None, upsample2x=False, mask_conv_names=None):
+                 n_mask_convs=4, mask_out_channels=None, upsample2x=False, mask_conv_names=None, norm=None, gn_groups=32):
+        """norm: None = the reference's conv + ReLU stacks; 'gn' = conv1 and every mask convolution are followed by a GroupNorm of
+        ``gn_groups`` groups with the ReLU behind it (Detectron's *_gn heads).  The parameters ``<conv>/gn/gamma``,
+        ``<conv>/gn/beta`` are registered directly after their convolution; every other parameter keeps its name and shape."""
+        if norm not in (None, 'gn'):
+            raise ValueError("norm must be None or 'gn', got %r" % (norm,))
         self.ps = ps if ps is not None else ParamStore()
         self.n_class, self.roi_size_box, self.roi_size_mask = n_class, roi_size_box, roi_size_mask
         c = in_channels
+        if norm == 'gn' and (gn_groups < 1 or c % gn_groups != 0):
+            raise ValueError('gn_groups = %d does not divide the %d channels of the head' % (gn_groups, c))
+        self.norm = norm
+        gn = norm == 'gn'
         p = prefix + '/'
-        self.conv1 = Conv(self.ps, p + 'conv1', c, c, 3, 1, 1, relu=True, fwd_tile=0)
+        self.conv1 = Conv(self.ps, p + 'conv1', c, c, 3, 1, 1, relu=not gn, fwd_tile=0)
+        self.gn1 = GroupNorm(self.ps, p + 'conv1/gn', c, gn_groups) if gn else None
         self.fc1 = Conv(self.ps, p + 'fc1', c * roi_size_box * roi_size_box, fc_channels, relu=True)
         self.fc2 = Conv(self.ps, p + 'fc2', fc_channels, fc_channels, relu=True)
         # fused [score | loc] linear layer
@@ -137,7 +147,10 @@ class FPNRoIMaskHead(object):
                             init=lambda shape: (lambda rs: np.concatenate([si(rs), li(rs)], 0)))
         mi = 0.01 if mask_initialW is None else mask_initialW
         names = mask_conv_names or ['mask%d' % (i + 1) for i in range(n_mask_convs)]
-        self.mask_convs = [Conv(self.ps, p + nm, c, c, 3, 1, 1, relu=True, fwd_tile=0) for nm in names]
+        self.mask_convs, self.mask_gns = [], []
+        for nm in names:
+            self.mask_convs.append(Conv(self.ps, p + nm, c, c, 3, 1, 1, relu=not gn, fwd_tile=0))
+            self.mask_gns.append(GroupNorm(self.ps, p + nm + '/gn', c, gn_groups) if gn else None)
         self.mask_out_channels = (n_class - 1) if mask_out_channels is None else mask_out_channels
         self.upsample2x = upsample2x
         # deconv1: W (Cin, Cout, 2, 2) in Chainer == 1x1 conv weight ((a*2+b)*Cout + o, Cin); bias added by the shuffle
@@ -155,22 +168,28 @@ class FPNRoIMaskHead(object):
     def box_branch(self, xs, rois_xy5, levels, spatial_scales):
         pool = roi_align_fpn_fwd(xs, rois_xy5, levels, self.roi_size_box, spatial_scales)
         h, t1 = self.conv1.fwd(pool)
+        n1 = None
+        if self.gn1 is not None:
+            h, n1 = self.gn1.fwd(h, relu=True)
         R = h.shape[0]
         h, t2 = self.fc1.fwd(h.view(R, 1, 1, -1))
         h, t3 = self.fc2.fwd(h)
         o, t4 = self.box_out.fwd(h)
         from chainer_maskrcnn.nn import core
         plan = _plan_beside_forward(xs, rois_xy5, levels, self.roi_size_box, spatial_scales) if core.TRAIN else None
-        self.box_tape = (t1, t2, t3, t4, tuple(pool.shape), rois_xy5, levels, spatial_scales, plan)
+        self.box_tape = ((t1, n1), t2, t3, t4, tuple(pool.shape), rois_xy5, levels, spatial_scales, plan)
         self.last_box_out = o.view(R, self.out_p)
         return o.view(R, self.out_p)          # [:, :n_class] scores, [:, LOC0:LOC0+4] loc
 
     def mask_branch(self, xs, rois_xy5, levels, spatial_scales):
         pool = roi_align_fpn_fwd(xs, rois_xy5, levels, self.roi_size_mask, spatial_scales)
         h, tapes = pool, []
-        for cv in self.mask_convs:
+        for cv, gn in zip(self.mask_convs, self.mask_gns):
             h, t = cv.fwd(h)
-            tapes.append(t)
+            nt = None
+            if gn is not None:
+                h, nt = gn.fwd(h, relu=True)
+            tapes.append((t, nt))
         if self.merge_deconv:
             m, td, t2 = self._merged_deconv_fwd(h)
         else:
@@ -228,7 +247,7 @@ class FPNRoIMaskHead(object):
         hnn.LOGICAL = (dc.cin, 4 * c2.cout)
         try:
             G, gb4 = hnn.conv2d_bwd_filter_raw(x_in, g4, tuple(wm.shape), 1, 0, True)
-            # x_in is the ReLU output of the last mask conv: its ReLU backward is fused here
+            # x_in is the ReLU output of the last mask conv (of its GroupNorm): its ReLU backward is fused here
             g = hnn.conv2d_bwd_data_raw(g4, wm, tuple(x_in.shape), 1, 0, relu_x=x_in if self.mask_convs else None)
         finally:
             hnn.LOGICAL = None
@@ -266,13 +285,16 @@ class FPNRoIMaskHead(object):
             self.backward_mask_pool(self.backward_mask_convs(g_mask), g_feats)
 
     def backward_box(self, g_box_out, g_feats, accumulate=False):
-        t1, t2, t3, t4, pool_shape, rois, levels, scales, plan = self.box_tape
+        (t1, n1), t2, t3, t4, pool_shape, rois, levels, scales, plan = self.box_tape
         R = g_box_out.shape[0]
         # every layer's input is the ReLU output of the layer below: the ReLU backward rides in the data-gradient epilogue
         g = self.box_out.bwd(t4, g_box_out.view(R, 1, 1, -1), mask_gx=True)
         g = self.fc2.bwd(t3, g, gy_masked=True, mask_gx=True)
         g = self.fc1.bwd(t2, g, gy_masked=True, mask_gx=True)
-        g = self.conv1.bwd(t1, g.view(pool_shape), gy_masked=True)
+        g = g.view(pool_shape)
+        if self.gn1 is not None:                # fc1's epilogue masked g on the GroupNorm's output
+            g = self.gn1.bwd(n1, g, gy_masked=True)
+        g = self.conv1.bwd(t1, g, gy_masked=True)
         # accumulate: g_feats already hold a gradient (the RPN's, computed early) - the backward then only touches the patches RoIs land on
         roi_align_fpn_bwd(g, g_feats, rois, levels, self.roi_size_box, scales, accumulate=accumulate, plan=plan)
         self.box_tape = None
@@ -287,7 +309,10 @@ class FPNRoIMaskHead(object):
             g = self._merged_deconv_bwd(td, g_mask)
             n = len(self.mask_convs)
             for i in range(n - 1, -1, -1):          # inputs of convs 1.. are ReLU outputs; conv 0 reads the pooled features
-                g = self.mask_convs[i].bwd(tapes[i], g, gy_masked=True, mask_gx=(i > 0))
+                t, nt = tapes[i]
+                if self.mask_gns[i] is not None:    # the layer above masked g on this GroupNorm's output
+                    g = self.mask_gns[i].bwd(nt, g, gy_masked=True)
+                g = self.mask_convs[i].bwd(t, g, gy_masked=True, mask_gx=(i > 0))
             return g
         g = self.conv2.bwd(tc2, g_mask)
         # deconv bias gradient = column sums of g over all output pixels: the filter-gradient call on the shuffled
@@ -303,7 +328,9 @@ class FPNRoIMaskHead(object):
         ops.add(gb, gb4[2 * C:3 * C], out=gb)
         ops.add(gb, gb4[3 * C:4 * C], out=gb)
         g = hnn.conv2d_bwd_data_raw(g4, self.deconv1.W, tuple(x_in.shape), 1, 0)
-        for cv, t in zip(reversed(self.mask_convs), reversed(tapes)):
+        for cv, gn, (t, nt) in zip(reversed(self.mask_convs), reversed(self.mask_gns), reversed(tapes)):
+            if gn is not None:                      # nothing above masked g: the GroupNorm recomputes its ReLU mask from x
+                g = gn.bwd(nt, g)
             g = cv.bwd(t, g)
         return g
 

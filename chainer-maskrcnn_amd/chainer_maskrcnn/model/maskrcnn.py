@@ -30,9 +30,16 @@ class MaskRCNN(object):
     def __init__(self, n_fg_class, n_keypoints=None, n_mask_convs=None, pretrained_model=None, min_size=600,
                  max_size=1000, ratios=[0.5, 1, 2], anchor_scales=[8], rpn_initialW=None, loc_initialW=None,
                  score_initialW=None, proposal_creator_params={}, backbone='fpn', head_arch='fpn',
-                 device='cuda', seed=1234, _test_shrink=None):
+                 device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32):
+        """head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
+        convolution of the 'fpn' / 'fpn_keypoint' heads."""
         if n_fg_class is None:
             raise ValueError('The n_fg_class needs to be supplied as an argument')
+        if head_norm not in (None, 'gn'):
+            raise ValueError("head_norm must be None or 'gn', got %r" % (head_norm,))
+        if head_norm is not None and head_arch in ('res5', 'light'):
+            raise ValueError("head_norm=%r exists for head_arch 'fpn' and 'fpn_keypoint' only, not %r" % (head_norm, head_arch))
+        self.head_norm, self.gn_groups = head_norm, int(gn_groups)
         self.ps = ParamStore()
         shrink = _test_shrink or {}
         if backbone == 'fpn':
@@ -73,7 +80,7 @@ class MaskRCNN(object):
         elif head_arch == 'fpn':
             self.head = FPNRoIMaskHead(n_fg_class + 1, roi_size_box=7, roi_size_mask=14, loc_initialW=loc_initialW,
                                        score_initialW=score_initialW, mask_initialW=0.01, ps=self.ps, in_channels=c,
-                                       fc_channels=1024 // shrink.get('width_div', 1))
+                                       fc_channels=1024 // shrink.get('width_div', 1), norm=head_norm, gn_groups=self.gn_groups)
             self.predict_mask = True
         elif head_arch == 'fpn_keypoint':
             if n_keypoints is None:
@@ -82,7 +89,8 @@ class MaskRCNN(object):
             self.head = FPNRoIKeypointHead(2, n_keypoints, roi_size_box=7, roi_size_mask=14,
                                            n_mask_convs=8 if n_mask_convs is None else n_mask_convs,
                                            loc_initialW=loc_initialW, score_initialW=score_initialW, mask_initialW=0.01,
-                                           ps=self.ps, in_channels=c, fc_channels=1024 // shrink.get('width_div', 1))
+                                           ps=self.ps, in_channels=c, fc_channels=1024 // shrink.get('width_div', 1), norm=head_norm,
+                                           gn_groups=self.gn_groups)
             self.predict_mask = False
         else:
             raise ValueError('unknown head archtecture specified. {}'.format(head_arch))

@@ -384,6 +384,41 @@ class BatchNorm(object):
         return gx, gres
 
 
+class GroupNorm(object):
+    """GroupNorm (Wu & He 2018; eps 1e-5) of the RoI heads: ``c`` logical channels, zero-padded like the convolution above, in
+    ``groups`` groups; statistics per RoI and group, the same in training and inference."""
+
+    def __init__(self, ps, name, c, groups=32):
+        if groups < 1 or c % groups != 0:
+            raise ValueError('GroupNorm %s: %d groups do not divide %d channels' % (name, groups, c))
+        self.ps, self.name, self.c, self.groups = ps, name, c, groups
+        self.c_p = pad_to(c, 32)
+
+        def ones(rs):
+            g = np.zeros((self.c_p,), np.float32)
+            g[:c] = 1.0
+            return g
+        ps.register(name + '/gamma', (self.c_p,), ones)
+        ps.register(name + '/beta', (self.c_p,), lambda rs: np.zeros((self.c_p,), np.float32))
+
+    def fwd(self, x, relu=False):
+        """Returns (y, ctx); ctx = (x, mean, rstd, relu), None in evaluation mode (no statistics are kept).  y is not kept: the next
+        layer's tape holds it."""
+        gamma, beta = self.ps.p(self.name + '/gamma'), self.ps.p(self.name + '/beta')
+        y, mean, rstd = ops.group_norm_fwd(x, gamma, beta, self.c, self.groups, relu=relu, want_stats=TRAIN)
+        return y, ((x, mean, rstd, relu) if TRAIN else None)
+
+    def bwd(self, ctx, gy, gy_masked=False, accumulate_params=False):
+        """gy_masked: the producer of gy already zeroed it where this layer's ReLU output is <= 0 (its data-gradient epilogue ran with
+        mask_gx on the tensor this layer produced); otherwise the mask of a ReLU layer is recomputed from x.  The parameter gradients go
+        straight into the flat gradient buffer."""
+        x, mean, rstd, relu = ctx
+        gx, _, _ = ops.group_norm_bwd(gy, x, self.ps.p(self.name + '/gamma'), self.ps.p(self.name + '/beta'), mean, rstd, self.c,
+                                      self.groups, relu=bool(relu) and not gy_masked, gg=self.ps.g(self.name + '/gamma'),
+                                      gb=self.ps.g(self.name + '/beta'), accumulate_params=accumulate_params)
+        return gx
+
+
 class Bottleneck(object):
     """ResNet bottleneck (Chainer BottleneckA when ``project`` else BottleneckB):
     relu(bn3(conv3(relu(bn2(conv2 3x3(relu(bn1(conv1 1x1/s))))))) + shortcut), stride on the first 1x1."""

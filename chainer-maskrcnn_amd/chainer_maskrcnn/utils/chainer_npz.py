@@ -3,7 +3,9 @@
 The reference snapshots ``model.faster_rcnn`` with ``chainer.serializers.save_npz`` (train.py:134-137) and loads
 with ``load_npz(..., strict=False)`` (train.py:99-101).  NPZ keys are Chainer link paths; arrays use Chainer's
 layouts:  Convolution2D W (Cout, Cin, KH, KW), Linear W (out, in) with the input flattened (C, H, W)-major,
-Deconvolution2D W (Cin, Cout, KH, KW), BatchNormalization gamma / beta / avg_mean / avg_var / N.
+Deconvolution2D W (Cin, Cout, KH, KW), BatchNormalization gamma / beta / avg_mean / avg_var / N.  The GroupNorm layers of a
+``head_norm='gn'`` model (no counterpart in the reference) go out as GroupNormalization gamma / beta (C,) under their store names
+``head/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.
 
 Storage here differs only mechanically - conv W (Cout_p, KH, KW, Cin_p) with zero-padded channels, NHWC
 flattening for ``fc1``, ``rpn/loc`` + ``rpn/score`` fused into ``rpn/loc_score``, ``head/cls_loc`` + ``head/score``
@@ -50,6 +52,7 @@ class ChainerNpzMap(object):
                    rpn.conv, head.conv1, head.fc2, head.conv2) + tuple(head.mask_convs):
             self._add_conv(cv)
         self.rpn, self.head = rpn, head
+        self.gns = [g for g in [getattr(head, 'gn1', None)] + list(getattr(head, 'mask_gns', [])) if g is not None]
 
     def _add_conv(self, cv):
         self.convs[cv.name] = cv
@@ -73,6 +76,9 @@ class ChainerNpzMap(object):
             for k in ('avg_mean', 'avg_var'):
                 out['%s/%s' % (bn.name, k)] = self.ps.buffers['%s/%s' % (bn.name, k)].cpu().numpy().copy()
             out[bn.name + '/N'] = np.array(0)
+        for gn in self.gns:             # logical channels only
+            for k in ('gamma', 'beta'):
+                out['%s/%s' % (gn.name, k)] = g('%s/%s' % (gn.name, k))[:gn.c].copy()
         A = self.rpn.n_anchor
         w = g(self.rpn.head.name + '/W')[:, 0, 0, :self.rpn.head.cin]
         b = g(self.rpn.head.name + '/b')
@@ -130,6 +136,12 @@ class ChainerNpzMap(object):
                 key = '%s/%s' % (bn.name, k)
                 if have(key):
                     put(key, arrays[key])
+                    loaded.append(key)
+        for gn in self.gns:             # the padding comes back as zeros
+            for k in ('gamma', 'beta'):
+                key = '%s/%s' % (gn.name, k)
+                if have(key):
+                    put(key, _vec_to_native(np.asarray(arrays[key]), gn.c_p))
                     loaded.append(key)
         A = self.rpn.n_anchor
         if have('rpn/loc/W', 'rpn/score/W', 'rpn/loc/b', 'rpn/score/b'):

@@ -997,6 +997,32 @@ int mrcnn_class_soft_nms_f32(const float *cls_bbox, const float *prob, int R, in
 int mrcnn_box_vote_f32(const float *cls_bbox, const float *prob, int R, int n_class, int l_begin, int l_end, float score_thresh,
                        float vote_thresh, const int32_t *keep_idx, const int32_t *keep_cnt, float *keep_box, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GroupNorm of the RoI heads (groupnorm.hip, gn_common.h; nn/core.py GroupNorm).  float32, NHWC (R,H,W,Cp): C logical
+ * channels zero-padded to Cp, G groups of cpg = C / G channels, statistics per (sample r, group g) over n = H * W * cpg elements:
+ *   mean = sum(x) / n, var = sum((x - mean)^2) / n (biased, taken about the mean: no E[x^2] - E[x]^2), rstd = 1.0f / sqrtf(var + eps).
+ * group_norm_fwd: y = gamma[c] * ((x - mean) * rstd) + beta[c], relu != 0: max(y, 0).  Channels c >= C of y are written as exact zeros.
+ *   mean, rstd (R,G): written when not NULL (training); each may be NULL.
+ * group_norm_bwd: with xh = (x - mean) * rstd, dz = gy (relu 0: also a gy that arrives masked) or gy where the forward's
+ *   gamma * xh + beta > 0, else 0 (relu 1: the mask recomputed from x, the bits of the forward's y > 0), gt = dz * gamma:
+ *   gx = rstd * (gt - sum_g(gt) / n - xh * (sum_g(gt * xh) / n)), the sums over the group of the sample; channels c >= C as exact zeros.
+ *   ggamma[c] = sum over r, h, w of dz * xh, gbeta[c] = sum of dz, (Cp) each, written (accumulate_params 0) or added to what is there
+ *   (1); channels c >= C receive 0.  ws: the per-sample partial rows, bwd_ws_bytes of the plan query, summed over r in a fixed order:
+ *   no float atomics, the same input gives the same bits on every run.
+ * group_norm_plan: host arithmetic only.  path (nullable): 0 = the register-resident kernels (cpg 1, 2 or a multiple of 4 up to 256, and
+ *   H * W up to 8 * (256 / cols) with cols = 8 float4 columns per workgroup where cpg divides 32, else cpg / 4: 256 pixels for the head's
+ *   cpg 8), which read x (and gy) once; 1 = the generic kernels, which re-read them.  bwd_ws_bytes (nullable) = 2 * R * Cp * 4.
+ * x, y, gy, gx, gamma, beta, ggamma, gbeta and ws 16-byte aligned.  R == 0 succeeds without a launch.  Errors, before any launch:
+ * MRCNN_E_INVALID for G not dividing C, Cp < C, Cp % 4 != 0, a non-positive H, W, C, G or eps, a negative R, H * W * Cp above 2^31 - 1,
+ * a relu outside 0..1, a NULL or misaligned pointer, a workspace too small.
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_group_norm_plan(int R, int H, int W, int C, int Cp, int G, int *path, size_t *bwd_ws_bytes);
+int mrcnn_group_norm_fwd_f32(const float *x, const float *gamma, const float *beta, int R, int H, int W, int C, int Cp, int G, float eps,
+                             int relu, float *y, float *mean, float *rstd, void *stream);
+int mrcnn_group_norm_bwd_f32(const float *gy, const float *x, const float *gamma, const float *beta, const float *mean, const float *rstd,
+                             int R, int H, int W, int C, int Cp, int G, int relu, float *gx, float *ggamma, float *gbeta,
+                             int accumulate_params, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,8 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_tta_flags, boxpost_settings, read_labels, tta_settings,  # noqa: E402,F401
-                                                use_boxpost, use_tta)
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_head_norm_flags, add_tta_flags, boxpost_settings,  # noqa: E402,F401
+                                                head_norm_settings, read_labels, tta_settings, use_boxpost, use_tta)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
@@ -126,6 +126,7 @@ def build_parser(keypoints=False):
                         help='Simple Copy-Paste on top of --lsj-size: with probability P an example receives a random half of the instances '
                              'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
                              'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
+    add_head_norm_flags(parser, both)
     return parser
 
 
@@ -281,6 +282,7 @@ def run(args, keypoints=False):
     if resume is not None and resume.get('augment', NO_AUGMENT) != augment_settings(args):
         raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
                          % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
+    head_norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
     freeze = freeze_settings(args)
     if resume is not None:
         check_resume_freeze(resume, args, args.resume)
@@ -328,7 +330,7 @@ def run(args, keypoints=False):
         n_fg, K = 1, 20 if args.dataset == 'depth' else 17          # DepthDataset.n_keypoints / COCOKeypointsLoader.n_keypoints
         labels = None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, n_keypoints=K, backbone=args.backbone, head_arch=args.head_arch, n_mask_convs=args.n_mask_convs,
-                               min_size=args.min_size, max_size=args.max_size, device=dev)
+                               min_size=args.min_size, max_size=args.max_size, device=dev, **head_norm)
         loss_fun = calc_keypoint_loss
         if K != 17:         # train_keypoints.py:122: lambda x, y, z, w: calc_mask_loss(x, y, z, w, num_keypoints=n_keypoints)
             loss_fun = lambda x, y, z, w: calc_keypoint_loss(x, y, z, w, num_keypoints=K)
@@ -337,7 +339,7 @@ def run(args, keypoints=False):
     else:
         labels = read_labels(args.label_file)
         n_fg, K = len(labels) if labels else 80, None
-        faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev)
+        faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, **head_norm)
         model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic)
     faster_rcnn.use_preset('evaluate')
     if args.resnet50_npz:           # ImageNet initialisation of the bottom-up pathway (before --weight, which may override it)
