@@ -133,6 +133,9 @@ def ptr(t):
 
 
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+# MRCNN_BOX_LOSS_* of include/mrcnn_hip.h: the kinds of mrcnn_box_iou_loss_f32 (ops.box_iou_loss), by the name the training chain takes
+BOX_LOSS_GIOU, BOX_LOSS_DIOU, BOX_LOSS_CIOU = 1, 2, 3
+BOX_LOSS_KINDS = {'giou': BOX_LOSS_GIOU, 'diou': BOX_LOSS_DIOU, 'ciou': BOX_LOSS_CIOU}
 
 
 # ---- host structs of the composite entry points (include/mrcnn_hip.h, ABI v9) --------------------------------------------------------

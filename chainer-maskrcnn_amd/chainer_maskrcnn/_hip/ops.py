@@ -564,6 +564,31 @@ def smooth_l1(x, ldx, t, label, M, sigma, want_grad=True, gfill=0, col0=0, gx=No
     return out, gx
 
 
+def box_iou_loss(x, ldx, t, rois, label, M, kind, mean, std, weight=1.0, roi_period=None, want_grad=True, gfill=0, col0=0, gx=None,
+                 out=None):
+    """GIoU / DIoU / CIoU on the decoded box (mrcnn_box_iou_loss_f32), with the buffers of ``smooth_l1``: x is an (M, ldx) buffer whose
+    4 predicted deltas of row r start at column col0, t (M,4) the encoded targets, rois (roi_period,4) the boxes both are relative to
+    (row r: rois[r % roi_period]; roi_period None = rois.shape[0]), mean / std the 4 normalisation constants of the encoding.  kind: a
+    key of _hip.BOX_LOSS_KINDS or its value.  gx (same buffer shape) receives columns [col0, col0+max(4,gfill))."""
+    _ck(x, t, rois, label, gx)
+    kind = _hip.BOX_LOSS_KINDS.get(kind, kind)
+    if roi_period is None:
+        roi_period = rois.shape[0]
+    if M > 0 and rois.numel() < 4 * roi_period:
+        raise ValueError('box_iou_loss: rois holds %d boxes, roi_period is %d' % (rois.numel() // 4, roi_period))
+    out = _empty((2,), x.device) if out is None else out
+    if want_grad and gx is None:
+        gx = torch.empty_like(x)
+    ws = _loss_ws(x.device)
+    xp = ctypes.c_void_p(x.data_ptr() + 4 * col0)
+    gp = ctypes.c_void_p(gx.data_ptr() + 4 * col0) if want_grad else None
+    f4 = ctypes.c_float * 4
+    check(lib().mrcnn_box_iou_loss_f32(xp, ldx, ptr(t), ptr(rois), int(roi_period), ptr(label), M, int(kind), f4(*[float(v) for v in mean]),
+                                       f4(*[float(v) for v in std]), float(weight), ptr(out), gp, ldx, gfill, ptr(ws), ws.numel(),
+                                       stream_ptr()))
+    return out, gx
+
+
 def mask_bce(x, gt, label, want_grad=True, out=None):
     """x (Rm,H,W,Cm) NHWC logits, gt (Rm,H,W) int32, label (Rm,) int32."""
     _ck(x, gt, label)

@@ -112,6 +112,24 @@ GEMM_ARITHMETIC = {'f32': ((0, 0, 0), True), 'bf16x6_behind_backbone': ((3, 3, 3
                    'bf16x6': ((3, 3, 3), True)}
 DEFAULT_GEMM_ARITHMETIC = 'bf16x6_behind_backbone'
 
+# Box regression losses of the chain (box_loss, rpn_box_loss): the reference's smooth L1 on the encoded deltas, or an IoU loss on the decoded
+# box (the kinds of ops.box_iou_loss)
+BOX_LOSSES = ('smooth_l1', 'giou', 'diou', 'ciou')
+
+
+def box_loss_settings(box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0):
+    """The four box-loss arguments of FPNMaskRCNNTrainChain as a dict, checked (the constructor and train.py's flags share the rule):
+    ValueError for a name outside BOX_LOSSES, a weight that is not a finite number above 0, a weight other than 1.0 with 'smooth_l1'."""
+    for arg, name, weight in (('box_loss', box_loss, box_loss_weight), ('rpn_box_loss', rpn_box_loss, rpn_box_loss_weight)):
+        if name not in BOX_LOSSES:
+            raise ValueError('%s must be one of %s, got %r' % (arg, list(BOX_LOSSES), name))
+        if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
+            raise ValueError('%s_weight must be a finite number above 0, got %r' % (arg, weight))
+        if name == 'smooth_l1' and weight != 1.0:
+            raise ValueError("%s_weight applies to giou / diou / ciou; %s='smooth_l1' takes 1.0 only, got %r" % (arg, arg, weight))
+    return dict(box_loss=box_loss, rpn_box_loss=rpn_box_loss, box_loss_weight=float(box_loss_weight),
+                rpn_box_loss_weight=float(rpn_box_loss_weight))
+
 
 def select_gemm_arithmetic(name):
     """Process-wide: the library's split-operand modes and the per-layer rule of nn/core.py."""
@@ -130,10 +148,19 @@ class FPNMaskRCNNTrainChain(object):
     ACCUMULATE_INTO_EARLY_RPN = True
 
     def __init__(self, faster_rcnn, mask_loss_fun=calc_mask_loss, binary_mask=True, rpn_sigma=3., roi_sigma=1.,
-                 anchor_target_creator=None, strict_batch1=False, mask_rows='positives', gemm_arithmetic=None):
+                 anchor_target_creator=None, strict_batch1=False, mask_rows='positives', gemm_arithmetic=None,
+                 box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0):
         """gemm_arithmetic: a key of GEMM_ARITHMETIC - the chain then selects it (process-wide library setting) at the start of every
         step; None (default of this constructor, used by the kernel-level tests) leaves the process setting alone.  train.py and
-        bench.py pass DEFAULT_GEMM_ARITHMETIC."""
+        bench.py pass DEFAULT_GEMM_ARITHMETIC.
+
+        box_loss / rpn_box_loss: the box regression loss of the RoI head / the RPN, one of BOX_LOSSES.  'smooth_l1' (default) is the
+        reference's loss on the encoded deltas; 'giou', 'diou', 'ciou' decode prediction and target against the sampled RoI / the anchor
+        and take the loss on the boxes (ops.box_iou_loss) - same targets, same normaliser, same report keys.
+        box_loss_weight / rpn_box_loss_weight multiply that loss and its gradient; smooth L1 takes no weight (1.0 only)."""
+        box_loss_settings(box_loss, rpn_box_loss, box_loss_weight, rpn_box_loss_weight)
+        self.box_loss, self.rpn_box_loss = box_loss, rpn_box_loss
+        self.box_loss_weight, self.rpn_box_loss_weight = float(box_loss_weight), float(rpn_box_loss_weight)
         if gemm_arithmetic is not None and gemm_arithmetic not in GEMM_ARITHMETIC:
             raise ValueError('gemm_arithmetic must be one of %s' % sorted(GEMM_ARITHMETIC))
         self.gemm_arithmetic = gemm_arithmetic
@@ -224,8 +251,13 @@ class FPNMaskRCNNTrainChain(object):
             aux.wait_stream(main)
             with torch.cuda.stream(aux):
                 br1['loc'], br1['label'] = self.anchor_target_creator(bboxes, anchors, img_size, n_gt=n_gt, keys=ak, per_image_hw=per_hw)
-                _, br1['g_locs'] = ops.smooth_l1(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), br1['label'].view(-1),
-                                                 n * A_, self.rpn_sigma, out=losses[0])
+                if self.rpn_box_loss == 'smooth_l1':
+                    _, br1['g_locs'] = ops.smooth_l1(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), br1['label'].view(-1),
+                                                     n * A_, self.rpn_sigma, out=losses[0])
+                else:   # on the decoded box: every image's rows are relative to the shared anchors; the RPN's targets are not normalised
+                    _, br1['g_locs'] = ops.box_iou_loss(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), anchors, br1['label'].view(-1),
+                                                        n * A_, self.rpn_box_loss, (0., 0., 0., 0.), (1., 1., 1., 1.),
+                                                        weight=self.rpn_box_loss_weight, roi_period=A_, out=losses[0])
                 _, br1['g_scores'] = ops.softmax_ce(scores.view(n * A_, 2), br1['label'].view(-1), n * A_, 2, (1, 2, 0, 1),
                                                     out=losses[1])
                 # The RPN's own backward pass needs nothing but these two gradients: when a backward pass is known to follow
@@ -262,8 +294,13 @@ class FPNMaskRCNNTrainChain(object):
             ld = head.out_p
             g_box = torch.empty_like(box)
             ops.softmax_ce(box, t['gt_roi_label'], R, head.n_class, (1, ld, 0, 1), Kfill=head.LOC0, gx=g_box, out=losses[3])
-            ops.smooth_l1(box, ld, t['gt_roi_loc'], t['gt_roi_label'], R, self.roi_sigma, gfill=ld - head.LOC0,
-                          col0=head.LOC0, gx=g_box, out=losses[2])
+            if self.box_loss == 'smooth_l1':
+                ops.smooth_l1(box, ld, t['gt_roi_loc'], t['gt_roi_label'], R, self.roi_sigma, gfill=ld - head.LOC0,
+                              col0=head.LOC0, gx=g_box, out=losses[2])
+            else:       # on the decoded box, against the sampled RoI the targets were encoded with
+                ops.box_iou_loss(box, ld, t['gt_roi_loc'], t['sample_roi'], t['gt_roi_label'], R, self.box_loss, self.loc_normalize_mean,
+                                 self.loc_normalize_std, weight=self.box_loss_weight, roi_period=R, gfill=ld - head.LOC0, col0=head.LOC0,
+                                 gx=g_box, out=losses[2])
 
         rows = t['mask_rows']
         if self.mask_loss_kind == 'generic':

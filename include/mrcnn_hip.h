@@ -566,6 +566,38 @@ int mrcnn_scale_by_dev_f32(float *x, size_t n, const float *scale, void *stream)
 int mrcnn_loss_total_f32(const float *losses, int n, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * IoU-based box regression losses on the DECODED box (box_loss.hip; no counterpart in the reference, which has the smooth L1 on the
+ * encoded deltas only).  A drop-in for mrcnn_smooth_l1_f32: same predictions, targets, labels, normaliser and gradient-buffer contract.
+ *   x (M, ldx >= 4): the predicted deltas of row r at x[r * ldx .. + 4) (the caller offsets the pointer to its first loc column)
+ *   t (M,4): the encoded, normalised targets of the target creators
+ *   rois (roi_period,4) (y1,x1,y2,x2): row r is relative to rois[r % roi_period] (the head: roi_period = M, the sampled RoIs; the RPN:
+ *     roi_period = A, the anchors every image of the batch shares)
+ *   label (M) int32: rows with label > 0 carry loss; the normaliser is #(label >= 0), at least 1
+ *   mean4, std4: HOST arrays of 4 floats, read during the call: d = v * std + mean for predictions and targets alike
+ * Both boxes are decoded with the arithmetic of mrcnn_detect_decode_f32 without un-scaling and clipping: centre = d_yx * size + centre,
+ * size = expf(d_hw) * size, corners = centre -+ size / 2.  The PREDICTED d_h, d_w are clamped above at log(1000 / 16) before expf: a
+ * clamped coordinate has gradient exactly 0, a coordinate at the bound itself passes it; the target is not clamped.  With eps = 1e-7, P the
+ * prediction, G the target, ih = max(0, min(P.y2, G.y2) - max(P.y1, G.y1)) (iw likewise), inter = ih * iw, union = aP + aG - inter + eps,
+ * iou = inter / union, ch and cw the sides of the enclosing box:
+ *   MRCNN_BOX_LOSS_GIOU  L = 1 - iou + (ch * cw - union) / (ch * cw + eps)
+ *   MRCNN_BOX_LOSS_DIOU  L = 1 - iou + rho2 / (ch^2 + cw^2 + eps), rho2 = the squared distance of the two centres
+ *   MRCNN_BOX_LOSS_CIOU  DIoU + alpha * v, v = 4 / pi^2 * (atan(wG / (hG + eps)) - atan(wP / (hP + eps)))^2, alpha = v / (1 - iou + v + eps)
+ *                        taken as a constant in the gradient
+ * loss_out[0] = weight * (sum of L over the rows with label > 0) / count, loss_out[1] = count.  gx (nullable; row stride ldg):
+ * gx[r * ldg .. + 4) = d loss / d x for d loss = 1 (weight and 1 / count included), zeros in rows with label <= 0; columns 4 .. gfill - 1
+ * of every row are zero-filled and nothing outside [0, max(4, gfill)) of a row is written.  A tie of a min / max splits the derivative
+ * evenly; the overlap's clamp at 0 passes it where the overlap is positive.  ws: mrcnn_loss_workspace_bytes() bytes.
+ * Three launches (block partials, fixed-order finalize, gradient; two without gx), no float atomics: bit-identical from run to run.  No
+ * host synchronisation, no allocation.  M == 0 writes loss 0, count 1.  Errors, before any launch: MRCNN_E_INVALID for M > 0 with a NULL
+ * x / t / rois / label, M < 0, ldx < 4, roi_period <= 0, a kind outside 1..3, a NULL loss_out / ws / mean4 / std4, ldg below
+ * max(4, gfill) with gx given; MRCNN_E_WORKSPACE for a short workspace.
+ * ---------------------------------------------------------------------------------------- */
+enum { MRCNN_BOX_LOSS_GIOU = 1, MRCNN_BOX_LOSS_DIOU = 2, MRCNN_BOX_LOSS_CIOU = 3 };
+int mrcnn_box_iou_loss_f32(const float *x, int ldx, const float *t, const float *rois, int roi_period, const int32_t *label, int M,
+                           int kind, const float *mean4, const float *std4 /* host */, float weight, float *loss_out, float *gx, int ldg,
+                           int gfill, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * RPN proposal path (rpn.hip).  Replaces the transposes/concats and the ChainerCV ProposalCreator +
  * non_maximum_suppression + map_rois_to_fpn_levels calls of
  * chainer_maskrcnn/model/rpn/multilevel_region_proposal_network.py:16-31,133-164.

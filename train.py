@@ -127,6 +127,15 @@ def build_parser(keypoints=False):
                              'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
                              'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
     add_head_norm_flags(parser, both)
+    parser.add_argument(*both('--box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
+                        help='box regression loss of the RoI head: smooth_l1 = the reference\'s, on the encoded deltas; giou / diou / ciou = on '
+                             'the decoded box against the decoded target (FPNMaskRCNNTrainChain box_loss; same targets, normaliser and '
+                             'checkpoints)')
+    parser.add_argument(*both('--rpn-box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
+                        help='the same choice for the RPN, against the anchors')
+    parser.add_argument(*both('--box-loss-weight'), type=float, default=1.0, metavar='W',
+                        help='multiplies the --box-loss giou / diou / ciou value and gradient (smooth_l1 takes 1.0 only)')
+    parser.add_argument(*both('--rpn-box-loss-weight'), type=float, default=1.0, metavar='W', help='the same for --rpn-box-loss')
     return parser
 
 
@@ -260,7 +269,7 @@ def _keypoint_flip_perm(args, data):
 
 def run(args, keypoints=False):
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
-    from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss
+    from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, box_loss_settings, calc_mask_loss, calc_keypoint_loss
     from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay, GradientClipping
     from chainer_maskrcnn.utils.synthetic import make_batch
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -283,6 +292,7 @@ def run(args, keypoints=False):
         raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
                          % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
     head_norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
+    box_loss = box_loss_settings(args.box_loss, args.rpn_box_loss, args.box_loss_weight, args.rpn_box_loss_weight)
     freeze = freeze_settings(args)
     if resume is not None:
         check_resume_freeze(resume, args, args.resume)
@@ -335,12 +345,12 @@ def run(args, keypoints=False):
         if K != 17:         # train_keypoints.py:122: lambda x, y, z, w: calc_mask_loss(x, y, z, w, num_keypoints=n_keypoints)
             loss_fun = lambda x, y, z, w: calc_keypoint_loss(x, y, z, w, num_keypoints=K)
             loss_fun.fused_kind = calc_keypoint_loss.fused_kind
-        model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=loss_fun, binary_mask=False, gemm_arithmetic=args.gemm_arithmetic)
+        model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=loss_fun, binary_mask=False, gemm_arithmetic=args.gemm_arithmetic, **box_loss)
     else:
         labels = read_labels(args.label_file)
         n_fg, K = len(labels) if labels else 80, None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, **head_norm)
-        model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic)
+        model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic, **box_loss)
     faster_rcnn.use_preset('evaluate')
     if args.resnet50_npz:           # ImageNet initialisation of the bottom-up pathway (before --weight, which may override it)
         from chainer_maskrcnn.utils import chainer_npz
