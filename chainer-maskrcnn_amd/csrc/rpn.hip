@@ -130,7 +130,8 @@ __global__ __launch_bounds__(256) void k_decode(const float *__restrict__ locs, 
         x1 = fmaxf(fminf(x1, img_w), 0.f); x2 = fmaxf(fminf(x2, img_w), 0.f);
         *reinterpret_cast<float4 *>(boxes + (size_t)i * 4) = make_float4(y1, x1, y2, x2);
         const bool ok = (y2 - y1 >= min_size) && (x2 - x1 >= min_size);
-        const float sc = scores[(size_t)i * 2 + 1];
+        // -0.0 + 0.0 = +0.0: the oracle's argsort compares the two zeros equal (index decides), orderable() would rank -0.0 lower
+        const float sc = scores[(size_t)i * 2 + 1] + 0.0f;
         // [image N-1-n] | valid | orderable score (32) | anchor index (ib bits): ONE descending sort of all images =>
         // image n's keys land in segment n, ordered (score desc, index desc); invalid keys close their segment
         const u64 img = batched ? (u64)(N - 1 - (int)(i / A)) << (ib + 33) : 0ull;

@@ -102,7 +102,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_proposal_target(
         int arg = 0;
         for (int g = 0; g < G; ++g) {
             const float v = box_iou(b, *reinterpret_cast<const float4 *>(gb + (size_t)g * 4));
-            if (g == 0 || v > best) { best = v; arg = g; }
+            // iou.max(axis=1) / argmax of NumPy: a NaN (0/0: two zero-area boxes) wins over every number and the first NaN stays
+            if (g == 0 || v > best || (v != v && best == best)) { best = v; arg = g; }
         }
         smax[c] = G > 0 ? best : 0.f;
         sarg[c] = (short)arg;

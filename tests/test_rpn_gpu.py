@@ -10,6 +10,7 @@ import torch
 
 from oracle import boxes as ob
 from oracle.proposal import ProposalCreator
+from tests import sampler_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -98,9 +99,11 @@ def _rpn_case(seed, N, feat_shapes, exact):
     return anchors, locs, scores
 
 
-# The top-n_pre selection is a radix select + an in-LDS bitonic sort whose shape depends on n_pre: 8192 keys (8 per thread),
-# 1024 (1 per thread, partner through LDS), 4096 (4 per thread), 128 (fewer threads than the block), and - with the larger
-# pyramid, A = 23,025 anchors - the training size: 12,000 of them in a 16,384-key sort (16 per thread).
+# The top-n_pre selection is a radix select + an in-LDS bitonic sort whose shape depends on np, the power of two >= n_pre (n_pre clamped
+# to A first).  Up to 2048 keys one workgroup sorts (k_sort_desc_lds<np>: 128 for n_pre = 100, 1024 for 600, 2048 for 2048); above that,
+# runs of 2048 keys are sorted and merged by rank (k_merge_runs<np / 2048>: 2 for 2049 and 3000; 4 for the 12000 that this pyramid's
+# A = 7,677 clamps; 8 - with the larger pyramid, A = 23,025 anchors - for the training size 12000 and for 16384).  Every other shape,
+# unclamped n_pre of 4097..8192 among them, is in test_proposals_every_sort_shape below.
 @pytest.mark.parametrize('n_pre,n_post,big', [(12000, 2000, False), (600, 100, False), (3000, 300, False), (100, 20, False),
                                               (12000, 2000, True), (2048, 300, False), (2049, 300, False), (16384, 2000, True)])
 def test_proposals_end_to_end_bit_exact(n_pre, n_post, big):
@@ -150,6 +153,72 @@ def test_proposals_per_image_size_and_scale_equal_separate_calls():
         np.testing.assert_array_equal(got[:nk], want)
         assert got[:nk, 2].max() <= sizes[i, 0] and got[:nk, 3].max() <= sizes[i, 1]
     assert not np.array_equal(o['rois'].cpu().numpy(), ops.rpn_proposals(dl, ds, da, (160, 192), 16.0, n_pre, n_post, 0.7)['rois'].cpu().numpy())
+
+
+# ---- the selection / sort edges of tests/sampler_cases.py (each case's edge is asserted from the oracle in test_sampler_cases_cpu.py) ----
+def _check_rpn_case(c):
+    """n_pre, sorted_anchor, keep, rois, roi_indices and levels of every image against the oracle's, bit for bit."""
+    N, n_eff, n_post = c['locs'].shape[0], c['n_eff'], c['n_post']
+    per = None if c['per_image'] is None else torch.from_numpy(c['per_image']).to(DEV)
+    o = ops.rpn_proposals(torch.from_numpy(c['locs']).to(DEV), torch.from_numpy(c['scores']).to(DEV), torch.from_numpy(c['anchors']).to(DEV),
+                          c['img_size'], c['min_size'], c['n_pre'], n_post, 0.7, debug=True, per_image=per)
+    o = {k: v.cpu().numpy() for k, v in o.items()}
+    for i, w in enumerate(c['want']):
+        npre = int(o['n_pre'][i])
+        assert npre == len(w['pre_nms_index']), (i, npre, len(w['pre_nms_index']))
+        np.testing.assert_array_equal(o['sorted_anchor'].reshape(N, n_eff)[i, :npre], w['pre_nms_index'], err_msg='image %d' % i)
+        nk = int(o['n_rois'][i])
+        assert nk == len(w['rois']), (i, nk, len(w['rois']))
+        np.testing.assert_array_equal(o['keep'].reshape(N, n_post)[i, :nk], w['nms_keep'])
+        got = o['rois'].reshape(N, n_post, 4)[i]
+        np.testing.assert_array_equal(got[:nk], w['rois'])
+        assert np.all(got[nk:] == 0)
+        idx = o['roi_indices'].reshape(N, n_post)[i]
+        assert np.all(idx[:nk] == i) and np.all(idx[nk:] == -1)
+        np.testing.assert_array_equal(o['levels'].reshape(N, n_post)[i, :nk], w['levels'])
+    return o
+
+
+@pytest.mark.parametrize('n_pre', sc.SORT_SHAPES)
+def test_proposals_every_sort_shape(n_pre):
+    """np = 64 .. 2048 in one workgroup (k_sort_desc_lds<64>: n_pre 1, 63, 64; <256>: 256; <512>: 257, 512; <1024>: 513, 1024; <2048>: 1025),
+    sorted runs + k_merge_runs<2> (4096), <4> (4097, 6000, 8192) and <8> (8193), n_pre on and beside every power of two."""
+    _check_rpn_case(sc.rpn_sort_shape(n_pre))
+
+
+@pytest.mark.parametrize('n_pre', [6000, 600])
+def test_proposals_fewer_valid_boxes_than_n_pre_in_a_mixed_batch(n_pre):
+    """Image 0 has more valid boxes than n_pre, image 1 fewer (1 .. 2047: the sort's and the merge's zero-padded tail, the n_valid rule of
+    k_gather_sorted), image 2 none: n_pre = n_rois = 0, all rois 0, roi_indices -1."""
+    c = sc.rpn_mixed_valid(n_pre)
+    o = _check_rpn_case(c)
+    assert o['n_pre'][2] == 0 and o['n_rois'][2] == 0
+    assert not o['rois'].reshape(3, -1)[2].any() and np.all(o['roi_indices'].reshape(3, -1)[2] == -1)
+
+
+def test_proposals_fewer_anchors_than_n_pre():
+    """A = 75 < n_pre = 2000: the entry point clamps n_pre to A; the outputs are the oracle's with n_pre = 75."""
+    _check_rpn_case(sc.rpn_fewer_anchors_than_n_pre())
+
+
+def test_proposals_second_trip_of_the_compaction():
+    """A = 524,288 + 2048 + 37: k_compact_ge's tile loop runs a second trip (256 workgroups x 2048 keys per trip); the 300 best scores sit
+    on both sides of row 524,288, the last row among them."""
+    _check_rpn_case(sc.rpn_second_compaction_trip())
+
+
+@pytest.mark.parametrize('n_pre', [600, 6000])
+@pytest.mark.parametrize('kind', ['equal', 'lowbit'])
+def test_proposals_keys_that_differ_only_in_the_index(kind, n_pre):
+    """Every score equal (positive in image 0, negative in image 1): the radix select walks through all 32 score bits into the index bits
+    and the order is the index, descending.  'lowbit': three score values whose bit patterns are neighbours."""
+    _check_rpn_case(sc.rpn_index_only_keys(kind, n_pre))
+
+
+def test_proposals_special_scores():
+    """+-inf, the largest and smallest normal, denormals of both signs and interleaved +0.0 / -0.0: the order is argsort_desc_pinned's, in
+    which the two zeros are EQUAL and the index decides (k_decode adds +0.0 before orderable(), which would rank -0.0 below +0.0)."""
+    _check_rpn_case(sc.rpn_special_scores())
 
 
 @pytest.mark.parametrize('ci', [0, 1, 2, 3])

@@ -9,6 +9,7 @@ import torch
 
 from oracle import boxes as ob
 from oracle import targets as ot
+from tests import sampler_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -299,3 +300,90 @@ def test_count_valid_labels_exact(N, G):
         got = ops.count_valid_labels(_t(lab)).cpu().numpy()
         assert got.dtype == np.int32
         np.testing.assert_array_equal(got, (lab >= 0).sum(1))
+
+
+# ---- the sampler edges of tests/sampler_cases.py (each case's edge is asserted from the oracle in test_sampler_cases_cpu.py) --------------
+ANCHOR_CASES = [('many_positives', sc.anchor_many_positives), ('few_negatives', sc.anchor_few_negatives),
+                ('equal_keys_zero', lambda: sc.anchor_equal_keys('zero')), ('equal_keys_ones', lambda: sc.anchor_equal_keys('ones')),
+                ('equal_keys_two', lambda: sc.anchor_equal_keys('two')), ('empty_beside_objects', sc.anchor_empty_beside_objects),
+                ('full_gt_cap', sc.anchor_full_gt_cap), ('ties', sc.anchor_ties), ('zero_area_gt', sc.anchor_zero_area_gt),
+                ('border_touch', sc.anchor_border_touch)]
+
+
+@pytest.mark.parametrize('build', [b for _, b in ANCHOR_CASES], ids=[n for n, _ in ANCHOR_CASES])
+def test_anchor_target_edges(build):
+    """Labels before sampling and after the key-driven sampling bit for bit, loc to the file's bar, for: more than 128 positives, fewer
+    negatives than wanted, equal keys (the anchor index decides), images without objects beside one with, gt_cap = G = 256 = AT_GCAP
+    (and 255, 1), tied IoUs (identical boxes, a box equal to an anchor, mirror-image boxes), a zero-area box (every inside anchor turns
+    positive through `ious == gt_max`), A no multiple of 64 with an anchor that touches the image border."""
+    c = build()
+    a, gt, n_gt = _t(c['anchors']), _t(c['gt']), _t(c['n_gt'])
+    loc, label = ops.anchor_target(a, gt, n_gt, c['img_size'], keys=None)
+    np.testing.assert_array_equal(label.cpu().numpy(), c['label_before'])
+    np.testing.assert_allclose(loc.cpu().numpy(), c['loc'], rtol=1e-5, atol=1e-5)
+    loc, label = ops.anchor_target(a, gt, n_gt, c['img_size'], keys=_t(c['keys'].view(np.int32)))
+    np.testing.assert_array_equal(label.cpu().numpy(), c['label'])
+    np.testing.assert_allclose(loc.cpu().numpy(), c['loc'], rtol=1e-5, atol=1e-5)
+
+
+def _check_proposal_target_case(c, n_sample=256):
+    """Everything test_proposal_target_matches_key_driven_oracle compares, plus n_cand and the padding rows, against the case's oracle."""
+    N = len(c['want'])
+    o = ops.proposal_target(_t(c['rois'].reshape(-1, 4)), _t(c['lev'].reshape(-1)), _t(c['n_r']), _t(c['gt']), _t(c['lab']), _t(c['n_gt']),
+                            _t(c['keys'].view(np.int32)), neg_lo=c['neg_lo'])
+    o = {k: v.cpu().numpy() for k, v in o.items()}
+    for i, w in enumerate(c['want']):
+        S = len(w['keep'])
+        rows, pad = slice(i * n_sample, i * n_sample + S), slice(i * n_sample + S, (i + 1) * n_sample)
+        assert tuple(o['n_cand'][i]) == tuple(w['n_cand']), (i, o['n_cand'][i], w['n_cand'])
+        assert o['n_pos'][i] == w['n_pos'] and o['n_sampled'][i] == S, (i, o['n_pos'][i], o['n_sampled'][i], w['n_pos'], S)
+        np.testing.assert_array_equal(o['sample_src'][rows], w['keep'])
+        np.testing.assert_array_equal(o['sample_roi'][rows], w['roi'])
+        np.testing.assert_array_equal(o['gt_roi_label'][rows], w['label'])
+        np.testing.assert_array_equal(o['gt_assign'][rows], w['assign'])
+        np.testing.assert_array_equal(o['sample_levels'][rows], w['levels'])
+        np.testing.assert_allclose(o['gt_roi_loc'][rows], w['loc'], rtol=1e-5, atol=1e-5)
+        np.testing.assert_array_equal(o['rois_xy5'][rows][:, 0], i)
+        np.testing.assert_array_equal(o['rois_xy5'][rows][:, 1:], w['roi'][:, [1, 0, 3, 2]])
+        assert np.all(o['gt_roi_label'][pad] == -1) and np.all(o['gt_assign'][pad] == -1) and np.all(o['sample_src'][pad] == -1)
+        assert not o['sample_roi'][pad].any() and not o['gt_roi_loc'][pad].any()
+
+
+@pytest.mark.parametrize('total', sc.PT_COUNTS)
+def test_proposal_target_candidate_counts_on_the_sort_boundaries(total):
+    """nr + G on and beside the powers of two of the in-LDS sort (64 at the least) and at PT_CAP = 4096 (roi_cap 3840 + gt_cap 256, G = 256)."""
+    _check_proposal_target_case(sc.pt_candidate_count(total))
+
+
+PT_CASES = [('no_proposals', sc.pt_no_proposals), ('empty_image_of_two', sc.pt_empty_image_of_two), ('short_sets', sc.pt_short_sets),
+            ('equal_keys_zero', lambda: sc.pt_equal_keys('zero')), ('equal_keys_ones', lambda: sc.pt_equal_keys('ones')),
+            ('equal_keys_class', lambda: sc.pt_equal_keys('class')), ('thresholds_neg_lo_0', lambda: sc.pt_exact_thresholds(0.0)),
+            ('thresholds_neg_lo_0.1', lambda: sc.pt_exact_thresholds(0.1))]
+
+
+@pytest.mark.parametrize('build', [b for _, b in PT_CASES], ids=[n for n, _ in PT_CASES])
+def test_proposal_target_edges(build):
+    """No proposals (the gt boxes are the only candidates); an image without objects beside one with (all proposals background, gt_assign
+    -1, loc 0); fewer than 64 positives / fewer than 192 negatives / no negative; equal keys (the candidate index decides); IoU exactly
+    0.5 is foreground and not background, IoU 0 is background only while neg_lo = 0."""
+    _check_proposal_target_case(build())
+
+
+@pytest.mark.parametrize('leading_zero_area', [False, True])
+def test_proposal_target_degenerate_gt_follows_numpy_nan_rule(leading_zero_area):
+    """Zero-area ground-truth boxes (and a zero-area proposal): 0/0 against a zero-area box.  iou.max(axis=1) is NaN for them - also when
+    the NaN is met after a number - and NaN is in neither candidate set: n_cand and every sampled row equal the oracle's."""
+    _check_proposal_target_case(sc.pt_degenerate_gt(leading_zero_area))
+
+
+@pytest.mark.parametrize('n_pos', sc.MK_N_POS, ids=['n_pos_40_0', 'n_pos_3_64'])
+def test_mask_and_keypoint_targets_second_image_offsets(n_pos):
+    """N = 2, n_sample = 256, pos_cap = 64, gt_cap = 6: the row img * n_sample + j, the slot img * pos_cap + j and the mask / keypoint row
+    (img * gt_cap + g) of the second image, against cv2_resize_linear_u8 and the keypoint restatement per row; unused slots -1; a RoI whose
+    truncated crop is empty gives an all-zero mask target."""
+    c = sc.mask_keypoint_batch(n_pos)
+    sr, ga, npos = _t(c['sample_roi']), _t(c['gt_assign']), _t(c['n_pos'])
+    got = ops.mask_target(_t(c['masks']), sr, ga, npos, sc.MK_SAMPLE, sc.MK_POS_CAP, c['msz']).cpu().numpy()
+    np.testing.assert_array_equal(got, c['want_mask'])
+    got = ops.keypoint_target(_t(c['kps']), sr, ga, npos, sc.MK_SAMPLE, sc.MK_POS_CAP, c['kp_size']).cpu().numpy()
+    np.testing.assert_array_equal(got, c['want_kp'])
