@@ -791,6 +791,61 @@ def detect_decode(rois, box_out, n_class, loc0, scale, mean, std, size):
     return cls_bbox, prob
 
 
+def cascade_refine(rois, box_out, loc0, N, mean, std_prev, size, prev_label=None, gt_boxes=None, gt_labels=None, n_gt=None,
+                   iou_thresh=0.5, std_next=None):
+    """One Cascade R-CNN stage to the next (mrcnn_cascade_refine_f32): rois (N*S,4) yx and the stage's box_out
+    (N*S,ld) -> dict(roi (R,4), rois_xy5 (R,5), levels (R,) int32), and with gt_boxes (N,G,4) / gt_labels (N,G) i32 / n_gt (N,) i32 also
+    gt_loc (R,4), label (R,) int32, gt_assign (R,) int32 at ``iou_thresh`` with ``std_next``.  size: an (N,2) float32 device tensor of
+    each image's (h, w), or one (h, w) pair.  prev_label (R,) int32: rows with a label < 0 pass through as padding.  One launch."""
+    hw = size if torch.is_tensor(size) else None
+    _ck(rois, box_out, prev_label, gt_boxes, gt_labels, n_gt, hw)
+    R, ld = box_out.shape
+    N = int(N)
+    if N < 0 or (N == 0 and R) or (N and R % N) or rois.numel() != R * 4:
+        raise ValueError('cascade_refine: %d rows of box_out, %d boxes, %d images' % (R, rois.numel() // 4, N))
+    S = R // N if N else 0
+    train = gt_boxes is not None
+    if train != (gt_labels is not None) or train != (n_gt is not None) or train != (std_next is not None):
+        raise ValueError('cascade_refine: gt_boxes, gt_labels, n_gt and std_next go together')
+    if train and (gt_boxes.dim() != 3 or gt_boxes.shape[0] != N or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]) or n_gt.numel() != N):
+        raise ValueError('cascade_refine: gt_boxes (N,G,4), gt_labels (N,G), n_gt (N,) expected for N = %d' % N)
+    if prev_label is not None and prev_label.numel() != R:
+        raise ValueError('cascade_refine: %d previous labels for %d rows' % (prev_label.numel(), R))
+    if hw is not None and (hw.dtype != f32 or hw.numel() != 2 * N):
+        raise ValueError('cascade_refine: per-image sizes are an (N,2) float32 tensor')
+    dev = box_out.device
+    o = dict(roi=_empty((R, 4), dev), rois_xy5=_empty((R, 5), dev), levels=_empty((R,), dev, i32))
+    if train:
+        o.update(gt_loc=_empty((R, 4), dev), label=_empty((R,), dev, i32), gt_assign=_empty((R,), dev, i32))
+    m4 = (ctypes.c_float * 4)(*mean)
+    sp4 = (ctypes.c_float * 4)(*std_prev)
+    sn4 = (ctypes.c_float * 4)(*std_next) if train else None
+    h, w = (0.0, 0.0) if hw is not None else (float(size[0]), float(size[1]))
+    check(lib().mrcnn_cascade_refine_f32(ptr(rois), ptr(box_out), ld, int(loc0), ptr(prev_label), N, S, ctypes.cast(m4, ctypes.c_void_p),
+                                         ctypes.cast(sp4, ctypes.c_void_p), ptr(hw), h, w, ptr(gt_boxes), ptr(gt_labels), ptr(n_gt),
+                                         gt_boxes.shape[1] if train else 0, float(iou_thresh),
+                                         ctypes.cast(sn4, ctypes.c_void_p) if train else ctypes.c_void_p(0), ptr(o['roi']),
+                                         ptr(o['rois_xy5']), ptr(o['levels']), ptr(o.get('gt_loc')), ptr(o.get('label')),
+                                         ptr(o.get('gt_assign')), stream_ptr()))
+    return o
+
+
+def cascade_prob(box_outs, n_class):
+    """The inference score of a cascade (mrcnn_cascade_prob_f32): the K stages' box_out (R,ld) -> prob (R,n_class), the stages' softmax
+    added in stage order and divided by K.  One launch."""
+    _ck(*box_outs)
+    K = len(box_outs)
+    if not 2 <= K <= 4:
+        raise ValueError('cascade_prob: %d stages (2 to 4)' % K)
+    R, ld = box_outs[0].shape
+    if any(tuple(b.shape) != (R, ld) for b in box_outs):
+        raise ValueError('cascade_prob: the stages\' outputs differ in shape')
+    prob = _empty((R, n_class), box_outs[0].device)
+    p = [ptr(b) for b in box_outs] + [ctypes.c_void_p(0)] * (4 - K)
+    check(lib().mrcnn_cascade_prob_f32(p[0], p[1], p[2], p[3], K, R, ld, int(n_class), ptr(prob), stream_ptr()))
+    return prob
+
+
 def class_nms(cls_bbox, prob, l_begin, l_end, score_thresh, nms_thresh):
     """-> keep_idx (n_class,R) int32, keep_cnt (n_class,) int32."""
     _ck(cls_bbox, prob)

@@ -116,6 +116,58 @@ def head_norm_settings(head_norm, gn_groups, head_arch):
     return {'head_norm': None if head_norm == 'none' else head_norm, 'gn_groups': int(gn_groups)}
 
 
+# ---- Cascade R-CNN box stages (MaskRCNN cascade_ious / cascade_stds) -------------------------------------------------------
+DEFAULT_CASCADE_IOUS = (0.5, 0.6, 0.7)
+NO_CASCADE = {'cascade_ious': None, 'cascade_stds': None}       # what a trainer state without the 'cascade' key was trained with
+
+
+def add_cascade_flags(parser, both=lambda name: (name,)):
+    """--cascade / --cascade-ious / --cascade-stds (train.py, train_keypoints.py - which takes both spellings through ``both`` -, evaluate.py,
+    demo.py)."""
+    parser.add_argument(*both('--cascade'), type=int, default=0, choices=[0, 1],
+                        help='1: Cascade R-CNN - the box head becomes K stages trained at rising IoU thresholds, each fed the boxes the stage '
+                             'before refined, their scores averaged at inference (MaskRCNN cascade_ious); a checkpoint is evaluated with the '
+                             'value it was trained with')
+    parser.add_argument(*both('--cascade-ious'), type=float, nargs='+', default=None, metavar='T',
+                        help='the IoU thresholds of --cascade 1, one per stage (2 to 4, not decreasing, the first 0.5); default %s'
+                             % ' '.join(str(v) for v in DEFAULT_CASCADE_IOUS))
+    parser.add_argument(*both('--cascade-stds'), type=float, nargs='+', default=None, metavar='S',
+                        help='the delta normalisation of the stages behind the first, 4 numbers each (default: 0.05 0.05 0.1 0.1  0.033 0.033 '
+                             '0.067 0.067; other stage counts: the first stage\'s divided by the stage number)')
+
+
+def cascade_flag_settings(cascade, ious, stds, head_arch, backbone='fpn'):
+    """The MaskRCNN arguments {'cascade_ious': None | tuple, 'cascade_stds': None | tuple of 4-tuples} of the flags; ValueError for a
+    combination the model refuses."""
+    if cascade not in (0, 1):
+        raise ValueError('--cascade must be 0 or 1, got %r' % (cascade,))
+    if not cascade:
+        if ious is not None or stds is not None:
+            raise ValueError('--cascade-ious / --cascade-stds belong to --cascade 1')
+        return dict(NO_CASCADE)
+    from chainer_maskrcnn.model.maskrcnn import cascade_settings
+    ious = tuple(float(v) for v in ious) if ious else DEFAULT_CASCADE_IOUS
+    if stds is not None:
+        if len(stds) % 4 or len(stds) // 4 not in (len(ious) - 1, len(ious)):
+            raise ValueError('--cascade-stds takes 4 numbers for each of the %d stages behind the first, got %d numbers' % (len(ious) - 1, len(stds)))
+        stds = tuple(tuple(float(v) for v in stds[i:i + 4]) for i in range(0, len(stds), 4))
+    try:
+        got = cascade_settings(ious, stds, head_arch, backbone)
+    except ValueError as e:
+        raise ValueError('--cascade 1: %s' % e)
+    return {'cascade_ious': got[0], 'cascade_stds': got[1]}
+
+
+def check_cascade_flags(args, tta_prefix='--'):
+    """The cascade flags of an inference script (evaluate.py, demo.py) checked before the model is built: cascade_flag_settings' refusals, and
+    no test-time augmentation on top of a cascade (MaskRCNN.use_test_augmentation refuses it)."""
+    settings = cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone)
+    if settings['cascade_ious'] and (args.tta_sizes or args.tta_hflip):
+        raise ValueError('--cascade 1 does not go with %stta-sizes / %stta-hflip: test-time augmentation of a cascade model is not supported'
+                         % (tta_prefix, tta_prefix))
+    return settings
+
+
 # ---- labels and the model -----------------------------------------------------------------------------------------------------------------
 def read_labels(label_file):
     """The category names of --label_file (None when the file does not exist: every category)."""
@@ -133,13 +185,14 @@ def use_score_preset(model, preset, score_thresh=None):
 
 
 def build_inference_model(args, preset=None):
-    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --gn-groups / --label_file with --weight loaded (keys missing from the file keep their
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --gn-groups / --cascade* / --label_file with --weight loaded (keys missing from the file keep their
     initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
     17 keypoints; a mask head has one class per label (80 without a label file)."""
     import torch
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     from chainer_maskrcnn.utils import chainer_npz
     norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
+    norm.update(cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone))
     dev = torch.device('cuda', args.gpu)
     torch.cuda.set_device(dev)
     if args.head_arch == 'fpn_keypoint':

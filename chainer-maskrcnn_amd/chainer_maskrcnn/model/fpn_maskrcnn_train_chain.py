@@ -167,6 +167,10 @@ class FPNMaskRCNNTrainChain(object):
         self.faster_rcnn = faster_rcnn
         self.proposal_target_creator = ProposalTargetCreator(faster_rcnn.extractor.anchor_sizes)
         self.anchor_target_creator = AnchorTargetCreator()      # the argument is ignored, as in the reference
+        cascade = getattr(faster_rcnn, 'cascade', None)
+        if cascade is not None and cascade[0][0] != float(self.proposal_target_creator.pos_iou_thresh):
+            raise ValueError('cascade_ious[0] = %r is not the sampler\'s pos_iou_thresh %r'
+                             % (cascade[0][0], self.proposal_target_creator.pos_iou_thresh))
         self.rpn_sigma, self.roi_sigma = 3., 1.                  # base-class defaults apply (:25-26)
         self.loc_normalize_mean = faster_rcnn.loc_normalize_mean
         self.loc_normalize_std = faster_rcnn.loc_normalize_std
@@ -190,6 +194,7 @@ class FPNMaskRCNNTrainChain(object):
         self.keep_outputs = False           # parity tests: keep the head outputs of the last step in self.outputs
         self.outputs = {}
         self._aux = {}
+        self._bwd_cascade = ()
         self._arith_found = None            # the process's GEMM arithmetic before this chain selected its own (restored by backward())
 
     def _aux_stream(self, dev):
@@ -241,7 +246,8 @@ class FPNMaskRCNNTrainChain(object):
         features = m.extractor(m.to_nhwc4(imgs))
         m.rpn.train = True
         pk, ak = self.sampler_keys if self.sampler_keys is not None else (None, None)
-        losses = torch.empty((5, 2), dtype=torch.float32, device=dev)
+        stages = list(getattr(m, 'cascade_heads', []))        # Cascade R-CNN: the box stages behind the head
+        losses = torch.empty((5 + 2 * len(stages), 2), dtype=torch.float32, device=dev)
         br1 = {}
 
         def rpn_loss_branch(locs, scores, anchors):
@@ -301,6 +307,32 @@ class FPNMaskRCNNTrainChain(object):
                 ops.box_iou_loss(box, ld, t['gt_roi_loc'], t['sample_roi'], t['gt_roi_label'], R, self.box_loss, self.loc_normalize_mean,
                                  self.loc_normalize_std, weight=self.box_loss_weight, roi_period=R, gfill=ld - head.LOC0, col0=head.LOC0,
                                  gx=g_box, out=losses[2])
+            # Stage k >= 2, behind stage k-1 on the same stream and the same N * n_sample rows (no resampling, no host sync): stage k-1's
+            # input boxes refined by its own deltas, re-levelled, re-matched at the stage's IoU threshold and re-encoded with the stage's
+            # std - a constant: no gradient flows through the refinement -, then the stage's box branch and the two losses of stage 1 with
+            # the same (sum, count) normalisation.  Losses rows 5 + 2 * (k - 2) (loc) and 6 + 2 * (k - 2) (cls).
+            g_boxes, casc = [g_box], []
+            prev = dict(roi=t['sample_roi'], label=t['gt_roi_label'], box=box)
+            for k, stage in enumerate(stages, 2):
+                ious, stds = m.cascade
+                ref = ops.cascade_refine(prev['roi'], prev['box'], head.LOC0, n, self.loc_normalize_mean, stds[k - 2],
+                                         per_hw if per_hw is not None else (float(H), float(W)), prev_label=prev['label'], gt_boxes=bboxes,
+                                         gt_labels=labels, n_gt=n_gt, iou_thresh=ious[k - 1], std_next=stds[k - 1])
+                box_k = stage.box_branch(features, ref['rois_xy5'], ref['levels'], scales)
+                g_k = torch.empty_like(box_k)
+                row = 5 + 2 * (k - 2)
+                ops.softmax_ce(box_k, ref['label'], R, head.n_class, (1, ld, 0, 1), Kfill=head.LOC0, gx=g_k, out=losses[row + 1])
+                if self.box_loss == 'smooth_l1':
+                    ops.smooth_l1(box_k, ld, ref['gt_loc'], ref['label'], R, self.roi_sigma, gfill=ld - head.LOC0, col0=head.LOC0, gx=g_k,
+                                  out=losses[row])
+                else:       # against the refined box the stage's targets were encoded with, with the stage's std
+                    ops.box_iou_loss(box_k, ld, ref['gt_loc'], ref['roi'], ref['label'], R, self.box_loss, self.loc_normalize_mean,
+                                     stds[k - 1], weight=self.box_loss_weight, roi_period=R, gfill=ld - head.LOC0, col0=head.LOC0, gx=g_k,
+                                     out=losses[row])
+                g_boxes.append(g_k)
+                ref['box'] = box_k
+                casc.append(ref)
+                prev = ref
 
         rows = t['mask_rows']
         if self.mask_loss_kind == 'generic':
@@ -333,11 +365,17 @@ class FPNMaskRCNNTrainChain(object):
         total = ops.loss_total(losses)
         self.observation = {'rpn_loc_loss': losses[0, 0], 'rpn_cls_loss': losses[1, 0], 'roi_loc_loss': losses[2, 0],
                             'roi_cls_loss': losses[3, 0], 'mask_loss': losses[4, 0], 'loss': total[0]}
+        for k in range(2, 2 + len(stages)):         # the existing keys are stage 1's
+            self.observation['roi_loc_loss_s%d' % k] = losses[5 + 2 * (k - 2), 0]
+            self.observation['roi_cls_loss_s%d' % k] = losses[6 + 2 * (k - 2), 0]
         self._bwd = (features, g_locs.view(n, A, 4), g_scores.view(n, A, 2), g_box, g_mask)
+        self._bwd_cascade = g_boxes[1:]          # the later box stages' loss gradients, in stage order
         self._early_rpn = br1.get('g_feats')
         self.targets = t
         if self.keep_outputs:
             self.outputs = dict(features=features, locs=r['locs'], scores=r['scores'], box=box, mask=mask_out)
+            if stages:      # per later stage: the refine outputs (roi, rois_xy5, levels, gt_loc, label, gt_assign) and 'box'; every stage's loss gradient
+                self.outputs.update(cascade=casc, g_boxes=g_boxes, losses=losses)
         self.rpn_targets = (gt_rpn_loc, gt_rpn_label)
         self.mask_inputs = (m_rois, m_levels, m_label)
         self.rpn_out = r
@@ -383,9 +421,10 @@ class FPNMaskRCNNTrainChain(object):
         None = 1): d(objective)/d(loss), multiplied into the four loss-gradient seeds."""
         m = self.faster_rcnn
         features, g_locs, g_scores, g_box, g_mask = self._bwd
+        g_later = self._bwd_cascade
         if upstream is not None:
             from chainer_maskrcnn.functions.loss import _scale_
-            for g_ in (g_locs, g_scores, g_box, g_mask):
+            for g_ in (g_locs, g_scores, g_box, g_mask) + tuple(g_later):
                 _scale_(g_, upstream)
         hook = self.grad_ready_hook
         dev = features[0].device
@@ -402,9 +441,13 @@ class FPNMaskRCNNTrainChain(object):
         aux.wait_stream(main)
         with torch.cuda.stream(aux):
             m.head.backward_box(g_box, g_feats, accumulate=into_early)     # overwrites g_feats (first pooled size) unless they hold the RPN's
+            for stage, g_k in zip(getattr(m, 'cascade_heads', []), g_later):      # the later box stages add theirs, in stage order
+                stage.backward_box(g_k, g_feats, accumulate=True)
         g_pool = m.head.backward_mask_convs(g_mask)       # main stream: the mask branch down to its pooled input
         main.wait_stream(aux)
         m.head.backward_mask_pool(g_pool, g_feats)        # accumulates into g_feats (second pooled size)
+        if self.keep_outputs and g_later:       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
+            self.outputs.update(g_mask_pool=g_pool, g_feats_heads=[g.clone() for g in g_feats])
         if hook:
             hook(self._offset_of('head/'))
         if into_early:
@@ -427,6 +470,7 @@ class FPNMaskRCNNTrainChain(object):
         if hook:
             hook(0)
         self._bwd = None
+        self._bwd_cascade = ()
         if self._arith_found is not None:
             from chainer_maskrcnn._hip import lib, check
             split, in_backbone = self._arith_found

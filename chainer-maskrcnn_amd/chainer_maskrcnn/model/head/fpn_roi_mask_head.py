@@ -114,19 +114,22 @@ def roi_align_fpn_bwd(gy, gxs, rois_xy5, levels, out_size, scales, accumulate, s
                                             ptr(ws), ws.numel() if ws is not None else 0, stream_ptr()))
 
 
-class FPNRoIMaskHead(object):
-    mask_size = 28
+class FPNRoIBoxHead(object):
+    """The box branch alone: ROIAlign -> conv1 [+ GroupNorm] -> fc1 -> fc2 -> the fused ``score_cls_loc`` layer, with its own tape and
+    ``backward_box``.  FPNRoIMaskHead adds the mask branch on top of it; on its own it is a later stage of a Cascade R-CNN
+    (``head/cascade<k>/...``) and registers no mask parameter."""
 
-    def __init__(self, n_class, roi_size_box, roi_size_mask, loc_initialW=None, score_initialW=None,
-                 mask_initialW=None, ps=None, prefix='head', in_channels=256, fc_channels=1024,
-                 n_mask_convs=4, mask_out_channels=None, upsample2x=False, mask_conv_names=None, norm=None, gn_groups=32):
-        """norm: None = the reference's conv + ReLU stacks; 'gn' = conv1 and every mask convolution are followed by a GroupNorm of
-        ``gn_groups`` groups with the ReLU behind it (Detectron's *_gn heads; DESIGN.md §3.19).  The parameters ``<conv>/gn/gamma``,
-        ``<conv>/gn/beta`` are registered directly after their convolution; every other parameter keeps its name and shape."""
+    # Cascade R-CNN: a (1,) float32 device tensor holding 1.0f / K, multiplied into the pooled-feature gradient before the ROIAlign backward
+    # (Detectron2's _ScaleGradient: the K stages share the pyramid); the head's own parameter gradients are not scaled.  None: no launch.
+    pool_grad_scale = None
+    keep_pool_grad = False
+
+    def __init__(self, n_class, roi_size_box, loc_initialW=None, score_initialW=None, ps=None, prefix='head', in_channels=256,
+                 fc_channels=1024, norm=None, gn_groups=32):
         if norm not in (None, 'gn'):
             raise ValueError("norm must be None or 'gn', got %r" % (norm,))
         self.ps = ps if ps is not None else ParamStore()
-        self.n_class, self.roi_size_box, self.roi_size_mask = n_class, roi_size_box, roi_size_mask
+        self.n_class, self.roi_size_box = n_class, roi_size_box
         c = in_channels
         if norm == 'gn' and (gn_groups < 1 or c % gn_groups != 0):
             raise ValueError('gn_groups = %d does not divide the %d channels of the head' % (gn_groups, c))
@@ -145,26 +148,8 @@ class FPNRoIMaskHead(object):
         self.box_out = Conv(self.ps, p + 'score_cls_loc', fc_channels, n_class + 4, 1, cout_p=self.out_p,
                             cout_index=list(range(n_class)) + list(range(self.LOC0, self.LOC0 + 4)),
                             init=lambda shape: (lambda rs: np.concatenate([si(rs), li(rs)], 0)))
-        mi = 0.01 if mask_initialW is None else mask_initialW
-        names = mask_conv_names or ['mask%d' % (i + 1) for i in range(n_mask_convs)]
-        self.mask_convs, self.mask_gns = [], []
-        for nm in names:
-            self.mask_convs.append(Conv(self.ps, p + nm, c, c, 3, 1, 1, relu=not gn, fwd_tile=0))
-            self.mask_gns.append(GroupNorm(self.ps, p + nm + '/gn', c, gn_groups) if gn else None)
-        self.mask_out_channels = (n_class - 1) if mask_out_channels is None else mask_out_channels
-        self.upsample2x = upsample2x
-        # deconv1: W (Cin, Cout, 2, 2) in Chainer == 1x1 conv weight ((a*2+b)*Cout + o, Cin); bias added by the shuffle
-        self.deconv1 = Conv(self.ps, p + 'deconv1', c, 4 * c, 1, bias=False, init=normal(mi))
-        self.ps.register(p + 'deconv1/b', (c,), lambda rs: np.zeros((c,), np.float32))
-        self.deconv_b = p + 'deconv1/b'
-        self.conv2 = Conv(self.ps, p + 'conv2', c, self.mask_out_channels, 1, init=normal(mi))
         self.channels = c
-        # No non-linearity sits between deconv1 and conv2 in the reference (:83), so the two run as ONE 2x2/2
-        # deconvolution to mask_out_channels with composed weights (include/mrcnn_hip.h, mrcnn_deconv_merge_*): same
-        # function, same parameters and gradients, 4x fewer MACs on the 28x28 maps.  False = layer by layer.
-        self.merge_deconv = (c % 8 == 0)
 
-    # ---- forward --------------------------------------------------------------------------------
     def box_branch(self, xs, rois_xy5, levels, spatial_scales):
         pool = roi_align_fpn_fwd(xs, rois_xy5, levels, self.roi_size_box, spatial_scales)
         h, t1 = self.conv1.fwd(pool)
@@ -181,6 +166,60 @@ class FPNRoIMaskHead(object):
         self.last_box_out = o.view(R, self.out_p)
         return o.view(R, self.out_p)          # [:, :n_class] scores, [:, LOC0:LOC0+4] loc
 
+    def backward_box(self, g_box_out, g_feats, accumulate=False):
+        (t1, n1), t2, t3, t4, pool_shape, rois, levels, scales, plan = self.box_tape
+        R = g_box_out.shape[0]
+        # every layer's input is the ReLU output of the layer below: the ReLU backward rides in the data-gradient epilogue
+        g = self.box_out.bwd(t4, g_box_out.view(R, 1, 1, -1), mask_gx=True)
+        g = self.fc2.bwd(t3, g, gy_masked=True, mask_gx=True)
+        g = self.fc1.bwd(t2, g, gy_masked=True, mask_gx=True)
+        g = g.view(pool_shape)
+        if self.gn1 is not None:                # fc1's epilogue masked g on the GroupNorm's output
+            g = self.gn1.bwd(n1, g, gy_masked=True)
+        g = self.conv1.bwd(t1, g, gy_masked=True)
+        if self.keep_pool_grad:                 # parity tests: the un-scaled gradient of the pooled features
+            self.kept_pool_grad = g.clone()
+        if self.pool_grad_scale is not None:
+            check(lib().mrcnn_scale_by_dev_f32(ptr(g), g.numel(), ptr(self.pool_grad_scale), stream_ptr()))
+        # accumulate: g_feats already hold a gradient (the RPN's, computed early) - the backward then only touches the patches RoIs land on
+        roi_align_fpn_bwd(g, g_feats, rois, levels, self.roi_size_box, scales, accumulate=accumulate, plan=plan)
+        self.box_tape = None
+
+
+class FPNRoIMaskHead(FPNRoIBoxHead):
+    mask_size = 28
+
+    def __init__(self, n_class, roi_size_box, roi_size_mask, loc_initialW=None, score_initialW=None,
+                 mask_initialW=None, ps=None, prefix='head', in_channels=256, fc_channels=1024,
+                 n_mask_convs=4, mask_out_channels=None, upsample2x=False, mask_conv_names=None, norm=None, gn_groups=32):
+        """norm: None = the reference's conv + ReLU stacks; 'gn' = conv1 and every mask convolution are followed by a GroupNorm of
+        ``gn_groups`` groups with the ReLU behind it (Detectron's *_gn heads; DESIGN.md §3.19).  The parameters ``<conv>/gn/gamma``,
+        ``<conv>/gn/beta`` are registered directly after their convolution; every other parameter keeps its name and shape."""
+        super().__init__(n_class, roi_size_box, loc_initialW=loc_initialW, score_initialW=score_initialW, ps=ps, prefix=prefix,
+                         in_channels=in_channels, fc_channels=fc_channels, norm=norm, gn_groups=gn_groups)
+        self.roi_size_mask = roi_size_mask
+        c = in_channels
+        gn = norm == 'gn'
+        p = prefix + '/'
+        mi = 0.01 if mask_initialW is None else mask_initialW
+        names = mask_conv_names or ['mask%d' % (i + 1) for i in range(n_mask_convs)]
+        self.mask_convs, self.mask_gns = [], []
+        for nm in names:
+            self.mask_convs.append(Conv(self.ps, p + nm, c, c, 3, 1, 1, relu=not gn, fwd_tile=0))
+            self.mask_gns.append(GroupNorm(self.ps, p + nm + '/gn', c, gn_groups) if gn else None)
+        self.mask_out_channels = (n_class - 1) if mask_out_channels is None else mask_out_channels
+        self.upsample2x = upsample2x
+        # deconv1: W (Cin, Cout, 2, 2) in Chainer == 1x1 conv weight ((a*2+b)*Cout + o, Cin); bias added by the shuffle
+        self.deconv1 = Conv(self.ps, p + 'deconv1', c, 4 * c, 1, bias=False, init=normal(mi))
+        self.ps.register(p + 'deconv1/b', (c,), lambda rs: np.zeros((c,), np.float32))
+        self.deconv_b = p + 'deconv1/b'
+        self.conv2 = Conv(self.ps, p + 'conv2', c, self.mask_out_channels, 1, init=normal(mi))
+        # No non-linearity sits between deconv1 and conv2 in the reference (:83), so the two run as ONE 2x2/2
+        # deconvolution to mask_out_channels with composed weights (include/mrcnn_hip.h, mrcnn_deconv_merge_*): same
+        # function, same parameters and gradients, 4x fewer MACs on the 28x28 maps.  False = layer by layer.
+        self.merge_deconv = (c % 8 == 0)
+
+    # ---- forward --------------------------------------------------------------------------------
     def mask_branch(self, xs, rois_xy5, levels, spatial_scales):
         pool = roi_align_fpn_fwd(xs, rois_xy5, levels, self.roi_size_mask, spatial_scales)
         h, tapes = pool, []
@@ -283,21 +322,6 @@ class FPNRoIMaskHead(object):
         self.backward_box(g_box_out, g_feats)
         if g_mask is not None:
             self.backward_mask_pool(self.backward_mask_convs(g_mask), g_feats)
-
-    def backward_box(self, g_box_out, g_feats, accumulate=False):
-        (t1, n1), t2, t3, t4, pool_shape, rois, levels, scales, plan = self.box_tape
-        R = g_box_out.shape[0]
-        # every layer's input is the ReLU output of the layer below: the ReLU backward rides in the data-gradient epilogue
-        g = self.box_out.bwd(t4, g_box_out.view(R, 1, 1, -1), mask_gx=True)
-        g = self.fc2.bwd(t3, g, gy_masked=True, mask_gx=True)
-        g = self.fc1.bwd(t2, g, gy_masked=True, mask_gx=True)
-        g = g.view(pool_shape)
-        if self.gn1 is not None:                # fc1's epilogue masked g on the GroupNorm's output
-            g = self.gn1.bwd(n1, g, gy_masked=True)
-        g = self.conv1.bwd(t1, g, gy_masked=True)
-        # accumulate: g_feats already hold a gradient (the RPN's, computed early) - the backward then only touches the patches RoIs land on
-        roi_align_fpn_bwd(g, g_feats, rois, levels, self.roi_size_box, scales, accumulate=accumulate, plan=plan)
-        self.box_tape = None
 
     def backward_mask_convs(self, g_mask):
         """Mask / keypoint branch backward down to the gradient of its pooled input."""

@@ -17,7 +17,47 @@ from chainer_maskrcnn.nn.core import ParamStore
 from chainer_maskrcnn._hip import ops
 from .extractor.feature_pyramid_network import FeaturePyramidNetwork
 from .rpn.multilevel_region_proposal_network import MultilevelRegionProposalNetwork
-from .head.fpn_roi_mask_head import FPNRoIMaskHead
+from .head.fpn_roi_mask_head import FPNRoIBoxHead, FPNRoIMaskHead
+
+# Cascade R-CNN (Cai & Vasconcelos 2018): the stages' normalisation of the box deltas; stage 1's is the model's loc_normalize_std
+CASCADE_STDS = ((0.1, 0.1, 0.2, 0.2), (0.05, 0.05, 0.1, 0.1), (0.033, 0.033, 0.067, 0.067))
+
+
+def cascade_settings(cascade_ious, cascade_stds=None, head_arch='fpn', backbone='fpn', pos_iou_thresh=0.5, stage1_std=CASCADE_STDS[0]):
+    """The checked cascade arguments of MaskRCNN: None (off), or (ious, stds) - K = len(ious) IoU thresholds, 2 <= K <= 4, non-decreasing,
+    the first the sampler's ``pos_iou_thresh``; K stds of 4 positive numbers, stage 1's being ``stage1_std``: ``cascade_stds`` (K entries whose
+    first is ignored in favour of stage 1's own, or the K - 1 later ones) or, by default, CASCADE_STDS for K <= 3 and stage1_std / k for
+    stage k otherwise.  ValueError for anything else, the legacy heads and backbones included."""
+    if cascade_ious is None:
+        if cascade_stds is not None:
+            raise ValueError('cascade_stds without cascade_ious')
+        return None
+    if head_arch not in ('fpn', 'fpn_keypoint') or backbone != 'fpn':
+        raise ValueError("cascade_ious exists for backbone 'fpn' with head_arch 'fpn' or 'fpn_keypoint', not %r / %r" % (backbone, head_arch))
+    try:
+        ious = tuple(float(v) for v in cascade_ious)
+    except (TypeError, ValueError):
+        raise ValueError('cascade_ious must be a sequence of numbers, got %r' % (cascade_ious,))
+    K = len(ious)
+    if not 2 <= K <= 4:
+        raise ValueError('cascade_ious: %d stages, 2 to 4 expected' % K)
+    if any(not 0 < v < 1 for v in ious) or any(b < a for a, b in zip(ious, ious[1:])):
+        raise ValueError('cascade_ious must lie in (0, 1) and not decrease, got %r' % (ious,))
+    if ious[0] != float(pos_iou_thresh):
+        raise ValueError('cascade_ious[0] = %r is not the sampler\'s pos_iou_thresh %r' % (ious[0], pos_iou_thresh))
+    s1 = tuple(float(v) for v in stage1_std)
+    if cascade_stds is None:
+        later = [CASCADE_STDS[k] if K <= 3 and s1 == CASCADE_STDS[0] else tuple(v / (k + 1) for v in s1) for k in range(1, K)]
+    else:
+        later = [tuple(float(v) for v in s) for s in cascade_stds]
+        if len(later) == K:
+            later = later[1:]
+        if len(later) != K - 1:
+            raise ValueError('cascade_stds: %d entries for %d stages' % (len(cascade_stds), K))
+    stds = (s1,) + tuple(later)
+    if any(len(s) != 4 or any(not (v > 0 and np.isfinite(v)) for v in s) for s in stds):
+        raise ValueError('cascade_stds: every stage takes 4 positive numbers, got %r' % (stds,))
+    return ious, stds
 
 
 class MaskRCNN(object):
@@ -26,13 +66,19 @@ class MaskRCNN(object):
     soft_nms = None                 # (method, sigma)
     vote_thresh = None
     max_detections = None
+    # Cascade R-CNN box stages, off unless the constructor's cascade_ious sets them
+    cascade = None                  # (ious, stds)
+    cascade_heads = ()
 
     def __init__(self, n_fg_class, n_keypoints=None, n_mask_convs=None, pretrained_model=None, min_size=600,
                  max_size=1000, ratios=[0.5, 1, 2], anchor_scales=[8], rpn_initialW=None, loc_initialW=None,
                  score_initialW=None, proposal_creator_params={}, backbone='fpn', head_arch='fpn',
-                 device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32):
+                 device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32, cascade_ious=None, cascade_stds=None):
         """head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
-        convolution of the 'fpn' / 'fpn_keypoint' heads."""
+        convolution of the 'fpn' / 'fpn_keypoint' heads.
+        cascade_ious: None = one box stage; (0.5, 0.6, 0.7) = Cascade R-CNN: K box stages trained at these IoU thresholds,
+        stage k > 1 a box-only head ``head/cascade<k>/...`` registered directly behind the stage-1 head's parameters and fed stage k-1's
+        refined boxes; ``cascade_stds`` their delta normalisation (cascade_settings)."""
         if n_fg_class is None:
             raise ValueError('The n_fg_class needs to be supplied as an argument')
         if head_norm not in (None, 'gn'):
@@ -40,6 +86,7 @@ class MaskRCNN(object):
         if head_norm is not None and head_arch in ('res5', 'light'):
             raise ValueError("head_norm=%r exists for head_arch 'fpn' and 'fpn_keypoint' only, not %r" % (head_norm, head_arch))
         self.head_norm, self.gn_groups = head_norm, int(gn_groups)
+        self.cascade = cascade_settings(cascade_ious, cascade_stds, head_arch, backbone)
         self.ps = ParamStore()
         shrink = _test_shrink or {}
         if backbone == 'fpn':
@@ -94,6 +141,13 @@ class MaskRCNN(object):
             self.predict_mask = False
         else:
             raise ValueError('unknown head archtecture specified. {}'.format(head_arch))
+        # Cascade R-CNN: the later box stages, behind every parameter of the stage-1 head (which keeps its names, shapes and offsets)
+        self.cascade_heads = []
+        if self.cascade is not None:
+            for k in range(2, len(self.cascade[0]) + 1):
+                self.cascade_heads.append(FPNRoIBoxHead(self.head.n_class, roi_size_box=7, loc_initialW=loc_initialW, score_initialW=score_initialW,
+                                                        ps=self.ps, prefix='head/cascade%d' % k, in_channels=c,
+                                                        fc_channels=1024 // shrink.get('width_div', 1), norm=head_norm, gn_groups=self.gn_groups))
         # FasterRCNN base-class state
         self.mean = np.array([122.7717, 115.9465, 102.9801], dtype=np.float32)[:, None, None]   # unused (maskrcnn.py:273-274)
         self.min_size, self.max_size = min_size, max_size
@@ -104,6 +158,10 @@ class MaskRCNN(object):
         self.tta = None                 # test-time augmentation, off (use_test_augmentation)
         self.device = torch.device(device)
         self.ps.materialise(self.device, seed)
+        if self.cascade is not None:         # Detectron2's _ScaleGradient: every stage's pooled-feature gradient times the float32 1.0f / K
+            inv_k = torch.from_numpy(np.array([np.float32(1.0) / np.float32(len(self.cascade[0]))], np.float32)).to(self.device)
+            for h in self.box_stages:
+                h.pool_grad_scale = inv_k
         self.freeze_state = (False, 0)
 
     def freeze(self, bn=False, at=0):
@@ -129,6 +187,16 @@ class MaskRCNN(object):
     def n_class(self):
         return self.head.n_class
 
+    @property
+    def box_stages(self):
+        """The box stages in order: the head, then the cascade's later stages."""
+        return [self.head] + list(self.cascade_heads)
+
+    @property
+    def cascade_stds(self):
+        """The delta normalisation of every box stage: stage 1's is loc_normalize_std."""
+        return (tuple(self.loc_normalize_std),) + (tuple(self.cascade[1][1:]) if self.cascade is not None else ())
+
     def use_preset(self, preset):
         if preset == 'visualize':
             self.nms_thresh, self.score_thresh = 0.3, 0.7
@@ -146,6 +214,8 @@ class MaskRCNN(object):
         if sizes is None:
             self.tta = None
             return
+        if self.cascade is not None:
+            raise ValueError('use_test_augmentation: test-time augmentation of a cascade model (cascade_ious) is not supported')
         sizes = [int(s) for s in sizes]
         if not sizes or any(s <= 0 for s in sizes):
             raise ValueError('use_test_augmentation: sizes must be positive, got %r' % (sizes,))
@@ -327,8 +397,22 @@ class MaskRCNN(object):
         scale = x.shape[2] / size[1]
         roi_cls_locs, roi_scores, rois, roi_indices, levels = self.__call__(x[None].contiguous(), scale=scale)
         box_out = self.head.last_box_out
-        cls_bbox, prob = ops.detect_decode(rois.contiguous(), box_out, self.n_class, self.head.LOC0, scale,
-                                           self.loc_normalize_mean, self.loc_normalize_std, size)
+        rois = rois.contiguous()
+        self.last_stages = [(rois, box_out)]        # parity tests read these: every box stage's (input boxes, box_out)
+        std = self.loc_normalize_std
+        if self.cascade is not None:
+            # stage k's input = stage k-1's decoded boxes, clipped to the prepared image (the forward's frame), on the pyramid kept in head.x
+            frame = (float(x.shape[1]), float(x.shape[2]))
+            stds = self.cascade_stds
+            for k, stage in enumerate(self.cascade_heads, 1):
+                ref = ops.cascade_refine(rois, box_out, self.head.LOC0, 1, self.loc_normalize_mean, stds[k - 1], frame)
+                rois, levels = ref['roi'], ref['levels']
+                box_out = stage.box_branch(self.head.x, ref['rois_xy5'], levels, self.extractor.spatial_scales)
+                self.last_stages.append((rois, box_out))
+            std = stds[-1]
+        cls_bbox, prob = ops.detect_decode(rois, box_out, self.n_class, self.head.LOC0, scale, self.loc_normalize_mean, std, size)
+        if self.cascade is not None:
+            prob = ops.cascade_prob([b for _, b in self.last_stages], self.n_class)
         self.last_rois, self.last_decoded = rois, (cls_bbox, prob)      # parity tests read these
         bbox, label, score, level = self._suppress(cls_bbox, prob, levels)
         return size, scale, bbox, label, score, level

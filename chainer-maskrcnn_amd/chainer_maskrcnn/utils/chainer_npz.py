@@ -53,6 +53,15 @@ class ChainerNpzMap(object):
             self._add_conv(cv)
         self.rpn, self.head = rpn, head
         self.gns = [g for g in [getattr(head, 'gn1', None)] + list(getattr(head, 'mask_gns', [])) if g is not None]
+        # the box stages: the head and, for a cascade model, its later stages under head/cascade<k>/ - the same link layout as the head's
+        # box branch (conv1, fc1, fc2, cls_loc, score)
+        self.box_stages = [('head', head)]
+        for k, st in enumerate(getattr(model, 'cascade_heads', []), 2):
+            self.box_stages.append(('head/cascade%d' % k, st))
+            self._add_conv(st.conv1)
+            self._add_conv(st.fc2)
+            if st.gn1 is not None:
+                self.gns.append(st.gn1)
 
     def _add_conv(self, cv):
         self.convs[cv.name] = cv
@@ -86,18 +95,20 @@ class ChainerNpzMap(object):
         out['rpn/loc/b'] = b[:4 * A].copy()
         out['rpn/score/W'] = w[4 * A:6 * A][:, :, None, None].copy()
         out['rpn/score/b'] = b[4 * A:6 * A].copy()
+        for pre, h in self.box_stages:
+            w = g(h.box_out.name + '/W')[:, 0, 0, :h.box_out.cin]
+            b = g(h.box_out.name + '/b')
+            out[pre + '/score/W'] = w[:h.n_class].copy()
+            out[pre + '/score/b'] = b[:h.n_class].copy()
+            out[pre + '/cls_loc/W'] = w[h.LOC0:h.LOC0 + 4].copy()
+            out[pre + '/cls_loc/b'] = b[h.LOC0:h.LOC0 + 4].copy()
+            # fc1: ours (out, 1, 1, (h, w, c)) -> Chainer Linear (out, (c, h, w))
+            c, s = h.channels, h.roi_size_box
+            w = g(h.fc1.name + '/W')[:h.fc1.cout, 0, 0, :]
+            out[pre + '/fc1/W'] = np.ascontiguousarray(w.reshape(-1, s, s, c).transpose(0, 3, 1, 2).reshape(w.shape[0], -1))
+            out[pre + '/fc1/b'] = g(h.fc1.name + '/b')[:h.fc1.cout].copy()
         h = self.head
-        w = g(h.box_out.name + '/W')[:, 0, 0, :h.box_out.cin]
-        b = g(h.box_out.name + '/b')
-        out['head/score/W'] = w[:h.n_class].copy()
-        out['head/score/b'] = b[:h.n_class].copy()
-        out['head/cls_loc/W'] = w[h.LOC0:h.LOC0 + 4].copy()
-        out['head/cls_loc/b'] = b[h.LOC0:h.LOC0 + 4].copy()
-        # fc1: ours (out, 1, 1, (h, w, c)) -> Chainer Linear (out, (c, h, w))
-        c, s = h.channels, h.roi_size_box
-        w = g(h.fc1.name + '/W')[:h.fc1.cout, 0, 0, :]
-        out['head/fc1/W'] = np.ascontiguousarray(w.reshape(-1, s, s, c).transpose(0, 3, 1, 2).reshape(w.shape[0], -1))
-        out['head/fc1/b'] = g(h.fc1.name + '/b')[:h.fc1.cout].copy()
+        c = h.channels
         # deconv1: ours ((a*2+b)*C + o, 1, 1, ci) -> Chainer Deconvolution2D (ci, o, a, b)
         w = g(h.deconv1.name + '/W')[:, 0, 0, :c].reshape(2, 2, c, c)
         out['head/deconv1/W'] = np.ascontiguousarray(w.transpose(3, 2, 0, 1))
@@ -155,26 +166,29 @@ class ChainerNpzMap(object):
             put(hd.name + '/W', w)
             put(hd.name + '/b', b)
             loaded += ['rpn/loc/W', 'rpn/score/W', 'rpn/loc/b', 'rpn/score/b']
+        for pre, h in self.box_stages:
+            keys = [pre + k for k in ('/score/W', '/cls_loc/W', '/score/b', '/cls_loc/b')]
+            if have(*keys):
+                bo = h.box_out
+                w = np.zeros((bo.cout_p, 1, 1, bo.cin_p), np.float32)
+                b = np.zeros((bo.cout_p,), np.float32)
+                w[:h.n_class, 0, 0, :bo.cin] = arrays[keys[0]]
+                w[h.LOC0:h.LOC0 + 4, 0, 0, :bo.cin] = arrays[keys[1]]
+                b[:h.n_class] = arrays[keys[2]]
+                b[h.LOC0:h.LOC0 + 4] = arrays[keys[3]]
+                put(bo.name + '/W', w)
+                put(bo.name + '/b', b)
+                loaded += keys
+            c, s = h.channels, h.roi_size_box
+            if have(pre + '/fc1/W', pre + '/fc1/b'):
+                w = np.asarray(arrays[pre + '/fc1/W'])
+                wn = np.zeros((h.fc1.cout_p, 1, 1, h.fc1.cin_p), np.float32)
+                wn[:w.shape[0], 0, 0, :] = w.reshape(-1, c, s, s).transpose(0, 2, 3, 1).reshape(w.shape[0], -1)
+                put(h.fc1.name + '/W', wn)
+                put(h.fc1.name + '/b', _vec_to_native(np.asarray(arrays[pre + '/fc1/b']), h.fc1.cout_p))
+                loaded += [pre + '/fc1/W', pre + '/fc1/b']
         h = self.head
-        if have('head/score/W', 'head/cls_loc/W', 'head/score/b', 'head/cls_loc/b'):
-            bo = h.box_out
-            w = np.zeros((bo.cout_p, 1, 1, bo.cin_p), np.float32)
-            b = np.zeros((bo.cout_p,), np.float32)
-            w[:h.n_class, 0, 0, :bo.cin] = arrays['head/score/W']
-            w[h.LOC0:h.LOC0 + 4, 0, 0, :bo.cin] = arrays['head/cls_loc/W']
-            b[:h.n_class] = arrays['head/score/b']
-            b[h.LOC0:h.LOC0 + 4] = arrays['head/cls_loc/b']
-            put(bo.name + '/W', w)
-            put(bo.name + '/b', b)
-            loaded += ['head/score/W', 'head/cls_loc/W', 'head/score/b', 'head/cls_loc/b']
-        c, s = h.channels, h.roi_size_box
-        if have('head/fc1/W', 'head/fc1/b'):
-            w = np.asarray(arrays['head/fc1/W'])
-            wn = np.zeros((h.fc1.cout_p, 1, 1, h.fc1.cin_p), np.float32)
-            wn[:w.shape[0], 0, 0, :] = w.reshape(-1, c, s, s).transpose(0, 2, 3, 1).reshape(w.shape[0], -1)
-            put(h.fc1.name + '/W', wn)
-            put(h.fc1.name + '/b', _vec_to_native(np.asarray(arrays['head/fc1/b']), h.fc1.cout_p))
-            loaded += ['head/fc1/W', 'head/fc1/b']
+        c = h.channels
         if have('head/deconv1/W', 'head/deconv1/b'):
             w = np.asarray(arrays['head/deconv1/W'])            # (ci, o, a, b)
             wn = np.zeros((4 * c, 1, 1, h.deconv1.cin_p), np.float32)

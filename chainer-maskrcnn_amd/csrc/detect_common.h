@@ -19,6 +19,20 @@ __device__ __forceinline__ unsigned orderable(float f) {     // monotone float -
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// The softmax of one box_out row's n_class scores (F.softmax, maskrcnn.py:205): the maximum, the sum of expf(o[c] - m) in class order, and
+// class c's probability expf(o[c] - m) / s.  Shared by detect_decode_row and the stage mean of cascade.hip.
+struct SoftmaxStats { float m, s; };
+
+__device__ __forceinline__ SoftmaxStats detect_softmax_stats(const float *__restrict__ o, int n_class) {
+    float m = -INFINITY;
+    for (int c = 0; c < n_class; ++c) m = fmaxf(m, o[c]);
+    float s = 0.f;
+    for (int c = 0; c < n_class; ++c) s += expf(o[c] - m);
+    return SoftmaxStats{m, s};
+}
+
+__device__ __forceinline__ float detect_softmax_prob(float v, SoftmaxStats st) { return expf(v - st.m) / st.s; }
+
 // One RoI (y1,x1,y2,x2) of the forward's scaled image and its box_out row o (n_class scores, then the class-agnostic loc at loc0):
 // the box in original-image pixels, clipped to size; softmax over the n_class scores into prob_row.
 __device__ __forceinline__ float4 detect_decode_row(const float *__restrict__ roi, const float *__restrict__ o, int n_class, int loc0,
@@ -35,11 +49,8 @@ __device__ __forceinline__ float4 detect_decode_row(const float *__restrict__ ro
     float y1 = ncy - 0.5f * nh, x1 = ncx - 0.5f * nw, y2 = ncy + 0.5f * nh, x2 = ncx + 0.5f * nw;
     y1 = fmaxf(fminf(y1, size_h), 0.f); y2 = fmaxf(fminf(y2, size_h), 0.f);                       // clip (:202-203)
     x1 = fmaxf(fminf(x1, size_w), 0.f); x2 = fmaxf(fminf(x2, size_w), 0.f);
-    float m = -INFINITY;
-    for (int c = 0; c < n_class; ++c) m = fmaxf(m, o[c]);
-    float s = 0.f;
-    for (int c = 0; c < n_class; ++c) s += expf(o[c] - m);
-    for (int c = 0; c < n_class; ++c) prob_row[c] = expf(o[c] - m) / s;                            // F.softmax (:205)
+    const SoftmaxStats st = detect_softmax_stats(o, n_class);
+    for (int c = 0; c < n_class; ++c) prob_row[c] = detect_softmax_prob(o[c], st);                 // F.softmax (:205)
     return make_float4(y1, x1, y2, x2);
 }
 

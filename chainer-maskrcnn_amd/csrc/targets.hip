@@ -11,41 +11,13 @@
 // All kernels are latency-bound (a few thousand boxes) except anchor_target (A = 261,888 anchors
 // x G boxes, HBM-trivial).
 #include "common.h"
+#include "box_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 typedef unsigned long long u64;
-constexpr float kEps = 1.1920929e-07f;   // np.finfo(np.float32).eps
-
-__device__ __forceinline__ float box_iou(const float4 a, const float4 b) {
-    // ChainerCV bbox_iou: area_i = prod(br - tl) * all(tl < br); iou = area_i / (area_a + area_b - area_i)
-    const float tly = fmaxf(a.x, b.x), tlx = fmaxf(a.y, b.y);
-    const float bry = fminf(a.z, b.z), brx = fminf(a.w, b.w);
-    float area_i = (bry - tly) * (brx - tlx);
-    area_i = area_i * ((tly < bry && tlx < brx) ? 1.0f : 0.0f);
-    const float area_a = (a.z - a.x) * (a.w - a.y);
-    const float area_b = (b.z - b.x) * (b.w - b.y);
-    return area_i / ((area_a + area_b) - area_i);
-}
-
-__device__ __forceinline__ float4 bbox2loc(const float4 s, const float4 d) {
-    float h = s.z - s.x, w = s.w - s.y;
-    const float cy = s.x + 0.5f * h, cx = s.y + 0.5f * w;
-    const float bh = d.z - d.x, bw = d.w - d.y;
-    const float bcy = d.x + 0.5f * bh, bcx = d.y + 0.5f * bw;
-    h = fmaxf(h, kEps);
-    w = fmaxf(w, kEps);
-    return make_float4((bcy - cy) / h, (bcx - cx) / w, logf(bh / h), logf(bw / w));
-}
-
-__device__ __forceinline__ float fpn_level(float4 b) {
-    const float area = (b.z - b.x) * (b.w - b.y);
-    const float v = sqrtf(area) / 224.0f + 1e-6f;
-    const float t = floorf(4.0f + (float)log2((double)v));
-    return fminf(fmaxf(t, 0.f), 4.f);
-}
 
 // In-LDS bitonic sort (ascending) of n = power of two keys by the whole block.
 __device__ void bitonic_sort(u64 *s, int n) {

@@ -1055,6 +1055,40 @@ int mrcnn_group_norm_bwd_f32(const float *gy, const float *x, const float *gamma
                              int R, int H, int W, int C, int Cp, int G, int relu, float *gx, float *ggamma, float *gbeta,
                              int accumulate_params, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Cascade R-CNN box stages (cascade.hip, box_common.h; no counterpart in the reference).  float32, no contraction,
+ * correctly rounded divisions.
+ * cascade_refine: stage k -> stage k+1 over the R = N * S rows of the sampler's fixed row block (image i owns rows [i * S, (i + 1) * S)),
+ *   one launch, grid (ceil(S / 256), N), no host synchronisation.
+ *   rois (R,4) (y1,x1,y2,x2): stage k's input boxes in the forward's frame; box_out (R,ld): stage k's output, its class-agnostic deltas in
+ *   columns loc0 .. loc0 + 3; prev_label (R) int32, nullable: rows with a label < 0 pass through as padding (zero box, level 0, label -1).
+ *   mean4, std_prev4, std_next4: HOST arrays of 4 floats, read during the call.  per_image_hw: (N,2) device floats (h, w) of each image, or
+ *   NULL = every image is img_h x img_w.
+ *   Decode: d = box_out * std_prev + mean, loc2bbox as mrcnn_detect_decode_f32 without the un-scale, every corner clipped
+ *   fmaxf(fminf(v, lim), 0); no clamp on dh / dw (an overflowing expf clips to the full extent, the box is always finite).  levels = the
+ *   level map of mrcnn_map_rois_to_fpn_levels_f32 (k_min 0, k_max 4) of the refined box; rois_xy5 = (i, x1, y1, x2, y2).
+ *   gt_boxes (N,gt_cap,4), nullable: NULL = inference, only roi, rois_xy5 and levels are written and gt_labels, n_gt, std_next4, gt_loc,
+ *   label, gt_assign must be NULL too.  Otherwise the refined box is matched against the image's first min(n_gt[i], gt_cap) boxes with the IoU
+ *   and the NumPy max / argmax of mrcnn_proposal_target_f32 (first maximum; a NaN wins, the first NaN stays):
+ *     empty refined box (a side <= 0 after clipping): label -1, assign -1, gt_loc 0 (ignored by both losses; box and level still written)
+ *     no ground truth in the image: label 0, assign -1, gt_loc 0
+ *     else assign = argmax, label = gt_labels[argmax] + 1 where max >= iou_thresh (a NaN maximum: background), else 0;
+ *     gt_loc = (bbox2loc(roi, gt[argmax]) - mean) / std_next where label > 0, zeros elsewhere.
+ *   N == 0 or S == 0 succeeds without a launch.  Errors, before any launch: MRCNN_E_INVALID for a NULL rois / box_out / roi / rois_xy5 /
+ *   levels / mean4 / std_prev4, ld < loc0 + 4, negative sizes, N > 65535, ground-truth arguments that do not come together;
+ *   MRCNN_E_UNSUPPORTED for gt_cap > 256.
+ * cascade_prob: prob (R,n_class) = the mean over the K stages (2 <= K <= 4; box_out0 .. box_out{K-1}, the rest NULL; all (R,ld)) of the
+ *   softmax of columns 0 .. n_class - 1, each softmax with the arithmetic of mrcnn_detect_decode_f32, added in stage order and divided by
+ *   (float)K: ((p1 + p2) + p3) / 3.  One launch, one wave per row.  R == 0 succeeds without a launch.
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_cascade_refine_f32(const float *rois, const float *box_out, int ld, int loc0, const int32_t *prev_label, int N, int S,
+                             const float *loc_mean4, const float *std_prev4 /* host */, const float *per_image_hw, float img_h, float img_w,
+                             const float *gt_boxes, const int32_t *gt_labels, const int32_t *n_gt, int gt_cap, float iou_thresh,
+                             const float *std_next4 /* host */, float *roi, float *rois_xy5, int32_t *levels, float *gt_loc, int32_t *label,
+                             int32_t *gt_assign, void *stream);
+int mrcnn_cascade_prob_f32(const float *box_out0, const float *box_out1, const float *box_out2, const float *box_out3, int K, int R, int ld,
+                           int n_class, float *prob, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,8 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_head_norm_flags, add_tta_flags, boxpost_settings,  # noqa: E402,F401
-                                                head_norm_settings, read_labels, tta_settings, use_boxpost, use_tta)
+from chainer_maskrcnn.inference_options import (NO_CASCADE, add_boxpost_flags, add_cascade_flags, add_head_norm_flags, add_tta_flags,  # noqa: E402,F401
+                                                boxpost_settings, cascade_flag_settings, head_norm_settings, read_labels, tta_settings, use_boxpost, use_tta)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
@@ -127,6 +127,7 @@ def build_parser(keypoints=False):
                              'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
                              'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
     add_head_norm_flags(parser, both)
+    add_cascade_flags(parser, both)
     parser.add_argument(*both('--box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
                         help='box regression loss of the RoI head: smooth_l1 = the reference\'s, on the encoded deltas; giou / diou / ciou = on '
                              'the decoded box against the decoded target (FPNMaskRCNNTrainChain box_loss; same targets, normaliser and '
@@ -166,6 +167,20 @@ def check_resume_optim(resume, args, path=''):
     was, now = resume.get('optim', NO_OPTIM), optim_settings(args)[0]
     if was != now:
         raise ValueError('--resume %s: the checkpoint was trained with the optimizer recipe %r, this run asks for %r' % (path, was, now))
+
+
+def cascade_run_settings(args):
+    """The Cascade R-CNN box stages of a run as recorded in trainer_<it>.pt (NO_CASCADE when off); raises on a combination MaskRCNN refuses."""
+    s = cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone)
+    return {k: None if v is None else [list(x) if isinstance(x, tuple) else x for x in v] for k, v in s.items()}
+
+
+def check_resume_cascade(resume, args, path=''):
+    """A resumed run has the box stages of its checkpoint: the flat parameter and momentum buffers are laid out by them (a state without the
+    key was trained with one stage)."""
+    was, now = resume.get('cascade', NO_CASCADE), cascade_run_settings(args)
+    if was != now:
+        raise ValueError('--resume %s: the checkpoint was trained with the cascade %r, this run asks for %r' % (path, was, now))
 
 
 def freeze_settings(args):
@@ -292,6 +307,12 @@ def run(args, keypoints=False):
         raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
                          % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
     head_norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
+    cascade = cascade_run_settings(args)
+    if resume is not None:
+        check_resume_cascade(resume, args, args.resume)
+    if cascade['cascade_ious'] and (args.eval_tta_sizes or args.eval_tta_hflip):
+        raise ValueError('--cascade 1 does not go with --eval-tta-*: test-time augmentation of a cascade model is not supported')
+    head_norm = dict(head_norm, **cascade)
     box_loss = box_loss_settings(args.box_loss, args.rpn_box_loss, args.box_loss_weight, args.rpn_box_loss_weight)
     freeze = freeze_settings(args)
     if resume is not None:
@@ -472,7 +493,7 @@ def run(args, keypoints=False):
             if rank == 0:
                 save_npz(os.path.join(args.out, 'model_%d.npz' % it), faster_rcnn)      # snapshot_object, train.py:134-137
                 torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets,
-                            'augment': augment_settings(args), 'freeze': freeze, 'optim': optim},
+                            'augment': augment_settings(args), 'freeze': freeze, 'optim': optim, 'cascade': cascade},
                            os.path.join(args.out, 'trainer_%d.pt' % it))
     if loader is not None:
         loader.close()
