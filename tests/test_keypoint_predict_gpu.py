@@ -18,6 +18,7 @@ sys.path.insert(0, HERE)
 
 from chainer_maskrcnn._hip import ops  # noqa: E402
 from test_keypoint_eval_cpu import ref_coco_keypoint_eval  # noqa: E402
+from tests import predict_cases as pc  # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -71,6 +72,24 @@ def test_decode_equals_numpy(D, K):
     out2, idx2 = ops.keypoint_decode(h_dev, b_dev, K, return_index=True)
     assert torch.equal(out2.view(torch.int32), out.view(torch.int32)) and torch.equal(idx2, idx)     # bit-identical repeat
     assert torch.equal(ops.keypoint_decode(h_dev, b_dev, K).view(torch.int32), out.view(torch.int32))
+
+
+@pytest.mark.parametrize('S,K,Cp,D', pc.KEYPOINT_SHAPES)
+def test_decode_case(S, K, Cp, D):
+    """tests/predict_cases.py: every lanes-per-cell value P in {1, 2, 8, 16, 64} at every S in {7, 14, 28, 56}, the split counts 1 .. 392
+    (asserted in tests/test_predict_cases_cpu.py).  Index, y, x and logit bit for bit, the probability against the float64 sum."""
+    c = pc.keypoint_case(S, K, Cp, D)
+    h_dev, b_dev = torch.from_numpy(c['heat']).to(DEV), torch.from_numpy(c['bbox']).to(DEV)
+    out, idx = ops.keypoint_decode(h_dev, b_dev, K, return_index=True)
+    assert out.shape == (D, K, 4) and out.dtype == torch.float32 and idx.shape == (D, K) and idx.dtype == torch.int32
+    widx, wy, wx, wl, wp = c['want']
+    o, i = out.cpu().numpy(), idx.cpu().numpy()
+    np.testing.assert_array_equal(i, widx)
+    np.testing.assert_array_equal(o[..., 0], wy)
+    np.testing.assert_array_equal(o[..., 1], wx)
+    np.testing.assert_array_equal(o[..., 2], wl)
+    np.testing.assert_allclose(o[..., 3], wp, rtol=1e-6, atol=0)
+    assert i[0, 0] == 0 and abs(o[0, 0, 3] * S * S - 1) < 1e-6
 
 
 def test_decode_rejects_bad_arguments():
