@@ -846,6 +846,91 @@ def cascade_prob(box_outs, n_class):
     return prob
 
 
+# ---- Mask Scoring R-CNN (maskiou.hip) -------------------------------------------------------------------------
+def maskiou_target(masks, n_gt, sample_roi, gt_assign, label, n_pos, n_sample, rows, mask_out, gt_roi_mask, n_channels, label_base=1,
+                   want_counts=False):
+    """The MaskIoU regression target of every mask row (mrcnn_maskiou_target, two launches): masks (N,G,H,W) u8, n_gt (N,) i32, the
+    sampler's sample_roi (N*n_sample,4) / gt_assign (N*n_sample,) / n_pos (N,), and the mask block's label (N*rows,), mask_out
+    (N*rows,S,S,Cp) logits and gt_roi_mask (N*rows,S,S) i32 -> dict(target (Rm,) f32, area (N,G) i32[, counts (Rm,5) i32 = full, crop, pred,
+    gt28, ovr])."""
+    _ck(masks, n_gt, sample_roi, gt_assign, label, n_pos, mask_out, gt_roi_mask)
+    if masks.dim() != 4 or masks.dtype != torch.uint8:
+        raise ValueError('maskiou_target: masks are an (N,G,H,W) uint8 tensor')
+    N, G, H, W = masks.shape
+    rows, n_sample = int(rows), int(n_sample)
+    Rm = N * rows
+    if mask_out.dim() != 4 or mask_out.shape[0] != Rm or mask_out.shape[1] != mask_out.shape[2]:
+        raise ValueError('maskiou_target: mask_out %r for %d rows' % (tuple(mask_out.shape), Rm))
+    S, Cp = mask_out.shape[1], mask_out.shape[3]
+    if label.numel() != Rm or gt_roi_mask.numel() != Rm * S * S or sample_roi.numel() != N * n_sample * 4 or gt_assign.numel() != N * n_sample \
+            or n_pos.numel() != N or n_gt.numel() != N:
+        raise ValueError('maskiou_target: the row counts of label / gt_roi_mask / sample_roi / gt_assign / n_pos / n_gt do not fit N = %d, '
+                         'n_sample = %d, rows = %d' % (N, n_sample, rows))
+    for t_, ty in ((n_gt, i32), (gt_assign, i32), (label, i32), (n_pos, i32), (gt_roi_mask, i32), (sample_roi, f32), (mask_out, f32)):
+        if t_.dtype != ty:
+            raise ValueError('maskiou_target: a %s tensor where %s is expected' % (t_.dtype, ty))
+    dev = masks.device
+    o = dict(target=_empty((Rm,), dev), area=_empty((N, G), dev, i32))
+    if want_counts:
+        o['counts'] = _empty((Rm, 5), dev, i32)
+    nb = lib().mrcnn_maskiou_target_workspace_bytes(N, G)
+    ws = workspace(nb, dev) if nb else None
+    check(lib().mrcnn_maskiou_target(ptr(masks), N, G, H, W, ptr(n_gt), ptr(sample_roi), ptr(gt_assign), ptr(label), ptr(n_pos), n_sample,
+                                     rows, ptr(mask_out), S, Cp, int(n_channels), ptr(gt_roi_mask), int(label_base), ptr(o['area']),
+                                     ptr(o['target']), ptr(o.get('counts')), ptr(ws), ws.numel() if ws is not None else 0, stream_ptr()))
+    return o
+
+
+def maskiou_input_fwd(feat, mask_out, label, n_channels, cin_p, label_base=1):
+    """The MaskIoU head's input (mrcnn_maskiou_input_fwd): feat (Rm,P,P,C) pooled features and mask_out (Rm,2P,2P,Cp) logits ->
+    (Rm,P,P,cin_p): the features, the 2x2/2 max of the row's class logit in channel C, zeros behind it."""
+    _ck(feat, mask_out, label)
+    Rm, P, P2, C = feat.shape
+    if P != P2 or tuple(mask_out.shape[:3]) != (Rm, 2 * P, 2 * P) or label.numel() != Rm or label.dtype != i32:
+        raise ValueError('maskiou_input_fwd: feat %r, mask_out %r, %d labels' % (tuple(feat.shape), tuple(mask_out.shape), label.numel()))
+    out = _empty((Rm, P, P, int(cin_p)), feat.device)
+    check(lib().mrcnn_maskiou_input_fwd(ptr(feat), ptr(mask_out), ptr(label), int(label_base), Rm, P, C, mask_out.shape[3], int(n_channels),
+                                        int(cin_p), ptr(out), stream_ptr()))
+    return out
+
+
+def maskiou_input_bwd(g_in, g_pool):
+    """g_pool (Rm,P,P,C) += g_in (Rm,P,P,cin_p)[..., :C] in place (mrcnn_maskiou_input_bwd); returns g_pool."""
+    _ck(g_in, g_pool)
+    Rm, P, _, C = g_pool.shape
+    if g_in.dim() != 4 or tuple(g_in.shape[:3]) != tuple(g_pool.shape[:3]):
+        raise ValueError('maskiou_input_bwd: g_in %r against g_pool %r' % (tuple(g_in.shape), tuple(g_pool.shape)))
+    check(lib().mrcnn_maskiou_input_bwd(ptr(g_in), Rm, P, C, g_in.shape[3], ptr(g_pool), stream_ptr()))
+    return g_pool
+
+
+def maskiou_l2(pred, target, label, n_channels, weight=1.0, label_base=1, want_grad=True, gx=None, out=None):
+    """The MaskIoU loss (mrcnn_maskiou_l2): pred (Rm,ld), target (Rm,), label (Rm,) i32 -> (out (2,) = (weight * mean of 0.5 (x - t)^2 over
+    the rows with target > 0, their count), gx (Rm,ld) with the gradient in the label's column and zeros elsewhere)."""
+    _ck(pred, target, label, gx)
+    Rm, ld = pred.shape
+    if target.numel() != Rm or label.numel() != Rm or label.dtype != i32:
+        raise ValueError('maskiou_l2: %d targets, %d labels for %d rows' % (target.numel(), label.numel(), Rm))
+    out = _empty((2,), pred.device) if out is None else out
+    if want_grad and gx is None:
+        gx = torch.empty_like(pred)
+    ws = _loss_ws(pred.device)
+    check(lib().mrcnn_maskiou_l2(ptr(pred), ld, int(n_channels), ptr(target), ptr(label), int(label_base), Rm, float(weight), ptr(out),
+                                 ptr(gx) if want_grad else None, ptr(ws), ws.numel(), stream_ptr()))
+    return out, gx
+
+
+def maskiou_rescore(score, pred, label, n_channels):
+    """score (D,) * clamp(pred (D,ld)[d, label[d]], 0, 1) -> (D,) (mrcnn_maskiou_rescore); label (D,) i32, 0-based."""
+    _ck(score, pred, label)
+    D, ld = pred.shape
+    if score.numel() != D or label.numel() != D or label.dtype != i32 or score.dtype != f32:
+        raise ValueError('maskiou_rescore: %d scores, %d labels for %d rows' % (score.numel(), label.numel(), D))
+    out = _empty((D,), pred.device)
+    check(lib().mrcnn_maskiou_rescore(ptr(score), ptr(pred), ld, int(n_channels), ptr(label), D, ptr(out), stream_ptr()))
+    return out
+
+
 def class_nms(cls_bbox, prob, l_begin, l_end, score_thresh, nms_thresh):
     """-> keep_idx (n_class,R) int32, keep_cnt (n_class,) int32."""
     _ck(cls_bbox, prob)

@@ -168,6 +168,50 @@ def check_cascade_flags(args, tta_prefix='--'):
     return settings
 
 
+# ---- Mask Scoring R-CNN (MaskRCNN mask_iou, FPNMaskRCNNTrainChain mask_iou_weight) ----------------------------------------
+NO_MASK_IOU = {'mask_iou': False, 'mask_iou_weight': 1.0}       # what a trainer state without the 'mask_iou' key was trained with
+
+
+def add_mask_iou_flags(parser, both=lambda name: (name,), weight=False):
+    """--mask-iou (train.py, evaluate.py, demo.py; train_keypoints.py takes it to refuse it) and, with ``weight``, --mask-iou-weight
+    (the training scripts)."""
+    parser.add_argument(*both('--mask-iou'), type=int, default=0, choices=[0, 1],
+                        help='1: Mask Scoring R-CNN - a MaskIoU head regresses the IoU of every predicted mask with its ground truth and '
+                             'inference ranks a detection by box score x predicted mask IoU (MaskRCNN mask_iou; --head-arch fpn only); a '
+                             'checkpoint is evaluated with the value it was trained with')
+    if weight:
+        parser.add_argument(*both('--mask-iou-weight'), type=float, default=None, metavar='W',
+                            help='the weight of the MaskIoU head\'s L2 loss under --mask-iou 1 (default 1.0)')
+
+
+def mask_iou_settings(mask_iou, weight=None, head_arch='fpn'):
+    """{'mask_iou': bool, 'mask_iou_weight': float} of the flags; ValueError for a combination the model or the training chain refuses."""
+    from chainer_maskrcnn.model.maskrcnn import mask_iou_setting
+    from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import mask_iou_weight_setting
+    if mask_iou not in (0, 1):
+        raise ValueError('--mask-iou must be 0 or 1, got %r' % (mask_iou,))
+    if not mask_iou:
+        if weight is not None:
+            raise ValueError('--mask-iou-weight belongs to --mask-iou 1')
+        return dict(NO_MASK_IOU)
+    try:
+        on = mask_iou_setting(bool(mask_iou), head_arch)
+        w = mask_iou_weight_setting(1.0 if weight is None else weight)
+    except ValueError as e:
+        raise ValueError('--mask-iou 1: %s' % e)
+    return {'mask_iou': on, 'mask_iou_weight': w}
+
+
+def check_mask_iou_flags(args, tta_prefix='--'):
+    """--mask-iou of an inference script (evaluate.py, demo.py) checked before the model is built: mask_iou_settings' refusals, and no
+    test-time augmentation on top of it (MaskRCNN.use_test_augmentation refuses it)."""
+    settings = mask_iou_settings(args.mask_iou, None, args.head_arch)
+    if settings['mask_iou'] and (args.tta_sizes or args.tta_hflip):
+        raise ValueError('--mask-iou 1 does not go with %stta-sizes / %stta-hflip: test-time augmentation of a Mask Scoring model is not '
+                         'supported' % (tta_prefix, tta_prefix))
+    return settings
+
+
 # ---- labels and the model -----------------------------------------------------------------------------------------------------------------
 def read_labels(label_file):
     """The category names of --label_file (None when the file does not exist: every category)."""
@@ -185,7 +229,7 @@ def use_score_preset(model, preset, score_thresh=None):
 
 
 def build_inference_model(args, preset=None):
-    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --gn-groups / --cascade* / --label_file with --weight loaded (keys missing from the file keep their
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --gn-groups / --cascade* / --mask-iou / --label_file with --weight loaded (keys missing from the file keep their
     initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
     17 keypoints; a mask head has one class per label (80 without a label file)."""
     import torch
@@ -193,7 +237,8 @@ def build_inference_model(args, preset=None):
     from chainer_maskrcnn.utils import chainer_npz
     norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
     norm.update(cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone))
-    dev = torch.device('cuda', args.gpu)
+    norm['mask_iou'] = mask_iou_settings(getattr(args, 'mask_iou', 0), None, args.head_arch)['mask_iou']
+    dev =torch.device('cuda', args.gpu)
     torch.cuda.set_device(dev)
     if args.head_arch == 'fpn_keypoint':
         model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev, **norm)

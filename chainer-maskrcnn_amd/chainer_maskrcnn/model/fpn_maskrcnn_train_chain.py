@@ -131,6 +131,14 @@ def box_loss_settings(box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_w
                 rpn_box_loss_weight=float(rpn_box_loss_weight))
 
 
+def mask_iou_weight_setting(weight):
+    """The mask_iou_weight argument of FPNMaskRCNNTrainChain as a float, checked like the box-loss weights: ValueError unless it is a finite
+    number above 0."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
+        raise ValueError('mask_iou_weight must be a finite number above 0, got %r' % (weight,))
+    return float(weight)
+
+
 def select_gemm_arithmetic(name):
     """Process-wide: the library's split-operand modes and the per-layer rule of nn/core.py."""
     from chainer_maskrcnn._hip import lib, check
@@ -149,7 +157,7 @@ class FPNMaskRCNNTrainChain(object):
 
     def __init__(self, faster_rcnn, mask_loss_fun=calc_mask_loss, binary_mask=True, rpn_sigma=3., roi_sigma=1.,
                  anchor_target_creator=None, strict_batch1=False, mask_rows='positives', gemm_arithmetic=None,
-                 box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0):
+                 box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0, mask_iou_weight=1.0):
         """gemm_arithmetic: a key of GEMM_ARITHMETIC - the chain then selects it (process-wide library setting) at the start of every
         step; None (default of this constructor, used by the kernel-level tests) leaves the process setting alone.  train.py and
         bench.py pass DEFAULT_GEMM_ARITHMETIC.
@@ -157,8 +165,13 @@ class FPNMaskRCNNTrainChain(object):
         box_loss / rpn_box_loss: the box regression loss of the RoI head / the RPN, one of BOX_LOSSES.  'smooth_l1' (default) is the
         reference's loss on the encoded deltas; 'giou', 'diou', 'ciou' decode prediction and target against the sampled RoI / the anchor
         and take the loss on the boxes (ops.box_iou_loss) - same targets, same normaliser, same report keys.
-        box_loss_weight / rpn_box_loss_weight multiply that loss and its gradient; smooth L1 takes no weight (1.0 only)."""
+        box_loss_weight / rpn_box_loss_weight multiply that loss and its gradient; smooth L1 takes no weight (1.0 only).
+
+        mask_iou_weight: multiplies the MaskIoU head's L2 loss and its gradient (a finite number above 0; Mask Scoring R-CNN, DESIGN.md
+        section 3.22).  It acts on a model built with ``mask_iou=True`` only: the chain then runs target -> input assembly -> head -> L2
+        behind the mask loss and reports ``maskiou_loss``."""
         box_loss_settings(box_loss, rpn_box_loss, box_loss_weight, rpn_box_loss_weight)
+        self.mask_iou_weight = mask_iou_weight_setting(mask_iou_weight)
         self.box_loss, self.rpn_box_loss = box_loss, rpn_box_loss
         self.box_loss_weight, self.rpn_box_loss_weight = float(box_loss_weight), float(rpn_box_loss_weight)
         if gemm_arithmetic is not None and gemm_arithmetic not in GEMM_ARITHMETIC:
@@ -182,6 +195,9 @@ class FPNMaskRCNNTrainChain(object):
         self.mask_loss_kind = getattr(mask_loss_fun, 'fused_kind', None)
         if self.mask_loss_kind not in ('mask_bce', 'keypoint_ce'):
             self.mask_loss_kind = 'generic'
+        if getattr(faster_rcnn, 'maskiou_head', None) is not None and self.mask_loss_kind != 'mask_bce':
+            raise ValueError('a mask_iou model trains with the fused binary mask loss (calc_mask_loss): a user-supplied mask_loss_fun '
+                             're-orders the mask rows, which the MaskIoU target does not follow')
         self.unit_upstream = False
         self.backward_follows = False       # set by MomentumSGD.update around its forward call: loss.backward() comes next, with d loss = 1
         self.binary_mask = binary_mask
@@ -195,6 +211,7 @@ class FPNMaskRCNNTrainChain(object):
         self.outputs = {}
         self._aux = {}
         self._bwd_cascade = ()
+        self._bwd_maskiou = None
         self._arith_found = None            # the process's GEMM arithmetic before this chain selected its own (restored by backward())
 
     def _aux_stream(self, dev):
@@ -247,7 +264,9 @@ class FPNMaskRCNNTrainChain(object):
         m.rpn.train = True
         pk, ak = self.sampler_keys if self.sampler_keys is not None else (None, None)
         stages = list(getattr(m, 'cascade_heads', []))        # Cascade R-CNN: the box stages behind the head
-        losses = torch.empty((5 + 2 * len(stages), 2), dtype=torch.float32, device=dev)
+        mh = getattr(m, 'maskiou_head', None)                 # Mask Scoring R-CNN: the MaskIoU head
+        iou_row = 5 + 2 * len(stages)                         # its loss row, behind the cascade's
+        losses = torch.empty((iou_row + (1 if mh is not None else 0), 2), dtype=torch.float32, device=dev)
         br1 = {}
 
         def rpn_loss_branch(locs, scores, anchors):
@@ -358,6 +377,20 @@ class FPNMaskRCNNTrainChain(object):
             g_mask = torch.empty_like(mask_out) if ops.softmax_ce_fills_gradient(Rm * K, Hm * Wm, xmap) else torch.zeros_like(mask_out)
             ops.softmax_ce(mask_out, t['gt_roi_mask'].view(-1), Rm * K, Hm * Wm, xmap, gx=g_mask, out=losses[4])
 
+        g_iou, iou = None, None
+        if mh is not None:
+            # Behind the mask loss, on the main stream and the mask branch's own rows: the IoU of each row's thresholded logits with its
+            # ground truth (integer counts), the head's input (pooled features + the max-pooled class logit, a constant), the head, the L2
+            # loss over the rows that have a target.  No host synchronisation.
+            m_label = m_label.contiguous()
+            iou = ops.maskiou_target(masks.contiguous(), n_gt, t['sample_roi'], t['gt_assign'], m_label, t['n_pos'], S, rows, mask_out, t['gt_roi_mask'],
+                                     mh.out_channels, label_base=1, want_counts=self.keep_outputs)
+            iou['input'] = mh.assemble(head.last_mask_pool, mask_out, m_label, label_base=1)
+            iou['pred'] = mh.forward(iou['input'])
+            _, g_iou = ops.maskiou_l2(iou['pred'], iou['target'], m_label, mh.out_channels, weight=self.mask_iou_weight, label_base=1,
+                                      out=losses[iou_row])
+            iou['g_pred'] = g_iou
+
         main.wait_stream(aux)
         if aux is not main:             # allocated on the aux stream, consumed by the RPN backward on the main stream
             g_locs.record_stream(main)
@@ -368,14 +401,19 @@ class FPNMaskRCNNTrainChain(object):
         for k in range(2, 2 + len(stages)):         # the existing keys are stage 1's
             self.observation['roi_loc_loss_s%d' % k] = losses[5 + 2 * (k - 2), 0]
             self.observation['roi_cls_loss_s%d' % k] = losses[6 + 2 * (k - 2), 0]
+        if mh is not None:
+            self.observation['maskiou_loss'] = losses[iou_row, 0]
         self._bwd = (features, g_locs.view(n, A, 4), g_scores.view(n, A, 2), g_box, g_mask)
         self._bwd_cascade = g_boxes[1:]          # the later box stages' loss gradients, in stage order
+        self._bwd_maskiou = g_iou                # the MaskIoU loss gradient (None without the head)
         self._early_rpn = br1.get('g_feats')
         self.targets = t
         if self.keep_outputs:
             self.outputs = dict(features=features, locs=r['locs'], scores=r['scores'], box=box, mask=mask_out)
             if stages:      # per later stage: the refine outputs (roi, rois_xy5, levels, gt_loc, label, gt_assign) and 'box'; every stage's loss gradient
                 self.outputs.update(cascade=casc, g_boxes=g_boxes, losses=losses)
+            if mh is not None:      # target, area, counts, input, pred, g_pred of the MaskIoU head, the mask loss gradient and the pooled features
+                self.outputs.update(maskiou=iou, g_mask=g_mask, mask_pool=head.last_mask_pool, losses=losses)
         self.rpn_targets = (gt_rpn_loc, gt_rpn_label)
         self.mask_inputs = (m_rois, m_levels, m_label)
         self.rpn_out = r
@@ -422,9 +460,10 @@ class FPNMaskRCNNTrainChain(object):
         m = self.faster_rcnn
         features, g_locs, g_scores, g_box, g_mask = self._bwd
         g_later = self._bwd_cascade
+        g_iou = self._bwd_maskiou
         if upstream is not None:
             from chainer_maskrcnn.functions.loss import _scale_
-            for g_ in (g_locs, g_scores, g_box, g_mask) + tuple(g_later):
+            for g_ in (g_locs, g_scores, g_box, g_mask) + tuple(g_later) + ((g_iou,) if g_iou is not None else ()):
                 _scale_(g_, upstream)
         hook = self.grad_ready_hook
         dev = features[0].device
@@ -443,10 +482,19 @@ class FPNMaskRCNNTrainChain(object):
             m.head.backward_box(g_box, g_feats, accumulate=into_early)     # overwrites g_feats (first pooled size) unless they hold the RPN's
             for stage, g_k in zip(getattr(m, 'cascade_heads', []), g_later):      # the later box stages add theirs, in stage order
                 stage.backward_box(g_k, g_feats, accumulate=True)
+        # the MaskIoU head first (main stream): its parameter gradients are final and its input gradient is at hand before the mask
+        # branch's; the feature part joins the mask convolutions' pooled gradient, so the ONE ROIAlign backward below carries both
+        g_iou_in = m.maskiou_head.backward(g_iou) if g_iou is not None else None
         g_pool = m.head.backward_mask_convs(g_mask)       # main stream: the mask branch down to its pooled input
+        if g_iou_in is not None:
+            if self.keep_outputs:       # parity tests: the two summands
+                self.outputs.update(g_mask_pool_convs=g_pool.clone(), g_maskiou_in=g_iou_in)
+            ops.maskiou_input_bwd(g_iou_in, g_pool)
         main.wait_stream(aux)
+        if self.keep_outputs and g_iou_in is not None:       # ... and the pyramid gradient the box stages left
+            self.outputs.update(g_feats_box=[g.clone() for g in g_feats])
         m.head.backward_mask_pool(g_pool, g_feats)        # accumulates into g_feats (second pooled size)
-        if self.keep_outputs and g_later:       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
+        if self.keep_outputs and (g_later or g_iou_in is not None):       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
             self.outputs.update(g_mask_pool=g_pool, g_feats_heads=[g.clone() for g in g_feats])
         if hook:
             hook(self._offset_of('head/'))
@@ -471,6 +519,7 @@ class FPNMaskRCNNTrainChain(object):
             hook(0)
         self._bwd = None
         self._bwd_cascade = ()
+        self._bwd_maskiou = None
         if self._arith_found is not None:
             from chainer_maskrcnn._hip import lib, check
             split, in_backbone = self._arith_found

@@ -186,8 +186,71 @@ class FPNRoIBoxHead(object):
         self.box_tape = None
 
 
+class MaskIoUHead(object):
+    """The MaskIoU head of Mask Scoring R-CNN (Huang et al. 2019): it regresses, per class, the IoU between a row's
+    predicted mask and its ground truth.  Input (Rm,14,14,C+1): the mask branch's pooled features and the 2x2/2 max of the row's class logit
+    (ops.maskiou_input_fwd - a constant: no gradient flows into the mask logits).  conv1..conv3 3x3/1, conv4 3x3/2 (14 -> 7), fc1, fc2,
+    ``maskiou`` (fc_channels -> n_class - 1); ReLU behind every layer but the last.  The convolutions are plain conv + ReLU whatever the
+    other heads' ``head_norm`` is.  Parameters ``head/maskiou/...``; its own tape and ``backward``."""
+    pool_size = 14
+
+    def __init__(self, n_class, ps, prefix='head/maskiou', in_channels=256, fc_channels=1024, initialW=None):
+        c = in_channels
+        if c % 32:
+            raise ValueError('MaskIoUHead: %d channels (a multiple of 32 expected)' % c)
+        self.ps, self.n_class, self.channels = ps, n_class, c
+        self.out_channels = n_class - 1
+        p = prefix + '/'
+        self.conv1 = Conv(ps, p + 'conv1', c + 1, c, 3, 1, 1, relu=True, fwd_tile=0)
+        self.conv2 = Conv(ps, p + 'conv2', c, c, 3, 1, 1, relu=True, fwd_tile=0)
+        self.conv3 = Conv(ps, p + 'conv3', c, c, 3, 1, 1, relu=True, fwd_tile=0)
+        self.conv4 = Conv(ps, p + 'conv4', c, c, 3, 2, 1, relu=True)
+        self.out_size = (self.pool_size + 2 - 3) // 2 + 1
+        self.fc1 = Conv(ps, p + 'fc1', c * self.out_size * self.out_size, fc_channels, relu=True)
+        self.fc2 = Conv(ps, p + 'fc2', fc_channels, fc_channels, relu=True)
+        self.out = Conv(ps, p + 'maskiou', fc_channels, self.out_channels, 1, init=normal(0.01 if initialW is None else initialW))
+        self.cin_p, self.out_p = self.conv1.cin_p, self.out.cout_p
+        self.convs = [self.conv1, self.conv2, self.conv3, self.conv4]
+        self.tape = None
+
+    def assemble(self, pool, mask_out, label, label_base=1):
+        """The head's input from the mask branch's pooled features, its logits and the rows' labels."""
+        return ops.maskiou_input_fwd(pool, mask_out, label, self.out_channels, self.cin_p, label_base=label_base)
+
+    def forward(self, x):
+        """x (Rm,14,14,cin_p) -> (Rm,out_p): column k = the predicted IoU of class k + 1's mask."""
+        h, tapes = x, []
+        for cv in self.convs:
+            h, t = cv.fwd(h)
+            tapes.append(t)
+        R = h.shape[0]
+        shape4 = tuple(h.shape)
+        h, t5 = self.fc1.fwd(h.view(R, 1, 1, -1))
+        h, t6 = self.fc2.fwd(h)
+        o, t7 = self.out.fwd(h)
+        self.tape = (tapes, shape4, t5, t6, t7)
+        return o.view(R, self.out_p)
+
+    def backward(self, g_pred):
+        """g_pred (Rm,out_p) -> the gradient of the input (Rm,14,14,cin_p); fills the head/maskiou/ parameter gradients."""
+        tapes, shape4, t5, t6, t7 = self.tape
+        R = g_pred.shape[0]
+        # every layer's input but conv1's is the ReLU output of the layer below: the ReLU backward rides in the data-gradient epilogue
+        g = self.out.bwd(t7, g_pred.view(R, 1, 1, -1), mask_gx=True)
+        g = self.fc2.bwd(t6, g, gy_masked=True, mask_gx=True)
+        g = self.fc1.bwd(t5, g, gy_masked=True, mask_gx=True)
+        g = g.view(shape4)
+        for i in (3, 2, 1):
+            g = self.convs[i].bwd(tapes[i], g, gy_masked=True, mask_gx=True)
+        g = self.conv1.bwd(tapes[0], g, gy_masked=True)
+        self.tape = None
+        return g
+
+
 class FPNRoIMaskHead(FPNRoIBoxHead):
     mask_size = 28
+    keep_mask_pool = False          # set by a model with a MaskIoU head: mask_branch leaves its pooled features in last_mask_pool
+    last_mask_pool = None
 
     def __init__(self, n_class, roi_size_box, roi_size_mask, loc_initialW=None, score_initialW=None,
                  mask_initialW=None, ps=None, prefix='head', in_channels=256, fc_channels=1024,
@@ -222,6 +285,8 @@ class FPNRoIMaskHead(FPNRoIBoxHead):
     # ---- forward --------------------------------------------------------------------------------
     def mask_branch(self, xs, rois_xy5, levels, spatial_scales):
         pool = roi_align_fpn_fwd(xs, rois_xy5, levels, self.roi_size_mask, spatial_scales)
+        if self.keep_mask_pool:                # the MaskIoU head reads the same pooled features
+            self.last_mask_pool = pool
         h, tapes = pool, []
         for cv, gn in zip(self.mask_convs, self.mask_gns):
             h, t = cv.fwd(h)

@@ -17,7 +17,7 @@ from chainer_maskrcnn.nn.core import ParamStore
 from chainer_maskrcnn._hip import ops
 from .extractor.feature_pyramid_network import FeaturePyramidNetwork
 from .rpn.multilevel_region_proposal_network import MultilevelRegionProposalNetwork
-from .head.fpn_roi_mask_head import FPNRoIBoxHead, FPNRoIMaskHead
+from .head.fpn_roi_mask_head import FPNRoIBoxHead, FPNRoIMaskHead, MaskIoUHead
 
 # Cascade R-CNN (Cai & Vasconcelos 2018): the stages' normalisation of the box deltas; stage 1's is the model's loc_normalize_std
 CASCADE_STDS = ((0.1, 0.1, 0.2, 0.2), (0.05, 0.05, 0.1, 0.1), (0.033, 0.033, 0.067, 0.067))
@@ -60,6 +60,16 @@ def cascade_settings(cascade_ious, cascade_stds=None, head_arch='fpn', backbone=
     return ious, stds
 
 
+def mask_iou_setting(mask_iou, head_arch='fpn'):
+    """The checked mask_iou argument of MaskRCNN as a bool; ValueError for a value that is no truth value and for the heads that have no
+    binary mask to score (the keypoint head, the legacy 'res5' / 'light' heads)."""
+    if mask_iou not in (False, True, 0, 1):
+        raise ValueError('mask_iou must be True or False, got %r' % (mask_iou,))
+    if mask_iou and head_arch != 'fpn':
+        raise ValueError("mask_iou exists for head_arch 'fpn' only, not %r" % (head_arch,))
+    return bool(mask_iou)
+
+
 class MaskRCNN(object):
     feat_stride = 16
     # box post-processing of _suppress (DESIGN.md §3.16), off until use_soft_nms / use_box_voting / use_max_detections set them on an instance
@@ -69,16 +79,23 @@ class MaskRCNN(object):
     # Cascade R-CNN box stages, off unless the constructor's cascade_ious sets them
     cascade = None                  # (ious, stds)
     cascade_heads = ()
+    # Mask Scoring R-CNN, off unless the constructor's mask_iou builds the head
+    maskiou_head = None
+    mask_iou_rescore = True         # predict: score = box score x predicted mask IoU (False: the box score, on a model that has the head)
+    last_box_scores = None          # predict: the box scores of the last call's detections, one array per image
 
     def __init__(self, n_fg_class, n_keypoints=None, n_mask_convs=None, pretrained_model=None, min_size=600,
                  max_size=1000, ratios=[0.5, 1, 2], anchor_scales=[8], rpn_initialW=None, loc_initialW=None,
                  score_initialW=None, proposal_creator_params={}, backbone='fpn', head_arch='fpn',
-                 device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32, cascade_ious=None, cascade_stds=None):
+                 device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32, cascade_ious=None, cascade_stds=None,
+                 mask_iou=False):
         """head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
         convolution of the 'fpn' / 'fpn_keypoint' heads.
         cascade_ious: None = one box stage; (0.5, 0.6, 0.7) = Cascade R-CNN: K box stages trained at these IoU thresholds,
         stage k > 1 a box-only head ``head/cascade<k>/...`` registered directly behind the stage-1 head's parameters and fed stage k-1's
-        refined boxes; ``cascade_stds`` their delta normalisation (cascade_settings)."""
+        refined boxes; ``cascade_stds`` their delta normalisation (cascade_settings).
+        mask_iou: True = Mask Scoring R-CNN: a MaskIoU head ``head/maskiou/...`` behind every other head parameter (the
+        cascade's included) regresses the IoU of each predicted mask; ``predict`` multiplies it into the score.  head_arch 'fpn' only."""
         if n_fg_class is None:
             raise ValueError('The n_fg_class needs to be supplied as an argument')
         if head_norm not in (None, 'gn'):
@@ -87,6 +104,7 @@ class MaskRCNN(object):
             raise ValueError("head_norm=%r exists for head_arch 'fpn' and 'fpn_keypoint' only, not %r" % (head_norm, head_arch))
         self.head_norm, self.gn_groups = head_norm, int(gn_groups)
         self.cascade = cascade_settings(cascade_ious, cascade_stds, head_arch, backbone)
+        self.mask_iou = mask_iou_setting(mask_iou, head_arch)
         self.ps = ParamStore()
         shrink = _test_shrink or {}
         if backbone == 'fpn':
@@ -148,6 +166,12 @@ class MaskRCNN(object):
                 self.cascade_heads.append(FPNRoIBoxHead(self.head.n_class, roi_size_box=7, loc_initialW=loc_initialW, score_initialW=score_initialW,
                                                         ps=self.ps, prefix='head/cascade%d' % k, in_channels=c,
                                                         fc_channels=1024 // shrink.get('width_div', 1), norm=head_norm, gn_groups=self.gn_groups))
+        # Mask Scoring R-CNN: the MaskIoU head, behind every existing head parameter - each keeps its offset and its initial draw
+        self.maskiou_head = None
+        if self.mask_iou:
+            self.maskiou_head = MaskIoUHead(self.head.n_class, ps=self.ps, prefix='head/maskiou', in_channels=c,
+                                            fc_channels=1024 // shrink.get('width_div', 1))
+            self.head.keep_mask_pool = True
         # FasterRCNN base-class state
         self.mean = np.array([122.7717, 115.9465, 102.9801], dtype=np.float32)[:, None, None]   # unused (maskrcnn.py:273-274)
         self.min_size, self.max_size = min_size, max_size
@@ -216,6 +240,8 @@ class MaskRCNN(object):
             return
         if self.cascade is not None:
             raise ValueError('use_test_augmentation: test-time augmentation of a cascade model (cascade_ious) is not supported')
+        if self.maskiou_head is not None:
+            raise ValueError('use_test_augmentation: test-time augmentation of a Mask Scoring model (mask_iou) is not supported')
         sizes = [int(s) for s in sizes]
         if not sizes or any(s <= 0 for s in sizes):
             raise ValueError('use_test_augmentation: sizes must be positive, got %r' % (sizes,))
@@ -366,16 +392,30 @@ class MaskRCNN(object):
         if branch and bbox.shape[0] > 0:        # not through _branch_per_view: the one view's levels are the proposals' own
             m = self.head.mask_branch(self.head.x, self._xy5(bbox, scale), level.to(torch.int32).contiguous(),
                                       self.extractor.spatial_scales)
+        self._box_score = score
+        self.last_maskiou = None
+        if m is not None and self.maskiou_head is not None and self.predict_mask:
+            # Mask Scoring R-CNN: the MaskIoU head on the kept detections, behind the mask branch and behind _suppress -
+            # the order, the count, the boxes and the masks of the detections are those of the box scores (use_max_detections included)
+            mh = self.maskiou_head
+            lab = label.to(torch.int32).contiguous()
+            x_in = mh.assemble(self.head.last_mask_pool, m, lab, label_base=0)
+            pred = mh.forward(x_in)
+            self.last_maskiou = (x_in, pred)        # parity tests read these
+            if self.mask_iou_rescore:
+                score = ops.maskiou_rescore(score.to(torch.float32).contiguous(), pred, lab, mh.out_channels)
         return size, bbox, label, score, m, None
 
     def predict(self, imgs):
         """maskrcnn.py:157-259: imgs = list of (3,H,W) float32 tensors (0..255).  Returns (masks, labels, scores) -
         lists with one entry per image: masks (D,H,W) bool, labels (D,) int32 in [0, n_fg_class-1], scores (D,) float32 -
-        and keeps the boxes in ``self.last_bboxes``.  One device->host copy per image (the per-class keep counts)."""
-        masks, labels, scores, bboxes = [], [], [], []
+        and keeps the boxes in ``self.last_bboxes``.  One device->host copy per image (the per-class keep counts).  On a ``mask_iou`` model
+        the scores are box score x predicted mask IoU (unless ``mask_iou_rescore`` is False); ``self.last_box_scores`` keeps the box scores."""
+        masks, labels, scores, bboxes, box_scores = [], [], [], [], []
         with self._inference_mode():
             for img in imgs:
                 size, bbox, label, score, m, mirrors = self._detect_and_branch(img, self.predict_mask)
+                box_scores.append(score if mirrors is not None else self._box_score)
                 if m is None:
                     mask = torch.zeros((bbox.shape[0],) + size, dtype=torch.bool, device=self.device)
                 elif mirrors is None:
@@ -387,6 +427,7 @@ class MaskRCNN(object):
                 scores.append(score)
                 bboxes.append(bbox)
         self.last_bboxes = bboxes
+        self.last_box_scores = box_scores       # the scores before the MaskIoU rescoring (the same tensors without a MaskIoU head)
         return masks, labels, scores
 
     def _detect(self, img):

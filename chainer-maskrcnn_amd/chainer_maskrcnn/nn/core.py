@@ -309,7 +309,14 @@ class Conv(object):
                 assert not (mask_gx and gx_acc is not None) or self.k == 1
                 return hnn.conv2d_bwd_data_raw(gy, self.W, tuple(x.shape), 1, self.pad, out=gx_acc,
                                                relu_x=x if mask_gx else None)
-            assert self.k == 1 and self.pad == 0, 'strided backward-data only for 1x1 convolutions'
+            if self.k > 1:
+                # a strided k x k layer (the MaskIoU head's 3x3/2): the library's data gradient is stride 1 only, so gy is scattered onto
+                # the stride-1 output lattice (zeros between) and that layer's data gradient is taken - the same sums plus zero terms
+                assert self.k == 2 * self.pad + 1 and gx_acc is None, 'strided k x k backward-data: odd kernel with "same" padding'
+                N, H, W, _ = x.shape
+                g_up = ops.subsample_bwd(gy, (N, H, W, gy.shape[3]), self.stride)
+                return hnn.conv2d_bwd_data_raw(g_up, self.W, tuple(x.shape), 1, self.pad, relu_x=x if mask_gx else None)
+            assert self.pad == 0, 'strided backward-data of a 1x1 convolution takes no padding'
             g_sub = self.bwd_data_sub(gy)
         finally:
             hnn.LOGICAL = None

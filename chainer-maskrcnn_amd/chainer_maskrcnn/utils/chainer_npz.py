@@ -5,7 +5,8 @@ with ``load_npz(..., strict=False)`` (train.py:99-101).  NPZ keys are Chainer li
 layouts:  Convolution2D W (Cout, Cin, KH, KW), Linear W (out, in) with the input flattened (C, H, W)-major,
 Deconvolution2D W (Cin, Cout, KH, KW), BatchNormalization gamma / beta / avg_mean / avg_var / N.  The GroupNorm layers of a
 ``head_norm='gn'`` model (no counterpart in the reference) go out as GroupNormalization gamma / beta (C,) under their store names
-``head/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.
+``head/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.  The MaskIoU head of a ``mask_iou`` model (no
+counterpart either) goes out as ``head/maskiou/{conv1..conv4}`` (Convolution2D) and ``head/maskiou/{fc1,fc2,maskiou}`` (Linear).
 
 Storage here differs only mechanically - conv W (Cout_p, KH, KW, Cin_p) with zero-padded channels, NHWC
 flattening for ``fc1``, ``rpn/loc`` + ``rpn/score`` fused into ``rpn/loc_score``, ``head/cls_loc`` + ``head/score``
@@ -62,6 +63,14 @@ class ChainerNpzMap(object):
             self._add_conv(st.fc2)
             if st.gn1 is not None:
                 self.gns.append(st.gn1)
+        # the MaskIoU head of a mask_iou model (no counterpart in the reference): head/maskiou/{conv1..conv4, fc1, fc2, maskiou}, the
+        # convolutions as Convolution2D, fc1 / fc2 / maskiou as Linear - fc1 with the flatten permutation of the box head's fc1
+        self.maskiou = getattr(model, 'maskiou_head', None)
+        self.linears = set()
+        if self.maskiou is not None:
+            for cv in self.maskiou.convs + [self.maskiou.fc2, self.maskiou.out]:
+                self._add_conv(cv)
+            self.linears.add(self.maskiou.out.name)
 
     def _add_conv(self, cv):
         self.convs[cv.name] = cv
@@ -71,9 +80,16 @@ class ChainerNpzMap(object):
         """dict of NumPy arrays keyed like a Chainer snapshot of ``model.faster_rcnn``."""
         g = lambda n: self.ps.p(n).detach().cpu().numpy()
         out = {}
+
+        def fc1_out(pre, fc1, c, s):
+            # fc1: ours (out, 1, 1, (h, w, c)) -> Chainer Linear (out, (c, h, w))
+            w = g(fc1.name + '/W')[:fc1.cout, 0, 0, :]
+            out[pre + '/fc1/W'] = np.ascontiguousarray(w.reshape(-1, s, s, c).transpose(0, 3, 1, 2).reshape(w.shape[0], -1))
+            out[pre + '/fc1/b'] = g(fc1.name + '/b')[:fc1.cout].copy()
+
         for name, cv in self.convs.items():
             wn = g(name + '/W')
-            if name.endswith('/fc2'):
+            if name.endswith('/fc2') or name in self.linears:
                 out[name + '/W'] = np.ascontiguousarray(wn[:cv.cout, 0, 0, :cv.cin])
             else:
                 out[name + '/W'] = _conv_from_native(wn, cv.cout, cv.cin)
@@ -102,11 +118,9 @@ class ChainerNpzMap(object):
             out[pre + '/score/b'] = b[:h.n_class].copy()
             out[pre + '/cls_loc/W'] = w[h.LOC0:h.LOC0 + 4].copy()
             out[pre + '/cls_loc/b'] = b[h.LOC0:h.LOC0 + 4].copy()
-            # fc1: ours (out, 1, 1, (h, w, c)) -> Chainer Linear (out, (c, h, w))
-            c, s = h.channels, h.roi_size_box
-            w = g(h.fc1.name + '/W')[:h.fc1.cout, 0, 0, :]
-            out[pre + '/fc1/W'] = np.ascontiguousarray(w.reshape(-1, s, s, c).transpose(0, 3, 1, 2).reshape(w.shape[0], -1))
-            out[pre + '/fc1/b'] = g(h.fc1.name + '/b')[:h.fc1.cout].copy()
+            fc1_out(pre, h.fc1, h.channels, h.roi_size_box)
+        if self.maskiou is not None:
+            fc1_out('head/maskiou', self.maskiou.fc1, self.maskiou.channels, self.maskiou.out_size)
         h = self.head
         c = h.channels
         # deconv1: ours ((a*2+b)*C + o, 1, 1, ci) -> Chainer Deconvolution2D (ci, o, a, b)
@@ -129,6 +143,16 @@ class ChainerNpzMap(object):
             if not ok and strict:
                 raise KeyError('missing %s' % (keys,))
             return ok
+
+        def fc1_in(pre, fc1, c, s):
+            # fc1: Chainer Linear (out, (c, h, w)) -> ours (out, 1, 1, (h, w, c))
+            if have(pre + '/fc1/W', pre + '/fc1/b'):
+                w = np.asarray(arrays[pre + '/fc1/W'])
+                wn = np.zeros((fc1.cout_p, 1, 1, fc1.cin_p), np.float32)
+                wn[:w.shape[0], 0, 0, :] = w.reshape(-1, c, s, s).transpose(0, 2, 3, 1).reshape(w.shape[0], -1)
+                put(fc1.name + '/W', wn)
+                put(fc1.name + '/b', _vec_to_native(np.asarray(arrays[pre + '/fc1/b']), fc1.cout_p))
+                loaded.extend([pre + '/fc1/W', pre + '/fc1/b'])
 
         for name, cv in self.convs.items():
             if name == self.head.fc1.name:
@@ -179,14 +203,9 @@ class ChainerNpzMap(object):
                 put(bo.name + '/W', w)
                 put(bo.name + '/b', b)
                 loaded += keys
-            c, s = h.channels, h.roi_size_box
-            if have(pre + '/fc1/W', pre + '/fc1/b'):
-                w = np.asarray(arrays[pre + '/fc1/W'])
-                wn = np.zeros((h.fc1.cout_p, 1, 1, h.fc1.cin_p), np.float32)
-                wn[:w.shape[0], 0, 0, :] = w.reshape(-1, c, s, s).transpose(0, 2, 3, 1).reshape(w.shape[0], -1)
-                put(h.fc1.name + '/W', wn)
-                put(h.fc1.name + '/b', _vec_to_native(np.asarray(arrays[pre + '/fc1/b']), h.fc1.cout_p))
-                loaded += [pre + '/fc1/W', pre + '/fc1/b']
+            fc1_in(pre, h.fc1, h.channels, h.roi_size_box)
+        if self.maskiou is not None:
+            fc1_in('head/maskiou', self.maskiou.fc1, self.maskiou.channels, self.maskiou.out_size)
         h = self.head
         c = h.channels
         if have('head/deconv1/W', 'head/deconv1/b'):

@@ -1089,6 +1089,47 @@ int mrcnn_cascade_refine_f32(const float *rois, const float *box_out, int ld, in
 int mrcnn_cascade_prob_f32(const float *box_out0, const float *box_out1, const float *box_out2, const float *box_out3, int K, int R, int ld,
                            int n_class, float *prob, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask Scoring R-CNN (maskiou.hip; no counterpart in the reference).  Integer counts, float32 without contraction,
+ * correctly rounded divisions, no float atomics: the same bits on every run.  Every launch is capture-safe.
+ * n_channels: the logical class channels a label may select (label - label_base in [0, n_channels)); MRCNN_E_INVALID when it is not in
+ *   [1, Cp] / [1, ld].  label_base: 1 for the sampler's labels (0 = background), 0 for the labels MaskRCNN.predict returns.  A row whose
+ *   channel is negative has no class: target 0, logit channel 0, no loss.
+ * maskiou_target: two launches.  masks (N,G,H,W) u8; n_gt (N) device; sample_roi (N*n_sample,4) (y1,x1,y2,x2), gt_assign (N*n_sample),
+ *   n_pos (N): the sampler's outputs; the mask block has Rm = N * rows rows, row r being sampler row (r / rows) * n_sample + r % rows;
+ *   label (Rm), mask_out (Rm,mask_size,mask_size,Cp), gt_roi_mask (Rm,mask_size,mask_size) int32.
+ *   (a) area (N,G) int32 = nonzero bytes of every mask with g < n_gt[i], 0 for the other slots whatever they hold: 16-byte loads between
+ *   a byte-wise head and tail, reduced in the wave, 32 partial counts per mask in ws (mrcnn_maskiou_target_workspace_bytes).
+ *   (b) one workgroup per row; full = area of the assigned mask, crop = nonzero bytes of it inside the rectangle mrcnn_mask_target_u8
+ *   crops (y0 = max((int)y1, 0), y1 = min((int)y2, H), x alike), pred = #(logit at the row's channel > 0), gt28 = #(gt_roi_mask > 0),
+ *   ovr = #(both);  full_est = ((float)gt28 * (float)full) / (float)crop;  uni = ((float)pred + full_est) - (float)ovr;
+ *   target = (float)ovr / fmaxf(uni, 1.0f).  target = 0 where crop == 0, full == 0, the rectangle is empty or the row is padding
+ *   (r % rows >= n_pos[i], no channel, gt_assign outside [0, min(G, n_gt[i]))).  counts (Rm,5) int32, nullable: (full, crop, pred, gt28, ovr), zeros
+ *   for padding rows.  rows == 0 succeeds without a launch.
+ * maskiou_input_fwd: feat (Rm,P,P,C), mask_out (Rm,2P,2P,Cp) -> out (Rm,P,P,cin_p): channels [0,C) = feat, channel C =
+ *   fmaxf(fmaxf(fmaxf(m[2y][2x], m[2y][2x+1]), m[2y+1][2x]), m[2y+1][2x+1]) of the row's channel (0 for a row without one), channels
+ *   (C,cin_p) = 0.  C and cin_p multiples of 4, cin_p >= C + 4.
+ * maskiou_input_bwd: g_pool (Rm,P,P,C) += g_in (Rm,P,P,cin_p)[..., :C], one float32 add per element.
+ * maskiou_l2: over the rows with target > 0 and a channel, d = pred[r*ld + channel] - target[r]: loss_out[0] = weight * sum(0.5 d^2) / count,
+ *   loss_out[1] = max(count, 1) (the (sum, count) form of mrcnn_smooth_l1_f32: block partials, one finalising wave in double);
+ *   gx (Rm,ld), nullable: d * (weight * (1 / loss_out[1])) at that column, 0 in every other element.  No such row: loss 0, gx 0.
+ *   ws: mrcnn_loss_workspace_bytes().
+ * maskiou_rescore: out[d] = score[d] * fminf(fmaxf(pred[d*ld + label[d]], 0), 1); label 0-based; a label outside [0, ld) gives 0.
+ * Rm == 0 / D == 0 succeed without a launch.
+ * ---------------------------------------------------------------------------------------- */
+size_t mrcnn_maskiou_target_workspace_bytes(int N, int G);
+int mrcnn_maskiou_target(const uint8_t *masks, int N, int G, int H, int W, const int32_t *n_gt, const float *sample_roi,
+                         const int32_t *gt_assign, const int32_t *label, const int32_t *n_pos, int n_sample, int rows,
+                         const float *mask_out, int mask_size, int Cp, int n_channels, const int32_t *gt_roi_mask, int label_base,
+                         int32_t *area, float *target, int32_t *counts, void *ws, size_t ws_bytes, void *stream);
+int mrcnn_maskiou_input_fwd(const float *feat, const float *mask_out, const int32_t *label, int label_base, int Rm, int P, int C, int Cp,
+                            int n_channels, int cin_p, float *out, void *stream);
+int mrcnn_maskiou_input_bwd(const float *g_in, int Rm, int P, int C, int cin_p, float *g_pool, void *stream);
+int mrcnn_maskiou_l2(const float *pred, int ld, int n_channels, const float *target, const int32_t *label, int label_base, int Rm,
+                     float weight, float *loss_out, float *gx, void *ws, size_t ws_bytes, void *stream);
+int mrcnn_maskiou_rescore(const float *score, const float *pred, int ld, int n_channels, const int32_t *label, int D, float *out,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
