@@ -165,6 +165,52 @@ def group_norm_bwd(gy, x, gamma, beta, mean, rstd, C, G, relu=False, gg=None, gb
     return gx, gg, gb
 
 
+# ---- group norm of whole maps (FPN; csrc/groupnorm_map.hip) ----------------------------------------
+def group_norm_map_plan(R, H, W, C, Cp, G):
+    """(pixels_per_chunk, chunks, forward workspace bytes, backward workspace bytes) of mrcnn_group_norm_map_plan: host arithmetic, no
+    device.  Raises on an invalid geometry, and on one the map path does not take (C / G not a multiple of 4 up to 256, Cp above 1024)."""
+    ppc, chunks, nf, nb = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(lib().mrcnn_group_norm_map_plan(int(R), int(H), int(W), int(C), int(Cp), int(G), ctypes.byref(ppc), ctypes.byref(chunks),
+                                          ctypes.byref(nf), ctypes.byref(nb)))
+    return ppc.value, chunks.value, nf.value, nb.value
+
+
+def group_norm_map_fwd(x, gamma, beta, C, G, want_stats=True, eps=1e-5):
+    """x (R,H,W,Cp) NHWC with C logical channels in G groups.  Returns (y, mean, rstd); mean / rstd (R,G) are None unless want_stats."""
+    _ck(x, gamma, beta)
+    R, H, W, Cp = x.shape
+    y = torch.empty_like(x)
+    mean = _empty((R, G), x.device) if want_stats else None
+    rstd = _empty((R, G), x.device) if want_stats else None
+    nf = group_norm_map_plan(R, H, W, C, Cp, G)[2]
+    ws = workspace(nf, x.device)
+    check(lib().mrcnn_group_norm_map_fwd_f32(ptr(x), ptr(gamma), ptr(beta), R, H, W, int(C), Cp, int(G), eps, ptr(y), ptr(mean), ptr(rstd),
+                                             ptr(ws), ws.numel(), stream_ptr()))
+    return y, mean, rstd
+
+
+def group_norm_map_bwd(gy, x, gamma, mean, rstd, C, G, gg=None, gb=None, accumulate_params=False):
+    """gg / gb: where the gradients of gamma / beta are written, or added with accumulate_params (the flat gradient buffer's views);
+    allocated when not given.  Returns (gx, gg, gb)."""
+    _ck(gy, x, gamma, mean, rstd, gg, gb)
+    R, H, W, Cp = x.shape
+    if tuple(gy.shape) != tuple(x.shape):
+        raise ValueError('group_norm_map_bwd: gy %r and x %r differ in shape' % (tuple(gy.shape), tuple(x.shape)))
+    if (gg is None or gb is None) and accumulate_params:
+        raise ValueError('group_norm_map_bwd: accumulate_params needs gg and gb')
+    gx = torch.empty_like(x)
+    gg = _empty((Cp,), x.device) if gg is None else gg
+    gb = _empty((Cp,), x.device) if gb is None else gb
+    nb = group_norm_map_plan(R, H, W, C, Cp, G)[3]
+    if R == 0 and not accumulate_params:        # the library launches nothing for an empty batch: the sums over no sample are zeros
+        gg.zero_()
+        gb.zero_()
+    ws = workspace(nb, x.device)
+    check(lib().mrcnn_group_norm_map_bwd_f32(ptr(gy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), R, H, W, int(C), Cp, int(G), ptr(gx), ptr(gg),
+                                             ptr(gb), int(bool(accumulate_params)), ptr(ws), ws.numel(), stream_ptr()))
+    return gx, gg, gb
+
+
 def relu_bwd(gy, y, out=None):
     _ck(gy, y)
     out = torch.empty_like(gy) if out is None else out

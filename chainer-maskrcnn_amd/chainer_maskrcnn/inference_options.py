@@ -116,6 +116,27 @@ def head_norm_settings(head_norm, gn_groups, head_arch):
     return {'head_norm': None if head_norm == 'none' else head_norm, 'gn_groups': int(gn_groups)}
 
 
+# ---- FPN normalisation (MaskRCNN fpn_norm) --------------------------------------------------------------------------------
+def add_fpn_norm_flags(parser, both=lambda name: (name,)):
+    """--fpn-norm (train.py, train_keypoints.py - which takes both spellings through ``both`` -, evaluate.py, demo.py); its groups are
+    --gn-groups, shared with --head-norm."""
+    parser.add_argument(*both('--fpn-norm'), default='none', choices=['none', 'gn'],
+                        help='gn: GroupNorm of --gn-groups groups behind each of the eight FPN convolutions (MaskRCNN fpn_norm; Detectron\'s '
+                             '*_gn configurations normalise the FPN and the heads together), for long schedules from scratch; --backbone fpn '
+                             'only; a checkpoint is evaluated with the value it was trained with')
+
+
+def fpn_norm_settings(fpn_norm, gn_groups, backbone):
+    """The MaskRCNN argument {'fpn_norm': None | 'gn'} of the flags; ValueError for a combination the model refuses."""
+    if fpn_norm not in ('none', 'gn'):
+        raise ValueError('--fpn-norm must be none or gn, got %r' % (fpn_norm,))
+    if fpn_norm == 'gn' and backbone != 'fpn':
+        raise ValueError('--fpn-norm gn exists for --backbone fpn, not %s' % backbone)
+    if fpn_norm == 'gn' and (gn_groups < 1 or 256 % gn_groups != 0):
+        raise ValueError('--gn-groups must be a positive divisor of the FPN\'s 256 channels, got %r' % (gn_groups,))
+    return {'fpn_norm': None if fpn_norm == 'none' else fpn_norm}
+
+
 # ---- Cascade R-CNN box stages (MaskRCNN cascade_ious / cascade_stds; DESIGN.md §3.21) -------------------------------------------------------
 DEFAULT_CASCADE_IOUS = (0.5, 0.6, 0.7)
 NO_CASCADE = {'cascade_ious': None, 'cascade_stds': None}       # what a trainer state without the 'cascade' key was trained with
@@ -229,13 +250,14 @@ def use_score_preset(model, preset, score_thresh=None):
 
 
 def build_inference_model(args, preset=None):
-    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --gn-groups / --cascade* / --mask-iou / --label_file with --weight loaded (keys missing from the file keep their
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --fpn-norm / --gn-groups / --cascade* / --mask-iou / --label_file with --weight loaded (keys missing from the file keep their
     initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
     17 keypoints; a mask head has one class per label (80 without a label file)."""
     import torch
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     from chainer_maskrcnn.utils import chainer_npz
     norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
+    norm.update(fpn_norm_settings(getattr(args, 'fpn_norm', 'none'), args.gn_groups, args.backbone))
     norm.update(cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone))
     norm['mask_iou'] = mask_iou_settings(getattr(args, 'mask_iou', 0), None, args.head_arch)['mask_iou']
     dev =torch.device('cuda', args.gpu)

@@ -6,7 +6,7 @@ Appendix A-8) spelled out.  Quirks kept on purpose (SURVEY.md Appendix B-1,2,4):
 max-pool after conv1, BatchNorm in training mode, no 3x3 smoothing on P5, P6 = 1x1 stride-2 conv of P5.
 Tensors are NHWC; the image enters as (N,H,W,4) with a zero 4th channel.
 """
-from chainer_maskrcnn.nn.core import Conv, BatchNorm, Bottleneck, ParamStore
+from chainer_maskrcnn.nn.core import Conv, BatchNorm, Bottleneck, MapGroupNorm, ParamStore
 from chainer_maskrcnn._hip import ops, nn as hnn
 
 # The ReLU backward of a bottleneck's output is applied by the kernels that WRITE that output's gradient (data-gradient epilogues,
@@ -20,6 +20,7 @@ MASK_IN_PRODUCER = True
 #   backward: their data gradients g_c2 .. g_c4 are not needed until the matching ResNet stage - computed on a stream of their own, off the
 #             chain conv_p2 -> conv_p3 -> conv_p4 -> toplayer -> res5.
 # Same kernels, same operands, same summation order: the same bits.
+# Ignored under fpn_norm='gn': each lateral's GroupNorm sits between it and the top-down add, and the laterals run on the chain.
 LATERALS_OFF_THE_CHAIN = False
 _lat_streams = {}
 
@@ -42,9 +43,16 @@ class FeaturePyramidNetwork(object):
     STAGES = (('res2', 3, 64, 64, 256, 1), ('res3', 4, 256, 128, 512, 2),
               ('res4', 6, 512, 256, 1024, 2), ('res5', 3, 1024, 512, 2048, 2))
 
-    def __init__(self, ps=None, prefix='extractor', stages=None, width_div=1):
+    def __init__(self, ps=None, prefix='extractor', stages=None, width_div=1, fpn_norm=None, gn_groups=32):
         """``stages`` / ``width_div`` shrink the network for tests (blocks per stage, channel divisor);
-        the defaults are the reference's ResNet-50."""
+        the defaults are the reference's ResNet-50.  fpn_norm: None = the reference's pyramid; 'gn' = a GroupNorm of ``gn_groups``
+        groups (parameters ``<conv>/gn/gamma``, ``<conv>/gn/beta``) behind each of the eight FPN convolutions, which keep their bias
+        (Detectron's *_gn configurations)."""
+        if fpn_norm not in (None, 'gn'):
+            raise ValueError("fpn_norm must be None or 'gn', got %r" % (fpn_norm,))
+        if fpn_norm == 'gn' and (gn_groups < 1 or (256 // width_div) % gn_groups != 0):
+            raise ValueError('gn_groups = %d does not divide the %d channels of the FPN' % (gn_groups, 256 // width_div))
+        self.fpn_norm = fpn_norm
         self.ps = ps if ps is not None else ParamStore()
         p = prefix + '/'
         d = width_div
@@ -60,14 +68,21 @@ class FeaturePyramidNetwork(object):
             self.stages.append(blocks)
         fc = 256 // d
         self.out_channels = fc
-        self.toplayer = Conv(self.ps, p + 'toplayer', 2048 // d, fc, 1)
-        self.conv_p4 = Conv(self.ps, p + 'conv_p4', fc, fc, 3, 1, 1, fwd_tile=0)
-        self.conv_p3 = Conv(self.ps, p + 'conv_p3', fc, fc, 3, 1, 1, fwd_tile=0)
-        self.conv_p2 = Conv(self.ps, p + 'conv_p2', fc, fc, 3, 1, 1, fwd_tile=0)
-        self.conv_p6 = Conv(self.ps, p + 'conv_p6', fc, fc, 1, 2, 0)
-        self.lat_p4 = Conv(self.ps, p + 'lat_p4', 1024 // d, fc, 1)
-        self.lat_p3 = Conv(self.ps, p + 'lat_p3', 512 // d, fc, 1)
-        self.lat_p2 = Conv(self.ps, p + 'lat_p2', 256 // d, fc, 1)
+        self.norms = {}                 # convolution name -> its MapGroupNorm (empty without fpn_norm)
+
+        def conv(name, *a, **kw):
+            c = Conv(self.ps, p + name, *a, **kw)
+            if fpn_norm == 'gn':        # registered directly behind its convolution: inside the FPN's range of the flat buffers
+                self.norms[c.name] = MapGroupNorm(self.ps, c.name + '/gn', fc, gn_groups)
+            return c
+        self.toplayer = conv('toplayer', 2048 // d, fc, 1)
+        self.conv_p4 = conv('conv_p4', fc, fc, 3, 1, 1, fwd_tile=0)
+        self.conv_p3 = conv('conv_p3', fc, fc, 3, 1, 1, fwd_tile=0)
+        self.conv_p2 = conv('conv_p2', fc, fc, 3, 1, 1, fwd_tile=0)
+        self.conv_p6 = conv('conv_p6', fc, fc, 1, 2, 0)
+        self.lat_p4 = conv('lat_p4', 1024 // d, fc, 1)
+        self.lat_p3 = conv('lat_p3', 512 // d, fc, 1)
+        self.lat_p2 = conv('lat_p2', 256 // d, fc, 1)
         self.anchor_scales = list(map(lambda x: x / float(self.anchor_base), self.anchor_sizes))
         self.freeze_bn, self.freeze_at = False, 0
 
@@ -116,7 +131,7 @@ class FeaturePyramidNetwork(object):
         h = ops.maxpool2x2_fwd(h)
         cs = []
         t['blocks'] = []
-        off_chain = LATERALS_OFF_THE_CHAIN and x.is_cuda and hnn.PROFILE is None
+        off_chain = self._laterals_off_chain(x)
         lat = {}
         if off_chain:
             import torch
@@ -136,31 +151,55 @@ class FeaturePyramidNetwork(object):
             main.wait_stream(side)
             for l_, _ in lat.values():
                 l_.record_stream(main)      # allocated on the side stream, consumed (and released) on the main stream
-        p5, t['top'] = self.toplayer.fwd(c5)
-        l4, t['lat4'] = lat[2] if off_chain else self.lat_p4.fwd(c4)
+        return self.top_down(c2, c3, c4, c5, _tape=t, _lat=lat if off_chain else None)
+
+    def _conv_fwd(self, conv, key, x, t, done=None):
+        """conv (+ its GroupNorm under fpn_norm) on x; the contexts go to t[key] and t[key + '/gn'].  done: the convolution's (output,
+        context) where it has already run (a lateral off the chain)."""
+        y, t[key] = done if done is not None else conv.fwd(x)
+        gn = self.norms.get(conv.name)
+        if gn is not None:
+            y, t[key + '/gn'] = gn.fwd(y)
+        return y
+
+    def _norm_bwd(self, conv, key, g):
+        """The gradient of conv's output from the gradient of its GroupNorm's output (g itself without fpn_norm)."""
+        gn = self.norms.get(conv.name)
+        return g if gn is None else gn.bwd(self.tape[key + '/gn'], g)
+
+    def top_down(self, c2, c3, c4, c5, _tape=None, _lat=None):
+        """The pyramid from the four stage outputs: (p2, p3, p4, p5, p6) NHWC; keeps the tape for top_down_backward()."""
+        t = {} if _tape is None else _tape
+        lat = _lat or {}
+        p5 = self._conv_fwd(self.toplayer, 'top', c5, t)
+        l4 = self._conv_fwd(self.lat_p4, 'lat4', c4, t, lat.get(2))
         m4 = ops.upsample2x_add_fwd(p5, l4)
-        p4, t['p4'] = self.conv_p4.fwd(m4)
-        l3, t['lat3'] = lat[1] if off_chain else self.lat_p3.fwd(c3)
+        p4 = self._conv_fwd(self.conv_p4, 'p4', m4, t)
+        l3 = self._conv_fwd(self.lat_p3, 'lat3', c3, t, lat.get(1))
         m3 = ops.upsample2x_add_fwd(p4, l3)
-        p3, t['p3'] = self.conv_p3.fwd(m3)
-        l2, t['lat2'] = lat[0] if off_chain else self.lat_p2.fwd(c2)
+        p3 = self._conv_fwd(self.conv_p3, 'p3', m3, t)
+        l2 = self._conv_fwd(self.lat_p2, 'lat2', c2, t, lat.get(0))
         m2 = ops.upsample2x_add_fwd(p3, l2)
-        p2, t['p2'] = self.conv_p2.fwd(m2)
-        p6, t['p6'] = self.conv_p6.fwd(p5)
+        p2 = self._conv_fwd(self.conv_p2, 'p2', m2, t)
+        p6 = self._conv_fwd(self.conv_p6, 'p6', p5, t)
         self.tape = t
         return p2, p3, p4, p5, p6
 
-    def backward(self, grads, progress=None):
-        """grads: [g_p2, g_p3, g_p4, g_p5, g_p6]; consumed (accumulated into in place).  ``progress(prefix)`` is
-        called when every parameter registered at or after ``prefix`` has its final gradient (data-parallel overlap)."""
+    def _laterals_off_chain(self, t):
+        return LATERALS_OFF_THE_CHAIN and self.fpn_norm is None and t.is_cuda and hnn.PROFILE is None
+
+    def top_down_backward(self, grads):
+        """grads: [g_p2, g_p3, g_p4, g_p5, g_p6]; consumed (accumulated into in place).  Returns (g_c2, g_c3, g_c4, g_c5), None where
+        freeze_at leaves the stage below untrained.  Under fpn_norm each GroupNorm's backward runs in front of its convolution's;
+        toplayer's runs last, when conv_p6, the upsampling and the caller have all added to g_p5."""
         t = self.tape
         g_p2, g_p3, g_p4, g_p5, g_p6 = grads
-        self.conv_p6.bwd(t['p6'], g_p6, gx_acc=g_p5)
-        g_m2 = self.conv_p2.bwd(t['p2'], g_p2)
+        self.conv_p6.bwd(t['p6'], self._norm_bwd(self.conv_p6, 'p6', g_p6), gx_acc=g_p5)
+        g_m2 = self.conv_p2.bwd(t['p2'], self._norm_bwd(self.conv_p2, 'p2', g_p2))
         ops.upsample2x_bwd(g_m2, gtop=g_p3)
         # c2..c5 are ReLU outputs (the last block of a stage): every contribution to their gradient is masked where it is written
         # (mask_gx: data-gradient epilogue / lattice scatter), so the blocks' bn3 backward gets its gy with the mask applied
-        off_chain = LATERALS_OFF_THE_CHAIN and g_p2.is_cuda and hnn.PROFILE is None
+        off_chain = self._laterals_off_chain(g_p2)
         if off_chain:
             import torch
             main, ls = torch.cuda.current_stream(g_p2.device), _lateral_stream(g_p2.device)
@@ -181,14 +220,27 @@ class FeaturePyramidNetwork(object):
                 g_c = conv.bwd(ctx, g_m, mask_gx=MASK_IN_PRODUCER)
             g_c.record_stream(main)             # accumulated into by the next stage's first block, on the main stream
             return g_c
-        g_c2 = lateral_bwd(self.lat_p2, t['lat2'], g_m2, 2)
-        g_m3 = self.conv_p3.bwd(t['p3'], g_p3)
+        g_c2 = lateral_bwd(self.lat_p2, t['lat2'], self._norm_bwd(self.lat_p2, 'lat2', g_m2), 2)
+        g_m3 = self.conv_p3.bwd(t['p3'], self._norm_bwd(self.conv_p3, 'p3', g_p3))
         ops.upsample2x_bwd(g_m3, gtop=g_p4)
-        g_c3 = lateral_bwd(self.lat_p3, t['lat3'], g_m3, 3)
-        g_m4 = self.conv_p4.bwd(t['p4'], g_p4)
+        g_c3 = lateral_bwd(self.lat_p3, t['lat3'], self._norm_bwd(self.lat_p3, 'lat3', g_m3), 3)
+        g_m4 = self.conv_p4.bwd(t['p4'], self._norm_bwd(self.conv_p4, 'p4', g_p4))
         ops.upsample2x_bwd(g_m4, gtop=g_p5)
-        g_c4 = lateral_bwd(self.lat_p4, t['lat4'], g_m4, 4)
-        g_c5 = self.toplayer.bwd(t['top'], g_p5, need_gx=k < 5, mask_gx=MASK_IN_PRODUCER)
+        g_c4 = lateral_bwd(self.lat_p4, t['lat4'], self._norm_bwd(self.lat_p4, 'lat4', g_m4), 4)
+        # (freeze_at = 5: toplayer's filter gradient still needs its GroupNorm's backward)
+        g_c5 = self.toplayer.bwd(t['top'], self._norm_bwd(self.toplayer, 'top', g_p5), need_gx=k < 5, mask_gx=MASK_IN_PRODUCER)
+        return g_c2, g_c3, g_c4, g_c5
+
+    def backward(self, grads, progress=None):
+        """grads: [g_p2, g_p3, g_p4, g_p5, g_p6]; consumed (accumulated into in place).  ``progress(prefix)`` is
+        called when every parameter registered at or after ``prefix`` has its final gradient (data-parallel overlap)."""
+        t = self.tape
+        k = self.freeze_at
+        off_chain = self._laterals_off_chain(grads[0])
+        if off_chain:
+            import torch
+            main, ls = torch.cuda.current_stream(grads[0].device), _lateral_stream(grads[0].device)
+        g_c2, g_c3, g_c4, g_c5 = self.top_down_backward(grads)
         if progress:
             progress(self.toplayer.name)        # the FPN layers are registered after the ResNet
         # The gradient of c2..c4 is (lateral gradient) + (input gradient of the next stage): the next

@@ -88,8 +88,10 @@ class MaskRCNN(object):
                  max_size=1000, ratios=[0.5, 1, 2], anchor_scales=[8], rpn_initialW=None, loc_initialW=None,
                  score_initialW=None, proposal_creator_params={}, backbone='fpn', head_arch='fpn',
                  device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32, cascade_ious=None, cascade_stds=None,
-                 mask_iou=False):
-        """head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
+                 mask_iou=False, fpn_norm=None):
+        """fpn_norm: None = the reference's pyramid; 'gn' = GroupNorm of ``gn_groups`` groups behind each of the eight FPN convolutions
+        (DESIGN.md §3.23); backbone 'fpn' only.
+        head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
         convolution of the 'fpn' / 'fpn_keypoint' heads.
         cascade_ious: None = one box stage; (0.5, 0.6, 0.7) = Cascade R-CNN: K box stages trained at these IoU thresholds,
         stage k > 1 a box-only head ``head/cascade<k>/...`` registered directly behind the stage-1 head's parameters and fed stage k-1's
@@ -102,13 +104,17 @@ class MaskRCNN(object):
             raise ValueError("head_norm must be None or 'gn', got %r" % (head_norm,))
         if head_norm is not None and head_arch in ('res5', 'light'):
             raise ValueError("head_norm=%r exists for head_arch 'fpn' and 'fpn_keypoint' only, not %r" % (head_norm, head_arch))
-        self.head_norm, self.gn_groups = head_norm, int(gn_groups)
+        if fpn_norm not in (None, 'gn'):
+            raise ValueError("fpn_norm must be None or 'gn', got %r" % (fpn_norm,))
+        if fpn_norm is not None and backbone != 'fpn':
+            raise ValueError("fpn_norm=%r exists for backbone 'fpn' only, not %r" % (fpn_norm, backbone))
+        self.head_norm, self.gn_groups, self.fpn_norm = head_norm, int(gn_groups), fpn_norm
         self.cascade = cascade_settings(cascade_ious, cascade_stds, head_arch, backbone)
         self.mask_iou = mask_iou_setting(mask_iou, head_arch)
         self.ps = ParamStore()
         shrink = _test_shrink or {}
         if backbone == 'fpn':
-            self.extractor = FeaturePyramidNetwork(self.ps, **shrink)
+            self.extractor = FeaturePyramidNetwork(self.ps, fpn_norm=fpn_norm, gn_groups=self.gn_groups, **shrink)
             self.rpn = MultilevelRegionProposalNetwork(
                 anchor_scales=self.extractor.anchor_scales, feat_strides=self.extractor.feat_strides,
                 in_channels=self.extractor.out_channels, mid_channels=self.extractor.out_channels,

@@ -426,6 +426,37 @@ class GroupNorm(object):
         return gx
 
 
+class MapGroupNorm(GroupNorm):
+    """GroupNorm behind a convolution of the FPN: the parameters and registration of GroupNorm, no ReLU.  Each call picks
+    its kernels by host arithmetic on the shape: a map small enough for the register-resident kernels takes them; a larger one takes the
+    split-reduction kernels of groupnorm_map.hip where they exist for the channel geometry, else the generic kernels."""
+
+    def uses_map_path(self, shape):
+        R, H, W, Cp = shape
+        if ops.group_norm_plan(R, H, W, self.c, Cp, self.groups)[0] == 0:
+            return False
+        cpg = self.c // self.groups
+        return cpg % 4 == 0 and cpg <= 256 and Cp <= 1024
+
+    def fwd(self, x):
+        """Returns (y, ctx); ctx = (x, mean, rstd), None in evaluation mode."""
+        gamma, beta = self.ps.p(self.name + '/gamma'), self.ps.p(self.name + '/beta')
+        if self.uses_map_path(x.shape):
+            y, mean, rstd = ops.group_norm_map_fwd(x, gamma, beta, self.c, self.groups, want_stats=TRAIN)
+        else:
+            y, mean, rstd = ops.group_norm_fwd(x, gamma, beta, self.c, self.groups, relu=False, want_stats=TRAIN)
+        return y, ((x, mean, rstd) if TRAIN else None)
+
+    def bwd(self, ctx, gy, accumulate_params=False):
+        """The parameter gradients go straight into the flat gradient buffer."""
+        x, mean, rstd = ctx
+        gamma, gg, gb = self.ps.p(self.name + '/gamma'), self.ps.g(self.name + '/gamma'), self.ps.g(self.name + '/beta')
+        if self.uses_map_path(x.shape):
+            return ops.group_norm_map_bwd(gy, x, gamma, mean, rstd, self.c, self.groups, gg=gg, gb=gb, accumulate_params=accumulate_params)[0]
+        return ops.group_norm_bwd(gy, x, gamma, self.ps.p(self.name + '/beta'), mean, rstd, self.c, self.groups, relu=False, gg=gg, gb=gb,
+                                  accumulate_params=accumulate_params)[0]
+
+
 class Bottleneck(object):
     """ResNet bottleneck (Chainer BottleneckA when ``project`` else BottleneckB):
     relu(bn3(conv3(relu(bn2(conv2 3x3(relu(bn1(conv1 1x1/s))))))) + shortcut), stride on the first 1x1."""

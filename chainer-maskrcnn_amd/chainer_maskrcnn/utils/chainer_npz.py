@@ -5,7 +5,7 @@ with ``load_npz(..., strict=False)`` (train.py:99-101).  NPZ keys are Chainer li
 layouts:  Convolution2D W (Cout, Cin, KH, KW), Linear W (out, in) with the input flattened (C, H, W)-major,
 Deconvolution2D W (Cin, Cout, KH, KW), BatchNormalization gamma / beta / avg_mean / avg_var / N.  The GroupNorm layers of a
 ``head_norm='gn'`` model (no counterpart in the reference) go out as GroupNormalization gamma / beta (C,) under their store names
-``head/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.  The MaskIoU head of a ``mask_iou`` model (no
+``head/<conv>/gn/{gamma,beta}``, those of an ``fpn_norm='gn'`` model under ``extractor/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.  The MaskIoU head of a ``mask_iou`` model (no
 counterpart either) goes out as ``head/maskiou/{conv1..conv4}`` (Convolution2D) and ``head/maskiou/{fc1,fc2,maskiou}`` (Linear).
 
 Storage here differs only mechanically - conv W (Cout_p, KH, KW, Cin_p) with zero-padded channels, NHWC
@@ -54,6 +54,7 @@ class ChainerNpzMap(object):
             self._add_conv(cv)
         self.rpn, self.head = rpn, head
         self.gns = [g for g in [getattr(head, 'gn1', None)] + list(getattr(head, 'mask_gns', [])) if g is not None]
+        self.gns = list(getattr(ext, 'norms', {}).values()) + self.gns         # the FPN's, under extractor/<conv>/gn (fpn_norm='gn')
         # the box stages: the head and, for a cascade model, its later stages under head/cascade<k>/ - the same link layout as the head's
         # box branch (conv1, fc1, fc2, cls_loc, score)
         self.box_stages = [('head', head)]

@@ -3,6 +3,10 @@
 // y > 0 by construction (bn_common.h does the same for BatchNorm; relu1 / relu_mask1 are its rules).  Device only.  No contraction: the
 // parenthesisation below IS the rounding order; the one fused operation is the explicit fmaf of the backward sums.
 //   statistics  mean = sum(x) / n, var = sum((x - mean)^2) / n about that mean (biased), rstd = 1 / sqrt(var + eps), n = H * W * cpg
+//   split statistics (groupnorm_map.hip, DESIGN.md §3.23: the FPN's maps)  a (sample, group) cut into chunks i = 0, 1, ... of n_i elements.
+//       Each chunk states its own mean m_i = sum(x) / n_i and M2_i = sum((x - m_i)^2) about it; gn_merge1 folds the chunks in index order
+//       (Chan, Golub & LeVeque 1979).  The group's mean is the merged m and its variance M2 / n: a SECOND statement of the mean, equal to
+//       sum(x) / n in exact arithmetic and within float32 rounding of it otherwise; still a variance about a mean, never E[x^2] - E[x]^2.
 #pragma once
 #include "bn_common.h"
 
@@ -21,6 +25,24 @@ __device__ __forceinline__ float gn_bwd_dx1(float gy, float xh, float ga, float 
     return s * (gy * ga - a - xh * b);
 }
 
+// (v - mean)^2: one term of a chunk's M2
+__device__ __forceinline__ float gn_sqdev1(float v, float m) {
+    const float d = v - m;
+    return d * d;
+}
+// (n, m, M2) of the chunks merged so far takes in chunk i's (ni, mi, M2i); n > 0 and ni > 0
+__device__ __forceinline__ void gn_merge1(float &n, float &m, float &M2, float ni, float mi, float M2i) {
+    const float nn = n + ni;
+    const float d = mi - m;
+    m = m + d * ni / nn;
+    M2 = M2 + (M2i + d * d * n * ni / nn);
+    n = nn;
+}
+
+__device__ __forceinline__ float4 gn_sqdev4(const float4 &v, const float4 &m) {
+    float4 o; o.x = gn_sqdev1(v.x, m.x); o.y = gn_sqdev1(v.y, m.y); o.z = gn_sqdev1(v.z, m.z); o.w = gn_sqdev1(v.w, m.w);
+    return o;
+}
 __device__ __forceinline__ float4 gn_xhat4(const float4 &v, const float4 &m, const float4 &s) {
     float4 o; o.x = gn_xhat1(v.x, m.x, s.x); o.y = gn_xhat1(v.y, m.y, s.y); o.z = gn_xhat1(v.z, m.z, s.z); o.w = gn_xhat1(v.w, m.w, s.w);
     return o;

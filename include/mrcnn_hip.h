@@ -1056,6 +1056,32 @@ int mrcnn_group_norm_bwd_f32(const float *gy, const float *x, const float *gamma
                              int accumulate_params, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GroupNorm of whole feature maps (groupnorm_map.hip, gn_common.h; nn/core.py MapGroupNorm).  The tensors, the
+ * channel geometry, y, gx, ggamma and gbeta of group_norm_* above without its relu, for maps too large for one workgroup per (sample,
+ * group): a sample is cut into `chunks` contiguous ranges of pixels_per_chunk pixels (the last may be shorter), one workgroup per (sample,
+ * chunk) over all channels, and every hand-over between workgroups is a kernel boundary - three launches forward, three backward, no
+ * atomics, no counters: the same input gives the same bits on every run.
+ *   statistics: each chunk i states, per group, its own mean m_i over its n_i elements and M2_i = sum((x - m_i)^2); they are merged in
+ *   chunk order by  d = m_i - m, m += d * n_i / (n + n_i), M2 += M2_i + d * d * n * n_i / (n + n_i);  mean = m,
+ *   rstd = 1.0f / sqrtf(M2 / n + eps) (a variance about a mean: no E[x^2] - E[x]^2).  mean, rstd (R,G): written when not NULL.
+ * group_norm_map_plan: host arithmetic only; every output is nullable.  pixels_per_chunk and chunks are functions of H * W and Cp alone
+ *   (chunks * pixels_per_chunk >= H * W > (chunks - 1) * pixels_per_chunk); fwd_ws_bytes = (2 * R * chunks * G + 2 * R * G) * 4,
+ *   bwd_ws_bytes = (2 * R * chunks * Cp + 2 * R * G) * 4.
+ * The map path takes cpg = C / G a multiple of 4 up to 256 (a float4 stays inside one group) and Cp up to 1024; every other geometry is
+ *   MRCNN_E_INVALID from all three calls - group_norm_* serves it.
+ * x, y, gy, gx, gamma, beta, ggamma, gbeta and ws 16-byte aligned.  R == 0 succeeds without a launch.  Errors, before any launch:
+ * MRCNN_E_INVALID for G not dividing C, Cp < C, Cp % 4 != 0, a non-positive H, W, C, G or eps, a negative R, H * W * Cp above 2^31 - 1,
+ * a NULL or misaligned pointer, a workspace too small.
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_group_norm_map_plan(int R, int H, int W, int C, int Cp, int G, int *pixels_per_chunk, int *chunks, size_t *fwd_ws_bytes,
+                              size_t *bwd_ws_bytes);
+int mrcnn_group_norm_map_fwd_f32(const float *x, const float *gamma, const float *beta, int R, int H, int W, int C, int Cp, int G, float eps,
+                                 float *y, float *mean, float *rstd, void *ws, size_t ws_bytes, void *stream);
+int mrcnn_group_norm_map_bwd_f32(const float *gy, const float *x, const float *gamma, const float *mean, const float *rstd, int R, int H, int W,
+                                 int C, int Cp, int G, float *gx, float *ggamma, float *gbeta, int accumulate_params, void *ws,
+                                 size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Cascade R-CNN box stages (cascade.hip, box_common.h; no counterpart in the reference).  float32, no contraction,
  * correctly rounded divisions.
  * cascade_refine: stage k -> stage k+1 over the R = N * S rows of the sampler's fixed row block (image i owns rows [i * S, (i + 1) * S)),

@@ -22,8 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (NO_CASCADE, NO_MASK_IOU, add_boxpost_flags, add_cascade_flags, add_head_norm_flags,  # noqa: E402,F401
-                                                add_mask_iou_flags, add_tta_flags, boxpost_settings, cascade_flag_settings, head_norm_settings,
+from chainer_maskrcnn.inference_options import (NO_CASCADE, NO_MASK_IOU, add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags,  # noqa: E402,F401
+                                                add_mask_iou_flags, add_tta_flags, boxpost_settings, cascade_flag_settings, fpn_norm_settings, head_norm_settings,
                                                 mask_iou_settings, read_labels, tta_settings, use_boxpost, use_tta)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
 
@@ -128,6 +128,7 @@ def build_parser(keypoints=False):
                              'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
                              'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
     add_head_norm_flags(parser, both)
+    add_fpn_norm_flags(parser, both)
     add_cascade_flags(parser, both)
     add_mask_iou_flags(parser, both, weight=True)
     parser.add_argument(*both('--box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
@@ -325,6 +326,7 @@ def run(args, keypoints=False):
         raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
                          % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
     head_norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
+    head_norm.update(fpn_norm_settings(args.fpn_norm, args.gn_groups, args.backbone))
     cascade = cascade_run_settings(args)
     if resume is not None:
         check_resume_cascade(resume, args, args.resume)
