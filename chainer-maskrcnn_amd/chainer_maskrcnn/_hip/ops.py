@@ -977,6 +977,154 @@ def maskiou_rescore(score, pred, label, n_channels):
     return out
 
 
+# ---- PointRend (pointrend.hip) --------------------------------------------------------------------------------
+def point_n_keys(P, n_cand, n_imp):
+    """uint32 keys per row mrcnn_point_train_coords reads: two per candidate and two per uniform point."""
+    return 2 * int(n_cand) + 2 * (int(P) - int(n_imp))
+
+
+def _point_dtypes(name, *pairs):
+    for t_, ty in pairs:
+        if t_ is not None and t_.dtype != ty:
+            raise ValueError('%s: a %s tensor where %s is expected' % (name, t_.dtype, ty))
+
+
+def point_train_coords(keys, coarse, label, n_channels, P, n_cand, n_imp, label_base=1):
+    """The training points of every mask row (mrcnn_point_train_coords): keys (rows, point_n_keys) int32 holding uint32 bits, coarse
+    (rows,S0,S0,Cp) logits, label (rows,) i32 -> coords (rows,P,2) (u, v) in [0,1): the n_imp most uncertain of n_cand candidates, the most
+    uncertain first, then P - n_imp uniform points."""
+    _ck(keys, coarse, label)
+    rows = coarse.shape[0]
+    if coarse.dim() != 4 or coarse.shape[1] != coarse.shape[2] or keys.dim() != 2 or keys.shape[0] != rows or label.numel() != rows:
+        raise ValueError('point_train_coords: keys %r, coarse %r, %d labels' % (tuple(keys.shape), tuple(coarse.shape), label.numel()))
+    _point_dtypes('point_train_coords', (keys, i32), (coarse, f32), (label, i32))
+    coords = _empty((rows, int(P), 2), coarse.device)
+    check(lib().mrcnn_point_train_coords(ptr(keys), keys.shape[1], ptr(coarse), coarse.shape[1], coarse.shape[3], int(n_channels), ptr(label),
+                                         int(label_base), rows, int(P), int(n_cand), int(n_imp), ptr(coords), stream_ptr()))
+    return coords
+
+
+def point_features_fwd(coords, rois_xy5, fmap, scale, coarse, n_channels, cin_p):
+    """The point head's input (mrcnn_point_features_fwd): coords (rows,P,2), rois_xy5 (rows,5), fmap (N,H,W,C) the stride-4 level, coarse
+    (rows,S0,S0,Cp) -> (rows,1,P,cin_p): C fine channels, n_channels coarse channels, zeros."""
+    _ck(coords, rois_xy5, fmap, coarse)
+    rows, P = coords.shape[0], coords.shape[1]
+    if coords.dim() != 3 or coords.shape[2] != 2 or tuple(rois_xy5.shape) != (rows, 5) or fmap.dim() != 4 or coarse.dim() != 4 \
+            or coarse.shape[0] != rows or coarse.shape[1] != coarse.shape[2]:
+        raise ValueError('point_features_fwd: coords %r, rois_xy5 %r, map %r, coarse %r' % (tuple(coords.shape), tuple(rois_xy5.shape),
+                                                                                           tuple(fmap.shape), tuple(coarse.shape)))
+    _point_dtypes('point_features_fwd', (coords, f32), (rois_xy5, f32), (fmap, f32), (coarse, f32))
+    N, H, W, C = fmap.shape
+    out = _empty((rows, 1, P, int(cin_p)), fmap.device)
+    check(lib().mrcnn_point_features_fwd(ptr(coords), ptr(rois_xy5), ptr(fmap), N, H, W, C, float(scale), ptr(coarse), coarse.shape[1],
+                                         coarse.shape[3], int(n_channels), rows, P, int(cin_p), ptr(out), stream_ptr()))
+    return out
+
+
+def point_features_bwd(g_in, coords, rois_xy5, scale, g_map):
+    """g_map (N,H,W,C) += the fine part g_in (rows,1,P,ld)[..., :C] scattered by point_sample's transpose, in place and in a fixed order
+    (mrcnn_point_features_bwd); returns g_map."""
+    _ck(g_in, coords, rois_xy5, g_map)
+    rows, P = coords.shape[0], coords.shape[1]
+    if g_in.numel() != rows * P * g_in.shape[-1] or tuple(rois_xy5.shape) != (rows, 5) or g_map.dim() != 4:
+        raise ValueError('point_features_bwd: g_in %r, coords %r, rois_xy5 %r, g_map %r' % (tuple(g_in.shape), tuple(coords.shape),
+                                                                                           tuple(rois_xy5.shape), tuple(g_map.shape)))
+    _point_dtypes('point_features_bwd', (g_in, f32), (coords, f32), (rois_xy5, f32), (g_map, f32))
+    N, H, W, C = g_map.shape
+    check(lib().mrcnn_point_features_bwd(ptr(g_in), g_in.shape[-1], ptr(coords), ptr(rois_xy5), rows, P, float(scale), ptr(g_map), N, H, W, C,
+                                         stream_ptr()))
+    return g_map
+
+
+def point_concat_fwd(h, x0, c0, n_coarse, cin_p):
+    """[h (..., Ch) | x0 (..., ld0)[..., c0 : c0 + n_coarse] | zeros] -> (..., cin_p) (mrcnn_point_concat_fwd)."""
+    _ck(h, x0)
+    n = h.numel() // h.shape[-1]
+    if x0.numel() != n * x0.shape[-1]:
+        raise ValueError('point_concat_fwd: h %r against x0 %r' % (tuple(h.shape), tuple(x0.shape)))
+    _point_dtypes('point_concat_fwd', (h, f32), (x0, f32))
+    out = _empty(tuple(h.shape[:-1]) + (int(cin_p),), h.device)
+    check(lib().mrcnn_point_concat_fwd(ptr(h), h.shape[-1], ptr(x0), x0.shape[-1], int(c0), int(n_coarse), n, int(cin_p), ptr(out), stream_ptr()))
+    return out
+
+
+def point_concat_bwd(g_in, Ch):
+    """g_in (..., cin_p)[..., :Ch] as a tensor of its own (mrcnn_point_concat_bwd): the coarse part is dropped."""
+    _ck(g_in)
+    _point_dtypes('point_concat_bwd', (g_in, f32))
+    out = _empty(tuple(g_in.shape[:-1]) + (int(Ch),), g_in.device)
+    check(lib().mrcnn_point_concat_bwd(ptr(g_in), g_in.shape[-1], int(Ch), g_in.numel() // g_in.shape[-1], ptr(out), stream_ptr()))
+    return out
+
+
+def point_target(masks, n_gt, rois_xy5, gt_assign, label, n_pos, n_sample, rows, coords):
+    """Soft targets (mrcnn_point_target): masks (N,G,H,W) u8, the sampler's gt_assign (N*n_sample,) / n_pos (N,), the mask block's rois_xy5
+    (N*rows,5) / label (N*rows,), coords (N*rows,P,2) -> (N*rows,P) in [0,1], -1 in the rows that are not live."""
+    _ck(masks, n_gt, rois_xy5, gt_assign, label, n_pos, coords)
+    if masks.dim() != 4 or masks.dtype != torch.uint8:
+        raise ValueError('point_target: masks are an (N,G,H,W) uint8 tensor')
+    N, G, H, W = masks.shape
+    rows, n_sample = int(rows), int(n_sample)
+    Rm = N * rows
+    if coords.dim() != 3 or coords.shape[0] != Rm or coords.shape[2] != 2 or tuple(rois_xy5.shape) != (Rm, 5) or label.numel() != Rm \
+            or gt_assign.numel() != N * n_sample or n_pos.numel() != N or n_gt.numel() != N:
+        raise ValueError('point_target: the row counts of coords / rois_xy5 / label / gt_assign / n_pos / n_gt do not fit N = %d, n_sample = %d, '
+                         'rows = %d' % (N, n_sample, rows))
+    _point_dtypes('point_target', (n_gt, i32), (gt_assign, i32), (label, i32), (n_pos, i32), (rois_xy5, f32), (coords, f32))
+    P = coords.shape[1]
+    out = _empty((Rm, P), masks.device)
+    check(lib().mrcnn_point_target(ptr(masks), N, G, H, W, ptr(n_gt), ptr(rois_xy5), ptr(gt_assign), ptr(label), ptr(n_pos), n_sample, rows,
+                                   ptr(coords), P, ptr(out), stream_ptr()))
+    return out
+
+
+def point_bce(pred, target, label, n_channels, weight=1.0, label_base=1, want_grad=True, gx=None, out=None):
+    """The point loss (mrcnn_point_bce): pred (rows,1,P,ld) or (rows*P,ld), target (rows,P) with -1 = skipped, label (rows,) i32 -> (out (2,)
+    = (weight * mean BCE with logits over the live points, their count), gx shaped like pred)."""
+    _ck(pred, target, label, gx)
+    rows, P = target.shape
+    ld = pred.shape[-1]
+    if pred.numel() != rows * P * ld or label.numel() != rows:
+        raise ValueError('point_bce: pred %r, target %r, %d labels' % (tuple(pred.shape), tuple(target.shape), label.numel()))
+    _point_dtypes('point_bce', (pred, f32), (target, f32), (label, i32))
+    out = _empty((2,), pred.device) if out is None else out
+    if want_grad and gx is None:
+        gx = torch.empty_like(pred)
+    ws = _loss_ws(pred.device)
+    check(lib().mrcnn_point_bce(ptr(pred), ld, int(n_channels), ptr(target), ptr(label), int(label_base), rows, P, float(weight), ptr(out),
+                                ptr(gx) if want_grad else None, ptr(ws), ws.numel(), stream_ptr()))
+    return out, gx
+
+
+def point_subdivide(grid, label, n_channels, n_points):
+    """One subdivision step's selection (mrcnn_point_subdivide): grid (D,S,S,ld) logits, label (D,) i32 0-based or None (channel 0) ->
+    (up (D,2S,2S), index (D,n_sel) i32 ascending flat cells, coords (D,n_sel,2) their centres), n_sel = min(n_points, 4 S^2)."""
+    _ck(grid, label)
+    if grid.dim() != 4 or grid.shape[1] != grid.shape[2] or (label is not None and label.numel() != grid.shape[0]):
+        raise ValueError('point_subdivide: grid %r' % (tuple(grid.shape),))
+    _point_dtypes('point_subdivide', (grid, f32), (label, i32))
+    D, S, _, ld = grid.shape
+    n_sel = min(int(n_points), 4 * S * S)
+    up = _empty((D, 2 * S, 2 * S), grid.device)
+    index = _empty((D, max(n_sel, 0)), grid.device, i32)
+    coords = _empty((D, max(n_sel, 0), 2), grid.device)
+    check(lib().mrcnn_point_subdivide(ptr(grid), D, S, ld, int(n_channels), ptr(label), n_sel, ptr(up), ptr(index), ptr(coords), stream_ptr()))
+    return up, index, coords
+
+
+def point_scatter(pred, label, index, n_channels, grid):
+    """grid (D,G,G)[d].flat[index[d, j]] = pred (D,1,n_sel,ld)[d, 0, j, label[d]] in place (mrcnn_point_scatter); returns grid."""
+    _ck(pred, label, index, grid)
+    D, n_sel = index.shape
+    ld = pred.shape[-1]
+    if pred.numel() != D * n_sel * ld or grid.shape[0] != D or (label is not None and label.numel() != D):
+        raise ValueError('point_scatter: pred %r, index %r, grid %r' % (tuple(pred.shape), tuple(index.shape), tuple(grid.shape)))
+    _point_dtypes('point_scatter', (pred, f32), (label, i32), (index, i32), (grid, f32))
+    check(lib().mrcnn_point_scatter(ptr(pred), ld, int(n_channels), ptr(label), ptr(index), D, n_sel, int(np.prod(grid.shape[1:])), ptr(grid),
+                                    stream_ptr()))
+    return grid
+
+
 def class_nms(cls_bbox, prob, l_begin, l_end, score_thresh, nms_thresh):
     """-> keep_idx (n_class,R) int32, keep_cnt (n_class,) int32."""
     _ck(cls_bbox, prob)

@@ -233,6 +233,77 @@ def check_mask_iou_flags(args, tta_prefix='--'):
     return settings
 
 
+# ---- PointRend (MaskRCNN point_rend ..., FPNMaskRCNNTrainChain point_loss_weight) ------------------------------------------
+POINT_SHAPE_DEFAULTS = {'point_train_points': 196, 'point_oversample': 3, 'point_importance': 0.75, 'subdivision_steps': 2,
+                        'subdivision_points': 784}
+# what a trainer state without the 'point_rend' key was trained with
+NO_POINT_REND = dict({'point_rend': False, 'point_loss_weight': 1.0}, **POINT_SHAPE_DEFAULTS)
+
+
+def add_point_rend_flags(parser, both=lambda name: (name,), weight=False):
+    """--point-rend and its five shape flags (train.py, evaluate.py, demo.py; train_keypoints.py takes them to refuse them) and, with
+    ``weight``, --point-loss-weight (the training scripts)."""
+    parser.add_argument(*both('--point-rend'), type=int, default=0, choices=[0, 1],
+                        help='1: PointRend - a point head predicts the mask at single points from the stride-4 level and the coarse logits; '
+                             'inference refines the 28 x 28 mask by subdivision (MaskRCNN point_rend; --head-arch fpn only, not with '
+                             '--mask-iou); a checkpoint is evaluated with the values it was trained with')
+    parser.add_argument(*both('--point-train-points'), type=int, default=None, metavar='P',
+                        help='--point-rend 1: training points per mask row (default %d)' % POINT_SHAPE_DEFAULTS['point_train_points'])
+    parser.add_argument(*both('--point-oversample'), type=int, default=None, metavar='K',
+                        help='--point-rend 1: candidates per training point (default %d)' % POINT_SHAPE_DEFAULTS['point_oversample'])
+    parser.add_argument(*both('--point-importance'), type=float, default=None, metavar='BETA',
+                        help='--point-rend 1: the share of the training points taken from the most uncertain candidates (default %s)'
+                             % POINT_SHAPE_DEFAULTS['point_importance'])
+    parser.add_argument(*both('--subdivision-steps'), type=int, default=None, metavar='N',
+                        help='--point-rend 1: 2x subdivision steps at inference, 1 or 2 (default %d)' % POINT_SHAPE_DEFAULTS['subdivision_steps'])
+    parser.add_argument(*both('--subdivision-points'), type=int, default=None, metavar='N',
+                        help='--point-rend 1: cells re-predicted per detection and step (default %d)' % POINT_SHAPE_DEFAULTS['subdivision_points'])
+    if weight:
+        parser.add_argument(*both('--point-loss-weight'), type=float, default=None, metavar='W',
+                            help='the weight of the point loss under --point-rend 1 (default 1.0)')
+
+
+def point_rend_flag_settings(args, head_arch='fpn', mask_iou=0, weight=False):
+    """The PointRend settings of the flags as a dict with NO_POINT_REND's keys; ValueError for a shape flag or a weight without
+    --point-rend 1 and for a combination the model or the training chain refuses."""
+    from chainer_maskrcnn.model.maskrcnn import point_rend_settings
+    from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import point_loss_weight_setting
+    on = getattr(args, 'point_rend', 0)
+    if on not in (0, 1):
+        raise ValueError('--point-rend must be 0 or 1, got %r' % (on,))
+    given = {k: getattr(args, k, None) for k in POINT_SHAPE_DEFAULTS}
+    w = getattr(args, 'point_loss_weight', None) if weight else None
+    if not on:
+        extra = [k for k, v in given.items() if v is not None] + (['point_loss_weight'] if w is not None else [])
+        if extra:
+            raise ValueError('--%s belongs to --point-rend 1' % extra[0].replace('_', '-'))
+        return dict(NO_POINT_REND)
+    shape = {k: (POINT_SHAPE_DEFAULTS[k] if v is None else v) for k, v in given.items()}
+    try:
+        point_rend_settings(True, head_arch=head_arch, mask_iou=bool(mask_iou), **shape)
+        w = point_loss_weight_setting(1.0 if w is None else w)
+    except ValueError as e:
+        raise ValueError('--point-rend 1: %s' % e)
+    return dict({'point_rend': True, 'point_loss_weight': w}, **shape)
+
+
+def point_rend_model_kwargs(settings):
+    """The MaskRCNN keyword arguments of point_rend_flag_settings' dict (nothing when it is off: a default model)."""
+    if not settings['point_rend']:
+        return {}
+    return dict({'point_rend': True}, **{k: settings[k] for k in POINT_SHAPE_DEFAULTS})
+
+
+def check_point_rend_flags(args, tta_prefix='--'):
+    """--point-rend of an inference script (evaluate.py, demo.py) checked before the model is built: point_rend_flag_settings' refusals,
+    and no test-time augmentation on top of it (MaskRCNN.use_test_augmentation refuses it)."""
+    settings = point_rend_flag_settings(args, args.head_arch, getattr(args, 'mask_iou', 0))
+    if settings['point_rend'] and (args.tta_sizes or args.tta_hflip):
+        raise ValueError('--point-rend 1 does not go with %stta-sizes / %stta-hflip: test-time augmentation of a PointRend model is not '
+                         'supported' % (tta_prefix, tta_prefix))
+    return settings
+
+
 # ---- labels and the model -----------------------------------------------------------------------------------------------------------------
 def read_labels(label_file):
     """The category names of --label_file (None when the file does not exist: every category)."""
@@ -250,7 +321,7 @@ def use_score_preset(model, preset, score_thresh=None):
 
 
 def build_inference_model(args, preset=None):
-    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --fpn-norm / --gn-groups / --cascade* / --mask-iou / --label_file with --weight loaded (keys missing from the file keep their
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --fpn-norm / --gn-groups / --cascade* / --mask-iou / --point-rend* / --label_file with --weight loaded (keys missing from the file keep their
     initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
     17 keypoints; a mask head has one class per label (80 without a label file)."""
     import torch
@@ -260,6 +331,7 @@ def build_inference_model(args, preset=None):
     norm.update(fpn_norm_settings(getattr(args, 'fpn_norm', 'none'), args.gn_groups, args.backbone))
     norm.update(cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone))
     norm['mask_iou'] = mask_iou_settings(getattr(args, 'mask_iou', 0), None, args.head_arch)['mask_iou']
+    norm.update(point_rend_model_kwargs(point_rend_flag_settings(args, args.head_arch, norm['mask_iou'])))
     dev =torch.device('cuda', args.gpu)
     torch.cuda.set_device(dev)
     if args.head_arch == 'fpn_keypoint':

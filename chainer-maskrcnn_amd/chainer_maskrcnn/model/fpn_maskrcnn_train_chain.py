@@ -139,6 +139,14 @@ def mask_iou_weight_setting(weight):
     return float(weight)
 
 
+def point_loss_weight_setting(weight):
+    """The point_loss_weight argument of FPNMaskRCNNTrainChain as a float, checked like mask_iou_weight: ValueError unless it is a finite
+    number above 0."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
+        raise ValueError('point_loss_weight must be a finite number above 0, got %r' % (weight,))
+    return float(weight)
+
+
 def select_gemm_arithmetic(name):
     """Process-wide: the library's split-operand modes and the per-layer rule of nn/core.py."""
     from chainer_maskrcnn._hip import lib, check
@@ -157,7 +165,8 @@ class FPNMaskRCNNTrainChain(object):
 
     def __init__(self, faster_rcnn, mask_loss_fun=calc_mask_loss, binary_mask=True, rpn_sigma=3., roi_sigma=1.,
                  anchor_target_creator=None, strict_batch1=False, mask_rows='positives', gemm_arithmetic=None,
-                 box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0, mask_iou_weight=1.0):
+                 box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0, mask_iou_weight=1.0,
+                 point_loss_weight=1.0):
         """gemm_arithmetic: a key of GEMM_ARITHMETIC - the chain then selects it (process-wide library setting) at the start of every
         step; None (default of this constructor, used by the kernel-level tests) leaves the process setting alone.  train.py and
         bench.py pass DEFAULT_GEMM_ARITHMETIC.
@@ -169,9 +178,14 @@ class FPNMaskRCNNTrainChain(object):
 
         mask_iou_weight: multiplies the MaskIoU head's L2 loss and its gradient (a finite number above 0; Mask Scoring R-CNN, DESIGN.md
         section 3.22).  It acts on a model built with ``mask_iou=True`` only: the chain then runs target -> input assembly -> head -> L2
-        behind the mask loss and reports ``maskiou_loss``."""
+        behind the mask loss and reports ``maskiou_loss``.
+
+        point_loss_weight: multiplies the point head's loss and its gradient (a finite number above 0; PointRend).
+        It acts on a model built with ``point_rend=True`` only: the chain then runs points -> features -> head -> target -> loss behind the
+        mask loss, on the mask branch's rows, and reports ``point_loss``."""
         box_loss_settings(box_loss, rpn_box_loss, box_loss_weight, rpn_box_loss_weight)
         self.mask_iou_weight = mask_iou_weight_setting(mask_iou_weight)
+        self.point_loss_weight = point_loss_weight_setting(point_loss_weight)
         self.box_loss, self.rpn_box_loss = box_loss, rpn_box_loss
         self.box_loss_weight, self.rpn_box_loss_weight = float(box_loss_weight), float(rpn_box_loss_weight)
         if gemm_arithmetic is not None and gemm_arithmetic not in GEMM_ARITHMETIC:
@@ -198,6 +212,9 @@ class FPNMaskRCNNTrainChain(object):
         if getattr(faster_rcnn, 'maskiou_head', None) is not None and self.mask_loss_kind != 'mask_bce':
             raise ValueError('a mask_iou model trains with the fused binary mask loss (calc_mask_loss): a user-supplied mask_loss_fun '
                              're-orders the mask rows, which the MaskIoU target does not follow')
+        if getattr(faster_rcnn, 'point_head', None) is not None and self.mask_loss_kind != 'mask_bce':
+            raise ValueError('a point_rend model trains with the fused binary mask loss (calc_mask_loss): a user-supplied mask_loss_fun '
+                             're-orders the mask rows, which the point targets do not follow')
         self.unit_upstream = False
         self.backward_follows = False       # set by MomentumSGD.update around its forward call: loss.backward() comes next, with d loss = 1
         self.binary_mask = binary_mask
@@ -206,12 +223,16 @@ class FPNMaskRCNNTrainChain(object):
         self.observation = {}
         self.grad_ready_hook = None         # called with the lowest finished parameter offset during backward (DP overlap)
         self.sampler_keys = None            # (proposal keys, anchor keys) override for parity tests
+        self.point_keys = None              # (mask rows, ops.point_n_keys) int32 keys of the PointRend training points, for parity tests
+        self.point_seed = 1 << 33
+        self._point_state = None            # the device-resident seed the point keys are drawn from
         self.use_aux_stream = True          # independent branches (RPN losses, box head) on a second compute stream
         self.keep_outputs = False           # parity tests: keep the head outputs of the last step in self.outputs
         self.outputs = {}
         self._aux = {}
         self._bwd_cascade = ()
         self._bwd_maskiou = None
+        self._bwd_point = None
         self._arith_found = None            # the process's GEMM arithmetic before this chain selected its own (restored by backward())
 
     def _aux_stream(self, dev):
@@ -266,7 +287,9 @@ class FPNMaskRCNNTrainChain(object):
         stages = list(getattr(m, 'cascade_heads', []))        # Cascade R-CNN: the box stages behind the head
         mh = getattr(m, 'maskiou_head', None)                 # Mask Scoring R-CNN: the MaskIoU head
         iou_row = 5 + 2 * len(stages)                         # its loss row, behind the cascade's
-        losses = torch.empty((iou_row + (1 if mh is not None else 0), 2), dtype=torch.float32, device=dev)
+        ph = getattr(m, 'point_head', None)                   # PointRend: the point head
+        pt_row = iou_row + (1 if mh is not None else 0)       # its loss row, behind the cascade's and the MaskIoU's
+        losses = torch.empty((pt_row + (1 if ph is not None else 0), 2), dtype=torch.float32, device=dev)
         br1 = {}
 
         def rpn_loss_branch(locs, scores, anchors):
@@ -391,6 +414,27 @@ class FPNMaskRCNNTrainChain(object):
                                       out=losses[iou_row])
             iou['g_pred'] = g_iou
 
+        pt = None
+        if ph is not None:
+            # Behind the mask loss, on the main stream and the mask branch's own rows: the training points from the coarse logits'
+            # uncertainty, the head's input sampled from the stride-4 level and the logits (constants for the head), the head, the soft
+            # targets from the ground-truth masks, the loss over the live rows.  No host synchronisation.
+            st = m.point_rend
+            m_label, m_rois = m_label.contiguous(), m_rois.contiguous()
+            keys = self.point_keys
+            if keys is None:
+                if self._point_state is None or self._point_state.device != dev:
+                    self._point_state = ops.seed_state(self.point_seed, dev)
+                keys = ops.random_keys_dev((mask_out.shape[0], ops.point_n_keys(st['train_points'], st['n_candidates'], st['n_important'])),
+                                           self._point_state)
+            pt = dict(coords=ops.point_train_coords(keys, mask_out, m_label, ph.out_channels, st['train_points'], st['n_candidates'],
+                                                    st['n_important'], label_base=1), rois=m_rois)
+            pt['input'] = ph.assemble(pt['coords'], m_rois, features[0], scales[0], mask_out)
+            pt['pred'] = ph.forward(pt['input'])
+            pt['target'] = ops.point_target(masks.contiguous(), n_gt, m_rois, t['gt_assign'], m_label, t['n_pos'], S, rows, pt['coords'])
+            _, pt['g_pred'] = ops.point_bce(pt['pred'], pt['target'], m_label, ph.out_channels, weight=self.point_loss_weight, label_base=1,
+                                            out=losses[pt_row])
+
         main.wait_stream(aux)
         if aux is not main:             # allocated on the aux stream, consumed by the RPN backward on the main stream
             g_locs.record_stream(main)
@@ -403,9 +447,12 @@ class FPNMaskRCNNTrainChain(object):
             self.observation['roi_cls_loss_s%d' % k] = losses[6 + 2 * (k - 2), 0]
         if mh is not None:
             self.observation['maskiou_loss'] = losses[iou_row, 0]
+        if ph is not None:
+            self.observation['point_loss'] = losses[pt_row, 0]
         self._bwd = (features, g_locs.view(n, A, 4), g_scores.view(n, A, 2), g_box, g_mask)
         self._bwd_cascade = g_boxes[1:]          # the later box stages' loss gradients, in stage order
         self._bwd_maskiou = g_iou                # the MaskIoU loss gradient (None without the head)
+        self._bwd_point = pt                     # the point head's coords, rois and loss gradient (None without the head)
         self._early_rpn = br1.get('g_feats')
         self.targets = t
         if self.keep_outputs:
@@ -414,6 +461,8 @@ class FPNMaskRCNNTrainChain(object):
                 self.outputs.update(cascade=casc, g_boxes=g_boxes, losses=losses)
             if mh is not None:      # target, area, counts, input, pred, g_pred of the MaskIoU head, the mask loss gradient and the pooled features
                 self.outputs.update(maskiou=iou, g_mask=g_mask, mask_pool=head.last_mask_pool, losses=losses)
+            if ph is not None:      # coords, rois, input, pred, target, g_pred of the point head (backward adds g_in), the mask loss gradient
+                self.outputs.update(point=pt, g_mask=g_mask, losses=losses)
         self.rpn_targets = (gt_rpn_loc, gt_rpn_label)
         self.mask_inputs = (m_rois, m_levels, m_label)
         self.rpn_out = r
@@ -461,9 +510,11 @@ class FPNMaskRCNNTrainChain(object):
         features, g_locs, g_scores, g_box, g_mask = self._bwd
         g_later = self._bwd_cascade
         g_iou = self._bwd_maskiou
+        pt = self._bwd_point
         if upstream is not None:
             from chainer_maskrcnn.functions.loss import _scale_
-            for g_ in (g_locs, g_scores, g_box, g_mask) + tuple(g_later) + ((g_iou,) if g_iou is not None else ()):
+            for g_ in (g_locs, g_scores, g_box, g_mask) + tuple(g_later) + ((g_iou,) if g_iou is not None else ()) \
+                    + ((pt['g_pred'],) if pt is not None else ()):
                 _scale_(g_, upstream)
         hook = self.grad_ready_hook
         dev = features[0].device
@@ -485,6 +536,8 @@ class FPNMaskRCNNTrainChain(object):
         # the MaskIoU head first (main stream): its parameter gradients are final and its input gradient is at hand before the mask
         # branch's; the feature part joins the mask convolutions' pooled gradient, so the ONE ROIAlign backward below carries both
         g_iou_in = m.maskiou_head.backward(g_iou) if g_iou is not None else None
+        # the point head likewise (main stream): its input gradient waits for the ROIAlign backward passes below
+        g_pt_in = m.point_head.backward(pt['g_pred']) if pt is not None else None
         g_pool = m.head.backward_mask_convs(g_mask)       # main stream: the mask branch down to its pooled input
         if g_iou_in is not None:
             if self.keep_outputs:       # parity tests: the two summands
@@ -494,6 +547,15 @@ class FPNMaskRCNNTrainChain(object):
         if self.keep_outputs and g_iou_in is not None:       # ... and the pyramid gradient the box stages left
             self.outputs.update(g_feats_box=[g.clone() for g in g_feats])
         m.head.backward_mask_pool(g_pool, g_feats)        # accumulates into g_feats (second pooled size)
+        if g_pt_in is not None:
+            # PointRend: the fine part of the point head's input gradient, added into the stride-4 level's gradient behind the heads' ROIAlign
+            # backward passes (and the RPN's, where it ran early) - what the map holds is the first addend, then ascending (row, point)
+            if self.keep_outputs:       # parity tests: the map before the addition and the addend
+                pt['g_in'] = g_pt_in
+                self.outputs.update(g_feats0_heads=g_feats[0].clone())
+            ops.point_features_bwd(g_pt_in, pt['coords'], pt['rois'], m.extractor.spatial_scales[0], g_feats[0])
+            if self.keep_outputs:
+                self.outputs.update(g_feats0_point=g_feats[0].clone())
         if self.keep_outputs and (g_later or g_iou_in is not None):       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
             self.outputs.update(g_mask_pool=g_pool, g_feats_heads=[g.clone() for g in g_feats])
         if hook:
@@ -520,6 +582,7 @@ class FPNMaskRCNNTrainChain(object):
         self._bwd = None
         self._bwd_cascade = ()
         self._bwd_maskiou = None
+        self._bwd_point = None
         if self._arith_found is not None:
             from chainer_maskrcnn._hip import lib, check
             split, in_backbone = self._arith_found

@@ -247,6 +247,59 @@ class MaskIoUHead(object):
         return g
 
 
+class PointHead(object):
+    """The point head of PointRend (Kirillov et al. 2020): an MLP that predicts, per class, the mask logit at single
+    points.  Input (rows,1,P,cin_p): the ``in_channels`` fine channels of the stride-4 level and the n_class - 1 coarse logits, both sampled
+    at the point (ops.point_features_fwd).  fc1..fc3 are 1x1 convolutions to ``fc_channels`` with ReLU, ``predictor`` a 1x1 convolution to
+    n_class - 1; the coarse channels are concatenated again behind the hidden channels in front of fc2, fc3 and the predictor
+    (ops.point_concat_fwd).  The coarse logits are a constant: the coarse slices of every input gradient are dropped.  Parameters
+    ``head/point/{fc1,fc2,fc3,predictor}``; its own tape and ``backward``."""
+
+    def __init__(self, n_class, ps, prefix='head/point', in_channels=256, fc_channels=256, initialW=None):
+        c = in_channels
+        if c % 4 or fc_channels % 32:
+            raise ValueError('PointHead: %d fine and %d hidden channels (multiples of 4 and of 32 expected)' % (c, fc_channels))
+        self.ps, self.n_class, self.channels, self.fc_channels = ps, n_class, c, fc_channels
+        self.out_channels = k = n_class - 1
+        p = prefix + '/'
+        self.fc1 = Conv(ps, p + 'fc1', c + k, fc_channels, 1, relu=True)
+        self.fc2 = Conv(ps, p + 'fc2', fc_channels + k, fc_channels, 1, relu=True)
+        self.fc3 = Conv(ps, p + 'fc3', fc_channels + k, fc_channels, 1, relu=True)
+        self.predictor = Conv(ps, p + 'predictor', fc_channels + k, k, 1, init=normal(0.001 if initialW is None else initialW))
+        self.cin_p, self.out_p = self.fc1.cin_p, self.predictor.cout_p
+        self.tape = None
+
+    def assemble(self, coords, rois_xy5, fmap, scale, coarse):
+        """The head's input at the points ``coords`` of the rows' boxes: fine features from ``fmap``, coarse from the rows' own logits."""
+        return ops.point_features_fwd(coords, rois_xy5, fmap, scale, coarse, self.out_channels, self.cin_p)
+
+    def forward(self, x0):
+        """x0 (rows,1,P,cin_p) -> (rows,1,P,out_p): column k = the logit of class k + 1's mask at the point."""
+        c, k = self.channels, self.out_channels
+        h, t1 = self.fc1.fwd(x0)
+        tapes = [t1]
+        for layer in (self.fc2, self.fc3, self.predictor):
+            x = ops.point_concat_fwd(h, x0, c, k, layer.cin_p)
+            h, t = layer.fwd(x)
+            tapes.append(t)
+        self.tape = tapes
+        return h
+
+    def backward(self, g_pred):
+        """g_pred (rows,1,P,out_p) -> the gradient of the input (rows,1,P,cin_p), whose first ``in_channels`` channels are the fine part;
+        fills the head/point/ parameter gradients."""
+        t1, t2, t3, t4 = self.tape
+        hc = self.fc_channels
+        # the hidden part of a layer's input is the ReLU output of the layer below: the ReLU backward rides in the data-gradient epilogue
+        # (it also masks the coarse part, which is dropped)
+        g = self.predictor.bwd(t4, g_pred, mask_gx=True)
+        g = self.fc3.bwd(t3, ops.point_concat_bwd(g, hc), gy_masked=True, mask_gx=True)
+        g = self.fc2.bwd(t2, ops.point_concat_bwd(g, hc), gy_masked=True, mask_gx=True)
+        g = self.fc1.bwd(t1, ops.point_concat_bwd(g, hc), gy_masked=True)
+        self.tape = None
+        return g
+
+
 class FPNRoIMaskHead(FPNRoIBoxHead):
     mask_size = 28
     keep_mask_pool = False          # set by a model with a MaskIoU head: mask_branch leaves its pooled features in last_mask_pool

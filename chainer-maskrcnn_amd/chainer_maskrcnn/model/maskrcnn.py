@@ -17,7 +17,7 @@ from chainer_maskrcnn.nn.core import ParamStore
 from chainer_maskrcnn._hip import ops
 from .extractor.feature_pyramid_network import FeaturePyramidNetwork
 from .rpn.multilevel_region_proposal_network import MultilevelRegionProposalNetwork
-from .head.fpn_roi_mask_head import FPNRoIBoxHead, FPNRoIMaskHead, MaskIoUHead
+from .head.fpn_roi_mask_head import FPNRoIBoxHead, FPNRoIMaskHead, MaskIoUHead, PointHead
 
 # Cascade R-CNN (Cai & Vasconcelos 2018): the stages' normalisation of the box deltas; stage 1's is the model's loc_normalize_std
 CASCADE_STDS = ((0.1, 0.1, 0.2, 0.2), (0.05, 0.05, 0.1, 0.1), (0.033, 0.033, 0.067, 0.067))
@@ -70,6 +70,38 @@ def mask_iou_setting(mask_iou, head_arch='fpn'):
     return bool(mask_iou)
 
 
+def point_rend_settings(point_rend=False, point_train_points=196, point_oversample=3, point_importance=0.75, subdivision_steps=2,
+                        subdivision_points=784, head_arch='fpn', mask_iou=False):
+    """The checked PointRend arguments of MaskRCNN: None when ``point_rend`` is off, else a dict with train_points P,
+    oversample k, importance beta, n_candidates = k * P, n_important = floor(beta * P), subdivision_steps and subdivision_points.
+    ValueError for a value out of range, for the heads that have no binary mask to refine (the keypoint head, the legacy 'res5' / 'light'
+    heads) and together with ``mask_iou`` (the MaskIoU target is defined on the 28 x 28 mask)."""
+    if point_rend not in (False, True, 0, 1):
+        raise ValueError('point_rend must be True or False, got %r' % (point_rend,))
+    if not point_rend:
+        return None
+    if head_arch != 'fpn':
+        raise ValueError("point_rend exists for head_arch 'fpn' only, not %r (a keypoint head has no binary mask to refine)" % (head_arch,))
+    if mask_iou:
+        raise ValueError('point_rend together with mask_iou is not supported: the MaskIoU target is defined on the 28 x 28 mask')
+    ints = dict(point_train_points=point_train_points, point_oversample=point_oversample, subdivision_steps=subdivision_steps,
+                subdivision_points=subdivision_points)
+    for k, v in ints.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('%s must be a positive integer, got %r' % (k, v))
+    if isinstance(point_importance, bool) or not isinstance(point_importance, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= point_importance <= 1.0:
+        raise ValueError('point_importance must be a number in [0, 1], got %r' % (point_importance,))
+    P, k = int(point_train_points), int(point_oversample)
+    if k * P > 4096:
+        raise ValueError('point_oversample * point_train_points = %d candidates per row exceed the 4096 the selection kernel sorts' % (k * P))
+    if int(subdivision_steps) > 2:      # 28 -> 56 -> 112: the grid one workgroup of the selection kernel holds
+        raise ValueError('subdivision_steps must be at most 2 (a 112 x 112 grid), got %r' % (subdivision_steps,))
+    return dict(train_points=P, oversample=k, importance=float(point_importance), n_candidates=k * P,
+                n_important=int(np.floor(float(point_importance) * P)), subdivision_steps=int(subdivision_steps),
+                subdivision_points=int(subdivision_points))
+
+
 class MaskRCNN(object):
     feat_stride = 16
     # box post-processing of _suppress (DESIGN.md §3.16), off until use_soft_nms / use_box_voting / use_max_detections set them on an instance
@@ -83,12 +115,19 @@ class MaskRCNN(object):
     maskiou_head = None
     mask_iou_rescore = True         # predict: score = box score x predicted mask IoU (False: the box score, on a model that has the head)
     last_box_scores = None          # predict: the box scores of the last call's detections, one array per image
+    # PointRend, off unless the constructor's point_rend builds the head
+    point_rend = None               # the settings dict of point_rend_settings
+    point_head = None
+    point_rend_refine = True        # predict: subdivide and refine the mask logits (False: paste the coarse 28 x 28 masks)
+    last_point_grid = None          # predict: the refined (D,G,G) logit grid of the last image (None where nothing was refined)
+    last_point_coarse = None        # ... and the coarse logits it started from
 
     def __init__(self, n_fg_class, n_keypoints=None, n_mask_convs=None, pretrained_model=None, min_size=600,
                  max_size=1000, ratios=[0.5, 1, 2], anchor_scales=[8], rpn_initialW=None, loc_initialW=None,
                  score_initialW=None, proposal_creator_params={}, backbone='fpn', head_arch='fpn',
                  device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32, cascade_ious=None, cascade_stds=None,
-                 mask_iou=False, fpn_norm=None):
+                 mask_iou=False, fpn_norm=None, point_rend=False, point_train_points=196, point_oversample=3, point_importance=0.75,
+                 subdivision_steps=2, subdivision_points=784):
         """fpn_norm: None = the reference's pyramid; 'gn' = GroupNorm of ``gn_groups`` groups behind each of the eight FPN convolutions
         (DESIGN.md §3.23); backbone 'fpn' only.
         head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
@@ -97,7 +136,12 @@ class MaskRCNN(object):
         stage k > 1 a box-only head ``head/cascade<k>/...`` registered directly behind the stage-1 head's parameters and fed stage k-1's
         refined boxes; ``cascade_stds`` their delta normalisation (cascade_settings).
         mask_iou: True = Mask Scoring R-CNN: a MaskIoU head ``head/maskiou/...`` behind every other head parameter (the
-        cascade's included) regresses the IoU of each predicted mask; ``predict`` multiplies it into the score.  head_arch 'fpn' only."""
+        cascade's included) regresses the IoU of each predicted mask; ``predict`` multiplies it into the score.  head_arch 'fpn' only.
+        point_rend: True = PointRend: a point head ``head/point/...`` behind every other head parameter predicts the mask
+        at single points from the stride-4 level and the coarse logits.  It trains on ``point_train_points`` points per mask row, the
+        ``floor(point_importance * point_train_points)`` most uncertain of ``point_oversample`` times as many candidates and uniform ones;
+        ``predict`` refines the 28 x 28 logits in ``subdivision_steps`` 2x steps, re-predicting the ``subdivision_points`` most uncertain
+        cells of each.  head_arch 'fpn' only, not together with ``mask_iou``."""
         if n_fg_class is None:
             raise ValueError('The n_fg_class needs to be supplied as an argument')
         if head_norm not in (None, 'gn'):
@@ -111,6 +155,8 @@ class MaskRCNN(object):
         self.head_norm, self.gn_groups, self.fpn_norm = head_norm, int(gn_groups), fpn_norm
         self.cascade = cascade_settings(cascade_ious, cascade_stds, head_arch, backbone)
         self.mask_iou = mask_iou_setting(mask_iou, head_arch)
+        self.point_rend = point_rend_settings(point_rend, point_train_points, point_oversample, point_importance, subdivision_steps,
+                                              subdivision_points, head_arch, self.mask_iou)
         self.ps = ParamStore()
         shrink = _test_shrink or {}
         if backbone == 'fpn':
@@ -178,6 +224,11 @@ class MaskRCNN(object):
             self.maskiou_head = MaskIoUHead(self.head.n_class, ps=self.ps, prefix='head/maskiou', in_channels=c,
                                             fc_channels=1024 // shrink.get('width_div', 1))
             self.head.keep_mask_pool = True
+        # PointRend: the point head, behind every other head parameter
+        self.point_head = None
+        if self.point_rend is not None:
+            self.point_head = PointHead(self.head.n_class, ps=self.ps, prefix='head/point', in_channels=c,
+                                        fc_channels=256 // shrink.get('width_div', 1))
         # FasterRCNN base-class state
         self.mean = np.array([122.7717, 115.9465, 102.9801], dtype=np.float32)[:, None, None]   # unused (maskrcnn.py:273-274)
         self.min_size, self.max_size = min_size, max_size
@@ -248,6 +299,8 @@ class MaskRCNN(object):
             raise ValueError('use_test_augmentation: test-time augmentation of a cascade model (cascade_ious) is not supported')
         if self.maskiou_head is not None:
             raise ValueError('use_test_augmentation: test-time augmentation of a Mask Scoring model (mask_iou) is not supported')
+        if self.point_head is not None:
+            raise ValueError('use_test_augmentation: test-time augmentation of a PointRend model (point_rend) is not supported')
         sizes = [int(s) for s in sizes]
         if not sizes or any(s <= 0 for s in sizes):
             raise ValueError('use_test_augmentation: sizes must be positive, got %r' % (sizes,))
@@ -400,6 +453,11 @@ class MaskRCNN(object):
                                       self.extractor.spatial_scales)
         self._box_score = score
         self.last_maskiou = None
+        self.last_point_grid = self.last_point_coarse = None
+        if m is not None and self.point_head is not None and self.predict_mask:
+            self.last_point_coarse = m
+            if self.point_rend_refine:
+                self.last_point_grid = self._point_refine(m, self._xy5(bbox, scale), label.to(torch.int32).contiguous())
         if m is not None and self.maskiou_head is not None and self.predict_mask:
             # Mask Scoring R-CNN: the MaskIoU head on the kept detections, behind the mask branch and behind _suppress -
             # the order, the count, the boxes and the masks of the detections are those of the box scores (use_max_detections included)
@@ -411,6 +469,22 @@ class MaskRCNN(object):
             if self.mask_iou_rescore:
                 score = ops.maskiou_rescore(score.to(torch.float32).contiguous(), pred, lab, mh.out_channels)
         return size, bbox, label, score, m, None
+
+    def _point_refine(self, m, rois_xy5, label):
+        """PointRend inference on the coarse logits m (D,S0,S0,Cp) of the detections with boxes ``rois_xy5`` (the forward's
+        frame) and 0-based labels: per subdivision step a 2x upsample of the class's grid, the most uncertain cells, the point head on their
+        centres - fine features from the pyramid kept in ``head.x``, coarse features from the ORIGINAL logits - and their predictions written
+        over those cells.  Returns the (D,G,G) logit grid, G = S0 * 2^steps."""
+        ph, st = self.point_head, self.point_rend
+        grid, lab = m, label
+        scale0 = self.extractor.spatial_scales[0]
+        for _ in range(st['subdivision_steps']):
+            up, index, coords = ops.point_subdivide(grid, lab, ph.out_channels if lab is not None else 1, st['subdivision_points'])
+            x_in = ph.assemble(coords, rois_xy5, self.head.x[0], scale0, m)
+            pred = ph.forward(x_in)
+            ops.point_scatter(pred, label, index, ph.out_channels, up)
+            grid, lab = up.view(up.shape[0], up.shape[1], up.shape[2], 1), None
+        return grid.view(grid.shape[0], grid.shape[1], grid.shape[2])
 
     def predict(self, imgs):
         """maskrcnn.py:157-259: imgs = list of (3,H,W) float32 tensors (0..255).  Returns (masks, labels, scores) -
@@ -424,6 +498,11 @@ class MaskRCNN(object):
                 box_scores.append(score if mirrors is not None else self._box_score)
                 if m is None:
                     mask = torch.zeros((bbox.shape[0],) + size, dtype=torch.bool, device=self.device)
+                elif mirrors is None and self.last_point_grid is not None:
+                    # the refined grid through the unchanged paste rule: one channel, so every detection's label is 0
+                    g = self.last_point_grid
+                    mask = ops.mask_paste(g.view(g.shape[0], g.shape[1], g.shape[2], 1), torch.zeros_like(label, dtype=torch.int32), bbox,
+                                          size).bool()
                 elif mirrors is None:
                     mask = ops.mask_paste(m, label.contiguous(), bbox, size).bool()
                 else:

@@ -396,6 +396,9 @@ class MomentumSGD(object):
             c = getattr(self.target, name, None)
             if c is not None:
                 d['samplers'][name] = {'seed': c.seed, 'state': None if c._state is None else c._state.detach().cpu()}
+        if getattr(getattr(self.target, 'faster_rcnn', None), 'point_head', None) is not None:      # PointRend: the chain's own point keys
+            st = self.target._point_state
+            d['samplers']['point_rend'] = {'seed': self.target.point_seed, 'state': None if st is None else st.detach().cpu()}
         return d
 
     def load_state_dict(self, d):
@@ -412,6 +415,11 @@ class MomentumSGD(object):
         self.average_accumulated = d.get('average_accumulated', False)
         self.pending = 0
         for name, st in d.get('samplers', {}).items():
+            if name == 'point_rend':
+                if hasattr(self.target, '_point_state'):
+                    self.target.point_seed = st['seed']
+                    self.target._point_state = None if st['state'] is None else st['state'].to(ps.params.device)
+                continue
             c = getattr(self.target, name, None)
             if c is not None:
                 c.seed = st['seed']

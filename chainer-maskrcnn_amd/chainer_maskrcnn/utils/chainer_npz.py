@@ -6,7 +6,8 @@ layouts:  Convolution2D W (Cout, Cin, KH, KW), Linear W (out, in) with the input
 Deconvolution2D W (Cin, Cout, KH, KW), BatchNormalization gamma / beta / avg_mean / avg_var / N.  The GroupNorm layers of a
 ``head_norm='gn'`` model (no counterpart in the reference) go out as GroupNormalization gamma / beta (C,) under their store names
 ``head/<conv>/gn/{gamma,beta}``, those of an ``fpn_norm='gn'`` model under ``extractor/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.  The MaskIoU head of a ``mask_iou`` model (no
-counterpart either) goes out as ``head/maskiou/{conv1..conv4}`` (Convolution2D) and ``head/maskiou/{fc1,fc2,maskiou}`` (Linear).
+counterpart either) goes out as ``head/maskiou/{conv1..conv4}`` (Convolution2D) and ``head/maskiou/{fc1,fc2,maskiou}`` (Linear), the
+point head of a ``point_rend`` model as ``head/point/{fc1,fc2,fc3,predictor}`` (Linear).
 
 Storage here differs only mechanically - conv W (Cout_p, KH, KW, Cin_p) with zero-padded channels, NHWC
 flattening for ``fc1``, ``rpn/loc`` + ``rpn/score`` fused into ``rpn/loc_score``, ``head/cls_loc`` + ``head/score``
@@ -72,6 +73,13 @@ class ChainerNpzMap(object):
             for cv in self.maskiou.convs + [self.maskiou.fc2, self.maskiou.out]:
                 self._add_conv(cv)
             self.linears.add(self.maskiou.out.name)
+        # the point head of a point_rend model (no counterpart either): head/point/{fc1,fc2,fc3,predictor}, per-point layers, as Linear
+        # (out, in) with the input channels in the head's order - fine or hidden channels first, the coarse logits behind them
+        self.point = getattr(model, 'point_head', None)
+        if self.point is not None:
+            for cv in (self.point.fc1, self.point.fc2, self.point.fc3, self.point.predictor):
+                self._add_conv(cv)
+                self.linears.add(cv.name)
 
     def _add_conv(self, cv):
         self.convs[cv.name] = cv

@@ -25,8 +25,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags, add_mask_iou_flags, add_tta_flags, boxpost_settings,  # noqa: E402
-                                                build_inference_model, check_cascade_flags, check_mask_iou_flags, fpn_norm_settings, head_norm_settings, read_labels, tta_settings, use_boxpost, use_score_preset, use_tta)
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags, add_mask_iou_flags, add_point_rend_flags, add_tta_flags, boxpost_settings,  # noqa: E402
+                                                build_inference_model, check_cascade_flags, check_mask_iou_flags, check_point_rend_flags, fpn_norm_settings, head_norm_settings, read_labels, tta_settings, use_boxpost, use_score_preset, use_tta)
 
 IMAGE_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
 SYNTHETIC_FIRST_SEED = 2000003      # far from the seeds of the synthetic training pool and of the synthetic val split
@@ -58,6 +58,7 @@ def build_parser():
     add_fpn_norm_flags(parser)
     add_cascade_flags(parser)
     add_mask_iou_flags(parser)
+    add_point_rend_flags(parser)
     add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--json', type=int, default=0, choices=[0, 1], help='1: also write <stem>.json per image')
@@ -123,6 +124,7 @@ def check_args(args):
     fpn_norm_settings(args.fpn_norm, args.gn_groups, args.backbone)
     check_cascade_flags(args)
     check_mask_iou_flags(args)
+    check_point_rend_flags(args)
     return collect_inputs(args.inputs)
 
 

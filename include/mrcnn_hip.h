@@ -1156,6 +1156,58 @@ int mrcnn_maskiou_l2(const float *pred, int ld, int n_channels, const float *tar
 int mrcnn_maskiou_rescore(const float *score, const float *pred, int ld, int n_channels, const int32_t *label, int D, float *out,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PointRend mask refinement (pointrend.hip, point_common.h; no counterpart in the reference).  float32 without
+ * contraction, no float atomics: the same bits on every run.  Every launch is capture-safe.  Zero rows / detections succeed without a launch.
+ * point_sample(map, px, py): pixel centres at i + 0.5; fx = px - 0.5, x0 = floor(fx), lx = fx - x0, the same in y; taps (y0,x0), (y0,x0+1),
+ *   (y0+1,x0), (y0+1,x0+1) with weights (1-ly)(1-lx), (1-ly)lx, ly(1-lx), ly*lx; a tap outside the map is zero and is not read; the four
+ *   products are added in that order.
+ * A row's box is its rois_xy5 entry (idx, x1, y1, x2, y2); the normalised point (u, v) has frame position X = x1 + u * (x2 - x1),
+ *   Y = y1 + v * (y2 - y1).  coords (rows, P, 2) = (u, v).  n_channels: the logical class channels (label - label_base in [0, n_channels));
+ *   MRCNN_E_INVALID when it is not in [1, Cp] / [1, ld].
+ * point_train_coords: keys (rows, n_keys) uint32, n_keys >= 2 * n_cand + 2 * (P - n_imp); a key gives (key >> 8) * 2^-24.  Candidate j
+ *   = keys (2j, 2j+1); its uncertainty is -|point_sample(coarse[r, :, :, label[r] - label_base], u * S0, v * S0)|, 0 for a row without a
+ *   channel.  Points [0, n_imp): the most uncertain candidates, the most uncertain first, ties to the lower index (a bitonic sort of
+ *   (bits of |value|, j) in LDS; n_cand <= 4096).  Points [n_imp, P): the keys 2 * n_cand + 2 * (p - n_imp) and the next.
+ * point_features_fwd: out (rows, P, cin_p): [0, C) = point_sample of map (N,H,W,C), image idx, at (X * scale, Y * scale) (zeros for an idx
+ *   outside [0, N)); [C, C + n_channels) = point_sample of coarse (rows,S0,S0,Cp) at (u * S0, v * S0); zeros behind.  C, Cp, cin_p
+ *   multiples of 4.
+ * point_features_bwd: g_map (N,H,W,C) += the transpose of the fine sampling applied to g_in (rows, P, ld)[..., :C].  Owner-computes: a wave
+ *   owns 2 x 4 cells, scans the rows whose box in map coordinates, widened by one cell, touches them and adds w * g per tap in ascending
+ *   (row, point) order, taps in the order above; the value the map held is the FIRST addend; every touched cell is written once, an
+ *   untouched patch is neither read nor written.  C <= 512.
+ * point_concat_fwd: out (n, cin_p) = [h (n, Ch) | x0 (n, ld0)[c0 : c0 + n_coarse] | zeros];  point_concat_bwd: g_h (n, Ch) = g_in (n, cin_p)[:, :Ch].
+ * point_target: target (N * rows, P) = point_sample at (X, Y) of masks (N,G,H,W) u8 [i, gt_assign[i * n_sample + j]] read as 1.0 / 0.0; -1
+ *   for a row that is not live (mrcnn_maskiou_target's rule: j < n_pos[i], label > 0, assignment in [0, min(G, n_gt[i]))).
+ * point_bce: over the points with target >= 0 of rows with a channel, x = pred[(r * P + p) * ld + channel]: loss_out[0] = weight * sum(BCE
+ *   with logits(x, t)) / count, loss_out[1] = max(count, 1) (block partials + one finalising wave in double, as mrcnn_smooth_l1_f32); gx
+ *   (rows * P, ld), nullable: (sigmoid(x) - t) * (weight * (1 / loss_out[1])) in that column, 0 in every other element.  ws:
+ *   mrcnn_loss_workspace_bytes().
+ * point_subdivide: one workgroup per detection, S <= 56.  up (D, 2S, 2S)[y][x] = the channel label[d] (0 for a null label array) of grid
+ *   (D,S,S,ld) at the centre ((x + 0.5) / 2, (y + 0.5) / 2), the weights and order of point_sample with the tap indices CLAMPED to the grid.
+ *   The n_sel <= 4 S^2 cells of smallest |up|, ties to the lower flat index, in ASCENDING flat index: index (D, n_sel) int32, coords
+ *   (D, n_sel, 2) = ((x + 0.5) / 2S, (y + 0.5) / 2S).
+ * point_scatter: grid (D, cells)[d, index[d, j]] = pred (D * n_sel, ld)[d * n_sel + j, label[d]].
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_point_train_coords(const uint32_t *keys, int n_keys, const float *coarse, int S0, int Cp, int n_channels, const int32_t *label,
+                             int label_base, int rows, int P, int n_cand, int n_imp, float *coords, void *stream);
+int mrcnn_point_features_fwd(const float *coords, const float *rois_xy5, const float *map, int N, int H, int W, int C, float scale,
+                             const float *coarse, int S0, int Cp, int n_channels, int rows, int P, int cin_p, float *out, void *stream);
+int mrcnn_point_features_bwd(const float *g_in, int ld, const float *coords, const float *rois_xy5, int rows, int P, float scale, float *g_map,
+                             int N, int H, int W, int C, void *stream);
+int mrcnn_point_concat_fwd(const float *h, int Ch, const float *x0, int ld0, int c0, int n_coarse, long long n_points, int cin_p, float *out,
+                           void *stream);
+int mrcnn_point_concat_bwd(const float *g_in, int cin_p, int Ch, long long n_points, float *g_h, void *stream);
+int mrcnn_point_target(const uint8_t *masks, int N, int G, int H, int W, const int32_t *n_gt, const float *rois_xy5, const int32_t *gt_assign,
+                       const int32_t *label, const int32_t *n_pos, int n_sample, int rows, const float *coords, int P, float *target,
+                       void *stream);
+int mrcnn_point_bce(const float *pred, int ld, int n_channels, const float *target, const int32_t *label, int label_base, int rows, int P,
+                    float weight, float *loss_out, float *gx, void *ws, size_t ws_bytes, void *stream);
+int mrcnn_point_subdivide(const float *grid, int D, int S, int ld, int n_channels, const int32_t *label, int n_sel, float *up, int32_t *index,
+                          float *coords, void *stream);
+int mrcnn_point_scatter(const float *pred, int ld, int n_channels, const int32_t *label, const int32_t *index, int D, int n_sel, int cells,
+                        float *grid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,9 +22,10 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (NO_CASCADE, NO_MASK_IOU, add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags,  # noqa: E402,F401
+from chainer_maskrcnn.inference_options import (NO_CASCADE, NO_MASK_IOU, NO_POINT_REND, add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags,  # noqa: E402,F401
                                                 add_mask_iou_flags, add_tta_flags, boxpost_settings, cascade_flag_settings, fpn_norm_settings, head_norm_settings,
-                                                mask_iou_settings, read_labels, tta_settings, use_boxpost, use_tta)
+                                                mask_iou_settings, read_labels, tta_settings, use_boxpost, use_tta,
+                                                add_point_rend_flags, point_rend_flag_settings, point_rend_model_kwargs)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
@@ -131,6 +132,7 @@ def build_parser(keypoints=False):
     add_fpn_norm_flags(parser, both)
     add_cascade_flags(parser, both)
     add_mask_iou_flags(parser, both, weight=True)
+    add_point_rend_flags(parser, both, weight=True)
     parser.add_argument(*both('--box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
                         help='box regression loss of the RoI head: smooth_l1 = the reference\'s, on the encoded deltas; giou / diou / ciou = on '
                              'the decoded box against the decoded target (FPNMaskRCNNTrainChain box_loss; same targets, normaliser and '
@@ -200,6 +202,22 @@ def check_resume_mask_iou(resume, args, path='', keypoints=False):
     was, now = resume.get('mask_iou', NO_MASK_IOU), mask_iou_run_settings(args, keypoints)
     if was != now:
         raise ValueError('--resume %s: the checkpoint was trained with the Mask Scoring settings %r, this run asks for %r' % (path, was, now))
+
+
+def point_rend_run_settings(args, keypoints=False):
+    """The PointRend settings of a run as recorded in trainer_<it>.pt (NO_POINT_REND when off); raises on a combination MaskRCNN or the
+    training chain refuses - a keypoint run among them: a keypoint head has no binary mask to refine."""
+    if keypoints and args.point_rend:
+        raise ValueError('--point-rend refines binary masks: it is defined for mask heads, not for keypoint training (train_keypoints.py)')
+    return point_rend_flag_settings(args, args.head_arch, args.mask_iou, weight=True)
+
+
+def check_resume_point_rend(resume, args, path='', keypoints=False):
+    """A resumed run has the point head, point counts and loss weight of its checkpoint: the flat parameter and momentum buffers are laid
+    out by the head (a state without the key was trained without it)."""
+    was, now = resume.get('point_rend', NO_POINT_REND), point_rend_run_settings(args, keypoints)
+    if was != now:
+        raise ValueError('--resume %s: the checkpoint was trained with the PointRend settings %r, this run asks for %r' % (path, was, now))
 
 
 def freeze_settings(args):
@@ -338,6 +356,11 @@ def run(args, keypoints=False):
         check_resume_mask_iou(resume, args, args.resume, keypoints)
     if mask_iou['mask_iou'] and (args.eval_tta_sizes or args.eval_tta_hflip):
         raise ValueError('--mask-iou 1 does not go with --eval-tta-*: test-time augmentation of a Mask Scoring model is not supported')
+    point_rend = point_rend_run_settings(args, keypoints)
+    if resume is not None:
+        check_resume_point_rend(resume, args, args.resume, keypoints)
+    if point_rend['point_rend'] and (args.eval_tta_sizes or args.eval_tta_hflip):
+        raise ValueError('--point-rend 1 does not go with --eval-tta-*: test-time augmentation of a PointRend model is not supported')
     box_loss = box_loss_settings(args.box_loss, args.rpn_box_loss, args.box_loss_weight, args.rpn_box_loss_weight)
     freeze = freeze_settings(args)
     if resume is not None:
@@ -396,9 +419,10 @@ def run(args, keypoints=False):
         labels = read_labels(args.label_file)
         n_fg, K = len(labels) if labels else 80, None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, mask_iou=mask_iou['mask_iou'],
-                               **head_norm)
+                               **dict(head_norm, **point_rend_model_kwargs(point_rend)))
         model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic,
-                                      mask_iou_weight=mask_iou['mask_iou_weight'], **box_loss)
+                                      mask_iou_weight=mask_iou['mask_iou_weight'], point_loss_weight=point_rend['point_loss_weight'],
+                                      **box_loss)
     faster_rcnn.use_preset('evaluate')
     if args.resnet50_npz:           # ImageNet initialisation of the bottom-up pathway (before --weight, which may override it)
         from chainer_maskrcnn.utils import chainer_npz
@@ -423,6 +447,8 @@ def run(args, keypoints=False):
     keys = ('loss', 'rpn_loc_loss', 'rpn_cls_loss', 'roi_loc_loss', 'roi_cls_loss', 'mask_loss')
     if mask_iou['mask_iou']:
         keys += ('maskiou_loss',)
+    if point_rend['point_rend']:
+        keys += ('point_loss',)
     acc ={k: 0.0 for k in keys}
     loader = None
     if not args.synthetic:          # train.py:111-126: COCOMaskLoader(category_filter=labels, data_type='2017') + Transform
@@ -523,7 +549,7 @@ def run(args, keypoints=False):
                 save_npz(os.path.join(args.out, 'model_%d.npz' % it), faster_rcnn)      # snapshot_object, train.py:134-137
                 torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets,
                             'augment': augment_settings(args), 'freeze': freeze, 'optim': optim, 'cascade': cascade,
-                            'mask_iou': mask_iou},
+                            'mask_iou': mask_iou, 'point_rend': point_rend},
                            os.path.join(args.out, 'trainer_%d.pt' % it))
     if loader is not None:
         loader.close()
