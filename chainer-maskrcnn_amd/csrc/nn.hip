@@ -59,6 +59,10 @@ RedPlan red_plan(int P, int C) {
     r.nblk = (P + r.rows_per_blk - 1) / r.rows_per_blk;
     return r;
 }
+// The three reduction passes below walk the channel groups with `for (cg = cg0; cg < C4; cg += G)` around block barriers: every thread of
+// a block must run the same number of trips, so past G = 256 groups C / 4 has to be a multiple of 256 (C = 1024, 2048, ...).  No layer of
+// the models has another count; the entry points refuse it (MRCNN_E_INVALID) before anything is launched.
+bool red_channels_ok(int C) { const int C4 = C / 4; return C4 <= NT || C4 % NT == 0; }
 
 // BN forward statistics: per block, per channel: sum(x - K), sum((x - K)^2) with K = x[0][c]
 // (shifted sums: no catastrophic cancellation when |mean| >> std).
@@ -185,8 +189,13 @@ __global__ __launch_bounds__(FIN_THREADS) void k_bn_stats_final(const float *__r
     // Un-shifted float32 partials lose var's digits to cancellation once mean^2 >> var (relative error ~1e-7 mean^2 / var:
     // 9e-6 at |mean|/std = 34, measured) - e.g. a pretrained backbone's first BatchNorms.  Past |mean|/std = 32 the block
     // recomputes its FIN_CH channels exactly: sums of (x - mean) and (x - mean)^2 over all P rows in double (a second pass
-    // over x for these channels only; never taken on the step's own activations).
-    if (slice == 0 && c < C && !shifted && var < ms * ms * (1.0 / 1024.0)) atomicOr(&sredo, 1);
+    // over x for these channels only; never taken on the step's own activations).  The shifted partials cancel in the same
+    // way once the shift K = x[0][c] lies far from the channel's mean (a nearly constant channel whose corner pixel differs):
+    // there ms is the mean of x - K.  Their float32 sums are worse than the epilogue's at the same ratio where one block adds
+    // the sums of many row lanes in float32 (RPI = 51 at C = 20: 1 / sigma off by 1.4e-5 at |ms|/std = 10, 9.6e-5 at 22,
+    // measured; 1.8e-5 at 30 for (8192, 64)), so the shifted sums take the exact pass past |ms|/std = 8.
+    const double redo_below = shifted ? 1.0 / 64.0 : 1.0 / 1024.0;
+    if (slice == 0 && c < C && var < ms * ms * redo_below) atomicOr(&sredo, 1);
     if (slice == 0) smean[cl] = m;
     __syncthreads();
     if (sredo) {            // block-uniform
@@ -991,6 +1000,7 @@ extern "C" int mrcnn_bn_train_fwd_f32(const float *x, const float *gamma, const 
                                       size_t ws_bytes, void *stream) {
     if (int e = chk(x && gamma && beta && y && save_mean && save_invstd && ws, "bn_train_fwd: null pointer")) return e;
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0, "bn_train_fwd: need P>0, C%4==0")) return e;
+    if (int e = chk(red_channels_ok(C), "bn_train_fwd: C / 4 above 256 must be a multiple of 256 (the reduction passes' channel loop)")) return e;
     if (ws_bytes < mrcnn_bn_workspace_bytes(P, C)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (int e = launch_bn_stats(st, x, nullptr, 0, P, C, eps, decay, ws, save_mean, save_invstd, running_mean, running_var)) return e;
@@ -1026,6 +1036,7 @@ extern "C" int mrcnn_bn_train_bwd_f32(const float *gy, const float *x, const flo
     if (int e = chk(!relu || y || beta, "bn_train_bwd: relu needs y, or beta to recompute the mask")) return e;
     const int rmode = !relu ? 0 : (y ? 1 : 2);
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0, "bn_train_bwd: need P>0, C%4==0")) return e;
+    if (int e = chk(red_channels_ok(C), "bn_train_bwd: C / 4 above 256 must be a multiple of 256 (the reduction passes' channel loop)")) return e;
     if (ws_bytes < mrcnn_bn_workspace_bytes(P, C)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const RedPlan r = red_plan(P, C);
@@ -1048,6 +1059,7 @@ extern "C" int mrcnn_bn_train_stats_f32(const float *x, const float *part, int r
                                         float *running_var, int P, int C, float eps, float decay, void *ws, size_t ws_bytes, void *stream) {
     if (int e = chk(x && save_mean && save_invstd, "bn_train_stats: null pointer")) return e;
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0 && rows >= 0 && (rows == 0) == (part == nullptr), "bn_train_stats: need P>0, C%4==0, part / rows together")) return e;
+    if (int e = chk(part || red_channels_ok(C), "bn_train_stats: C / 4 above 256 must be a multiple of 256 (the statistics pass' channel loop)")) return e;
     if (!part && (!ws || ws_bytes < mrcnn_bn_workspace_bytes(P, C))) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_stats: workspace too small");
     return launch_bn_stats((hipStream_t)stream, x, part, rows, P, C, eps, decay, ws, save_mean, save_invstd, running_mean, running_var);
 }
@@ -1068,6 +1080,7 @@ extern "C" int mrcnn_bn_train_fwd_pair_f32(const float *xa, const float *part_a,
     if (int e = chk(xa && gamma_a && beta_a && mean_a && invstd_a && xb && gamma_b && beta_b && mean_b && invstd_b && y, "bn_train_fwd_pair: null pointer")) return e;
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0 && rows_a >= 0 && rows_b >= 0, "bn_train_fwd_pair: need P>0, C%4==0, rows>=0")) return e;
     if (int e = chk((rows_a == 0) == (part_a == nullptr) && (rows_b == 0) == (part_b == nullptr), "bn_train_fwd_pair: part / rows must come together")) return e;
+    if (int e = chk((part_a && part_b) || red_channels_ok(C), "bn_train_fwd_pair: C / 4 above 256 must be a multiple of 256 (the statistics pass' channel loop)")) return e;
     if ((!part_a || !part_b) && (!ws || ws_bytes < mrcnn_bn_workspace_bytes(P, C)))
         return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_fwd_pair: a statistics pass needs mrcnn_bn_workspace_bytes() of workspace");
     hipStream_t st = (hipStream_t)stream;
@@ -1088,6 +1101,7 @@ extern "C" int mrcnn_bn_train_bwd_pair_f32(const float *gy, const float *y, cons
     if (int e = chk(gy && xa && xb && gamma_a && mean_a && invstd_a && gamma_b && mean_b && invstd_b && gxa && gxb && ggamma_a && gbeta_a && ggamma_b &&
                         gbeta_b && ws, "bn_train_bwd_pair: null pointer")) return e;
     if (int e = chk(P > 0 && C > 0 && (C % 4) == 0, "bn_train_bwd_pair: need P>0, C%4==0")) return e;
+    if (int e = chk(red_channels_ok(C), "bn_train_bwd_pair: C / 4 above 256 must be a multiple of 256 (the reduction passes' channel loop)")) return e;
     if (ws_bytes < mrcnn_bn_pair_workspace_bytes(P, C)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "bn_train_bwd_pair: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const RedPlan r = red_plan(P, C);

@@ -336,7 +336,10 @@ int mrcnn_conv2d_bwd_filter_f32(const float *x, const float *gy, float *gw, floa
 size_t mrcnn_bn_workspace_bytes(int P, int C);
 /* Training-mode BN: batch statistics over P, y = gamma*(x-mean)*invstd + beta (+ residual) (ReLU if
  * relu != 0); save_mean / save_invstd (C) are kept for backward; running_* (nullable) are updated with
- * Chainer's rule (decay, unbiased variance). */
+ * Chainer's rule (decay, unbiased variance).
+ * Channel counts: C % 4 == 0, and C / 4 either at most 256 or a multiple of 256 (C = 1024, 2048, ...): the reduction passes of
+ * mrcnn_bn_train_fwd_f32, _bwd_f32, _stats_f32 / _fwd_pair_f32 without partial rows and _bwd_pair_f32 walk the channel groups 256 at a
+ * time around workgroup barriers; every other count is MRCNN_E_INVALID before any launch (the forms fed by partial rows take it). */
 int mrcnn_bn_train_fwd_f32(const float *x, const float *gamma, const float *beta, const float *residual,
                            float *y, float *save_mean, float *save_invstd, float *running_mean,
                            float *running_var, int P, int C, float eps, float decay, int relu, void *ws,

@@ -127,6 +127,24 @@ int main() {
         EXPECT_ERR(mrcnn_bn_train_bwd_pair_f32(b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, 64, 32, b2, 16, V));
         EXPECT_ERR(mrcnn_bn_train_bwd_pair_f32(b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, b2, 64, 30, b2, sizeof(b2), V));
     }
+    {   // C / 4 above 256 and no multiple of 256: the reduction passes' channel loop cannot take it; refused with buffers and a workspace that
+        // would do, by the five entry points that run such a pass (the forms fed by partial rows for both layers never run one)
+        static float b3[8 * 2048];
+        for (int C : {1028, 1536, 2044}) {
+            EXPECT(sizeof(b3) >= mrcnn_bn_pair_workspace_bytes(2, C) && mrcnn_bn_pair_workspace_bytes(2, C) > 0);
+            EXPECT_ERR(mrcnn_bn_train_fwd_f32(b3, b3, b3, nullptr, b3, b3, b3, nullptr, nullptr, 2, C, 2e-5f, 0.9f, 1, b3, sizeof(b3), V));
+            EXPECT(std::strstr(mrcnn_last_error(), "multiple of 256") != nullptr);
+            EXPECT_ERR(mrcnn_bn_train_bwd_f32(b3, b3, b3, b3, b3, b3, b3, b3, nullptr, b3, b3, 2, C, 1, b3, sizeof(b3), V));
+            EXPECT(std::strstr(mrcnn_last_error(), "multiple of 256") != nullptr);
+            EXPECT_ERR(mrcnn_bn_train_stats_f32(b3, nullptr, 0, b3, b3, nullptr, nullptr, 2, C, 2e-5f, 0.9f, b3, sizeof(b3), V));
+            EXPECT(std::strstr(mrcnn_last_error(), "multiple of 256") != nullptr);
+            EXPECT_ERR(mrcnn_bn_train_fwd_pair_f32(b3, nullptr, 0, b3, b3, b3, b3, nullptr, nullptr, b3, b3, 1, b3, b3, b3, b3, nullptr, nullptr, b3, 2, C, 2e-5f,
+                                                   0.9f, b3, sizeof(b3), V));
+            EXPECT(std::strstr(mrcnn_last_error(), "multiple of 256") != nullptr);
+            EXPECT_ERR(mrcnn_bn_train_bwd_pair_f32(b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, b3, 2, C, b3, sizeof(b3), V));
+            EXPECT(std::strstr(mrcnn_last_error(), "multiple of 256") != nullptr);
+        }
+    }
     EXPECT_ERR(mrcnn_relu_bwd_f32(CF, CF, F, 64, V));
     EXPECT_ERR(mrcnn_relu_fwd_f32(CF, F, 64, V));
     EXPECT_ERR(mrcnn_add_f32(CF, CF, F, 64, V));
