@@ -1,6 +1,8 @@
 """The inference options of the entry scripts, stated once: the test-time augmentation and box post-processing flags of evaluate.py and
-demo.py (train.py declares them with the prefix '--eval-' for its periodic evaluator), what they turn into on a model, the label file and
-the model a checkpoint is scored or drawn with.  Importing this module needs neither a device nor the training script."""
+demo.py (train.py declares them with the prefix '--eval-' for its periodic evaluator), what they turn into on a model, the table of the
+optional model extensions that all four scripts walk (EXTENSIONS), the label file and the model a checkpoint is scored or drawn with.
+Importing this module needs neither a device nor the training script."""
+import collections
 import os
 
 DEFAULT_SOFT_NMS_SIGMA = 0.5        # --soft-nms-sigma when not given (Detectron's TEST.SOFT_NMS.SIGMA)
@@ -179,16 +181,6 @@ def cascade_flag_settings(cascade, ious, stds, head_arch, backbone='fpn'):
     return {'cascade_ious': got[0], 'cascade_stds': got[1]}
 
 
-def check_cascade_flags(args, tta_prefix='--'):
-    """The cascade flags of an inference script (evaluate.py, demo.py) checked before the model is built: cascade_flag_settings' refusals, and
-    no test-time augmentation on top of a cascade (MaskRCNN.use_test_augmentation refuses it)."""
-    settings = cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone)
-    if settings['cascade_ious'] and (args.tta_sizes or args.tta_hflip):
-        raise ValueError('--cascade 1 does not go with %stta-sizes / %stta-hflip: test-time augmentation of a cascade model is not supported'
-                         % (tta_prefix, tta_prefix))
-    return settings
-
-
 # ---- Mask Scoring R-CNN (MaskRCNN mask_iou, FPNMaskRCNNTrainChain mask_iou_weight; DESIGN.md §3.22) ----------------------------------------
 NO_MASK_IOU = {'mask_iou': False, 'mask_iou_weight': 1.0}       # what a trainer state without the 'mask_iou' key was trained with
 
@@ -221,16 +213,6 @@ def mask_iou_settings(mask_iou, weight=None, head_arch='fpn'):
     except ValueError as e:
         raise ValueError('--mask-iou 1: %s' % e)
     return {'mask_iou': on, 'mask_iou_weight': w}
-
-
-def check_mask_iou_flags(args, tta_prefix='--'):
-    """--mask-iou of an inference script (evaluate.py, demo.py) checked before the model is built: mask_iou_settings' refusals, and no
-    test-time augmentation on top of it (MaskRCNN.use_test_augmentation refuses it)."""
-    settings = mask_iou_settings(args.mask_iou, None, args.head_arch)
-    if settings['mask_iou'] and (args.tta_sizes or args.tta_hflip):
-        raise ValueError('--mask-iou 1 does not go with %stta-sizes / %stta-hflip: test-time augmentation of a Mask Scoring model is not '
-                         'supported' % (tta_prefix, tta_prefix))
-    return settings
 
 
 # ---- PointRend (MaskRCNN point_rend ..., FPNMaskRCNNTrainChain point_loss_weight; DESIGN.md §3.24) ------------------------------------------
@@ -294,14 +276,97 @@ def point_rend_model_kwargs(settings):
     return dict({'point_rend': True}, **{k: settings[k] for k in POINT_SHAPE_DEFAULTS})
 
 
-def check_point_rend_flags(args, tta_prefix='--'):
-    """--point-rend of an inference script (evaluate.py, demo.py) checked before the model is built: point_rend_flag_settings' refusals,
-    and no test-time augmentation on top of it (MaskRCNN.use_test_augmentation refuses it)."""
-    settings = point_rend_flag_settings(args, args.head_arch, getattr(args, 'mask_iou', 0))
-    if settings['point_rend'] and (args.tta_sizes or args.tta_hflip):
-        raise ValueError('--point-rend 1 does not go with %stta-sizes / %stta-hflip: test-time augmentation of a PointRend model is not '
-                         'supported' % (tta_prefix, tta_prefix))
-    return settings
+# ---- the optional model extensions, declared once for train.py, train_keypoints.py, evaluate.py and demo.py --------------------------------
+# One record per extension, holding what the scripts' glue differs in:
+#   add_flags(parser, both[, weight]) declares its flags; weight_flag names the one that only the training scripts take
+#   settings(args, training) is its settings dict from parsed flags (ValueError for what the model refuses), is_on(settings) tells whether it is on
+#   off is that dict with the flags off, state_key its key in trainer_<it>.pt (a state without the key was trained with ``off``)
+#   the two norms have neither: trainer_<it>.pt has never recorded them, and that is kept
+#   switch turns it on; with model_noun and settings_noun it words the refusals; refuses_tta: MaskRCNN.use_test_augmentation refuses it
+#   mask_heads_only: (asked(args), the sentence keypoint training refuses it with)
+#   model_kwargs(settings) are the MaskRCNN arguments it contributes, chain_keys the settings FPNMaskRCNNTrainChain takes, loss_key what it logs
+Extension = collections.namedtuple('Extension', 'name add_flags settings is_on weight_flag off state_key switch model_noun settings_noun refuses_tta '
+                                                'mask_heads_only model_kwargs chain_keys loss_key',
+                                   defaults=(None, None, None, None, None, None, False, None, dict, (), None))
+
+
+def _cascade_settings_of(args, training):
+    s = cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone)
+    if training:        # trainer_<it>.pt records lists
+        s = {k: None if v is None else [list(x) if isinstance(x, tuple) else x for x in v] for k, v in s.items()}
+    return s
+
+
+EXTENSIONS = (
+    Extension('head_norm', add_head_norm_flags, lambda a, training: head_norm_settings(a.head_norm, a.gn_groups, a.head_arch),
+              is_on=lambda s: s['head_norm'] is not None, switch='--head-norm gn'),
+    Extension('fpn_norm', add_fpn_norm_flags, lambda a, training: fpn_norm_settings(a.fpn_norm, a.gn_groups, a.backbone),
+              is_on=lambda s: s['fpn_norm'] is not None, switch='--fpn-norm gn'),
+    Extension('cascade', add_cascade_flags, _cascade_settings_of, is_on=lambda s: bool(s['cascade_ious']), off=NO_CASCADE, state_key='cascade',
+              switch='--cascade 1', model_noun='a cascade model', settings_noun='the cascade', refuses_tta=True),
+    Extension('mask_iou', add_mask_iou_flags, lambda a, training: mask_iou_settings(a.mask_iou, a.mask_iou_weight if training else None, a.head_arch),
+              is_on=lambda s: s['mask_iou'], weight_flag='--mask-iou-weight', off=NO_MASK_IOU, state_key='mask_iou',
+              switch='--mask-iou 1', model_noun='a Mask Scoring model', settings_noun='the Mask Scoring settings', refuses_tta=True,
+              mask_heads_only=(lambda a: a.mask_iou or a.mask_iou_weight is not None,
+                               '--mask-iou scores binary masks: it is defined for mask heads, not for keypoint training (train_keypoints.py)'),
+              model_kwargs=lambda s: {'mask_iou': s['mask_iou']}, chain_keys=('mask_iou_weight',), loss_key='maskiou_loss'),
+    Extension('point_rend', add_point_rend_flags, lambda a, training: point_rend_flag_settings(a, a.head_arch, a.mask_iou, weight=training),
+              is_on=lambda s: s['point_rend'], weight_flag='--point-loss-weight', off=NO_POINT_REND, state_key='point_rend',
+              switch='--point-rend 1', model_noun='a PointRend model', settings_noun='the PointRend settings', refuses_tta=True,
+              mask_heads_only=(lambda a: a.point_rend,
+                               '--point-rend refines binary masks: it is defined for mask heads, not for keypoint training (train_keypoints.py)'),
+              model_kwargs=point_rend_model_kwargs, chain_keys=('point_loss_weight',), loss_key='point_loss'))
+# how each script's refusal spells its test-time augmentation flags
+TTA_FLAGS = {'--tta-': '--tta-sizes / --tta-hflip', '--eval-tta-': '--eval-tta-*'}
+
+
+def add_extension_flags(parser, both=lambda name: (name,), training=False):
+    """The flags of every extension (train_keypoints.py takes both spellings through ``both``); the weight flags with ``training`` only."""
+    for e in EXTENSIONS:
+        e.add_flags(parser, both, **({'weight': training} if e.weight_flag else {}))
+
+
+def extension_settings(args, tta_prefix='--tta-', training=False, keypoints=False):
+    """{name: settings} of every extension from the parsed flags, checked before the model is built.  ValueError, extension by extension: for
+    keypoint training of a mask-heads-only one, for what its settings refuse, and for test-time augmentation (the flags ``tta_prefix``sizes /
+    hflip: '--tta-' in evaluate.py and demo.py, '--eval-tta-' in train.py) on top of one MaskRCNN.use_test_augmentation refuses."""
+    tta = tta_prefix.strip('-').replace('-', '_') + '_'
+    tta = getattr(args, tta + 'sizes') or getattr(args, tta + 'hflip')
+    out = {}
+    for e in EXTENSIONS:
+        if keypoints and e.mask_heads_only and e.mask_heads_only[0](args):
+            raise ValueError(e.mask_heads_only[1])
+        out[e.name] = e.settings(args, training)
+        if tta and e.refuses_tta and e.is_on(out[e.name]):
+            raise ValueError('%s does not go with %s: test-time augmentation of %s is not supported' % (e.switch, TTA_FLAGS[tta_prefix], e.model_noun))
+    return out
+
+
+def model_kwargs(settings, keypoints=False):
+    """The MaskRCNN keyword arguments of extension_settings' result (a keypoint model takes none from the mask-heads-only extensions)."""
+    out = {}
+    for e in EXTENSIONS:
+        if not (keypoints and e.mask_heads_only):
+            out.update(e.model_kwargs(settings[e.name]))
+    return out
+
+
+def chain_kwargs(settings):
+    """The FPNMaskRCNNTrainChain keyword arguments of extension_settings' result, for a mask model."""
+    return {k: settings[e.name][k] for e in EXTENSIONS for k in e.chain_keys}
+
+
+def state_records(settings):
+    """What trainer_<it>.pt records of extension_settings' result: {state key: settings}."""
+    return {e.state_key: settings[e.name] for e in EXTENSIONS if e.state_key}
+
+
+def check_resume(resume, key, off_record, now, noun, path=''):
+    """A resumed run has the settings its checkpoint recorded under ``key`` (a state without the key: ``off_record``): the flat parameter and
+    momentum buffers, the data order and the schedule follow from them."""
+    was = resume.get(key, off_record)
+    if was != now:
+        raise ValueError('--resume %s: the checkpoint was trained with %s %r, this run asks for %r' % (path, noun, was, now))
 
 
 # ---- labels and the model -----------------------------------------------------------------------------------------------------------------
@@ -327,18 +392,14 @@ def build_inference_model(args, preset=None):
     import torch
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     from chainer_maskrcnn.utils import chainer_npz
-    norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
-    norm.update(fpn_norm_settings(getattr(args, 'fpn_norm', 'none'), args.gn_groups, args.backbone))
-    norm.update(cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone))
-    norm['mask_iou'] = mask_iou_settings(getattr(args, 'mask_iou', 0), None, args.head_arch)['mask_iou']
-    norm.update(point_rend_model_kwargs(point_rend_flag_settings(args, args.head_arch, norm['mask_iou'])))
+    extensions = model_kwargs(extension_settings(args))
     dev =torch.device('cuda', args.gpu)
     torch.cuda.set_device(dev)
     if args.head_arch == 'fpn_keypoint':
-        model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev, **norm)
+        model = MaskRCNN(n_fg_class=1, n_keypoints=17, backbone=args.backbone, head_arch=args.head_arch, device=dev, **extensions)
     else:
         labels = read_labels(args.label_file)
-        model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev, **norm)
+        model = MaskRCNN(n_fg_class=len(labels) if labels else 80, backbone=args.backbone, head_arch=args.head_arch, device=dev, **extensions)
     if args.weight:
         if not os.path.exists(args.weight):
             raise FileNotFoundError('--weight %s does not exist' % args.weight)

@@ -25,8 +25,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags, add_mask_iou_flags, add_point_rend_flags, add_tta_flags, boxpost_settings,  # noqa: E402
-                                                build_inference_model, check_cascade_flags, check_mask_iou_flags, check_point_rend_flags, fpn_norm_settings, head_norm_settings, read_labels, tta_settings, use_boxpost, use_score_preset, use_tta)
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model,  # noqa: E402
+                                                extension_settings, read_labels, tta_settings, use_boxpost, use_score_preset, use_tta)
 
 IMAGE_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
 SYNTHETIC_FIRST_SEED = 2000003      # far from the seeds of the synthetic training pool and of the synthetic val split
@@ -54,11 +54,7 @@ def build_parser():
     parser.add_argument('--no-contours', action='store_true')
     parser.add_argument('--kp-thresh', type=float, default=None,
                         help='keypoint heads: the heat-map logit from which a keypoint is drawn (%s)' % DEFAULT_KP_THRESH)
-    add_head_norm_flags(parser)
-    add_fpn_norm_flags(parser)
-    add_cascade_flags(parser)
-    add_mask_iou_flags(parser)
-    add_point_rend_flags(parser)
+    add_extension_flags(parser)
     add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--json', type=int, default=0, choices=[0, 1], help='1: also write <stem>.json per image')
@@ -120,11 +116,7 @@ def check_args(args):
         raise ValueError('--tta-sizes: every size must be positive, got %s' % (args.tta_sizes,))
     tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, 1)      # a max size without views
     boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
-    head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
-    fpn_norm_settings(args.fpn_norm, args.gn_groups, args.backbone)
-    check_cascade_flags(args)
-    check_mask_iou_flags(args)
-    check_point_rend_flags(args)
+    extension_settings(args)
     return collect_inputs(args.inputs)
 
 

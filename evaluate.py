@@ -22,8 +22,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 sys.path.insert(0, ROOT)
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags, add_mask_iou_flags, add_point_rend_flags, add_tta_flags, boxpost_settings,  # noqa: E402
-                                                build_inference_model, check_cascade_flags, check_mask_iou_flags, check_point_rend_flags, fpn_norm_settings, head_norm_settings, read_labels, tta_settings, use_boxpost, use_tta)
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model,  # noqa: E402
+                                                extension_settings, read_labels, tta_settings, use_boxpost, use_tta)
 
 SYNTHETIC_VAL_IMAGES = 16           # train.py's synthetic val split of --eval-images 0
 
@@ -44,11 +44,7 @@ def build_parser():
     parser.add_argument('--image-size', type=int, nargs=2, default=[800, 800], help='--synthetic 1: image height and width')
     parser.add_argument('--score-thresh', type=float, default=None, help="overrides the 'evaluate' preset's score threshold (0.05)")
     parser.add_argument('--no-results', action='store_true', help='do not write the COCO results files')
-    add_head_norm_flags(parser)
-    add_fpn_norm_flags(parser)
-    add_cascade_flags(parser)
-    add_mask_iou_flags(parser)
-    add_point_rend_flags(parser)
+    add_extension_flags(parser)
     add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--out', '-o', default='result_eval', help='Output directory')
@@ -61,11 +57,7 @@ def check_args(args):
     world = int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
         raise ValueError('evaluate.py runs in a single process; with %d ranks it is not supported' % world)
-    head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
-    fpn_norm_settings(args.fpn_norm, args.gn_groups, args.backbone)
-    check_cascade_flags(args)
-    check_mask_iou_flags(args)
-    check_point_rend_flags(args)
+    extension_settings(args)
     return boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
 
 

@@ -261,18 +261,26 @@ def test_flags_refuse_the_cascade_on_the_legacy_heads(arch):
 
 def test_resume_with_another_cascade_is_refused(tmp_path):
     import train
+    from chainer_maskrcnn.inference_options import EXTENSIONS, check_resume, extension_settings
+    e = {x.name: x for x in EXTENSIONS}['cascade']
+
+    def run_settings(args):
+        return extension_settings(args, '--eval-tta-', training=True)['cascade']
+
+    def check(resume, args, path=''):
+        check_resume(resume, e.state_key, e.off, run_settings(args), e.settings_noun, path)
     p = train.build_parser()
     on, off = p.parse_args(['--cascade', '1']), p.parse_args([])
-    state = {'cascade': train.cascade_run_settings(on)}
+    state = {'cascade': run_settings(on)}
     assert state['cascade'] == {'cascade_ious': [0.5, 0.6, 0.7], 'cascade_stds': [list(s) for s in CASCADE_STDS]}
     ck = str(tmp_path / 'trainer_5.pt')
     torch.save(dict(state, iteration=5), ck)                              # what trainer_<it>.pt records survives the file
     state = torch.load(ck, map_location='cpu', weights_only=False)
-    train.check_resume_cascade(state, on, ck)
-    train.check_resume_cascade({}, off)                                     # a state from before the key existed: one stage
+    check(state, on, ck)
+    check({}, off)                                                    # a state from before the key existed: one stage
     for resume, args in ((state, off), ({}, on), (state, p.parse_args(['--cascade', '1', '--cascade-ious', '0.5', '0.6']))):
         with pytest.raises(ValueError, match='--resume .* cascade'):
-            train.check_resume_cascade(resume, args, ck)
+            check(resume, args, ck)
     old = str(tmp_path / 'trainer_old.pt')
     torch.save({'iteration': 3}, old)
     with pytest.raises(ValueError, match='--resume .* cascade'):          # through run(): refused before any device work

@@ -141,21 +141,25 @@ def test_freeze_flags(keypoints):
 def test_freeze_key_of_the_trainer_state(tmp_path):
     import torch
     import train
+    record = [c for c in train.RESUME_CHECKS if c[0] == 'freeze'][0]            # (key, the record of a state without it, its noun) as run() checks it
+
+    def check(resume, args, path=''):
+        train.check_resume(resume, record[0], record[1], train.freeze_settings(args), record[2], path)
     p = train.build_parser()
     frozen, plain = p.parse_args(['--freeze-bn', '1', '--freeze-at', '2']), p.parse_args([])
     path = str(tmp_path / 'trainer_1.pt')
     torch.save({'iteration': 1, 'freeze': train.freeze_settings(frozen)}, path)
     state = torch.load(path, map_location='cpu', weights_only=False)
     assert state['freeze'] == {'bn': 1, 'at': 2}
-    train.check_resume_freeze(state, frozen, path)                      # round trip: the same settings resume
+    check(state, frozen, path)                                    # round trip: the same settings resume
     with pytest.raises(ValueError, match='freezing'):
-        train.check_resume_freeze(state, plain, path)
+        check(state, plain, path)
     with pytest.raises(ValueError, match='freezing'):
-        train.check_resume_freeze(state, p.parse_args(['--freeze-bn', '1']), path)
+        check(state, p.parse_args(['--freeze-bn', '1']), path)
     old = {'iteration': 1}                                              # a state written before the key existed: nothing was frozen
-    train.check_resume_freeze(old, plain)
+    check(old, plain)
     with pytest.raises(ValueError, match='freezing'):
-        train.check_resume_freeze(old, frozen)
+        check(old, frozen)
 
 
 def test_run_refuses_a_frozen_prefix_without_frozen_batchnorm(tmp_path):

@@ -274,17 +274,25 @@ def test_scripts_refuse_what_the_model_refuses():
 def test_resume_with_another_setting_is_refused(tmp_path):
     import train
     p = train.build_parser()
+    from chainer_maskrcnn.inference_options import EXTENSIONS, check_resume, extension_settings
+    e = {x.name: x for x in EXTENSIONS}['mask_iou']
+
+    def run_settings(args):
+        return extension_settings(args, '--eval-tta-', training=True)['mask_iou']
+
+    def check(resume, args, path=''):
+        check_resume(resume, e.state_key, e.off, run_settings(args), e.settings_noun, path)
     on, off, half = p.parse_args(['--mask-iou', '1']), p.parse_args([]), p.parse_args(['--mask-iou', '1', '--mask-iou-weight', '0.5'])
-    state = {'mask_iou': train.mask_iou_run_settings(on)}
+    state = {'mask_iou': run_settings(on)}
     assert state['mask_iou'] == {'mask_iou': True, 'mask_iou_weight': 1.0}
     ck = str(tmp_path / 'trainer_5.pt')
     torch.save(dict(state, iteration=5), ck)
     state = torch.load(ck, map_location='cpu', weights_only=False)
-    train.check_resume_mask_iou(state, on, ck)
-    train.check_resume_mask_iou({}, off)                    # a state from before the key existed: no MaskIoU head
+    check(state, on, ck)
+    check({}, off)                                    # a state from before the key existed: no MaskIoU head
     for resume, args in ((state, off), ({}, on), (state, half)):
         with pytest.raises(ValueError, match='--resume .* Mask Scoring'):
-            train.check_resume_mask_iou(resume, args, ck)
+            check(resume, args, ck)
     old = str(tmp_path / 'trainer_old.pt')
     torch.save({'iteration': 3}, old)
     with pytest.raises(ValueError, match='--resume .* Mask Scoring'):          # through run(): refused before any device work

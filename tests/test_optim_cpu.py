@@ -74,14 +74,18 @@ def test_warmup_in_front_of_lr_shift_interval_keeps_the_periodic_drops():
 
 
 def test_resume_with_another_recipe_is_refused():
+    record = [c for c in train.RESUME_CHECKS if c[0] == 'optim'][0]             # (key, the record of a state without it, its noun) as run() checks it
+
+    def check(resume, args, path=''):
+        train.check_resume(resume, record[0], record[1], train.optim_settings(args)[0], record[2], path)
     p = train.build_parser()
     a = p.parse_args('--accum-steps 2'.split())
-    train.check_resume_optim({'optim': train.optim_settings(a)[0]}, a)
-    train.check_resume_optim({}, p.parse_args([]))                  # a state from before the key existed: all off
+    check({'optim': train.optim_settings(a)[0]}, a)
+    check({}, p.parse_args([]))                               # a state from before the key existed: all off
     with pytest.raises(ValueError, match='optimizer recipe'):
-        train.check_resume_optim({}, a)
+        check({}, a)
     with pytest.raises(ValueError, match='optimizer recipe'):
-        train.check_resume_optim({'optim': train.optim_settings(a)[0]}, p.parse_args('--accum-steps 2 --grad-clip 5'.split()))
+        check({'optim': train.optim_settings(a)[0]}, p.parse_args('--accum-steps 2 --grad-clip 5'.split()))
 
 
 def test_hooks():

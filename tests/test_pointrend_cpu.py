@@ -259,16 +259,24 @@ def test_resume_with_another_setting_is_refused(tmp_path):
     p = train.build_parser()
     on, off = p.parse_args(['--point-rend', '1']), p.parse_args([])
     fewer, half = p.parse_args(['--point-rend', '1', '--point-train-points', '98']), p.parse_args(['--point-rend', '1', '--point-loss-weight', '0.5'])
-    state = {'point_rend': train.point_rend_run_settings(on)}
+    from chainer_maskrcnn.inference_options import EXTENSIONS, check_resume, extension_settings
+    e = {x.name: x for x in EXTENSIONS}['point_rend']
+
+    def run_settings(args):
+        return extension_settings(args, '--eval-tta-', training=True)['point_rend']
+
+    def check(resume, args, path=''):
+        check_resume(resume, e.state_key, e.off, run_settings(args), e.settings_noun, path)
+    state = {'point_rend': run_settings(on)}
     assert state['point_rend']['point_rend'] is True and state['point_rend']['point_train_points'] == 196
     ck = str(tmp_path / 'trainer_5.pt')
     torch.save(dict(state, iteration=5), ck)
     state = torch.load(ck, map_location='cpu', weights_only=False)
-    train.check_resume_point_rend(state, on, ck)
-    train.check_resume_point_rend({}, off)                  # a state from before the key existed: no point head
+    check(state, on, ck)
+    check({}, off)                                    # a state from before the key existed: no point head
     for resume, args in ((state, off), ({}, on), (state, fewer), (state, half)):
         with pytest.raises(ValueError, match='--resume .* PointRend'):
-            train.check_resume_point_rend(resume, args, ck)
+            check(resume, args, ck)
     old = str(tmp_path / 'trainer_old.pt')
     torch.save({'iteration': 3}, old)
     with pytest.raises(ValueError, match='--resume .* PointRend'):          # through run(): refused before any device work

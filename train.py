@@ -22,10 +22,9 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (NO_CASCADE, NO_MASK_IOU, NO_POINT_REND, add_boxpost_flags, add_cascade_flags, add_fpn_norm_flags, add_head_norm_flags,  # noqa: E402,F401
-                                                add_mask_iou_flags, add_tta_flags, boxpost_settings, cascade_flag_settings, fpn_norm_settings, head_norm_settings,
-                                                mask_iou_settings, read_labels, tta_settings, use_boxpost, use_tta,
-                                                add_point_rend_flags, point_rend_flag_settings, point_rend_model_kwargs)
+from chainer_maskrcnn.inference_options import (EXTENSIONS, add_boxpost_flags, add_extension_flags, add_tta_flags, boxpost_settings, chain_kwargs,  # noqa: E402
+                                                check_resume, extension_settings, model_kwargs, read_labels, state_records, tta_settings, use_boxpost,
+                                                use_tta)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
 
 SYNTHETIC_VAL_IMAGES = 16           # the synthetic "val split" of --synthetic 1 --eval-images 0
@@ -33,6 +32,9 @@ AUGMENT_SEED = 5678                 # seed of the per-example augmentation decis
 NO_FREEZE = {'bn': 0, 'at': 0}       # what a trainer state without the 'freeze' key was trained with
 NO_OPTIM = {'accum_steps': 1, 'grad_clip': 0.0, 'schedule': None}      # what a trainer state without the 'optim' key was trained with
 NO_AUGMENT = {'hflip': 0, 'min_sizes': None, 'seed': AUGMENT_SEED}     # what a trainer state without the 'augment' key was trained with
+# what a resumed run must repeat of its trainer_<it>.pt, in the order it is checked: (key, a state without the key, the noun of the refusal)
+RESUME_CHECKS = ((('augment', NO_AUGMENT, 'augmentation'),) + tuple((e.state_key, e.off, e.settings_noun) for e in EXTENSIONS if e.state_key)
+                 + (('freeze', NO_FREEZE, 'freezing'), ('optim', NO_OPTIM, 'the optimizer recipe')))
 
 
 def build_parser(keypoints=False):
@@ -128,11 +130,7 @@ def build_parser(keypoints=False):
                         help='Simple Copy-Paste on top of --lsj-size: with probability P an example receives a random half of the instances '
                              'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
                              'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
-    add_head_norm_flags(parser, both)
-    add_fpn_norm_flags(parser, both)
-    add_cascade_flags(parser, both)
-    add_mask_iou_flags(parser, both, weight=True)
-    add_point_rend_flags(parser, both, weight=True)
+    add_extension_flags(parser, both, training=True)
     parser.add_argument(*both('--box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
                         help='box regression loss of the RoI head: smooth_l1 = the reference\'s, on the encoded deltas; giou / diou / ciou = on '
                              'the decoded box against the decoded target (FPNMaskRCNNTrainChain box_loss; same targets, normaliser and '
@@ -167,59 +165,6 @@ def optim_settings(args):
     return {'accum_steps': k, 'grad_clip': clip, 'schedule': None if schedule is None else schedule.describe()}, schedule
 
 
-def check_resume_optim(resume, args, path=''):
-    """A resumed run accumulates, clips and schedules as its checkpoint did (a state without the key: all off)."""
-    was, now = resume.get('optim', NO_OPTIM), optim_settings(args)[0]
-    if was != now:
-        raise ValueError('--resume %s: the checkpoint was trained with the optimizer recipe %r, this run asks for %r' % (path, was, now))
-
-
-def cascade_run_settings(args):
-    """The Cascade R-CNN box stages of a run as recorded in trainer_<it>.pt (NO_CASCADE when off); raises on a combination MaskRCNN refuses."""
-    s = cascade_flag_settings(args.cascade, args.cascade_ious, args.cascade_stds, args.head_arch, args.backbone)
-    return {k: None if v is None else [list(x) if isinstance(x, tuple) else x for x in v] for k, v in s.items()}
-
-
-def check_resume_cascade(resume, args, path=''):
-    """A resumed run has the box stages of its checkpoint: the flat parameter and momentum buffers are laid out by them (a state without the
-    key was trained with one stage)."""
-    was, now = resume.get('cascade', NO_CASCADE), cascade_run_settings(args)
-    if was != now:
-        raise ValueError('--resume %s: the checkpoint was trained with the cascade %r, this run asks for %r' % (path, was, now))
-
-
-def mask_iou_run_settings(args, keypoints=False):
-    """The Mask Scoring settings of a run as recorded in trainer_<it>.pt (NO_MASK_IOU when off); raises on a combination MaskRCNN or the
-    training chain refuses - a keypoint run among them: a keypoint head has no binary mask to score."""
-    if keypoints and (args.mask_iou or args.mask_iou_weight is not None):
-        raise ValueError('--mask-iou scores binary masks: it is defined for mask heads, not for keypoint training (train_keypoints.py)')
-    return mask_iou_settings(args.mask_iou, args.mask_iou_weight, args.head_arch)
-
-
-def check_resume_mask_iou(resume, args, path='', keypoints=False):
-    """A resumed run has the MaskIoU head and loss weight of its checkpoint: the flat parameter and momentum buffers are laid out by the
-    head (a state without the key was trained without it)."""
-    was, now = resume.get('mask_iou', NO_MASK_IOU), mask_iou_run_settings(args, keypoints)
-    if was != now:
-        raise ValueError('--resume %s: the checkpoint was trained with the Mask Scoring settings %r, this run asks for %r' % (path, was, now))
-
-
-def point_rend_run_settings(args, keypoints=False):
-    """The PointRend settings of a run as recorded in trainer_<it>.pt (NO_POINT_REND when off); raises on a combination MaskRCNN or the
-    training chain refuses - a keypoint run among them: a keypoint head has no binary mask to refine."""
-    if keypoints and args.point_rend:
-        raise ValueError('--point-rend refines binary masks: it is defined for mask heads, not for keypoint training (train_keypoints.py)')
-    return point_rend_flag_settings(args, args.head_arch, args.mask_iou, weight=True)
-
-
-def check_resume_point_rend(resume, args, path='', keypoints=False):
-    """A resumed run has the point head, point counts and loss weight of its checkpoint: the flat parameter and momentum buffers are laid
-    out by the head (a state without the key was trained without it)."""
-    was, now = resume.get('point_rend', NO_POINT_REND), point_rend_run_settings(args, keypoints)
-    if was != now:
-        raise ValueError('--resume %s: the checkpoint was trained with the PointRend settings %r, this run asks for %r' % (path, was, now))
-
-
 def freeze_settings(args):
     """The freezing of a run as recorded in trainer_<it>.pt (NO_FREEZE when off); raises on a combination MaskRCNN.freeze refuses."""
     bn, at = int(args.freeze_bn), int(args.freeze_at)
@@ -230,13 +175,6 @@ def freeze_settings(args):
     if at > 0 and not bn:
         raise ValueError('--freeze-at %d needs --freeze-bn 1 (a frozen prefix with batch-statistics BatchNorm is not implemented)' % at)
     return {'bn': bn, 'at': at}
-
-
-def check_resume_freeze(resume, args, path=''):
-    """A resumed run freezes what its checkpoint froze (a state without the key was trained with everything trainable)."""
-    was, now = resume.get('freeze', NO_FREEZE), freeze_settings(args)
-    if was != now:
-        raise ValueError('--resume %s: the checkpoint was trained with freezing %r, this run asks for %r' % (path, was, now))
 
 
 def augment_settings(args):
@@ -340,34 +278,14 @@ def run(args, keypoints=False):
     _check_augment_args(args, keypoints)
     eval_boxpost = _eval_boxpost_settings(args)
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
-    if resume is not None and resume.get('augment', NO_AUGMENT) != augment_settings(args):
-        raise ValueError('--resume %s: the checkpoint was trained with augmentation %r, this run asks for %r'
-                         % (args.resume, resume.get('augment', NO_AUGMENT), augment_settings(args)))
-    head_norm = head_norm_settings(args.head_norm, args.gn_groups, args.head_arch)
-    head_norm.update(fpn_norm_settings(args.fpn_norm, args.gn_groups, args.backbone))
-    cascade = cascade_run_settings(args)
-    if resume is not None:
-        check_resume_cascade(resume, args, args.resume)
-    if cascade['cascade_ious'] and (args.eval_tta_sizes or args.eval_tta_hflip):
-        raise ValueError('--cascade 1 does not go with --eval-tta-*: test-time augmentation of a cascade model is not supported')
-    head_norm = dict(head_norm, **cascade)
-    mask_iou = mask_iou_run_settings(args, keypoints)
-    if resume is not None:
-        check_resume_mask_iou(resume, args, args.resume, keypoints)
-    if mask_iou['mask_iou'] and (args.eval_tta_sizes or args.eval_tta_hflip):
-        raise ValueError('--mask-iou 1 does not go with --eval-tta-*: test-time augmentation of a Mask Scoring model is not supported')
-    point_rend = point_rend_run_settings(args, keypoints)
-    if resume is not None:
-        check_resume_point_rend(resume, args, args.resume, keypoints)
-    if point_rend['point_rend'] and (args.eval_tta_sizes or args.eval_tta_hflip):
-        raise ValueError('--point-rend 1 does not go with --eval-tta-*: test-time augmentation of a PointRend model is not supported')
+    extensions = extension_settings(args, '--eval-tta-', training=True, keypoints=keypoints)
     box_loss = box_loss_settings(args.box_loss, args.rpn_box_loss, args.box_loss_weight, args.rpn_box_loss_weight)
     freeze = freeze_settings(args)
-    if resume is not None:
-        check_resume_freeze(resume, args, args.resume)
     optim, schedule = optim_settings(args)
+    recorded = dict({'augment': augment_settings(args), 'freeze': freeze, 'optim': optim}, **state_records(extensions))     # of trainer_<it>.pt
     if resume is not None:
-        check_resume_optim(resume, args, args.resume)
+        for key, off_record, noun in RESUME_CHECKS:
+            check_resume(resume, key, off_record, recorded[key], noun, args.resume)
     accum = optim['accum_steps']
     if freeze['bn'] and not (args.weight or args.resnet50_npz or args.resume) and rank == 0:
         print('warning: --freeze-bn 1 without --weight / --resnet50-npz / --resume freezes freshly initialised BatchNorm statistics '
@@ -409,7 +327,7 @@ def run(args, keypoints=False):
         n_fg, K = 1, 20 if args.dataset == 'depth' else 17          # DepthDataset.n_keypoints / COCOKeypointsLoader.n_keypoints
         labels = None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, n_keypoints=K, backbone=args.backbone, head_arch=args.head_arch, n_mask_convs=args.n_mask_convs,
-                               min_size=args.min_size, max_size=args.max_size, device=dev, **head_norm)
+                               min_size=args.min_size, max_size=args.max_size, device=dev, **model_kwargs(extensions, keypoints=True))
         loss_fun = calc_keypoint_loss
         if K != 17:         # train_keypoints.py:122: lambda x, y, z, w: calc_mask_loss(x, y, z, w, num_keypoints=n_keypoints)
             loss_fun = lambda x, y, z, w: calc_keypoint_loss(x, y, z, w, num_keypoints=K)
@@ -418,10 +336,8 @@ def run(args, keypoints=False):
     else:
         labels = read_labels(args.label_file)
         n_fg, K = len(labels) if labels else 80, None
-        faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, mask_iou=mask_iou['mask_iou'],
-                               **dict(head_norm, **point_rend_model_kwargs(point_rend)))
-        model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic,
-                                      mask_iou_weight=mask_iou['mask_iou_weight'], point_loss_weight=point_rend['point_loss_weight'],
+        faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, **model_kwargs(extensions))
+        model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic, **chain_kwargs(extensions),
                                       **box_loss)
     faster_rcnn.use_preset('evaluate')
     if args.resnet50_npz:           # ImageNet initialisation of the bottom-up pathway (before --weight, which may override it)
@@ -445,10 +361,7 @@ def run(args, keypoints=False):
     os.makedirs(args.out, exist_ok=True)
     log = open(os.path.join(args.out, 'log'), 'a') if rank == 0 else None
     keys = ('loss', 'rpn_loc_loss', 'rpn_cls_loss', 'roi_loc_loss', 'roi_cls_loss', 'mask_loss')
-    if mask_iou['mask_iou']:
-        keys += ('maskiou_loss',)
-    if point_rend['point_rend']:
-        keys += ('point_loss',)
+    keys += tuple(e.loss_key for e in EXTENSIONS if e.loss_key and e.is_on(extensions[e.name]))
     acc ={k: 0.0 for k in keys}
     loader = None
     if not args.synthetic:          # train.py:111-126: COCOMaskLoader(category_filter=labels, data_type='2017') + Transform
@@ -547,9 +460,7 @@ def run(args, keypoints=False):
             tickets = _all_rank_tickets(loader.ticket if loader is not None else 0, world, dev)
             if rank == 0:
                 save_npz(os.path.join(args.out, 'model_%d.npz' % it), faster_rcnn)      # snapshot_object, train.py:134-137
-                torch.save({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets,
-                            'augment': augment_settings(args), 'freeze': freeze, 'optim': optim, 'cascade': cascade,
-                            'mask_iou': mask_iou, 'point_rend': point_rend},
+                torch.save(dict({'iteration': it, 'optimizer': optimizer.state_dict(), 'loader_ticket': tickets}, **recorded),
                            os.path.join(args.out, 'trainer_%d.pt' % it))
     if loader is not None:
         loader.close()
