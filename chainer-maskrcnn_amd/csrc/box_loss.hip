@@ -1,14 +1,16 @@
 // IoU-based box regression losses (GIoU, DIoU, CIoU) on the decoded box, forward + hand-derived gradient, for gfx950.
 //
 // An alternative to mrcnn_smooth_l1_f32 with the same inputs, the same normaliser and the same gradient-buffer contract: the predicted
-// deltas and the encoded targets of a row are both decoded against the row's RoI / anchor with the arithmetic of detect_decode_row
-// (detect_common.h: d = v * std + mean, centre / size, expf, corners; no un-scaling, no clipping), and the loss is taken on the two boxes.
-// The gradient goes back through the IoU terms, the decode and std to the deltas.
+// deltas and the encoded targets of a row are both decoded against the row's RoI / anchor with box_common.h's loc_denorm4, box_cs,
+// loc2cs and cs_corners (d = v * std + mean, centre / size, expf, corners: the functions detect_decode_row, k_decode and
+// k_cascade_refine call; no un-scaling, no clipping), and the loss is taken on the two boxes.  The IoU here carries BOX_EPS and
+// derivatives: a rule of its own, not box_common.h's.  The gradient goes back through the IoU terms, the decode and std to the deltas.
 //
 // Latency-bound, not bandwidth-bound: almost every row of the RPN call (and three quarters of the head's) has label <= 0 and costs one
 // label load and, in the gradient pass, one zero store.  The label is tested first; x, t and the RoI are loaded for positive rows only.
 // Three launches like k_sl1: block partials, k_finalize (loss_common.h: fixed order, no float atomics), gradient.
 #include "loss_common.h"
+#include "box_common.h"
 
 #pragma clang fp contract(off)
 
@@ -51,22 +53,18 @@ __device__ __forceinline__ Axis axis_terms(float p1, float p2, float g1, float g
 // The loss of one row; GRAD: g[0..4) = d L / d x (without weight and normaliser).
 template <bool GRAD>
 __device__ __forceinline__ float box_loss_row(float4 xv, float4 tv, float4 roi, int kind, float4 mean, float4 stdv, float *g) {
-    const float h = roi.z - roi.x, w = roi.w - roi.y;
-    const float cy = roi.x + 0.5f * h, cx = roi.y + 0.5f * w;
-    // prediction: centre (pcy, pcx), size (ph, pw)
-    const float dy = xv.x * stdv.x + mean.x, dx = xv.y * stdv.y + mean.y;
-    const float dh = xv.z * stdv.z + mean.z, dw = xv.w * stdv.w + mean.w;
-    const float pcy = dy * h + cy, pcx = dx * w + cx;
-    const float ph = expf(fminf(dh, BOX_DSIZE_MAX)) * h, pw = expf(fminf(dw, BOX_DSIZE_MAX)) * w;
-    const float py1 = pcy - 0.5f * ph, px1 = pcx - 0.5f * pw, py2 = pcy + 0.5f * ph, px2 = pcx + 0.5f * pw;
+    const float4 rc = box_cs(roi), dp = loc_denorm4(xv, stdv, mean);
+    const float h = rc.z, w = rc.w, dh = dp.z, dw = dp.w;
+    // prediction: centre (pcy, pcx), size (ph, pw); dh, dw clamped above before the decode
+    const float pcy = loc2centre1(dp.x, h, rc.x), pcx = loc2centre1(dp.y, w, rc.y);
+    const float ph = loc2size1(fminf(dh, BOX_DSIZE_MAX), h), pw = loc2size1(fminf(dw, BOX_DSIZE_MAX), w);
+    const float4 pb = cs_corners(make_float4(pcy, pcx, ph, pw));
     // target (not clamped)
-    const float ty = tv.x * stdv.x + mean.x, tx = tv.y * stdv.y + mean.y;
-    const float th = tv.z * stdv.z + mean.z, tw = tv.w * stdv.w + mean.w;
-    const float gcy = ty * h + cy, gcx = tx * w + cx;
-    const float gh = expf(th) * h, gw = expf(tw) * w;
-    const float gy1 = gcy - 0.5f * gh, gx1 = gcx - 0.5f * gw, gy2 = gcy + 0.5f * gh, gx2 = gcx + 0.5f * gw;
+    const float4 gc = loc2cs(rc, loc_denorm4(tv, stdv, mean));
+    const float gcy = gc.x, gcx = gc.y, gh = gc.z, gw = gc.w;
+    const float4 gb = cs_corners(gc);
 
-    const Axis ay = axis_terms<GRAD>(py1, py2, gy1, gy2), ax = axis_terms<GRAD>(px1, px2, gx1, gx2);
+    const Axis ay = axis_terms<GRAD>(pb.x, pb.z, gb.x, gb.z), ax = axis_terms<GRAD>(pb.y, pb.w, gb.y, gb.w);
     const float inter = ay.i * ax.i;
     const float uni = ((ph * pw + gh * gw) - inter) + BOX_EPS;
     const float iou = inter / uni;

@@ -1,6 +1,6 @@
 // Soft-NMS and box voting on gfx950: Detectron's TEST.SOFT_NMS (Bodla et al. 2017) and TEST.BBOX_VOTE on the decoded
 // candidates of predict.hip / tta.hip, for the single view (R <= 300) and the union of the test-time views (R <= 4096).  The rules - the
-// candidate test, the IoU, the score weight - are detect_common.h's, shared with the hard NMS kernels.  Latency-bound kernels.
+// candidate test, the IoU (box_common.h nms_iou), the score weight - are detect_common.h's, shared with the hard NMS kernels.  Latency-bound kernels.
 //   k_class_soft_nms  one workgroup per class.  The class's candidates (prob > score_thresh) are compacted in row order into three arrays
 //                     (working score, row, box): in LDS for up to kLdsCap candidates, in the caller's workspace above.  Every trip of
 //                     the loop selects one detection: the workgroup's arg-max over the packed keys valid | orderable(s) << 31 | slot
@@ -101,7 +101,7 @@ __device__ __forceinline__ void soft_nms_class(float *sc, int *ix, float4 *bx, u
                 sc[slot] = -INFINITY;
                 continue;
             }
-            const float w = soft_nms_weight(method, box_iou(bm, area_m, bx[slot]), nms_thresh, sigma);
+            const float w = soft_nms_weight(method, nms_iou(bm, area_m, bx[slot]), nms_thresh, sigma);
             if (w != 1.0f) {
                 s = s * w;
                 sc[slot] = s;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(kT) void k_box_vote(const float *__restrict__ cls_b
             const float p = prob[(size_t)i * n_class + l];
             if (!(p > score_thresh)) continue;
             const float4 c = *reinterpret_cast<const float4 *>(cls_bbox + (size_t)i * 4);
-            if (!(box_iou(b, area, c) >= vote_thresh)) continue;
+            if (!(nms_iou(b, area, c) >= vote_thresh)) continue;
             a0 += p * c.x; a1 += p * c.y; a2 += p * c.z; a3 += p * c.w;
             ws += p;
             ++nv;

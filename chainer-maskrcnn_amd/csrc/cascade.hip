@@ -7,21 +7,20 @@
 // The rules of cascade_refine, row r of image i (float32, operation for operation, FP contraction off; restated in NumPy by
 // tests/cascade_reference.py):
 //   padding   prev_label[r] < 0: roi = 0, xy5 = (i,0,0,0,0), level 0, gt_loc = 0, label -1, assign -1.
-//   decode    detect_decode_row's loc2bbox without the un-scale: d = o[loc0 + c] * std_prev[c] + mean[c]; h, w, cy, cx of rois[r];
-//             ncy = dy * h + cy, nh = expf(dh) * h, corners ncy -+ 0.5 * nh (x likewise); each corner clipped fmaxf(fminf(v, lim), 0)
-//             against image i's h / w.  dh / dw are not clamped: an expf that overflows gives -inf / +inf corners, which clip to the
-//             full extent; fminf / fmaxf drop a NaN, so the box is finite whatever the deltas are.
-//   level     fpn_level (box_common.h) of the refined box: the sampler's level of a ground-truth box.
+//   decode    box_clip(loc2bbox(rois[r], loc_denorm4(o[loc0 ..], std_prev, mean)), h, w) of box_common.h with image i's h / w: what
+//             detect_decode_row calls after its un-scale.  dh / dw are not clamped: an expf that overflows gives -inf / +inf corners,
+//             which clip to the full extent; fminf / fmaxf drop a NaN, so the box is finite whatever the deltas are.
+//   level     fpn_level(b, 0, 4) (box_common.h) of the refined box: the sampler's level of a ground-truth box.
 //   xy5       (i, x1, y1, x2, y2) of the refined box.
 //   -- with ground truth only --
 //   empty     y2 - y1 <= 0 or x2 - x1 <= 0 after clipping: label -1 (both losses ignore the row; the fixed-shape form of Detectron2
 //             dropping empty boxes between stages), assign -1, gt_loc = 0.  The box and the level are written as computed.
 //   no gt     G = min(n_gt[i], gt_cap) == 0: label 0, assign -1, gt_loc = 0.
-//   match     box_iou (box_common.h) against the image's first G boxes; max / argmax as NumPy's, the way k_proposal_target states it: the
-//             first maximum, a NaN wins over every number and the first NaN stays.  label = gt_labels[arg] + 1 where max >= iou_thresh
-//             (false for a NaN maximum), else 0; assign = arg.
-//   targets   label > 0: gt_loc = (bbox2loc(roi, gt[arg]) - mean) / std_next; every other row zeros, so no -inf of a zero-size box
-//             reaches a loss.
+//   match     match_iou (box_common.h) against the image's first G boxes; max / argmax by max_arg_step, as k_proposal_target: NumPy's,
+//             the first maximum, a NaN wins and the first NaN stays.  label = gt_labels[arg] + 1 where max >= iou_thresh (false for a NaN
+//             maximum), else 0; assign = arg.
+//   targets   label > 0: gt_loc = bbox2loc(roi, gt[arg]) through loc_norm4(mean, std_next); every other row zeros, so no -inf of a
+//             zero-size box reaches a loss.
 // One thread per row; the image's ground-truth boxes are staged in LDS, so a workgroup never straddles two images:
 // grid (ceil(S / 256), N).
 #include "common.h"
@@ -56,32 +55,18 @@ __global__ __launch_bounds__(CR_THREADS) void k_cascade_refine(
     if (!prev_label || prev_label[row] >= 0) {
         const float4 r = *reinterpret_cast<const float4 *>(rois + row * 4);
         const float *o = box_out + row * ld;
-        const float dy = o[loc0] * std_prev.x + mean.x, dx = o[loc0 + 1] * std_prev.y + mean.y;
-        const float dh = o[loc0 + 2] * std_prev.z + mean.z, dw = o[loc0 + 3] * std_prev.w + mean.w;
-        const float h = r.z - r.x, w = r.w - r.y;
-        const float cy = r.x + 0.5f * h, cx = r.y + 0.5f * w;
-        const float ncy = dy * h + cy, ncx = dx * w + cx;
-        const float nh = expf(dh) * h, nw = expf(dw) * w;
-        b = make_float4(ncy - 0.5f * nh, ncx - 0.5f * nw, ncy + 0.5f * nh, ncx + 0.5f * nw);
-        b.x = fmaxf(fminf(b.x, img_h), 0.f); b.z = fmaxf(fminf(b.z, img_h), 0.f);
-        b.y = fmaxf(fminf(b.y, img_w), 0.f); b.w = fmaxf(fminf(b.w, img_w), 0.f);
-        lev = (int)fpn_level(b);
+        const float4 d = loc_denorm4(make_float4(o[loc0], o[loc0 + 1], o[loc0 + 2], o[loc0 + 3]), std_prev, mean);
+        b = box_clip(loc2bbox(r, d), img_h, img_w);
+        lev = (int)fpn_level(b, 0.f, 4.f);
         if (train && !(b.z - b.x <= 0.f || b.w - b.y <= 0.f)) {
             lab = 0;
             if (G > 0) {
                 float best = -INFINITY;
                 arg = 0;
-                for (int g = 0; g < G; ++g) {
-                    const float v = box_iou(b, sg[g]);
-                    if (g == 0 || v > best || (v != v && best == best)) { best = v; arg = g; }
-                }
+                for (int g = 0; g < G; ++g) max_arg_step(g, match_iou(b, sg[g]), best, arg);
                 if (best >= iou_thresh) {
                     lab = gt_labels[(size_t)img * gt_cap + arg] + 1;
-                    if (lab > 0) {
-                        loc = bbox2loc(b, sg[arg]);
-                        loc.x = (loc.x - mean.x) / std_next.x; loc.y = (loc.y - mean.y) / std_next.y;
-                        loc.z = (loc.z - mean.z) / std_next.z; loc.w = (loc.w - mean.w) / std_next.w;
-                    }
+                    if (lab > 0) { loc = bbox2loc(b, sg[arg]); loc_norm4(loc, mean, std_next); }
                 }
             }
         }

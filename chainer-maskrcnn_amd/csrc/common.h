@@ -50,6 +50,9 @@ __device__ __forceinline__ float4 ld4s(const float *p) {
 }
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 
+// the logistic function: the mask probabilities of predict.hip / tta.hip; sigmoid1(v) - t is the gradient of loss_common.h's bce_logit1
+__device__ __forceinline__ float sigmoid1(float v) { return 1.0f / (1.0f + expf(-v)); }
+
 namespace mrcnn {
 // Hand-written selection / sorting of unsigned 64-bit keys (sort.hip; no library): segments = images.
 // select_kth: kth[seg * kth_stride] = the kreq[seg * kreq_stride]-th largest (descending) or smallest key of the segment (radix select,

@@ -4,9 +4,11 @@
 //   decode       chainer_maskrcnn/model/maskrcnn.py:178-205  (un-scale, loc2bbox, clip, softmax)
 //   candidates   maskrcnn.py:278-312  (_suppress: prob > score_thresh, score descending then index descending, ChainerCV NMS)
 //   paste        maskrcnn.py:231-246  (cv2.resize to the box, *255, truncate, > 127, paste)
-// and the rules of Soft-NMS and box voting (boxpost.hip): the IoU as a value and the score weight.
+// and the score weight of Soft-NMS and box voting (boxpost.hip).  The box arithmetic inside them (de-normalised loc,
+// loc2bbox, clip, nms_iou / nms_suppresses) is box_common.h's, the functions the training kernels call.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "box_common.h"
 
 #pragma clang fp contract(off)
 
@@ -40,18 +42,11 @@ __device__ __forceinline__ float4 detect_decode_row(const float *__restrict__ ro
                                                     float *__restrict__ prob_row) {
     const float4 rr = *reinterpret_cast<const float4 *>(roi);
     const float4 r = make_float4(rr.x / scale, rr.y / scale, rr.z / scale, rr.w / scale);         // roi = rois / scale (:178)
-    const float dy = o[loc0] * stdv.x + mean.x, dx = o[loc0 + 1] * stdv.y + mean.y;                // (:191-195)
-    const float dh = o[loc0 + 2] * stdv.z + mean.z, dw = o[loc0 + 3] * stdv.w + mean.w;
-    const float h = r.z - r.x, w = r.w - r.y;                                                      // loc2bbox (:196)
-    const float cy = r.x + 0.5f * h, cx = r.y + 0.5f * w;
-    const float ncy = dy * h + cy, ncx = dx * w + cx;
-    const float nh = expf(dh) * h, nw = expf(dw) * w;
-    float y1 = ncy - 0.5f * nh, x1 = ncx - 0.5f * nw, y2 = ncy + 0.5f * nh, x2 = ncx + 0.5f * nw;
-    y1 = fmaxf(fminf(y1, size_h), 0.f); y2 = fmaxf(fminf(y2, size_h), 0.f);                       // clip (:202-203)
-    x1 = fmaxf(fminf(x1, size_w), 0.f); x2 = fmaxf(fminf(x2, size_w), 0.f);
+    const float4 d = loc_denorm4(make_float4(o[loc0], o[loc0 + 1], o[loc0 + 2], o[loc0 + 3]), stdv, mean);   // (:191-195)
+    const float4 b = box_clip(loc2bbox(r, d), size_h, size_w);                                     // loc2bbox (:196), clip (:202-203)
     const SoftmaxStats st = detect_softmax_stats(o, n_class);
     for (int c = 0; c < n_class; ++c) prob_row[c] = detect_softmax_prob(o[c], st);                 // F.softmax (:205)
-    return make_float4(y1, x1, y2, x2);
+    return b;
 }
 
 // NMS candidate i with class probability p: valid | orderable score << 31 | index, 0 when p <= score_thresh.  Descending key order is
@@ -77,25 +72,6 @@ __device__ __forceinline__ void bitonic_sort_desc(u64 *skey, int P, int tid) {
             }
             __syncthreads();
         }
-}
-
-// Box b (of area area_b, the product of its sides) suppresses box c: IoU = ai / ((area_b + area_c) - ai) >= thresh, the division
-// correctly rounded (ChainerCV's non_maximum_suppression).
-__device__ __forceinline__ bool nms_suppresses(float4 b, float area_b, float4 c, float thresh) {
-    const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y), bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
-    const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
-    const float ai = hgt * wid;
-    const float iou = ai / ((area_b + (c.z - c.x) * (c.w - c.y)) - ai);
-    return iou >= thresh;
-}
-
-// The IoU of nms_suppresses as a value: box b (of area area_b, the product of its sides) against box c, the division correctly rounded.
-// Two zero-area boxes give NaN; the callers' comparisons are written so that NaN has no effect.
-__device__ __forceinline__ float box_iou(float4 b, float area_b, float4 c) {
-    const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y), bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
-    const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
-    const float ai = hgt * wid;
-    return ai / ((area_b + (c.z - c.x) * (c.w - c.y)) - ai);
 }
 
 // The weight a selected box puts on the score of a remaining candidate of its class at this IoU (Soft-NMS, Bodla et al. 2017; method =

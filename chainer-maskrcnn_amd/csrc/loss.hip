@@ -224,10 +224,10 @@ __global__ __launch_bounds__(NT) void k_mask_bce(const float *__restrict__ x, co
         const size_t o = (size_t)i * Cm + (lb - 1);
         const float v = x[o], tf = (float)tt;
         if (PHASE == 0) {
-            ls += -(v * (tf - (v >= 0.f ? 1.f : 0.f)) - log1pf(expf(-fabsf(v))));
+            ls += bce_logit1(v, tf);
             cnt += 1.f;
         } else {
-            gx[o] = (1.0f / (1.0f + expf(-v)) - tf) * inv;
+            gx[o] = (sigmoid1(v) - tf) * inv;
         }
     }
     if (PHASE == 0) block_partial(ls, cnt, part);
@@ -246,11 +246,11 @@ __global__ __launch_bounds__(NT) void k_sigmoid_ce(const float *__restrict__ x, 
         const float v = x[i], tf = (float)tt;
         if (PHASE == 0) {
             if (tt != -1) {
-                ls += -(v * (tf - (v >= 0.f ? 1.f : 0.f)) - log1pf(expf(-fabsf(v))));
+                ls += bce_logit1(v, tf);
                 cnt += 1.f;
             }
         } else {
-            gx[i] = tt != -1 ? (1.0f / (1.0f + expf(-v)) - tf) * inv : 0.f;
+            gx[i] = tt != -1 ? (sigmoid1(v) - tf) * inv : 0.f;
         }
     }
     if (PHASE == 0) block_partial(ls, cnt, part);

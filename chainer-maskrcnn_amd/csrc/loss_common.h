@@ -16,6 +16,9 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// binary cross entropy of logit v against target t in [0, 1] (F.sigmoid_cross_entropy's stable form); gradient sigmoid1(v) - t
+__device__ __forceinline__ float bce_logit1(float v, float t) { return -(v * (t - (v >= 0.f ? 1.f : 0.f)) - log1pf(expf(-fabsf(v)))); }
+
 // block-level deterministic sum of (a, b) -> part[blockIdx.x*2 + {0,1}]
 __device__ __forceinline__ void block_partial(float a, float b, float *part) {
     __shared__ float sa[NT / 64], sb[NT / 64];

@@ -272,7 +272,7 @@ __global__ __launch_bounds__(NT) void k_point_bce(const float *__restrict__ pred
             const float t = target[i];
             if (!(t >= 0.f) || ch < 0 || ch >= n_channels) continue;
             const float v = pred[(size_t)i * ld + ch];
-            ls += -(v * (t - (v >= 0.f ? 1.f : 0.f)) - log1pf(expf(-fabsf(v))));
+            ls += bce_logit1(v, t);
             cnt += 1.f;
         }
         block_partial(ls * weight, cnt, part);
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(NT) void k_point_bce(const float *__restrict__ pred
             const long long i = e / ld;
             const int c = (int)(e % ld), ch = label[i / P] - label_base;
             const float t = target[i];
-            gx[e] = (t >= 0.f && ch >= 0 && ch < n_channels && c == ch) ? (1.0f / (1.0f + expf(-pred[e])) - t) * scale : 0.f;
+            gx[e] = (t >= 0.f && ch >= 0 && ch < n_channels && c == ch) ? (sigmoid1(pred[e]) - t) * scale : 0.f;
         }
     }
 }

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_mask_paste(const float *__restrict__ lo
     const int d = blockIdx.y;
     const float *lg = logits + (size_t)d * S * S * Cm + label[d];
     mask_paste_box(*reinterpret_cast<const float4 *>(bbox + (size_t)d * 4), S, H, W, out + (size_t)d * H * W,
-                   [&](int yy, int xx) { return 1.0f / (1.0f + expf(-lg[((size_t)yy * S + xx) * Cm])); });
+                   [&](int yy, int xx) { return sigmoid1(lg[((size_t)yy * S + xx) * Cm]); });
 }
 
 }  // namespace

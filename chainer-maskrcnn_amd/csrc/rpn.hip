@@ -14,7 +14,7 @@
 // index desc).  NMS keep lists are bit-exact given identical boxes.  All kernels are latency/HBM
 // bound; sizes at config 3: A = 261,888 anchors, n_pre = 12,000 (18 MB of bit masks), n_post = 2,000.
 #include "common.h"
-#include "detect_common.h"          // orderable(); FP contraction off
+#include "detect_common.h"          // orderable(), box_common.h (loc2bbox, box_clip, nms_inter / nms_union, fpn_level); FP contraction off
 
 namespace {
 
@@ -121,15 +121,9 @@ __global__ __launch_bounds__(256) void k_decode(const float *__restrict__ locs, 
         }
         const float4 an = *reinterpret_cast<const float4 *>(anchors + (size_t)a * 4);
         const float4 l = *reinterpret_cast<const float4 *>(locs + (size_t)i * 4);
-        const float h = an.z - an.x, w = an.w - an.y;
-        const float cy = an.x + 0.5f * h, cx = an.y + 0.5f * w;
-        const float ncy = l.x * h + cy, ncx = l.y * w + cx;
-        const float nh = expf(l.z) * h, nw = expf(l.w) * w;
-        float y1 = ncy - 0.5f * nh, x1 = ncx - 0.5f * nw, y2 = ncy + 0.5f * nh, x2 = ncx + 0.5f * nw;
-        y1 = fmaxf(fminf(y1, img_h), 0.f); y2 = fmaxf(fminf(y2, img_h), 0.f);
-        x1 = fmaxf(fminf(x1, img_w), 0.f); x2 = fmaxf(fminf(x2, img_w), 0.f);
-        *reinterpret_cast<float4 *>(boxes + (size_t)i * 4) = make_float4(y1, x1, y2, x2);
-        const bool ok = (y2 - y1 >= min_size) && (x2 - x1 >= min_size);
+        const float4 b = box_clip(loc2bbox(an, l), img_h, img_w);
+        *reinterpret_cast<float4 *>(boxes + (size_t)i * 4) = b;
+        const bool ok = (b.z - b.x >= min_size) && (b.w - b.y >= min_size);
         // -0.0 + 0.0 = +0.0: the oracle's argsort compares the two zeros equal (index decides), orderable() would rank -0.0 lower
         const float sc = scores[(size_t)i * 2 + 1] + 0.0f;
         // [image N-1-n] | valid | orderable score (32) | anchor index (ib bits): ONE descending sort of all images =>
@@ -180,12 +174,7 @@ __global__ __launch_bounds__(64) void k_nms_mask(const float *__restrict__ sboxe
     const int jmax = min(64, n - cb * 64);
     for (int j = 0; j < jmax; ++j) {
         const float4 c = cbox[j];
-        const float top = fmaxf(b.x, c.x), left = fmaxf(b.y, c.y);
-        const float bottom = fminf(b.z, c.z), right = fminf(b.w, c.w);
-        const float hgt = fmaxf(bottom - top, 0.f), wid = fmaxf(right - left, 0.f);
-        const float ai = hgt * wid;
-        const float area_j = (c.z - c.x) * (c.w - c.y);
-        const float u = (area_i + area_j) - ai;
+        const float ai = nms_inter(b, c), u = nms_union(area_i, c, ai);
         // iou >= thresh with the correctly-rounded division of the reference is decided WITHOUT the division (a dozen
         // instructions) whenever ai is outside a 4e-7 band around thresh * u: fl(ai / u) >= thresh <=> ai / u >= thresh (1 - 6e-8 ..),
         // and thresh * u is known to 6e-8.  Inside the band - and for u <= 0, where the sign rules of the division decide -
@@ -362,16 +351,6 @@ __global__ __launch_bounds__(NMS_RED_THREADS) void k_nms_reduce(const u64 *__res
     if (tid == 0) n_keep[img] = s_kept;
 }
 
-__device__ __forceinline__ float fpn_level(float y1, float x1, float y2, float x2, float k_min, float k_max) {
-    // multilevel_region_proposal_network.py:23-31: floor(4 + log2(sqrt(area)/224 + 1e-6)) clipped
-    const float area = (y2 - y1) * (x2 - x1);
-    const float s = sqrtf(area);
-    const float v = s / 224.0f + 1e-6f;
-    const float lg = (float)log2((double)v);
-    const float t = floorf(4.0f + lg);
-    return fminf(fmaxf(t, k_min), k_max);
-}
-
 // rois (N*n_post, 4) padded with zeros; roi_indices (N*n_post) i32 (-1 padding); levels f32.
 __global__ __launch_bounds__(256) void k_emit_rois(const float *__restrict__ sboxes, const int32_t *__restrict__ keep,
                                                    const int32_t *__restrict__ n_keep, int n_pre, int n_post,
@@ -387,7 +366,7 @@ __global__ __launch_bounds__(256) void k_emit_rois(const float *__restrict__ sbo
     if (j < n_keep[img]) {
         b = *reinterpret_cast<const float4 *>(sboxes + ((size_t)img * n_pre + keep[o]) * 4);
         idx = img;
-        lv = fpn_level(b.x, b.y, b.z, b.w, 0.f, 4.f);
+        lv = fpn_level(b, 0.f, 4.f);
     }
     *reinterpret_cast<float4 *>(rois + o * 4) = b;
     roi_idx[o] = idx;
@@ -399,7 +378,7 @@ __global__ __launch_bounds__(256) void k_levels(const float *__restrict__ rois, 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= R) return;
     const float4 b = *reinterpret_cast<const float4 *>(rois + (size_t)i * 4);
-    levels[i] = fpn_level(b.x, b.y, b.z, b.w, k_min, k_max);
+    levels[i] = fpn_level(b, k_min, k_max);
 }
 
 __global__ void k_set_i32(int32_t *p, int32_t v) { *p = v; }

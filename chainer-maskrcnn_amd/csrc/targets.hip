@@ -72,11 +72,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_proposal_target(
         const float4 b = cand(c);
         float best = -INFINITY;
         int arg = 0;
-        for (int g = 0; g < G; ++g) {
-            const float v = box_iou(b, *reinterpret_cast<const float4 *>(gb + (size_t)g * 4));
-            // iou.max(axis=1) / argmax of NumPy: a NaN (0/0: two zero-area boxes) wins over every number and the first NaN stays
-            if (g == 0 || v > best || (v != v && best == best)) { best = v; arg = g; }
-        }
+        for (int g = 0; g < G; ++g) max_arg_step(g, match_iou(b, *reinterpret_cast<const float4 *>(gb + (size_t)g * 4)), best, arg);
         smax[c] = G > 0 ? best : 0.f;
         sarg[c] = (short)arg;
     }
@@ -131,13 +127,10 @@ __global__ __launch_bounds__(PT_THREADS) void k_proposal_target(
             *reinterpret_cast<float4 *>(sample_roi + (size_t)row * 4) = b;
             float *r5 = rois_xy5 + (size_t)row * 5;
             r5[0] = (float)img; r5[1] = b.y; r5[2] = b.x; r5[3] = b.w; r5[4] = b.z;
-            sample_levels[row] = (int)(c < nr ? roi_levels[(size_t)img * roi_cap + c] : fpn_level(b));
+            sample_levels[row] = (int)(c < nr ? roi_levels[(size_t)img * roi_cap + c] : fpn_level(b, 0.f, 4.f));
             float4 loc = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (G > 0) {             // (no gt: row 0 is padding, its zero size would give -inf targets)
-                loc = bbox2loc(b, gbx);
-                loc.x = (loc.x - mean.x) / stdv.x; loc.y = (loc.y - mean.y) / stdv.y;
-                loc.z = (loc.z - mean.z) / stdv.z; loc.w = (loc.w - mean.w) / stdv.w;
-            }
+            // (no gt: row 0 is padding, its zero size would give -inf targets)
+            if (G > 0) { loc = bbox2loc(b, gbx); loc_norm4(loc, mean, stdv); }
             *reinterpret_cast<float4 *>(gt_roi_loc + (size_t)row * 4) = loc;
             gt_roi_label[row] = phase == 0 ? gt_labels[(size_t)img * gt_cap + g] + 1 : 0;
             gt_assign[row] = G > 0 ? g : -1;
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(256) void k_at_iou(const float *__restrict__ anchor
     for (int g = 0; g < G; ++g) {
         float v = 0.f;
         if (in) {
-            v = box_iou(an, sg[g]);
+            v = match_iou(an, sg[g]);
             if (g == 0 || v > best) { best = v; arg = g; }
         }
         // per-gt maximum over the inside anchors: wave reduction first, one atomic per wave (IoU >= 0: int order == float order)
@@ -315,7 +308,7 @@ __global__ __launch_bounds__(256) void k_at_label(const float *__restrict__ anch
         if (m < neg_thresh) lab = 0;
         const float4 an = *reinterpret_cast<const float4 *>(anchors + (size_t)a * 4);
         for (int g = 0; g < G; ++g)
-            if (box_iou(an, sg[g]) == sgm[g]) lab = 1;
+            if (match_iou(an, sg[g]) == sgm[g]) lab = 1;
         if (m >= pos_thresh) lab = 1;
     }
     if (a < A) {

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(NT) void k_tta_mask_merge(const MergeViews vs, int 
     for (int u = 0; u < V; ++u) {
         const int xu = vs.mirror[u] ? S - 1 - x : x;
         const float z = vs.src[u][(((size_t)d * S + y) * S + xu) * Cm + ch];
-        const float p = 1.0f / (1.0f + expf(-z));
+        const float p = sigmoid1(z);
         acc = u == 0 ? p : acc + p;
     }
     prob[i] = acc / (float)V;

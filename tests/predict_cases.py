@@ -131,7 +131,7 @@ NMS_OVER_CAP = 'grid-R513-e5'                       # the workspace kernel only
 
 
 def iou_f32(b, c):
-    """The IoU of detect_common.h's nms_suppresses in float32 NumPy (oracle.boxes.nms's expression)."""
+    """box_common.h's nms_iou, the IoU inside nms_suppresses, in float32 NumPy (oracle.boxes.nms's expression)."""
     b, c = np.asarray(b, F), np.asarray(c, F)
     top, left, bottom, right = np.maximum(b[0], c[0]), np.maximum(b[1], c[1]), np.minimum(b[2], c[2]), np.minimum(b[3], c[3])
     ai = np.maximum(bottom - top, F(0)) * np.maximum(right - left, F(0))
