@@ -1493,3 +1493,58 @@ def vis_render(img, masks=None, bbox=None, colors=None, order=None, mask_a256=12
                                     ptr(prims_d), 0 if pr is None else int(pr.shape[0]), ptr(font_d), 0 if ft is None else int(ft.shape[0]),
                                     ptr(out), stream_ptr()))
     return out
+
+
+# ---- deformable convolution (csrc/deform.hip) --------------------------------------------------------------------------------
+DEFORM_GEOMETRY = (3, 3, 1, 1, 1, 1)        # KH, KW, stride, pad, dilation, deformable groups: the one geometry the kernels take
+
+
+def _deform_args(name, x_shape, off, ts):
+    _ck(off, *ts)
+    for t_ in (off,) + tuple(ts):
+        if t_ is not None and t_.dtype != f32:
+            raise ValueError('%s: a %s tensor where %s is expected' % (name, t_.dtype, f32))
+    if len(x_shape) != 4 or off.dim() != 4 or tuple(off.shape[:3]) != tuple(x_shape[:3]):
+        raise ValueError('%s: a map of shape %r against offsets %r' % (name, tuple(x_shape), tuple(off.shape)))
+
+
+def deform_cols_fwd(x, off, modulated):
+    """x (N,H,W,C), off (N,H,W,ld): (dy, dx) of tap k in channels 2k, 2k + 1, modulated the logit of its mask in channel 18 + k -> the sampled
+    columns (N,H,W,9*C), tap-major (mrcnn_deform_cols_fwd_f32)."""
+    _deform_args('deform_cols_fwd', x.shape, off, (x,))
+    N, H, W, C = x.shape
+    cols = _empty((N, H, W, 9 * C), x.device)
+    check(lib().mrcnn_deform_cols_fwd_f32(ptr(x), ptr(off), off.shape[3], int(bool(modulated)), N, H, W, C, *DEFORM_GEOMETRY, ptr(cols),
+                                          stream_ptr()))
+    return cols
+
+
+def deform_offset_bwd(g_cols, x, off, modulated):
+    """The gradient of the whole offset row (N,H,W,ld) from g_cols (N,H,W,9*C): channels 2k, 2k + 1, modulated 18 + k, zeros behind them
+    (mrcnn_deform_offset_bwd_f32)."""
+    _deform_args('deform_offset_bwd', x.shape, off, (g_cols, x))
+    N, H, W, C = x.shape
+    if g_cols.numel() != 9 * x.numel():
+        raise ValueError('deform_offset_bwd: g_cols %r against x %r' % (tuple(g_cols.shape), tuple(x.shape)))
+    g_off = _empty(tuple(off.shape), x.device)
+    check(lib().mrcnn_deform_offset_bwd_f32(ptr(g_cols), ptr(x), ptr(off), off.shape[3], int(bool(modulated)), N, H, W, C, *DEFORM_GEOMETRY,
+                                            ptr(g_off), stream_ptr()))
+    return g_off
+
+
+def deform_input_bwd(g_cols, off, modulated, x_shape, gx=None, relu_x=None):
+    """The gradient of x (N,H,W,C) from g_cols (N,H,W,9*C), the same bits on every run (mrcnn_deform_input_bwd_f32).  gx given: added into it,
+    its prior value first; relu_x: the TOTAL is zeroed where relu_x <= 0.  Returns gx."""
+    _deform_args('deform_input_bwd', x_shape, off, (g_cols, gx, relu_x))
+    N, H, W, C = x_shape
+    if g_cols.numel() != 9 * N * H * W * C or (gx is not None and tuple(gx.shape) != tuple(x_shape)) \
+            or (relu_x is not None and tuple(relu_x.shape) != tuple(x_shape)):
+        raise ValueError('deform_input_bwd: g_cols %r, gx %r, relu_x %r against a map of %r' % (
+            tuple(g_cols.shape), None if gx is None else tuple(gx.shape), None if relu_x is None else tuple(relu_x.shape), tuple(x_shape)))
+    acc = gx is not None
+    if gx is None:
+        gx = _empty(tuple(x_shape), g_cols.device)
+    ws = workspace(lib().mrcnn_deform_input_bwd_workspace_bytes(N, H, W), g_cols.device)
+    check(lib().mrcnn_deform_input_bwd_f32(ptr(g_cols), ptr(off), off.shape[3], int(bool(modulated)), N, H, W, C, *DEFORM_GEOMETRY, ptr(gx),
+                                           ptr(relu_x), int(acc), ptr(ws), ws.numel(), stream_ptr()))
+    return gx

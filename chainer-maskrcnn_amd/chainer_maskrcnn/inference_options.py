@@ -1,6 +1,7 @@
 """The inference options of the entry scripts, stated once: the test-time augmentation and box post-processing flags of evaluate.py and
 demo.py (train.py declares them with the prefix '--eval-' for its periodic evaluator), what they turn into on a model, the table of the
-optional model extensions that all four scripts walk (EXTENSIONS), the label file and the model a checkpoint is scored or drawn with.
+optional model extensions that all four scripts walk (EXTENSIONS), the deformable-convolution flags beside it, the label file and the
+model a checkpoint is scored or drawn with.
 Importing this module needs neither a device nor the training script."""
 import collections
 import os
@@ -276,6 +277,47 @@ def point_rend_model_kwargs(settings):
     return dict({'point_rend': True}, **{k: settings[k] for k in POINT_SHAPE_DEFAULTS})
 
 
+# ---- deformable convolution in res3-res5 (MaskRCNN dcn_stages / dcn_modulated) ------------------------------------------------
+# Beside the table below, like train.py's freeze and box-loss flags: the two MaskRCNN arguments are passed only when --dcn-stages is given.
+NO_DCN = {'stages': [], 'modulated': False}        # what a trainer state without the 'dcn' key was trained with
+DCN_NOUN = 'the deformable convolution settings'    # the noun of the --resume refusal
+
+
+def add_dcn_flags(parser, both=lambda name: (name,)):
+    """--dcn-stages / --dcn-modulated (train.py, train_keypoints.py - which takes both spellings through ``both`` -, evaluate.py, demo.py)."""
+    parser.add_argument(*both('--dcn-stages'), nargs='+', default=None, metavar='STAGE',
+                        help='deformable convolution (MaskRCNN dcn_stages): every bottleneck of these stages among res3 res4 res5 runs its 3x3 '
+                             'layer as a deformable convolution (the dconv_c3-c5 configurations name all three); --backbone fpn only; a '
+                             'checkpoint is evaluated with the value it was trained with; no accuracy effect has been measured; off by default')
+    parser.add_argument(*both('--dcn-modulated'), type=int, default=0, choices=[0, 1],
+                        help='1: the modulated form (v2, the mdconv_c3-c5 configurations): every sample is scaled by a learned mask; needs '
+                             '--dcn-stages')
+
+
+def dcn_settings(stages, modulated, backbone='fpn'):
+    """{'stages': the stages in network order ([] = off), 'modulated': bool} of the flags, as trainer_<it>.pt records it; ValueError, before
+    any device work, for what MaskRCNN refuses (maskrcnn.dcn_settings states it): an unknown stage name, --dcn-modulated 1 without
+    --dcn-stages, another --backbone."""
+    from chainer_maskrcnn.model.maskrcnn import dcn_settings as model_rule
+    try:
+        got = model_rule(tuple(stages) if stages else None, modulated, backbone)
+    except ValueError as e:
+        raise ValueError('--dcn-stages / --dcn-modulated: %s' % e)
+    return {'stages': list(got[0]), 'modulated': got[1]}
+
+
+def dcn_model_kwargs(settings):
+    """The MaskRCNN keyword arguments of dcn_settings' dict (nothing when it is off: a default model)."""
+    if not settings['stages']:
+        return {}
+    return {'dcn_stages': tuple(settings['stages']), 'dcn_modulated': bool(settings['modulated'])}
+
+
+def dcn_settings_of(args):
+    """dcn_settings of a script's parsed flags."""
+    return dcn_settings(getattr(args, 'dcn_stages', None), getattr(args, 'dcn_modulated', 0), args.backbone)
+
+
 # ---- the optional model extensions, declared once for train.py, train_keypoints.py, evaluate.py and demo.py --------------------------------
 # One record per extension, holding what the scripts' glue differs in:
 #   add_flags(parser, both[, weight]) declares its flags; weight_flag names the one that only the training scripts take
@@ -386,13 +428,14 @@ def use_score_preset(model, preset, score_thresh=None):
 
 
 def build_inference_model(args, preset=None):
-    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --fpn-norm / --gn-groups / --cascade* / --mask-iou / --point-rend* / --label_file with --weight loaded (keys missing from the file keep their
+    """MaskRCNN of the flags --gpu / --backbone / --head-arch / --head-norm / --fpn-norm / --gn-groups / --cascade* / --mask-iou / --point-rend* / --dcn-* / --label_file with --weight loaded (keys missing from the file keep their
     initial values) and, when ``preset`` is given, use_score_preset(model, preset, --score-thresh).  A keypoint head is COCO's: one class,
     17 keypoints; a mask head has one class per label (80 without a label file)."""
     import torch
     from chainer_maskrcnn.model.maskrcnn import MaskRCNN
     from chainer_maskrcnn.utils import chainer_npz
     extensions = model_kwargs(extension_settings(args))
+    extensions.update(dcn_model_kwargs(dcn_settings_of(args)))
     dev =torch.device('cuda', args.gpu)
     torch.cuda.set_device(dev)
     if args.head_arch == 'fpn_keypoint':

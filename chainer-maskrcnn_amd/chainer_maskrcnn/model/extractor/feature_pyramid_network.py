@@ -33,6 +33,27 @@ def _lateral_stream(device):
     return _lat_streams[key]
 
 
+DCN_STAGES = ('res3', 'res4', 'res5')       # the stages dcn_stages may name
+
+
+def dcn_stage_settings(dcn_stages=None, dcn_modulated=False):
+    """The one statement of what dcn_stages / dcn_modulated may be: (the stages in network order - () when off,
+    modulated).  ValueError for a stage other than DCN_STAGES or one named twice, and for ``dcn_modulated`` without stages."""
+    if dcn_modulated not in (False, True, 0, 1):
+        raise ValueError('dcn_modulated must be True or False, got %r' % (dcn_modulated,))
+    if isinstance(dcn_stages, str):
+        raise ValueError('dcn_stages must be a sequence of stage names, got %r' % (dcn_stages,))
+    stages = tuple(dcn_stages or ())
+    for s in stages:
+        if s not in DCN_STAGES:
+            raise ValueError('dcn_stages: unknown stage %r (one of %s)' % (s, ', '.join(DCN_STAGES)))
+    if len(set(stages)) != len(stages):
+        raise ValueError('dcn_stages names a stage twice: %r' % (stages,))
+    if dcn_modulated and not stages:
+        raise ValueError('dcn_modulated needs dcn_stages')
+    return tuple(s for s in DCN_STAGES if s in stages), bool(dcn_modulated)
+
+
 class FeaturePyramidNetwork(object):
     feat_strides = [4, 8, 16, 32, 64]
     spatial_scales = list(map(lambda x: 1. / x, feat_strides))
@@ -43,11 +64,14 @@ class FeaturePyramidNetwork(object):
     STAGES = (('res2', 3, 64, 64, 256, 1), ('res3', 4, 256, 128, 512, 2),
               ('res4', 6, 512, 256, 1024, 2), ('res5', 3, 1024, 512, 2048, 2))
 
-    def __init__(self, ps=None, prefix='extractor', stages=None, width_div=1, fpn_norm=None, gn_groups=32):
+    def __init__(self, ps=None, prefix='extractor', stages=None, width_div=1, fpn_norm=None, gn_groups=32, dcn_stages=(), dcn_modulated=False):
         """``stages`` / ``width_div`` shrink the network for tests (blocks per stage, channel divisor);
         the defaults are the reference's ResNet-50.  fpn_norm: None = the reference's pyramid; 'gn' = a GroupNorm of ``gn_groups``
         groups (parameters ``<conv>/gn/gamma``, ``<conv>/gn/beta``) behind each of the eight FPN convolutions, which keep their bias
-        (Detectron's *_gn configurations)."""
+        (Detectron's *_gn configurations).  dcn_stages: the stages among 'res3', 'res4', 'res5' whose every block runs its
+        3x3 layer as a deformable convolution, modulated (v2) with ``dcn_modulated`` (the dconv_c3-c5 / mdconv_c3-c5 configurations;
+        parameters ``<block>/conv2_offset/{W,b}`` directly behind ``<block>/conv2/W``)."""
+        self.dcn_stages, self.dcn_modulated = dcn_stage_settings(dcn_stages, dcn_modulated)
         if fpn_norm not in (None, 'gn'):
             raise ValueError("fpn_norm must be None or 'gn', got %r" % (fpn_norm,))
         if fpn_norm == 'gn' and (gn_groups < 1 or (256 // width_div) % gn_groups != 0):
@@ -62,9 +86,10 @@ class FeaturePyramidNetwork(object):
         for si, (name, n, cin, mid, cout, stride) in enumerate(self.STAGES):
             n = n if stages is None else stages[si]
             cin, mid, cout = cin // d, mid // d, cout // d
-            blocks = [Bottleneck(self.ps, p + 'resnet/%s/a' % name, cin, mid, cout, stride, True)]
+            deform = None if name not in self.dcn_stages else ('v2' if self.dcn_modulated else 'v1')
+            blocks = [Bottleneck(self.ps, p + 'resnet/%s/a' % name, cin, mid, cout, stride, True, deform=deform)]
             for i in range(1, n):
-                blocks.append(Bottleneck(self.ps, p + 'resnet/%s/b%d' % (name, i), cout, mid, cout, 1, False))
+                blocks.append(Bottleneck(self.ps, p + 'resnet/%s/b%d' % (name, i), cout, mid, cout, 1, False, deform=deform))
             self.stages.append(blocks)
         fc = 256 // d
         self.out_channels = fc

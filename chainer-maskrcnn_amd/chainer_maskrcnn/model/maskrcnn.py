@@ -15,7 +15,7 @@ import torch
 
 from chainer_maskrcnn.nn.core import ParamStore
 from chainer_maskrcnn._hip import ops
-from .extractor.feature_pyramid_network import FeaturePyramidNetwork
+from .extractor.feature_pyramid_network import DCN_STAGES, FeaturePyramidNetwork, dcn_stage_settings      # noqa: F401
 from .rpn.multilevel_region_proposal_network import MultilevelRegionProposalNetwork
 from .head.fpn_roi_mask_head import FPNRoIBoxHead, FPNRoIMaskHead, MaskIoUHead, PointHead
 
@@ -102,6 +102,15 @@ def point_rend_settings(point_rend=False, point_train_points=196, point_oversamp
                 subdivision_points=int(subdivision_points))
 
 
+def dcn_settings(dcn_stages=None, dcn_modulated=False, backbone='fpn'):
+    """The checked deformable-convolution arguments of MaskRCNN as (stages in network order - () when off, modulated):
+    dcn_stage_settings' rule, and ValueError for another backbone than 'fpn'."""
+    stages, modulated = dcn_stage_settings(dcn_stages, dcn_modulated)
+    if stages and backbone != 'fpn':
+        raise ValueError("dcn_stages exists for backbone 'fpn' only, not %r" % (backbone,))
+    return stages, modulated
+
+
 class MaskRCNN(object):
     feat_stride = 16
     # box post-processing of _suppress (DESIGN.md §3.16), off until use_soft_nms / use_box_voting / use_max_detections set them on an instance
@@ -127,8 +136,12 @@ class MaskRCNN(object):
                  score_initialW=None, proposal_creator_params={}, backbone='fpn', head_arch='fpn',
                  device='cuda', seed=1234, _test_shrink=None, head_norm=None, gn_groups=32, cascade_ious=None, cascade_stds=None,
                  mask_iou=False, fpn_norm=None, point_rend=False, point_train_points=196, point_oversample=3, point_importance=0.75,
-                 subdivision_steps=2, subdivision_points=784):
-        """fpn_norm: None = the reference's pyramid; 'gn' = GroupNorm of ``gn_groups`` groups behind each of the eight FPN convolutions
+                 subdivision_steps=2, subdivision_points=784, dcn_stages=None, dcn_modulated=False):
+        """dcn_stages: None = the reference's ResNet; a selection of 'res3', 'res4', 'res5' = every bottleneck of those stages runs its 3x3
+        layer as a deformable convolution, modulated (v2) with ``dcn_modulated`` (the dconv_c3-c5 / mdconv_c3-c5
+        configurations): ``<block>/conv2_offset/{W,b}`` directly behind ``<block>/conv2/W``, zero-initialised.  backbone 'fpn' only; mask and
+        keypoint heads alike.  No accuracy effect has been measured.
+        fpn_norm: None = the reference's pyramid; 'gn' = GroupNorm of ``gn_groups`` groups behind each of the eight FPN convolutions
         (DESIGN.md §3.23); backbone 'fpn' only.
         head_norm: None = the reference's heads; 'gn' = GroupNorm of ``gn_groups`` groups behind conv1 and every mask / keypoint
         convolution of the 'fpn' / 'fpn_keypoint' heads.
@@ -153,6 +166,7 @@ class MaskRCNN(object):
         if fpn_norm is not None and backbone != 'fpn':
             raise ValueError("fpn_norm=%r exists for backbone 'fpn' only, not %r" % (fpn_norm, backbone))
         self.head_norm, self.gn_groups, self.fpn_norm = head_norm, int(gn_groups), fpn_norm
+        self.dcn_stages, self.dcn_modulated = dcn_settings(dcn_stages, dcn_modulated, backbone)
         self.cascade = cascade_settings(cascade_ious, cascade_stds, head_arch, backbone)
         self.mask_iou = mask_iou_setting(mask_iou, head_arch)
         self.point_rend = point_rend_settings(point_rend, point_train_points, point_oversample, point_importance, subdivision_steps,
@@ -160,7 +174,8 @@ class MaskRCNN(object):
         self.ps = ParamStore()
         shrink = _test_shrink or {}
         if backbone == 'fpn':
-            self.extractor = FeaturePyramidNetwork(self.ps, fpn_norm=fpn_norm, gn_groups=self.gn_groups, **shrink)
+            self.extractor = FeaturePyramidNetwork(self.ps, fpn_norm=fpn_norm, gn_groups=self.gn_groups, dcn_stages=self.dcn_stages,
+                                                   dcn_modulated=self.dcn_modulated, **shrink)
             self.rpn = MultilevelRegionProposalNetwork(
                 anchor_scales=self.extractor.anchor_scales, feat_strides=self.extractor.feat_strides,
                 in_channels=self.extractor.out_channels, mid_channels=self.extractor.out_channels,

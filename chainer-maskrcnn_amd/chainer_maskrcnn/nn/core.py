@@ -227,6 +227,10 @@ class Conv(object):
     def b(self):
         return self.ps.p(self.name + '/b') if self.has_bias else None
 
+    @property
+    def gW(self):
+        return self.ps.g(self.name + '/W')
+
     def fwd(self, x, relu=None, bn_stats=False, tape=True):
         """bn_stats: the output feeds a training-mode BatchNorm - where the geometry allows, the GEMM epilogue also leaves the
         statistics partials in ``self.last_bn_part`` (None otherwise) and BatchNorm.fwd skips its statistics pass.
@@ -266,7 +270,7 @@ class Conv(object):
         x, y, v = ctx
         if y is not None and not gy_masked:
             gy = ops.relu_bwd(gy, y)
-        gw = self.ps.g(self.name + '/W')
+        gw = self.gW
         gb = self.ps.g(self.name + '/b') if self.has_bias else None
         hnn.LOGICAL = (self.cin, self.cout)
         try:
@@ -330,6 +334,63 @@ class Conv(object):
         g = hnn.conv2d_bwd_data_raw(gy, self.W, (N, Ho, Wo, self.cin_p), 1, 0, out=out)
         hnn.LOGICAL = keep
         return g
+
+
+class _ColsGemm(Conv):
+    """The 1x1 layer a deformable convolution runs over its sampled columns: the (Cout,1,1,9*Cin) VIEW of the 3x3 filter (Cout,3,3,Cin) - the
+    same memory, tap-major like the columns - and the same view of its gradient.  It registers nothing; every call goes through Conv's."""
+
+    def __init__(self, conv):
+        self.ps, self.name, self.fwd_tile, self.in_backbone = conv.ps, conv.name, None, conv.in_backbone
+        self.cin, self.cout, self.k, self.stride, self.pad, self.relu = 9 * conv.cin, conv.cout, 1, 1, 0, False
+        self.cin_p, self.cout_p, self.has_bias = 9 * conv.cin_p, conv.cout_p, False
+
+    @property
+    def W(self):
+        return self.ps.p(self.name + '/W').view(self.cout_p, 1, 1, self.cin_p)
+
+    @property
+    def gW(self):
+        return self.ps.g(self.name + '/W').view(self.cout_p, 1, 1, self.cin_p)
+
+
+class DeformConv(Conv):
+    """Deformable convolution (Dai et al. 2017; modulated=True: v2, Zhu et al. 2019) in place of a 3x3, stride 1, pad 1 layer without bias
+    (DESIGN.md §3.25).  It owns the layer's ordinary parameters ``<name>/W`` (Cout,3,3,Cin) - registered as the plain layer registers them -
+    and, directly behind them, an offset convolution ``<name>_offset/{W,b}``: 3x3, stride 1, pad 1, with a bias, 18 (v1) or 27 (v2) logical
+    outputs, zero-initialised, so a fresh layer computes the plain convolution (v2: half of it, its masks being sigmoid(0)).
+    Forward: the offset convolution on x, the sampled columns (N,H,W,9*Cin) (csrc/deform.hip), the library's convolution as a 1x1 layer over
+    the columns.  The columns stay on the tape for the filter gradient.  No accuracy effect of the layer has been measured."""
+
+    def __init__(self, ps, name, cin, cout, modulated=False, init=None, in_backbone=None):
+        Conv.__init__(self, ps, name, cin, cout, 3, 1, 1, bias=False, init=init, in_backbone=in_backbone)
+        self.modulated = bool(modulated)
+        self.n_offset = 27 if self.modulated else 18
+        zeros = lambda shape: (lambda rs: np.zeros(shape, np.float32))
+        # (its output feeds no BatchNorm: not a backbone layer in the sense of Conv.in_backbone)
+        self.offset = Conv(ps, name + '_offset', cin, self.n_offset, 3, 1, 1, bias=True, init=zeros, in_backbone=False)
+        self.gemm = _ColsGemm(self)
+
+    def fwd(self, x, relu=None, bn_stats=False, tape=True):
+        """As Conv.fwd; the context is (x, offsets, the offset convolution's context, the 1x1 layer's context - which holds the columns)."""
+        off, octx = self.offset.fwd(x, relu=False, tape=tape)
+        cols = ops.deform_cols_fwd(x, off, self.modulated)
+        y, gctx = self.gemm.fwd(cols, relu=self.relu if relu is None else relu, bn_stats=bn_stats, tape=tape)
+        self.last_bn_part = self.gemm.last_bn_part
+        return y, ((x, off, octx, gctx) if tape else None)
+
+    def bwd(self, ctx, gy, need_gx=True, gx_acc=None, accumulate_params=False, gy_masked=False, mask_gx=False):
+        """As Conv.bwd.  The filter gradient and the gradient of the columns are the 1x1 layer's; the offset (and mask) gradient goes through
+        the offset convolution, whose data gradient and the sampling's input gradient are summed in one tensor (gx_acc when given), the ReLU
+        mask of mask_gx applied once, to the total."""
+        x, off, octx, gctx = ctx
+        g_cols = self.gemm.bwd(gctx, gy, accumulate_params=accumulate_params, gy_masked=gy_masked)
+        g_off = ops.deform_offset_bwd(g_cols, x, off, self.modulated)
+        if not need_gx:
+            self.offset.bwd(octx, g_off, need_gx=False, accumulate_params=accumulate_params)
+            return None
+        gx = self.offset.bwd(octx, g_off, gx_acc=gx_acc, accumulate_params=accumulate_params)
+        return ops.deform_input_bwd(g_cols, off, self.modulated, tuple(x.shape), gx=gx, relu_x=x if mask_gx else None)
 
 
 class BatchNorm(object):
@@ -461,12 +522,19 @@ class Bottleneck(object):
     """ResNet bottleneck (Chainer BottleneckA when ``project`` else BottleneckB):
     relu(bn3(conv3(relu(bn2(conv2 3x3(relu(bn1(conv1 1x1/s))))))) + shortcut), stride on the first 1x1."""
 
-    def __init__(self, ps, name, cin, mid, cout, stride, project):
-        self.project, self.stride = project, stride
+    def __init__(self, ps, name, cin, mid, cout, stride, project, deform=None):
+        """deform: None = the plain 3x3 conv2; 'v1' / 'v2' = a (modulated) deformable convolution in its place (DeformConv: the same
+        ``conv2/W`` plus ``conv2_offset/{W,b}`` registered directly behind it).  A deformable block never takes the composite call."""
+        if deform not in (None, 'v1', 'v2'):
+            raise ValueError("deform must be None, 'v1' or 'v2', got %r" % (deform,))
+        self.project, self.stride, self.deform = project, stride, deform
         he = lambda fan_in: (lambda shape: (lambda rs: rs.standard_normal(shape) * math.sqrt(2.0 / fan_in)))
         self.conv1 = Conv(ps, name + '/conv1', cin, mid, 1, stride, 0, bias=False, init=he(cin), in_backbone=True)
         self.bn1 = BatchNorm(ps, name + '/bn1', mid)
-        self.conv2 = Conv(ps, name + '/conv2', mid, mid, 3, 1, 1, bias=False, init=he(mid * 9), in_backbone=True)
+        if deform is None:
+            self.conv2 = Conv(ps, name + '/conv2', mid, mid, 3, 1, 1, bias=False, init=he(mid * 9), in_backbone=True)
+        else:
+            self.conv2 = DeformConv(ps, name + '/conv2', mid, mid, modulated=deform == 'v2', init=he(mid * 9), in_backbone=True)
         self.bn2 = BatchNorm(ps, name + '/bn2', mid)
         self.conv3 = Conv(ps, name + '/conv3', mid, cout, 1, 1, 0, bias=False, init=he(mid), in_backbone=True)
         self.bn3 = BatchNorm(ps, name + '/bn3', cout)
@@ -538,7 +606,7 @@ class Bottleneck(object):
 
     def _composite_ok(self, x):
         return (COMPOSITE_BLOCKS and TRAIN and FUSE_BN_STATS and x.is_cuda and hnn.PROFILE is None and FWD_TILE_RULE is None
-                and not WINOGRAD_SHARED_GY_TRANSFORM)
+                and not WINOGRAD_SHARED_GY_TRANSFORM and self.deform is None)
 
     def _descriptor(self, x):
         """mrcnn_bottleneck_t for this block on input x (cached: the parameter / gradient pointers are views of the flat buffers)."""

@@ -7,7 +7,9 @@ Deconvolution2D W (Cin, Cout, KH, KW), BatchNormalization gamma / beta / avg_mea
 ``head_norm='gn'`` model (no counterpart in the reference) go out as GroupNormalization gamma / beta (C,) under their store names
 ``head/<conv>/gn/{gamma,beta}``, those of an ``fpn_norm='gn'`` model under ``extractor/<conv>/gn/{gamma,beta}``; a file without them leaves them at their initial values.  The MaskIoU head of a ``mask_iou`` model (no
 counterpart either) goes out as ``head/maskiou/{conv1..conv4}`` (Convolution2D) and ``head/maskiou/{fc1,fc2,maskiou}`` (Linear), the
-point head of a ``point_rend`` model as ``head/point/{fc1,fc2,fc3,predictor}`` (Linear).
+point head of a ``point_rend`` model as ``head/point/{fc1,fc2,fc3,predictor}`` (Linear).  The offset convolutions of a ``dcn_stages``
+model (no counterpart either) go out as Convolution2D ``extractor/resnet/<stage>/<block>/conv2_offset/{W,b}`` with their 18 or 27 logical
+outputs; the deformable layer's own filter stays ``.../conv2/W``, so a ResNet-50 file loads as before and leaves the offsets at zero.
 
 Storage here differs only mechanically - conv W (Cout_p, KH, KW, Cin_p) with zero-padded channels, NHWC
 flattening for ``fc1``, ``rpn/loc`` + ``rpn/score`` fused into ``rpn/loc_score``, ``head/cls_loc`` + ``head/score``
@@ -49,6 +51,8 @@ class ChainerNpzMap(object):
             for b in blocks:
                 for cv in (b.conv1, b.conv2, b.conv3) + ((b.conv4,) if b.project else ()):
                     self._add_conv(cv)
+                if getattr(b.conv2, 'offset', None) is not None:        # a deformable block (dcn_stages): its offset convolution
+                    self._add_conv(b.conv2.offset)
                 self.bns += [b.bn1, b.bn2, b.bn3] + ([b.bn4] if b.project else [])
         for cv in (ext.toplayer, ext.conv_p4, ext.conv_p3, ext.conv_p2, ext.conv_p6, ext.lat_p4, ext.lat_p3, ext.lat_p2,
                    rpn.conv, head.conv1, head.fc2, head.conv2) + tuple(head.mask_convs):

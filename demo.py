@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model,  # noqa: E402
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_dcn_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model, dcn_settings_of,  # noqa: E402
                                                 extension_settings, read_labels, tta_settings, use_boxpost, use_score_preset, use_tta)
 
 IMAGE_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
@@ -55,6 +55,7 @@ def build_parser():
     parser.add_argument('--kp-thresh', type=float, default=None,
                         help='keypoint heads: the heat-map logit from which a keypoint is drawn (%s)' % DEFAULT_KP_THRESH)
     add_extension_flags(parser)
+    add_dcn_flags(parser)
     add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--json', type=int, default=0, choices=[0, 1], help='1: also write <stem>.json per image')
@@ -117,6 +118,7 @@ def check_args(args):
     tta_settings(args.tta_sizes, args.tta_hflip, args.tta_max_size, 1)      # a max size without views
     boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
     extension_settings(args)
+    dcn_settings_of(args)
     return collect_inputs(args.inputs)
 
 

@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 sys.path.insert(0, ROOT)
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model,  # noqa: E402
+from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_dcn_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model, dcn_settings_of,  # noqa: E402
                                                 extension_settings, read_labels, tta_settings, use_boxpost, use_tta)
 
 SYNTHETIC_VAL_IMAGES = 16           # train.py's synthetic val split of --eval-images 0
@@ -45,6 +45,7 @@ def build_parser():
     parser.add_argument('--score-thresh', type=float, default=None, help="overrides the 'evaluate' preset's score threshold (0.05)")
     parser.add_argument('--no-results', action='store_true', help='do not write the COCO results files')
     add_extension_flags(parser)
+    add_dcn_flags(parser)
     add_tta_flags(parser)
     add_boxpost_flags(parser)
     parser.add_argument('--out', '-o', default='result_eval', help='Output directory')
@@ -58,6 +59,7 @@ def check_args(args):
     if world > 1:
         raise ValueError('evaluate.py runs in a single process; with %d ranks it is not supported' % world)
     extension_settings(args)
+    dcn_settings_of(args)
     return boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
 
 

@@ -1211,6 +1211,38 @@ int mrcnn_point_subdivide(const float *grid, int D, int S, int ld, int n_channel
 int mrcnn_point_scatter(const float *pred, int ld, int n_channels, const int32_t *label, const int32_t *index, int D, int n_sel, int cells,
                         float *grid, void *stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Deformable convolution (v1) and its modulated form (v2) around a 3x3, stride 1, pad 1, dilation 1 layer with one deformable group
+ * (csrc/deform.hip, csrc/deform_common.h).  No counterpart in the reference.  Every other KH, KW, stride, pad,
+ * dilation or groups: MRCNN_E_UNSUPPORTED.  The GEMM of the layer is the caller's: mrcnn_conv2d_* as a 1x1 layer over cols.
+ * x (N,H,W,C) NHWC, C % 4 == 0.  off (N,H,W,ld_off): for output pixel (n, y, x) and tap k = 3 * i + j, channels 2k, 2k + 1 = (dy, dx) and,
+ *   modulated, channel 18 + k = a logit; only these 18 / 27 channels are read (ld_off >= that).  The sampling position is
+ *   (y - 1 + i + dy, x - 1 + j + dx); the sample is the bilinear interpolation of the four cells around it, a cell outside the map counting
+ *   as zero, times sigmoid(logit) when modulated.  Positions are compared in float before any conversion to an integer: a position at or
+ *   beyond -1 or H (W), a huge or a non-finite offset samples zero, has a zero gradient and never indexes memory.
+ * deform_cols_fwd: cols (N,H,W,9*C), tap-major: cols[n, y, x, k * C + c] = the sample of channel c at tap k.  One launch.
+ * deform_offset_bwd: g_off (N,H,W,ld_off), the WHOLE row: channels 2k, 2k + 1 = m * sum_c g_cols * d sample / d (py, px), modulated channel
+ *   18 + k = m (1 - m) * sum_c g_cols * sample, every other channel 0.  A wave reduction over the channels in a fixed order.  One launch.
+ * deform_input_bwd: gx (N,H,W,C) = [accumulate: the value gx held, first] + the sum over every (source pixel, tap, corner) that touches the
+ *   cell, in ascending (source pixel, tap, corner) order, of weight * m * g_cols; relu_x (N,H,W,C), nullable: the TOTAL is zeroed where
+ *   relu_x <= 0.  No float atomics - the same bits on every run: an inverted index is built per call in ws (counts by integer atomics, an
+ *   exclusive scan, a fill), each destination's list is ordered and summed by one wave; a list of more than 256 entries is ordered and
+ *   summed by one workgroup in chunks of 128 entries whose partial sums are added in chunk order.  C <= 512.  One memset, five launches.
+ *   ws: mrcnn_deform_input_bwd_workspace_bytes(N, H, W) bytes (0 for sizes the call refuses), 16-byte aligned.
+ * x, cols, g_cols, gx, relu_x 16-byte aligned.  N == 0 succeeds without a launch.  Errors, before any launch: MRCNN_E_UNSUPPORTED for the
+ * geometry above, N * H * W * 36 above 2^31 - 1, H or W above 2^20, C > 512 (input_bwd); MRCNN_E_INVALID for a modulated / accumulate outside
+ * 0..1, a negative N, a non-positive H, W, C, C % 4 != 0, ld_off below 18 / 27, a NULL or misaligned pointer; MRCNN_E_WORKSPACE for a short
+ * or NULL workspace.
+ * ---------------------------------------------------------------------------------------- */
+int mrcnn_deform_cols_fwd_f32(const float *x, const float *off, int ld_off, int modulated, int N, int H, int W, int C, int KH, int KW, int stride,
+                              int pad, int dilation, int groups, float *cols, void *stream);
+int mrcnn_deform_offset_bwd_f32(const float *g_cols, const float *x, const float *off, int ld_off, int modulated, int N, int H, int W, int C,
+                                int KH, int KW, int stride, int pad, int dilation, int groups, float *g_off, void *stream);
+size_t mrcnn_deform_input_bwd_workspace_bytes(int N, int H, int W);
+int mrcnn_deform_input_bwd_f32(const float *g_cols, const float *off, int ld_off, int modulated, int N, int H, int W, int C, int KH, int KW,
+                               int stride, int pad, int dilation, int groups, float *gx, const float *relu_x, int accumulate, void *ws,
+                               size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,8 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (EXTENSIONS, add_boxpost_flags, add_extension_flags, add_tta_flags, boxpost_settings, chain_kwargs,  # noqa: E402
-                                                check_resume, extension_settings, model_kwargs, read_labels, state_records, tta_settings, use_boxpost,
+from chainer_maskrcnn.inference_options import (DCN_NOUN, EXTENSIONS, NO_DCN, add_boxpost_flags, add_dcn_flags, add_extension_flags, add_tta_flags, boxpost_settings, chain_kwargs,  # noqa: E402
+                                                check_resume, dcn_model_kwargs, dcn_settings_of, extension_settings, model_kwargs, read_labels, state_records, tta_settings, use_boxpost,
                                                 use_tta)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
 
@@ -34,7 +34,7 @@ NO_OPTIM = {'accum_steps': 1, 'grad_clip': 0.0, 'schedule': None}      # what a 
 NO_AUGMENT = {'hflip': 0, 'min_sizes': None, 'seed': AUGMENT_SEED}     # what a trainer state without the 'augment' key was trained with
 # what a resumed run must repeat of its trainer_<it>.pt, in the order it is checked: (key, a state without the key, the noun of the refusal)
 RESUME_CHECKS = ((('augment', NO_AUGMENT, 'augmentation'),) + tuple((e.state_key, e.off, e.settings_noun) for e in EXTENSIONS if e.state_key)
-                 + (('freeze', NO_FREEZE, 'freezing'), ('optim', NO_OPTIM, 'the optimizer recipe')))
+                 + (('dcn', NO_DCN, DCN_NOUN), ('freeze', NO_FREEZE, 'freezing'), ('optim', NO_OPTIM, 'the optimizer recipe')))
 
 
 def build_parser(keypoints=False):
@@ -131,6 +131,7 @@ def build_parser(keypoints=False):
                              'of the next example of its batch, pasted over it (occluded masks are cut, boxes recomputed, covered instances '
                              'dropped); mask heads only, --batch-size >= 2, --synthetic 0.  0 = off')
     add_extension_flags(parser, both, training=True)
+    add_dcn_flags(parser, both)
     parser.add_argument(*both('--box-loss'), default='smooth_l1', choices=['smooth_l1', 'giou', 'diou', 'ciou'],
                         help='box regression loss of the RoI head: smooth_l1 = the reference\'s, on the encoded deltas; giou / diou / ciou = on '
                              'the decoded box against the decoded target (FPNMaskRCNNTrainChain box_loss; same targets, normaliser and '
@@ -279,10 +280,11 @@ def run(args, keypoints=False):
     eval_boxpost = _eval_boxpost_settings(args)
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
     extensions = extension_settings(args, '--eval-tta-', training=True, keypoints=keypoints)
+    dcn = dcn_settings_of(args)
     box_loss = box_loss_settings(args.box_loss, args.rpn_box_loss, args.box_loss_weight, args.rpn_box_loss_weight)
     freeze = freeze_settings(args)
     optim, schedule = optim_settings(args)
-    recorded = dict({'augment': augment_settings(args), 'freeze': freeze, 'optim': optim}, **state_records(extensions))     # of trainer_<it>.pt
+    recorded = dict({'augment': augment_settings(args), 'dcn': dcn, 'freeze': freeze, 'optim': optim}, **state_records(extensions))     # of trainer_<it>.pt
     if resume is not None:
         for key, off_record, noun in RESUME_CHECKS:
             check_resume(resume, key, off_record, recorded[key], noun, args.resume)
@@ -327,7 +329,8 @@ def run(args, keypoints=False):
         n_fg, K = 1, 20 if args.dataset == 'depth' else 17          # DepthDataset.n_keypoints / COCOKeypointsLoader.n_keypoints
         labels = None
         faster_rcnn = MaskRCNN(n_fg_class=n_fg, n_keypoints=K, backbone=args.backbone, head_arch=args.head_arch, n_mask_convs=args.n_mask_convs,
-                               min_size=args.min_size, max_size=args.max_size, device=dev, **model_kwargs(extensions, keypoints=True))
+                               min_size=args.min_size, max_size=args.max_size, device=dev, **model_kwargs(extensions, keypoints=True),
+                               **dcn_model_kwargs(dcn))
         loss_fun = calc_keypoint_loss
         if K != 17:         # train_keypoints.py:122: lambda x, y, z, w: calc_mask_loss(x, y, z, w, num_keypoints=n_keypoints)
             loss_fun = lambda x, y, z, w: calc_keypoint_loss(x, y, z, w, num_keypoints=K)
@@ -336,7 +339,8 @@ def run(args, keypoints=False):
     else:
         labels = read_labels(args.label_file)
         n_fg, K = len(labels) if labels else 80, None
-        faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, **model_kwargs(extensions))
+        faster_rcnn = MaskRCNN(n_fg_class=n_fg, backbone=args.backbone, head_arch=args.head_arch, device=dev, **model_kwargs(extensions),
+                               **dcn_model_kwargs(dcn))
         model = FPNMaskRCNNTrainChain(faster_rcnn, mask_loss_fun=calc_mask_loss, gemm_arithmetic=args.gemm_arithmetic, **chain_kwargs(extensions),
                                       **box_loss)
     faster_rcnn.use_preset('evaluate')
