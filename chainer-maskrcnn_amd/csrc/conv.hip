@@ -1177,7 +1177,7 @@ void filter_plan(const ConvP &p, int &ksplit, int &kchunk) {
 // FWD / BWD_DATA split-K: when even the smallest useful tile leaves CUs idle (deep layers: few pixels, long K) the K
 // steps are split over `ksplit` workgroups per tile; partial tiles go to slabs and are summed in fixed order.
 template <int MODE>
-void data_plan(ConvP &p, TileChoice &t, int nsteps) {
+void data_plan_fill(ConvP &p, TileChoice &t, int nsteps) {
     t = choose_tile<MODE>(p.M, p.Ng, 1);
     const long long tiles = (long long)mrcnn::cdiv(p.M, t.bm) * mrcnn::cdiv(p.Ng, t.bn);
     const long long fill = (long long)g_plan_fill * g_cus();
@@ -1203,6 +1203,28 @@ void data_plan(ConvP &p, TileChoice &t, int nsteps) {
     if (ks < 2) return;
     p.kchunk = (int)((nsteps + ks - 1) / ks);
     p.ksplit = (nsteps + p.kchunk - 1) / p.kchunk;
+}
+// Arithmetic 3 is held to 2e-6 of max|y| (tests/test_conv_paths_gpu.py), and one float32 accumulator over all the K steps of a deep
+// layer loses more than that, as the float32 MFMA does: measured on an MI355X, without bias, 1.2e-6 - 1.3e-6 at K = 1152, 1.7e-6 -
+// 1.8e-6 at K = 2304, 2.3e-6 - 2.9e-6 at K = 4608 (about 4e-8 sqrt(K)).  A forward launch of DEEP_STEPS or more K steps (K >= 4096)
+// in which a tile would add up all of K - the un-split launch, and the whole tiles of a tail split, which then gives way - therefore
+// adds up DEEP_SPLIT parts of K in slabs, like any split-K launch.
+// DEEP_STEPS is NOT taken from that error model: by it K = 2304 has some 10 % of headroom on the seeds that were run, and a rule that
+// kept a margin would have to start near K = 1200.  It is set where no launch of the shipped model changes: the 3x3 layers over 256
+// channels behind the backbone (K = 2304) keep their launches, the shipped arithmetic runs a backbone layer's forward pass on the
+// float32 MFMA, res5's 3x3 layers take Winograd and the box head's first layer (K = 12544) is split by the plan above.  What it reaches
+// is the deformable layers' 1x1 GEMM over 9 C channels when arithmetic 3 is asked for everywhere.  (The Winograd GEMMs plan through
+// here too: K = Cin, at most 64 steps.)
+constexpr int DEEP_STEPS = 128, DEEP_SPLIT = 4;
+bool deep_forward(int nsteps) { return g_split_mode[0] == 3 && nsteps >= DEEP_STEPS; }
+template <int MODE>
+void data_plan(ConvP &p, TileChoice &t, int nsteps) {
+    data_plan_fill<MODE>(p, t, nsteps);
+    if (MODE == MODE_FWD && !p.smallc && p.ksplit == 1 && deep_forward(nsteps)) {
+        p.tail_ks = 0;
+        p.kchunk = (nsteps + DEEP_SPLIT - 1) / DEEP_SPLIT;
+        p.ksplit = (nsteps + p.kchunk - 1) / p.kchunk;
+    }
 }
 size_t data_ws_bytes(const ConvP &p, long long ldc) { return p.ksplit > 1 ? (size_t)p.ksplit * p.M * ldc * sizeof(float) : 0; }
 size_t tail_ws_bytes(const ConvP &p, const TileChoice &t) {
@@ -2125,6 +2147,8 @@ extern "C" size_t mrcnn_conv2d_workspace_bytes(int N, int H, int W, int Cin, int
     // tail split: at most one round of workgroup slots of partial 128x128 tiles (<= 4 workgroups per CU)
     const size_t tail = (size_t)4 * g_cus() * 128 * 128 * sizeof(float);
     size_t bytes = std::max((size_t)need * 16 * sizeof(float), tail);
+    // a deep forward launch under arithmetic 3 splits K whatever its tile count (data_plan)
+    if (Cin % BK == 0 && deep_forward(KH * KW * (Cin / BK))) bytes = std::max(bytes, (size_t)a * DEEP_SPLIT * sizeof(float));
     // the same query serves forward (Cin->Cout) and backward-data (Cout->Cin)
     if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD)) bytes = std::max(bytes, wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD));
     if (wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, PASS_BWD_DATA)) bytes = std::max(bytes, wino_ws_bytes(N, H, W, Cout, Cin, PASS_BWD_DATA));

@@ -8,7 +8,8 @@ threshold or of a kernel's occupancy can then no longer move a case onto another
 
 Reference: torch CPU float64 (F.conv2d, F.conv_transpose2d, torch.nn.grad.conv2d_weight); error = max|got - ref| / max|ref|.
 Bars (the ones tests/test_conv_gpu.py holds these kernels to): direct float32 forward 1e-5, backward-data / filter 2e-5, bias gradient
-2e-5, Winograd F(2x2) 3e-5, F(4x4) 3e-4; arithmetic 3 (bf16x6): direct 2e-6, Winograd 3e-4.  Split-K / tail-split: the bar of the pass."""
+2e-5, Winograd F(2x2) 3e-5, F(4x4) 3e-4; arithmetic 3 (bf16x6): direct 2e-6, Winograd 3e-4.  Split-K / tail-split: the bar of the pass.
+COLS_CASES: the 1x1 layer over the 9 C channels of a deformable layer's columns, K up to 4608, all three passes in both arithmetics."""
 import contextlib
 
 import pytest
@@ -68,13 +69,17 @@ def rel(got, ref):
 class Layer:
     """Random operands of one layer (N, H, W, Cin, Cout, K, stride, pad), on the CPU and on the device, and its float64 results."""
 
-    def __init__(self, case, seed):
+    def __init__(self, case, seed, forward_only=False):
         N, H, W, Cin, Cout, K, s, p = self.case = case
         self.s, self.p = s, p
         g = torch.Generator().manual_seed(seed + sum(case))
         self.x = torch.randn((N, H, W, Cin), generator=g)
         self.w = torch.randn((Cout, K, K, Cin), generator=g) / (K * K * Cin) ** 0.5
         self.b = torch.randn((Cout,), generator=g)
+        self._ref = {}
+        if forward_only:                     # a case too large to keep the operands of the backward passes as well
+            self.xd, self.wd, self.bd = (t.to(DEV) for t in (self.x, self.w, self.b))
+            return
         Ho, Wo = hnn.conv_out(H, K, s, p), hnn.conv_out(W, K, s, p)
         self.gy = torch.randn((N, Ho, Wo, Cout), generator=g)
         self.base_x = torch.randn((N, H, W, Cin), generator=g)                    # what the accumulating calls add to
@@ -85,6 +90,8 @@ class Layer:
         self._ref = {}
 
     def ref_y(self, bias):
+        if not bias and bias not in self._ref and True in self._ref:      # the bias is added last: one convolution serves both
+            self._ref[bias] = self._ref[True] - self.b.double()
         if bias not in self._ref:
             self._ref[bias] = _ref_conv(self.x, self.w, self.b if bias else None, self.s, self.p)
         return self._ref[bias]
@@ -286,6 +293,126 @@ def test_float32_split_k_backward_data(case):
     with settings():
         _fill_that_splits(BWD_DATA, case)
         Layer(case, 32).check_backward_data(direct_tol(BWD_DATA, 0))
+
+
+# ---- the 1x1 layer over the 9 C channels of a deformable layer's columns, executed ----------------------------------
+# K = 1152 / 2304 / 4608: the deepest GEMMs of the library.  The plan of a 1x1 layer depends on its pixel count alone - and on the chip: the
+# tail split and the filter gradient's ksplit count workgroup slots with the occupancy the runtime reports for the kernel, which a host
+# without a device replaces by 2 per CU, so the pixel counts below were found with the host-only query ON an MI355X (every count up to
+# 2200 and 64 k, 64 k + 1 up to 89600) and are asserted there.  For every (width, pass, path) the section tabulates for the device the
+# list holds the SMALLEST pixel count that takes that path, as a map of exactly that many pixels, and runs all three passes on it: one
+# case serves several pairs.  A forward split-K and a direct backward-data launch start at one pixel; (1, 5, 7) stands beside (1, 1, 1)
+# so that they also run on more than one row.  Filter gradient: the first split (512 pixels, two K chunks) and the largest ksplit of each
+# width - 85 at 21760 pixels, 21 at 5376, 5 at 1280.  A forward tail split is on no line of the table; at K = 4608 it starts at 24577
+# pixels (a 453 MB operand), where only the forward pass is run; at K = 2304 it starts at 49153 pixels and at K = 1152 beyond 89600:
+# left out.  The float64 references of every other case take under a second on the CPU.
+#   case, (forward, backward data, filter gradient) paths, ksplit of the filter gradient, the passes that are run
+ALL3 = (FWD, BWD_DATA, BWD_FILTER)
+COLS_CASES = [
+    ((2, 16, 16, 1152, 128, 1, 1, 0), (SPLIT_K, DIRECT, SPLIT_K), 2, ALL3),                # res3, C = 128
+    ((1, 3, 2731, 1152, 128, 1, 1, 0), (DIRECT, DIRECT, SPLIT_K), 29, ALL3),               # 8193 pixels: the first direct forward
+    ((2, 85, 128, 1152, 128, 1, 1, 0), (DIRECT, DIRECT, SPLIT_K), 85, ALL3),               # 21760: the largest ksplit at this depth
+    ((2, 16, 16, 2304, 256, 1, 1, 0), (SPLIT_K, DIRECT, SPLIT_K), 2, ALL3),                # res4, C = 256
+    ((1, 17, 241, 2304, 256, 1, 1, 0), (DIRECT, DIRECT, SPLIT_K), 15, ALL3),               # 4097: the first direct forward
+    ((2, 48, 56, 2304, 256, 1, 1, 0), (DIRECT, DIRECT, SPLIT_K), 21, ALL3),                # 5376: the largest ksplit
+    ((1, 19, 283, 2304, 256, 1, 1, 0), (DIRECT, TAIL_SPLIT, SPLIT_K), 19, ALL3),           # 5377: the first tail-split backward data
+    ((1, 1, 1, 4608, 512, 1, 1, 0), (SPLIT_K, SPLIT_K, DIRECT), 1, ALL3),                  # res5, C = 512
+    ((1, 5, 7, 4608, 512, 1, 1, 0), (SPLIT_K, SPLIT_K, DIRECT), 1, ALL3),
+    ((1, 1, 193, 4608, 512, 1, 1, 0), (SPLIT_K, DIRECT, DIRECT), 1, ALL3),                 # the first direct backward data
+    ((2, 16, 16, 4608, 512, 1, 1, 0), (SPLIT_K, DIRECT, SPLIT_K), 2, ALL3),
+    ((2, 20, 32, 4608, 512, 1, 1, 0), (SPLIT_K, DIRECT, SPLIT_K), 5, ALL3),                # 1280: the largest ksplit
+    ((1, 3, 683, 4608, 512, 1, 1, 0), (DIRECT, DIRECT, SPLIT_K), 5, ALL3),                 # 2049: the first direct forward
+    ((1, 1, 2689, 4608, 512, 1, 1, 0), (DIRECT, TAIL_SPLIT, SPLIT_K), 5, ALL3),            # the first tail-split backward data
+    ((1, 7, 3511, 4608, 512, 1, 1, 0), (TAIL_SPLIT, TAIL_SPLIT, SPLIT_K), 5, (FWD,)),      # 24577: the first tail-split forward
+]
+
+
+@pytest.fixture(scope='module')
+def cols_layer():
+    """The operands and float64 results of one case, shared by its two arithmetics: one layer at a time, none after the last case."""
+    kept = {}
+
+    def get(case, passes):
+        if case not in kept:
+            kept.clear()
+            kept[case] = Layer(case, 81, forward_only=passes == (FWD,))
+        return kept[case]
+
+    def release():
+        kept.clear()
+        torch.cuda.empty_cache()
+    get.release = release
+    yield get
+    release()
+
+
+def test_cols_cases_cover_the_table_of_the_deformable_layer():
+    """Host only: widths 128 / 256 / 512 with K = 9 C; at K = 4608 direct, tail-split and split-K in forward and backward data and split-K
+    in the filter gradient, each of them run; every pair DESIGN.md section 3.25 tabulates for the device; the largest ksplit of each width."""
+    assert {(c[3], c[4]) for c, _, _, _ in COLS_CASES} == {(1152, 128), (2304, 256), (4608, 512)}
+    run = {(c[4], pass_, paths[pass_]) for c, paths, _, passes in COLS_CASES for pass_ in passes}
+    assert {(512, p, path) for p in (FWD, BWD_DATA) for path in (DIRECT, TAIL_SPLIT, SPLIT_K)} | {(512, BWD_FILTER, SPLIT_K)} <= run
+    table = {(128, FWD, DIRECT), (128, BWD_DATA, DIRECT), (256, FWD, DIRECT), (256, BWD_DATA, DIRECT), (256, BWD_DATA, TAIL_SPLIT),
+             (512, FWD, SPLIT_K), (512, FWD, DIRECT), (512, BWD_DATA, DIRECT)}
+    assert table | {(C, BWD_FILTER, SPLIT_K) for C in (128, 256, 512)} <= run
+    assert {C: max(ks for c, _, ks, _ in COLS_CASES if c[4] == C) for C in (128, 256, 512)} == {128: 85, 256: 21, 512: 5}
+
+
+def _deep_forward(case, arith):
+    """csrc/conv.hip deep_forward: under arithmetic 3 a forward launch of K >= 4096 never adds all of K in one accumulator."""
+    return arith == 3 and case[3] * case[5] * case[5] >= 4096
+
+
+@pytest.mark.parametrize('arith', [0, 3])          # (the inner loop: a case's two arithmetics share its layer)
+@pytest.mark.parametrize('case,paths,ksplit,passes', COLS_CASES, ids=['x'.join(map(str, c[:4])) for c, _, _, _ in COLS_CASES])
+def test_cols_layer_all_three_passes(case, paths, ksplit, passes, arith, cols_layer):
+    """All three passes of every case, path asserted first.  The regression test of csrc/conv.hip's deep_forward rule: with all 144 K steps
+    of K = 4608 in one float32 accumulator the un-split forward launch under arithmetic 3 measured 2.30e-06 at 2049 pixels and 2.92e-06 at
+    2689 (without bias) against that arithmetic's bar of 2e-6 - the float32 MFMA measures 2.85e-06 / 3.17e-06 against its bar of 1e-5, and
+    the same launch 1.2e-06 - 1.3e-06 at K = 1152 and 1.7e-06 - 1.8e-06 at K = 2304 -; in four parts of K it measures 1.02e-06 and 8.53e-07.
+    The whole tiles of a tail split add up all of K as well (24577 pixels under the float32 MFMA: 2.88e-06 without bias), so under
+    arithmetic 3 the rule takes that case too (8.19e-07); its three forward variants run in both arithmetics, the reference without
+    bias being the one with bias minus the bias.
+    The backward passes run first, so that a forward failure does not hide them."""
+    with settings(split=(arith,) * 3):
+        if _deep_forward(case, arith) and paths[FWD] != SPLIT_K:      # four parts of K instead of one sum, tail split or not
+            paths = (SPLIT_K,) + paths[1:]
+            assert plan_of(FWD, case)['ksplit'] == 4
+        for pass_ in ALL3:
+            pl = plan_of(pass_, case)
+            assert pl['path'] == paths[pass_] and pl['arithmetic'] == arith and pl['wino_m'] == 0 and pl['smallc'] == 0, (pass_, pl)
+            assert (pl['ksplit'] > 1) == (paths[pass_] == SPLIT_K) and (pl['tail_ks'] > 0) == (paths[pass_] == TAIL_SPLIT), (pass_, pl)
+        assert pl['ksplit'] == ksplit, pl
+        if paths[BWD_FILTER] == SPLIT_K:
+            assert pl['ksplit'] > 1
+        L = cols_layer(case, passes)
+        try:
+            if BWD_DATA in passes:
+                L.check_backward_data(direct_tol(BWD_DATA, arith))
+            if BWD_FILTER in passes:
+                L.check_backward_filter(direct_tol(BWD_FILTER, arith))
+            # the same three variants everywhere; with the bias first, Layer.ref_y takes the reference without it from that one
+            L.check_forward(direct_tol(FWD, arith), variants=((True, False), (True, True), (False, False)))
+        finally:
+            if case == COLS_CASES[-1][0] and arith == 3:
+                cols_layer.release()
+
+
+# (case index, pass, the path from that pixel count on): one pixel fewer takes another path - the host-only query on the same chip
+COLS_BOUNDARIES = [(1, FWD, DIRECT), (4, FWD, DIRECT), (6, BWD_DATA, TAIL_SPLIT), (9, BWD_DATA, DIRECT), (12, FWD, DIRECT),
+                   (13, BWD_DATA, TAIL_SPLIT), (14, FWD, TAIL_SPLIT), (0, BWD_FILTER, SPLIT_K), (3, BWD_FILTER, SPLIT_K),
+                   (10, BWD_FILTER, SPLIT_K)]
+
+
+@pytest.mark.parametrize('index,pass_,path', COLS_BOUNDARIES)
+def test_cols_cases_are_the_first_of_their_path(index, pass_, path):
+    """Nothing launched: a case named the first of a path sits on the boundary - its pixel count takes the path, one pixel fewer does not."""
+    case = COLS_CASES[index][0]
+    pixels = case[0] * case[1] * case[2]
+    with settings():
+        assert plan_of(pass_, case)['path'] == path == COLS_CASES[index][1][pass_]
+        assert plan_of(pass_, (1, 1, pixels - 1) + case[3:])['path'] != path
+        assert plan_of(pass_, (1, 1, pixels) + case[3:])['path'] == path          # the count decides, not the map's shape
 
 
 # ---- tail split on a small case found through the query --------------------------------------------------------------------------------
