@@ -507,6 +507,23 @@ def random_keys_dev(shape, state):
     return out
 
 
+class KeyStream(object):
+    """A sampler's keys: ``seed`` and the device-resident ``state`` every draw advances (created by the first draw, and anew when the
+    device changes).  The trainer state saves the two (MomentumSGD.state_dict, 'samplers')."""
+
+    def __init__(self, seed):
+        self.seed, self.state = seed, None
+
+    def set_seed(self, seed, device=None):
+        self.seed = seed
+        self.state = None if device is None else seed_state(seed, device)
+
+    def draw(self, shape, device):
+        if self.state is None or self.state.device != device:
+            self.state = seed_state(self.seed, device)
+        return random_keys_dev(shape, self.state)
+
+
 def sgd_momentum_wd(p, g, v, lr, momentum=0.9, weight_decay=5e-4):
     _ck(p, g, v)
     check(lib().mrcnn_sgd_momentum_wd_f32(ptr(p), ptr(g), ptr(v), p.numel(), lr, momentum, weight_decay, stream_ptr()))

@@ -29,12 +29,12 @@ class AnchorTargetCreator(object):
 
     def __init__(self, n_sample=256, pos_iou_thresh=0.7, neg_iou_thresh=0.3, pos_ratio=0.5):
         self.n_sample, self.pos_iou_thresh, self.neg_iou_thresh, self.pos_ratio = n_sample, pos_iou_thresh, neg_iou_thresh, pos_ratio
-        self.seed = 1 << 32
-        self._state = None
+        self.keys = ops.KeyStream(1 << 32)
 
-    def set_seed(self, seed):
-        self.seed = seed
-        self._state = None
+    seed = property(lambda self: self.keys.seed)
+
+    def set_seed(self, seed, device=None):
+        self.keys.set_seed(seed, device)
 
     def __call__(self, bbox, anchor, img_size, n_gt=None, keys=None, per_image_hw=None):
         """bbox (N,G,4) (or (G,4)), anchor (A,4) -> (loc (N,A,4), label (N,A)).  per_image_hw (N,2): each image's own size."""
@@ -44,9 +44,7 @@ class AnchorTargetCreator(object):
         if n_gt is None:
             n_gt = torch.full((N,), G, dtype=torch.int32, device=bbox.device)
         if keys is None:
-            if self._state is None or self._state.device != bbox.device:
-                self._state = ops.seed_state(self.seed, bbox.device)
-            keys = ops.random_keys_dev((N, anchor.shape[0]), self._state)
+            keys = self.keys.draw((N, anchor.shape[0]), bbox.device)
         return ops.anchor_target(anchor, bbox.contiguous(), n_gt, img_size, keys, self.n_sample, self.pos_iou_thresh,
                                  self.neg_iou_thresh, self.pos_ratio, per_image_hw=per_image_hw)
 
@@ -117,14 +115,20 @@ DEFAULT_GEMM_ARITHMETIC = 'bf16x6_behind_backbone'
 BOX_LOSSES = ('smooth_l1', 'giou', 'diou', 'ciou')
 
 
+def _weight(name, weight):
+    """The one rule of the chain's loss weights: a finite number above 0, as a float."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
+        raise ValueError('%s must be a finite number above 0, got %r' % (name, weight))
+    return float(weight)
+
+
 def box_loss_settings(box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_weight=1.0, rpn_box_loss_weight=1.0):
     """The four box-loss arguments of FPNMaskRCNNTrainChain as a dict, checked (the constructor and train.py's flags share the rule):
     ValueError for a name outside BOX_LOSSES, a weight that is not a finite number above 0, a weight other than 1.0 with 'smooth_l1'."""
     for arg, name, weight in (('box_loss', box_loss, box_loss_weight), ('rpn_box_loss', rpn_box_loss, rpn_box_loss_weight)):
         if name not in BOX_LOSSES:
             raise ValueError('%s must be one of %s, got %r' % (arg, list(BOX_LOSSES), name))
-        if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
-            raise ValueError('%s_weight must be a finite number above 0, got %r' % (arg, weight))
+        _weight(arg + '_weight', weight)
         if name == 'smooth_l1' and weight != 1.0:
             raise ValueError("%s_weight applies to giou / diou / ciou; %s='smooth_l1' takes 1.0 only, got %r" % (arg, arg, weight))
     return dict(box_loss=box_loss, rpn_box_loss=rpn_box_loss, box_loss_weight=float(box_loss_weight),
@@ -134,17 +138,26 @@ def box_loss_settings(box_loss='smooth_l1', rpn_box_loss='smooth_l1', box_loss_w
 def mask_iou_weight_setting(weight):
     """The mask_iou_weight argument of FPNMaskRCNNTrainChain as a float, checked like the box-loss weights: ValueError unless it is a finite
     number above 0."""
-    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
-        raise ValueError('mask_iou_weight must be a finite number above 0, got %r' % (weight,))
-    return float(weight)
+    return _weight('mask_iou_weight', weight)
 
 
 def point_loss_weight_setting(weight):
     """The point_loss_weight argument of FPNMaskRCNNTrainChain as a float, checked like mask_iou_weight: ValueError unless it is a finite
     number above 0."""
-    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight) or weight <= 0:
-        raise ValueError('point_loss_weight must be a finite number above 0, got %r' % (weight,))
-    return float(weight)
+    return _weight('point_loss_weight', weight)
+
+
+def loss_rows(later_stages, mask_iou=False, point=False):
+    """The rows of the step's ``losses`` tensor: ([(observation key, row), ...] in row order, number of rows).  The reference's five, then a
+    (loc, cls) pair per box stage behind the first (Cascade R-CNN: stages 2 .. 1 + later_stages), the MaskIoU head's, the point head's."""
+    rows = [('rpn_loc_loss', 0), ('rpn_cls_loss', 1), ('roi_loc_loss', 2), ('roi_cls_loss', 3), ('mask_loss', 4)]
+    for k in range(2, 2 + later_stages):
+        loc = 5 + 2 * (k - 2)
+        rows += [('roi_loc_loss_s%d' % k, loc), ('roi_cls_loss_s%d' % k, loc + 1)]
+    for key, present in (('maskiou_loss', mask_iou), ('point_loss', point)):
+        if present:
+            rows.append((key, len(rows)))
+    return rows, len(rows)
 
 
 def select_gemm_arithmetic(name):
@@ -156,8 +169,26 @@ def select_gemm_arithmetic(name):
     core.FWD_EMULATION_IN_BACKBONE = bool(backbone_fwd)
 
 
+class _PendingBackward(object):
+    """What a forward pass leaves for backward(): the pyramid and the loss gradients the tape walk starts from."""
+
+    def __init__(self, features, g_locs, g_scores, g_box, g_mask, g_later, g_iou, point, early_rpn):
+        self.features = features
+        self.g_locs, self.g_scores = g_locs, g_scores       # RPN: (n, A, 4) and (n, A, 2)
+        self.g_box, self.g_mask = g_box, g_mask             # the head's box and mask outputs
+        self.g_later = g_later          # the later box stages' loss gradients, in stage order
+        self.g_iou = g_iou              # the MaskIoU loss gradient (None without the head)
+        self.point = point              # the point head's coords, rois and loss gradient 'g_pred' (None without the head)
+        self.early_rpn = early_rpn      # the RPN's per-level feature gradients where its backward pass ran in the forward pass, or None
+
+    def seeds(self):
+        """Every loss gradient, for the upstream-scaling pass."""
+        return ([self.g_locs, self.g_scores, self.g_box, self.g_mask] + list(self.g_later) + ([self.g_iou] if self.g_iou is not None else [])
+                + ([self.point['g_pred']] if self.point is not None else []))
+
+
 class FPNMaskRCNNTrainChain(object):
-    EARLY_RPN_BACKWARD = True       # A/B switch of the early RPN backward (see rpn_loss_branch in __call__)
+    EARLY_RPN_BACKWARD = True      # A/B switch of the early RPN backward (see _rpn_loss_branch)
     # (r6) the heads' ROIAlign backward passes ACCUMULATE into the feature gradients the early RPN backward left (the kernel then touches
     # only the patches RoIs land on instead of writing every map), instead of five add_ kernels over the pyramid afterwards: same sums in
     # another order - (rpn + box) + mask instead of (box + mask) + rpn -, 0.5 GB and 5 launches less on the main stream
@@ -224,16 +255,27 @@ class FPNMaskRCNNTrainChain(object):
         self.grad_ready_hook = None         # called with the lowest finished parameter offset during backward (DP overlap)
         self.sampler_keys = None            # (proposal keys, anchor keys) override for parity tests
         self.point_keys = None              # (mask rows, ops.point_n_keys) int32 keys of the PointRend training points, for parity tests
-        self.point_seed = 1 << 33
-        self._point_state = None            # the device-resident seed the point keys are drawn from
+        self._point_stream = ops.KeyStream(1 << 33)     # the point keys are drawn from it
         self.use_aux_stream = True          # independent branches (RPN losses, box head) on a second compute stream
         self.keep_outputs = False           # parity tests: keep the head outputs of the last step in self.outputs
         self.outputs = {}
         self._aux = {}
-        self._bwd_cascade = ()
-        self._bwd_maskiou = None
-        self._bwd_point = None
+        # Cascade R-CNN: the box stages behind the head; Mask Scoring R-CNN: the MaskIoU head (section 3.22);
+        # PointRend: the point head (section 3.24).  Their loss rows follow the reference's five, in this order
+        self._loss_rows, self._n_loss_rows = loss_rows(len(getattr(faster_rcnn, 'cascade_heads', [])),
+                                                       getattr(faster_rcnn, 'maskiou_head', None) is not None,
+                                                       getattr(faster_rcnn, 'point_head', None) is not None)
+        self._row = dict(self._loss_rows)
+        self.pending = None                 # the _PendingBackward of a forward pass whose backward pass has not run yet
         self._arith_found = None            # the process's GEMM arithmetic before this chain selected its own (restored by backward())
+
+    @property
+    def key_streams(self):
+        """The chain's ops.KeyStream objects by their names in the trainer state (MomentumSGD.state_dict, 'samplers')."""
+        streams = {'proposal_target_creator': self.proposal_target_creator.keys, 'anchor_target_creator': self.anchor_target_creator.keys}
+        if getattr(self.faster_rcnn, 'point_head', None) is not None:
+            streams['point_rend'] = self._point_stream
+        return streams
 
     def _aux_stream(self, dev):
         key = (dev.type, dev.index)
@@ -284,44 +326,14 @@ class FPNMaskRCNNTrainChain(object):
         features = m.extractor(m.to_nhwc4(imgs))
         m.rpn.train = True
         pk, ak = self.sampler_keys if self.sampler_keys is not None else (None, None)
-        stages = list(getattr(m, 'cascade_heads', []))        # Cascade R-CNN: the box stages behind the head
-        mh = getattr(m, 'maskiou_head', None)                 # Mask Scoring R-CNN: the MaskIoU head
-        iou_row = 5 + 2 * len(stages)                         # its loss row, behind the cascade's
-        ph = getattr(m, 'point_head', None)                   # PointRend: the point head
-        pt_row = iou_row + (1 if mh is not None else 0)       # its loss row, behind the cascade's and the MaskIoU's
-        losses = torch.empty((pt_row + (1 if ph is not None else 0), 2), dtype=torch.float32, device=dev)
-        br1 = {}
+        losses = torch.empty((self._n_loss_rows, 2), dtype=torch.float32, device=dev)
+        rpn = {}
 
         def rpn_loss_branch(locs, scores, anchors):
-            # Branch 1 (aux stream): anchor targets + RPN losses (:81-85).  It needs the RPN head outputs only, so it is
-            # enqueued before the proposal kernels and runs beside them.
-            A_ = anchors.shape[0]
-            aux.wait_stream(main)
-            with torch.cuda.stream(aux):
-                br1['loc'], br1['label'] = self.anchor_target_creator(bboxes, anchors, img_size, n_gt=n_gt, keys=ak, per_image_hw=per_hw)
-                if self.rpn_box_loss == 'smooth_l1':
-                    _, br1['g_locs'] = ops.smooth_l1(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), br1['label'].view(-1),
-                                                     n * A_, self.rpn_sigma, out=losses[0])
-                else:   # on the decoded box: every image's rows are relative to the shared anchors; the RPN's targets are not normalised
-                    _, br1['g_locs'] = ops.box_iou_loss(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), anchors, br1['label'].view(-1),
-                                                        n * A_, self.rpn_box_loss, (0., 0., 0., 0.), (1., 1., 1., 1.),
-                                                        weight=self.rpn_box_loss_weight, roi_period=A_, out=losses[0])
-                _, br1['g_scores'] = ops.softmax_ce(scores.view(n * A_, 2), br1['label'].view(-1), n * A_, 2, (1, 2, 0, 1),
-                                                    out=losses[1])
-                # The RPN's own backward pass needs nothing but these two gradients: when a backward pass is known to follow
-                # (MomentumSGD.update) it is enqueued HERE, on the aux stream, and fills the chip while the main stream walks the
-                # latency-bound proposal chain (decode, select, sort, NMS, target sampling: small kernels on a few CUs).  Its
-                # per-level feature gradients are kept and added in backward() where rpn.backward() used to run.
-                if self.EARLY_RPN_BACKWARD and self.backward_follows and aux is not main:
-                    for c1, c2, _, _ in m.rpn.tape:         # saved activations were allocated on the main stream and are released by
-                        for t_ in tuple(c1) + tuple(c2):    # this call: the allocator must not hand them out again before aux is done
-                            if torch.is_tensor(t_):
-                                t_.record_stream(aux)
-                    br1['g_feats'] = m.rpn.backward(br1['g_locs'].view(n, A_, 4), br1['g_scores'].view(n, A_, 2), None)
+            rpn.update(self._rpn_loss_branch(locs, scores, anchors, bboxes, img_size, n_gt, ak, per_hw, losses, main, aux))
 
         r = m.rpn.forward_padded(features, per_hw if per_hw is not None else img_size, scale, after_heads=rpn_loss_branch, batch_size=img_size)
         A = r['anchors'].shape[0]
-        gt_rpn_loc, gt_rpn_label, g_locs, g_scores = br1['loc'], br1['label'], br1['g_locs'], br1['g_scores']
         # Branch 2 (main stream): proposals -> sampled RoIs and targets
         t = self.proposal_target_creator.sample_batch(
             r['rois'], r['levels'], r['n_rois'], bboxes, labels, n_gt,
@@ -332,144 +344,207 @@ class FPNMaskRCNNTrainChain(object):
 
         # head (:88-89) on the n*n_sample sampled rows (padding rows have label -1 and get zero gradient): the box branch
         # runs on the aux stream concurrently with the (much larger) mask branch on the main stream
-        head = m.head
-        S = self.proposal_target_creator.n_sample
-        R = n * S
         scales = m.extractor.spatial_scales
         aux.wait_stream(main)
         with torch.cuda.stream(aux):
-            box = head.box_branch(features, t['rois_xy5'], t['sample_levels'], scales)
-            ld = head.out_p
-            g_box = torch.empty_like(box)
-            ops.softmax_ce(box, t['gt_roi_label'], R, head.n_class, (1, ld, 0, 1), Kfill=head.LOC0, gx=g_box, out=losses[3])
-            if self.box_loss == 'smooth_l1':
-                ops.smooth_l1(box, ld, t['gt_roi_loc'], t['gt_roi_label'], R, self.roi_sigma, gfill=ld - head.LOC0,
-                              col0=head.LOC0, gx=g_box, out=losses[2])
-            else:       # on the decoded box, against the sampled RoI the targets were encoded with
-                ops.box_iou_loss(box, ld, t['gt_roi_loc'], t['sample_roi'], t['gt_roi_label'], R, self.box_loss, self.loc_normalize_mean,
-                                 self.loc_normalize_std, weight=self.box_loss_weight, roi_period=R, gfill=ld - head.LOC0, col0=head.LOC0,
-                                 gx=g_box, out=losses[2])
-            # Stage k >= 2, behind stage k-1 on the same stream and the same N * n_sample rows (no resampling, no host sync): stage k-1's
-            # input boxes refined by its own deltas, re-levelled, re-matched at the stage's IoU threshold and re-encoded with the stage's
-            # std - a constant: no gradient flows through the refinement -, then the stage's box branch and the two losses of stage 1 with
-            # the same (sum, count) normalisation.  Losses rows 5 + 2 * (k - 2) (loc) and 6 + 2 * (k - 2) (cls).
-            g_boxes, casc = [g_box], []
-            prev = dict(roi=t['sample_roi'], label=t['gt_roi_label'], box=box)
-            for k, stage in enumerate(stages, 2):
-                ious, stds = m.cascade
-                ref = ops.cascade_refine(prev['roi'], prev['box'], head.LOC0, n, self.loc_normalize_mean, stds[k - 2],
-                                         per_hw if per_hw is not None else (float(H), float(W)), prev_label=prev['label'], gt_boxes=bboxes,
-                                         gt_labels=labels, n_gt=n_gt, iou_thresh=ious[k - 1], std_next=stds[k - 1])
-                box_k = stage.box_branch(features, ref['rois_xy5'], ref['levels'], scales)
-                g_k = torch.empty_like(box_k)
-                row = 5 + 2 * (k - 2)
-                ops.softmax_ce(box_k, ref['label'], R, head.n_class, (1, ld, 0, 1), Kfill=head.LOC0, gx=g_k, out=losses[row + 1])
-                if self.box_loss == 'smooth_l1':
-                    ops.smooth_l1(box_k, ld, ref['gt_loc'], ref['label'], R, self.roi_sigma, gfill=ld - head.LOC0, col0=head.LOC0, gx=g_k,
-                                  out=losses[row])
-                else:       # against the refined box the stage's targets were encoded with, with the stage's std
-                    ops.box_iou_loss(box_k, ld, ref['gt_loc'], ref['roi'], ref['label'], R, self.box_loss, self.loc_normalize_mean,
-                                     stds[k - 1], weight=self.box_loss_weight, roi_period=R, gfill=ld - head.LOC0, col0=head.LOC0, gx=g_k,
-                                     out=losses[row])
-                g_boxes.append(g_k)
-                ref['box'] = box_k
-                casc.append(ref)
-                prev = ref
-
-        rows = t['mask_rows']
-        if self.mask_loss_kind == 'generic':
-            g_mask = self._generic_mask_loss(t, features, scales, losses)
-            m_rois, m_levels, m_label = self._generic_inputs
-            mask_out = None
-        elif rows == S:
-            m_rois, m_levels, m_label = t['rois_xy5'], t['sample_levels'], t['gt_roi_label']
-        else:   # the first `rows` rows of every image block (positives come first)
-            m_rois = t['rois_xy5'].view(n, S, 5)[:, :rows].reshape(n * rows, 5)
-            m_levels = t['sample_levels'].view(n, S)[:, :rows].reshape(n * rows)
-            m_label = t['gt_roi_label'].view(n, S)[:, :rows].reshape(n * rows)
-        if self.mask_loss_kind != 'generic':
-            mask_out = head.mask_branch(features, m_rois, m_levels, scales)
-        if self.mask_loss_kind == 'generic':
-            pass
-        elif self.mask_loss_kind == 'mask_bce':
-            _, g_mask = ops.mask_bce(mask_out, t['gt_roi_mask'], m_label, out=losses[4])
-        else:
-            Rm, Hm, Wm, Cm = mask_out.shape
-            K = head.n_keypoints
-            xmap = (K, Hm * Wm * Cm, 1, Cm)
-            g_mask = torch.empty_like(mask_out) if ops.softmax_ce_fills_gradient(Rm * K, Hm * Wm, xmap) else torch.zeros_like(mask_out)
-            ops.softmax_ce(mask_out, t['gt_roi_mask'].view(-1), Rm * K, Hm * Wm, xmap, gx=g_mask, out=losses[4])
-
-        g_iou, iou = None, None
-        if mh is not None:
-            # Behind the mask loss, on the main stream and the mask branch's own rows: the IoU of each row's thresholded logits with its
-            # ground truth (integer counts), the head's input (pooled features + the max-pooled class logit, a constant), the head, the L2
-            # loss over the rows that have a target.  No host synchronisation.
-            m_label = m_label.contiguous()
-            iou = ops.maskiou_target(masks.contiguous(), n_gt, t['sample_roi'], t['gt_assign'], m_label, t['n_pos'], S, rows, mask_out, t['gt_roi_mask'],
-                                     mh.out_channels, label_base=1, want_counts=self.keep_outputs)
-            iou['input'] = mh.assemble(head.last_mask_pool, mask_out, m_label, label_base=1)
-            iou['pred'] = mh.forward(iou['input'])
-            _, g_iou = ops.maskiou_l2(iou['pred'], iou['target'], m_label, mh.out_channels, weight=self.mask_iou_weight, label_base=1,
-                                      out=losses[iou_row])
-            iou['g_pred'] = g_iou
-
-        pt = None
-        if ph is not None:
-            # Behind the mask loss, on the main stream and the mask branch's own rows: the training points from the coarse logits'
-            # uncertainty, the head's input sampled from the stride-4 level and the logits (constants for the head), the head, the soft
-            # targets from the ground-truth masks, the loss over the live rows.  No host synchronisation.
-            st = m.point_rend
-            m_label, m_rois = m_label.contiguous(), m_rois.contiguous()
-            keys = self.point_keys
-            if keys is None:
-                if self._point_state is None or self._point_state.device != dev:
-                    self._point_state = ops.seed_state(self.point_seed, dev)
-                keys = ops.random_keys_dev((mask_out.shape[0], ops.point_n_keys(st['train_points'], st['n_candidates'], st['n_important'])),
-                                           self._point_state)
-            pt = dict(coords=ops.point_train_coords(keys, mask_out, m_label, ph.out_channels, st['train_points'], st['n_candidates'],
-                                                    st['n_important'], label_base=1), rois=m_rois)
-            pt['input'] = ph.assemble(pt['coords'], m_rois, features[0], scales[0], mask_out)
-            pt['pred'] = ph.forward(pt['input'])
-            pt['target'] = ops.point_target(masks.contiguous(), n_gt, m_rois, t['gt_assign'], m_label, t['n_pos'], S, rows, pt['coords'])
-            _, pt['g_pred'] = ops.point_bce(pt['pred'], pt['target'], m_label, ph.out_channels, weight=self.point_loss_weight, label_base=1,
-                                            out=losses[pt_row])
+            box, g_boxes, casc = self._box_stages(features, t, scales, bboxes, labels, n_gt,
+                                                  per_hw if per_hw is not None else (float(H), float(W)), losses)
+        m_rois, m_levels, m_label, mask_out, g_mask = self._mask_loss(features, t, scales, losses)
+        iou = self._maskiou_branch(masks, n_gt, t, m_label, mask_out, losses) if getattr(m, 'maskiou_head', None) is not None else None
+        pt = (self._point_branch(masks, n_gt, t, m_rois, m_label, mask_out, features, scales, losses)
+              if getattr(m, 'point_head', None) is not None else None)
 
         main.wait_stream(aux)
         if aux is not main:             # allocated on the aux stream, consumed by the RPN backward on the main stream
-            g_locs.record_stream(main)
-            g_scores.record_stream(main)
+            rpn['g_locs'].record_stream(main)
+            rpn['g_scores'].record_stream(main)
         total = ops.loss_total(losses)
-        self.observation = {'rpn_loc_loss': losses[0, 0], 'rpn_cls_loss': losses[1, 0], 'roi_loc_loss': losses[2, 0],
-                            'roi_cls_loss': losses[3, 0], 'mask_loss': losses[4, 0], 'loss': total[0]}
-        for k in range(2, 2 + len(stages)):         # the existing keys are stage 1's
-            self.observation['roi_loc_loss_s%d' % k] = losses[5 + 2 * (k - 2), 0]
-            self.observation['roi_cls_loss_s%d' % k] = losses[6 + 2 * (k - 2), 0]
-        if mh is not None:
-            self.observation['maskiou_loss'] = losses[iou_row, 0]
-        if ph is not None:
-            self.observation['point_loss'] = losses[pt_row, 0]
-        self._bwd = (features, g_locs.view(n, A, 4), g_scores.view(n, A, 2), g_box, g_mask)
-        self._bwd_cascade = g_boxes[1:]          # the later box stages' loss gradients, in stage order
-        self._bwd_maskiou = g_iou                # the MaskIoU loss gradient (None without the head)
-        self._bwd_point = pt                     # the point head's coords, rois and loss gradient (None without the head)
-        self._early_rpn = br1.get('g_feats')
+        self.pending = _PendingBackward(features, rpn['g_locs'].view(n, A, 4), rpn['g_scores'].view(n, A, 2), g_boxes[0], g_mask, g_boxes[1:],
+                                        iou['g_pred'] if iou is not None else None, pt, rpn.get('g_feats'))
+        self._publish(losses, total, features, r, box, mask_out, casc, g_boxes, iou, pt, g_mask)
         self.targets = t
-        if self.keep_outputs:
-            self.outputs = dict(features=features, locs=r['locs'], scores=r['scores'], box=box, mask=mask_out)
-            if stages:      # per later stage: the refine outputs (roi, rois_xy5, levels, gt_loc, label, gt_assign) and 'box'; every stage's loss gradient
-                self.outputs.update(cascade=casc, g_boxes=g_boxes, losses=losses)
-            if mh is not None:      # target, area, counts, input, pred, g_pred of the MaskIoU head, the mask loss gradient and the pooled features
-                self.outputs.update(maskiou=iou, g_mask=g_mask, mask_pool=head.last_mask_pool, losses=losses)
-            if ph is not None:      # coords, rois, input, pred, target, g_pred of the point head (backward adds g_in), the mask loss gradient
-                self.outputs.update(point=pt, g_mask=g_mask, losses=losses)
-        self.rpn_targets = (gt_rpn_loc, gt_rpn_label)
+        self.rpn_targets = (rpn['loc'], rpn['label'])
         self.mask_inputs = (m_rois, m_levels, m_label)
         self.rpn_out = r
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         return _LossHandle.apply(self._anchor, self, total[0])
 
-    # ------------------------------------------------------------------------------------------
+    def backward(self, upstream=None):
+        """Explicit backward pass: fills the flat gradient buffer of ``faster_rcnn.ps``.  ``upstream`` (device scalar or
+        None = 1): d(objective)/d(loss), multiplied into the loss-gradient seeds."""
+        m = self.faster_rcnn
+        st = self.pending
+        features = st.features
+        if upstream is not None:
+            from chainer_maskrcnn.functions.loss import _scale_
+            for g_ in st.seeds():
+                _scale_(g_, upstream)
+        hook = self.grad_ready_hook
+        dev = features[0].device
+        main = torch.cuda.current_stream(dev)
+        aux = self._aux_stream(dev) if self.use_aux_stream else main
+        into_early = (self.ACCUMULATE_INTO_EARLY_RPN and st.early_rpn is not None and upstream is None
+                      and len(st.early_rpn) == len(features))
+        if into_early:
+            g_feats = list(st.early_rpn)
+            for g in g_feats:
+                g.record_stream(main)
+        else:
+            g_feats = [torch.empty_like(f) for f in features]
+        aux.wait_stream(main)
+        with torch.cuda.stream(aux):
+            self._box_stages_backward(st, g_feats, into_early)
+        # the MaskIoU head first (main stream): its parameter gradients are final and its input gradient is at hand before the mask
+        # branch's; the feature part joins the mask convolutions' pooled gradient, so the ONE ROIAlign backward below carries both
+        g_iou_in = m.maskiou_head.backward(st.g_iou) if st.g_iou is not None else None
+        # the point head likewise (main stream): its input gradient waits for the ROIAlign backward passes below
+        g_pt_in = m.point_head.backward(st.point['g_pred']) if st.point is not None else None
+        g_pool = m.head.backward_mask_convs(st.g_mask)    # main stream: the mask branch down to its pooled input
+        if g_iou_in is not None:
+            self._maskiou_input_backward(g_iou_in, g_pool)
+        main.wait_stream(aux)
+        if self.keep_outputs and g_iou_in is not None:       # parity tests: the pyramid gradient the box stages left
+            self.outputs.update(g_feats_box=[g.clone() for g in g_feats])
+        m.head.backward_mask_pool(g_pool, g_feats)        # accumulates into g_feats (second pooled size)
+        if g_pt_in is not None:
+            self._point_input_backward(st.point, g_pt_in, g_feats)
+        if self.keep_outputs and (st.g_later or g_iou_in is not None):       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
+            self.outputs.update(g_mask_pool=g_pool, g_feats_heads=[g.clone() for g in g_feats])
+        if hook:
+            hook(self._offset_of('head/'))
+        self._rpn_backward(st, g_feats, into_early, upstream, main)
+        if hook:
+            hook(self._offset_of('rpn/'))
+        m.extractor.backward(g_feats, progress=(lambda prefix: hook(self._offset_of(prefix))) if hook else None)
+        from chainer_maskrcnn.nn import core
+        core.join_side_stream(features[0].device)
+        if hook:
+            hook(0)
+        self.pending = None
+        if self._arith_found is not None:
+            from chainer_maskrcnn._hip import lib, check
+            split, in_backbone = self._arith_found
+            check(lib().mrcnn_conv2d_set_split_operands(*split))
+            core.FWD_EMULATION_IN_BACKBONE = in_backbone
+            self._arith_found = None
+
+    # ---- the stages of the step: each forward piece, then its backward piece ---------------------------------------------
+    def _rpn_loss_branch(self, locs, scores, anchors, bboxes, img_size, n_gt, keys, per_hw, losses, main, aux):
+        """Branch 1 (aux stream): anchor targets + RPN losses (:81-85).  It needs the RPN head outputs only, so it is
+        enqueued before the proposal kernels and runs beside them.  -> loc, label, g_locs, g_scores (and g_feats, below)."""
+        m, row, br1 = self.faster_rcnn, self._row, {}
+        n, A_ = bboxes.shape[0], anchors.shape[0]
+        aux.wait_stream(main)
+        with torch.cuda.stream(aux):
+            br1['loc'], br1['label'] = self.anchor_target_creator(bboxes, anchors, img_size, n_gt=n_gt, keys=keys, per_image_hw=per_hw)
+            if self.rpn_box_loss == 'smooth_l1':
+                _, br1['g_locs'] = ops.smooth_l1(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), br1['label'].view(-1),
+                                                 n * A_, self.rpn_sigma, out=losses[row['rpn_loc_loss']])
+            else:   # on the decoded box: every image's rows are relative to the shared anchors; the RPN's targets are not normalised
+                _, br1['g_locs'] = ops.box_iou_loss(locs.view(n * A_, 4), 4, br1['loc'].view(n * A_, 4), anchors, br1['label'].view(-1),
+                                                    n * A_, self.rpn_box_loss, (0., 0., 0., 0.), (1., 1., 1., 1.),
+                                                    weight=self.rpn_box_loss_weight, roi_period=A_, out=losses[row['rpn_loc_loss']])
+            _, br1['g_scores'] = ops.softmax_ce(scores.view(n * A_, 2), br1['label'].view(-1), n * A_, 2, (1, 2, 0, 1),
+                                                out=losses[row['rpn_cls_loss']])
+            # The RPN's own backward pass needs nothing but these two gradients: when a backward pass is known to follow
+            # (MomentumSGD.update) it is enqueued HERE, on the aux stream, and fills the chip while the main stream walks the
+            # latency-bound proposal chain (decode, select, sort, NMS, target sampling: small kernels on a few CUs).  Its
+            # per-level feature gradients are kept and added in backward() where rpn.backward() used to run.
+            if self.EARLY_RPN_BACKWARD and self.backward_follows and aux is not main:
+                for c1, c2, _, _ in m.rpn.tape:         # saved activations were allocated on the main stream and are released by
+                    for t_ in tuple(c1) + tuple(c2):    # this call: the allocator must not hand them out again before aux is done
+                        if torch.is_tensor(t_):
+                            t_.record_stream(aux)
+                br1['g_feats'] = m.rpn.backward(br1['g_locs'].view(n, A_, 4), br1['g_scores'].view(n, A_, 2), None)
+        return br1
+
+    def _rpn_backward(self, st, g_feats, into_early, upstream, main):
+        """The RPN's part of g_feats, behind the heads': already in them (into_early), added from the early pass, or computed now."""
+        if into_early:
+            st.early_rpn = None
+        elif st.early_rpn is not None:        # computed beside the proposal chain of the forward pass (aux stream, joined at its end)
+            if upstream is not None:        # (its parameter gradients are already in the buffer, un-scaled: they cannot be fixed up here)
+                raise RuntimeError('the RPN backward pass ran early with d(objective)/d(loss) = 1 (backward_follows was set): '
+                                   'a scaled loss needs chain.backward_follows = False during the forward call')
+            for gf, g in zip(g_feats, st.early_rpn):
+                gf.add_(g)
+                g.record_stream(main)
+            st.early_rpn = None
+        else:
+            self.faster_rcnn.rpn.backward(st.g_locs, st.g_scores, g_feats)
+
+    def _box_stage_losses(self, box, roi, gt_loc, label, std, loc_row, cls_row):
+        """The two losses of one box stage on its output ``box`` (R, head.out_p) -> their gradient: softmax cross entropy over the class
+        columns, then smooth L1 on the encoded deltas or - an IoU loss - on the decoded box, against ``roi``, the box the stage's targets
+        ``gt_loc`` were encoded with, and the stage's ``std``.  Every stage normalises by the same (sum, count)."""
+        head = self.faster_rcnn.head
+        R, ld = label.shape[0], head.out_p
+        g_box = torch.empty_like(box)
+        ops.softmax_ce(box, label, R, head.n_class, (1, ld, 0, 1), Kfill=head.LOC0, gx=g_box, out=cls_row)
+        if self.box_loss == 'smooth_l1':
+            ops.smooth_l1(box, ld, gt_loc, label, R, self.roi_sigma, gfill=ld - head.LOC0, col0=head.LOC0, gx=g_box, out=loc_row)
+        else:
+            ops.box_iou_loss(box, ld, gt_loc, roi, label, R, self.box_loss, self.loc_normalize_mean, std, weight=self.box_loss_weight,
+                             roi_period=R, gfill=ld - head.LOC0, col0=head.LOC0, gx=g_box, out=loc_row)
+        return g_box
+
+    def _box_stages(self, features, t, scales, bboxes, labels, n_gt, img_hw, losses):
+        """The head's box branch and, behind it on the same stream, the cascade's -> (stage 1's output, every stage's loss gradient,
+        the later stages' refine outputs + 'box')."""
+        m, row = self.faster_rcnn, self._row
+        head, n = m.head, bboxes.shape[0]
+        box = head.box_branch(features, t['rois_xy5'], t['sample_levels'], scales)
+        g_boxes = [self._box_stage_losses(box, t['sample_roi'], t['gt_roi_loc'], t['gt_roi_label'], self.loc_normalize_std,
+                                          losses[row['roi_loc_loss']], losses[row['roi_cls_loss']])]
+        # Stage k >= 2, behind stage k-1 on the same stream and the same N * n_sample rows (no resampling, no host sync): stage k-1's
+        # input boxes refined by its own deltas, re-levelled, re-matched at the stage's IoU threshold and re-encoded with the stage's
+        # std - a constant: no gradient flows through the refinement -, then the stage's box branch and the two losses of stage 1
+        casc = []
+        prev = dict(roi=t['sample_roi'], label=t['gt_roi_label'], box=box)
+        for k, stage in enumerate(getattr(m, 'cascade_heads', []), 2):
+            ious, stds = m.cascade
+            ref = ops.cascade_refine(prev['roi'], prev['box'], head.LOC0, n, self.loc_normalize_mean, stds[k - 2], img_hw,
+                                     prev_label=prev['label'], gt_boxes=bboxes, gt_labels=labels, n_gt=n_gt, iou_thresh=ious[k - 1],
+                                     std_next=stds[k - 1])
+            ref['box'] = stage.box_branch(features, ref['rois_xy5'], ref['levels'], scales)
+            g_boxes.append(self._box_stage_losses(ref['box'], ref['roi'], ref['gt_loc'], ref['label'], stds[k - 1],
+                                                  losses[row['roi_loc_loss_s%d' % k]], losses[row['roi_cls_loss_s%d' % k]]))
+            casc.append(ref)
+            prev = ref
+        return box, g_boxes, casc
+
+    def _box_stages_backward(self, st, g_feats, into_early):
+        m = self.faster_rcnn
+        m.head.backward_box(st.g_box, g_feats, accumulate=into_early)     # overwrites g_feats (first pooled size) unless they hold the RPN's
+        for stage, g_k in zip(getattr(m, 'cascade_heads', []), st.g_later):      # the later box stages add theirs, in stage order
+            stage.backward_box(g_k, g_feats, accumulate=True)
+
+    def _mask_loss(self, features, t, scales, losses):
+        """The mask branch on its rows and the mask loss -> (the rows' rois, levels and labels, the NHWC logits, the loss gradient)."""
+        head = self.faster_rcnn.head
+        if self.mask_loss_kind == 'generic':
+            g_mask = self._generic_mask_loss(t, features, scales, losses)
+            return self._generic_inputs + (None, g_mask)
+        S, rows = self.proposal_target_creator.n_sample, t['mask_rows']
+        n = t['rois_xy5'].shape[0] // S
+        if rows == S:
+            m_rois, m_levels, m_label = t['rois_xy5'], t['sample_levels'], t['gt_roi_label']
+        else:   # the first `rows` rows of every image block (positives come first)
+            m_rois = t['rois_xy5'].view(n, S, 5)[:, :rows].reshape(n * rows, 5)
+            m_levels = t['sample_levels'].view(n, S)[:, :rows].reshape(n * rows)
+            m_label = t['gt_roi_label'].view(n, S)[:, :rows].reshape(n * rows)
+        mask_out = head.mask_branch(features, m_rois, m_levels, scales)
+        out = losses[self._row['mask_loss']]
+        if self.mask_loss_kind == 'mask_bce':
+            _, g_mask = ops.mask_bce(mask_out, t['gt_roi_mask'], m_label, out=out)
+        else:
+            Rm, Hm, Wm, Cm = mask_out.shape
+            K = head.n_keypoints
+            xmap = (K, Hm * Wm * Cm, 1, Cm)
+            g_mask = torch.empty_like(mask_out) if ops.softmax_ce_fills_gradient(Rm * K, Hm * Wm, xmap) else torch.zeros_like(mask_out)
+            ops.softmax_ce(mask_out, t['gt_roi_mask'].view(-1), Rm * K, Hm * Wm, xmap, gx=g_mask, out=out)
+        return m_rois, m_levels, m_label, mask_out, g_mask
+
     def _generic_mask_loss(self, t, features, scales, losses):
         """A user-supplied ``mask_loss_fun`` (not one of the two recognised functions): call it like the reference does
         (:103-104) - ``roi_cls_mask`` (R, C, S, S) with the positive rows first, ``gt_roi_mask`` with exactly n_pos rows,
@@ -499,96 +574,77 @@ class FPNMaskRCNNTrainChain(object):
             if not torch.is_tensor(loss) or loss.numel() != 1:
                 raise TypeError('mask_loss_fun must return a scalar tensor')
             (g_mask,) = torch.autograd.grad(loss.reshape(()), leaf)
-        losses[4, 0].copy_(loss.detach().reshape(()))
-        losses[4, 1].fill_(1.0)
+        out = losses[self._row['mask_loss']]
+        out[0].copy_(loss.detach().reshape(()))
+        out[1].fill_(1.0)
         return g_mask.contiguous()
 
-    def backward(self, upstream=None):
-        """Explicit backward pass: fills the flat gradient buffer of ``faster_rcnn.ps``.  ``upstream`` (device scalar or
-        None = 1): d(objective)/d(loss), multiplied into the four loss-gradient seeds."""
+    def _maskiou_branch(self, masks, n_gt, t, m_label, mask_out, losses):
+        """Behind the mask loss, on the main stream and the mask branch's own rows: the IoU of each row's thresholded logits with its
+        ground truth (integer counts), the head's input (pooled features + the max-pooled class logit, a constant), the head, the L2
+        loss over the rows that have a target.  No host synchronisation.  -> target, area, (counts,) input, pred, g_pred."""
         m = self.faster_rcnn
-        features, g_locs, g_scores, g_box, g_mask = self._bwd
-        g_later = self._bwd_cascade
-        g_iou = self._bwd_maskiou
-        pt = self._bwd_point
-        if upstream is not None:
-            from chainer_maskrcnn.functions.loss import _scale_
-            for g_ in (g_locs, g_scores, g_box, g_mask) + tuple(g_later) + ((g_iou,) if g_iou is not None else ()) \
-                    + ((pt['g_pred'],) if pt is not None else ()):
-                _scale_(g_, upstream)
-        hook = self.grad_ready_hook
-        dev = features[0].device
-        main = torch.cuda.current_stream(dev)
-        aux = self._aux_stream(dev) if self.use_aux_stream else main
-        into_early = (self.ACCUMULATE_INTO_EARLY_RPN and self._early_rpn is not None and upstream is None
-                      and len(self._early_rpn) == len(features))
-        if into_early:
-            g_feats = list(self._early_rpn)
-            for g in g_feats:
-                g.record_stream(main)
-        else:
-            g_feats = [torch.empty_like(f) for f in features]
-        aux.wait_stream(main)
-        with torch.cuda.stream(aux):
-            m.head.backward_box(g_box, g_feats, accumulate=into_early)     # overwrites g_feats (first pooled size) unless they hold the RPN's
-            for stage, g_k in zip(getattr(m, 'cascade_heads', []), g_later):      # the later box stages add theirs, in stage order
-                stage.backward_box(g_k, g_feats, accumulate=True)
-        # the MaskIoU head first (main stream): its parameter gradients are final and its input gradient is at hand before the mask
-        # branch's; the feature part joins the mask convolutions' pooled gradient, so the ONE ROIAlign backward below carries both
-        g_iou_in = m.maskiou_head.backward(g_iou) if g_iou is not None else None
-        # the point head likewise (main stream): its input gradient waits for the ROIAlign backward passes below
-        g_pt_in = m.point_head.backward(pt['g_pred']) if pt is not None else None
-        g_pool = m.head.backward_mask_convs(g_mask)       # main stream: the mask branch down to its pooled input
-        if g_iou_in is not None:
-            if self.keep_outputs:       # parity tests: the two summands
-                self.outputs.update(g_mask_pool_convs=g_pool.clone(), g_maskiou_in=g_iou_in)
-            ops.maskiou_input_bwd(g_iou_in, g_pool)
-        main.wait_stream(aux)
-        if self.keep_outputs and g_iou_in is not None:       # ... and the pyramid gradient the box stages left
-            self.outputs.update(g_feats_box=[g.clone() for g in g_feats])
-        m.head.backward_mask_pool(g_pool, g_feats)        # accumulates into g_feats (second pooled size)
-        if g_pt_in is not None:
-            # PointRend: the fine part of the point head's input gradient, added into the stride-4 level's gradient behind the heads' ROIAlign
-            # backward passes (and the RPN's, where it ran early) - what the map holds is the first addend, then ascending (row, point)
-            if self.keep_outputs:       # parity tests: the map before the addition and the addend
-                pt['g_in'] = g_pt_in
-                self.outputs.update(g_feats0_heads=g_feats[0].clone())
-            ops.point_features_bwd(g_pt_in, pt['coords'], pt['rois'], m.extractor.spatial_scales[0], g_feats[0])
-            if self.keep_outputs:
-                self.outputs.update(g_feats0_point=g_feats[0].clone())
-        if self.keep_outputs and (g_later or g_iou_in is not None):       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
-            self.outputs.update(g_mask_pool=g_pool, g_feats_heads=[g.clone() for g in g_feats])
-        if hook:
-            hook(self._offset_of('head/'))
-        if into_early:
-            self._early_rpn = None
-        elif self._early_rpn is not None:     # computed beside the proposal chain of the forward pass (aux stream, joined at its end)
-            if upstream is not None:        # (its parameter gradients are already in the buffer, un-scaled: they cannot be fixed up here)
-                raise RuntimeError('the RPN backward pass ran early with d(objective)/d(loss) = 1 (backward_follows was set): '
-                                   'a scaled loss needs chain.backward_follows = False during the forward call')
-            for gf, g in zip(g_feats, self._early_rpn):
-                gf.add_(g)
-                g.record_stream(main)
-            self._early_rpn = None
-        else:
-            m.rpn.backward(g_locs, g_scores, g_feats)
-        if hook:
-            hook(self._offset_of('rpn/'))
-        m.extractor.backward(g_feats, progress=(lambda prefix: hook(self._offset_of(prefix))) if hook else None)
-        from chainer_maskrcnn.nn import core
-        core.join_side_stream(features[0].device)
-        if hook:
-            hook(0)
-        self._bwd = None
-        self._bwd_cascade = ()
-        self._bwd_maskiou = None
-        self._bwd_point = None
-        if self._arith_found is not None:
-            from chainer_maskrcnn._hip import lib, check
-            split, in_backbone = self._arith_found
-            check(lib().mrcnn_conv2d_set_split_operands(*split))
-            core.FWD_EMULATION_IN_BACKBONE = in_backbone
-            self._arith_found = None
+        mh, S = m.maskiou_head, self.proposal_target_creator.n_sample
+        m_label = m_label.contiguous()
+        iou = ops.maskiou_target(masks.contiguous(), n_gt, t['sample_roi'], t['gt_assign'], m_label, t['n_pos'], S, t['mask_rows'], mask_out,
+                                 t['gt_roi_mask'], mh.out_channels, label_base=1, want_counts=self.keep_outputs)
+        iou['input'] = mh.assemble(m.head.last_mask_pool, mask_out, m_label, label_base=1)
+        iou['pred'] = mh.forward(iou['input'])
+        _, iou['g_pred'] = ops.maskiou_l2(iou['pred'], iou['target'], m_label, mh.out_channels, weight=self.mask_iou_weight, label_base=1,
+                                          out=losses[self._row['maskiou_loss']])
+        return iou
+
+    def _maskiou_input_backward(self, g_iou_in, g_pool):
+        if self.keep_outputs:       # parity tests: the two summands
+            self.outputs.update(g_mask_pool_convs=g_pool.clone(), g_maskiou_in=g_iou_in)
+        ops.maskiou_input_bwd(g_iou_in, g_pool)
+
+    def _point_branch(self, masks, n_gt, t, m_rois, m_label, mask_out, features, scales, losses):
+        """Behind the mask loss, on the main stream and the mask branch's own rows: the training points from the coarse logits'
+        uncertainty, the head's input sampled from the stride-4 level and the logits (constants for the head), the head, the soft
+        targets from the ground-truth masks, the loss over the live rows.  No host synchronisation.  -> coords, rois, input, pred,
+        target, g_pred."""
+        m = self.faster_rcnn
+        ph, st, S = m.point_head, m.point_rend, self.proposal_target_creator.n_sample
+        m_label, m_rois = m_label.contiguous(), m_rois.contiguous()
+        keys = self.point_keys
+        if keys is None:
+            keys = self._point_stream.draw((mask_out.shape[0], ops.point_n_keys(st['train_points'], st['n_candidates'], st['n_important'])),
+                                           mask_out.device)
+        pt = dict(coords=ops.point_train_coords(keys, mask_out, m_label, ph.out_channels, st['train_points'], st['n_candidates'],
+                                                st['n_important'], label_base=1), rois=m_rois)
+        pt['input'] = ph.assemble(pt['coords'], m_rois, features[0], scales[0], mask_out)
+        pt['pred'] = ph.forward(pt['input'])
+        pt['target'] = ops.point_target(masks.contiguous(), n_gt, m_rois, t['gt_assign'], m_label, t['n_pos'], S, t['mask_rows'], pt['coords'])
+        _, pt['g_pred'] = ops.point_bce(pt['pred'], pt['target'], m_label, ph.out_channels, weight=self.point_loss_weight, label_base=1,
+                                        out=losses[self._row['point_loss']])
+        return pt
+
+    def _point_input_backward(self, pt, g_pt_in, g_feats):
+        """PointRend: the fine part of the point head's input gradient, added into the stride-4 level's gradient behind the heads' ROIAlign
+        backward passes (and the RPN's, where it ran early) - what the map holds is the first addend, then ascending (row, point)."""
+        if self.keep_outputs:       # parity tests: the map before the addition and the addend
+            pt['g_in'] = g_pt_in
+            self.outputs.update(g_feats0_heads=g_feats[0].clone())
+        ops.point_features_bwd(g_pt_in, pt['coords'], pt['rois'], self.faster_rcnn.extractor.spatial_scales[0], g_feats[0])
+        if self.keep_outputs:
+            self.outputs.update(g_feats0_point=g_feats[0].clone())
+
+    def _publish(self, losses, total, features, r, box, mask_out, casc, g_boxes, iou, pt, g_mask):
+        """``observation`` (device scalars; 'loss' sixth, behind the reference's five) and, for the parity tests, ``outputs``."""
+        self.observation = {}
+        for key, row in self._loss_rows:
+            self.observation[key] = losses[row, 0]
+            if key == 'mask_loss':
+                self.observation['loss'] = total[0]
+        if self.keep_outputs:
+            self.outputs = dict(features=features, locs=r['locs'], scores=r['scores'], box=box, mask=mask_out)
+            if casc:        # per later stage: the refine outputs (roi, rois_xy5, levels, gt_loc, label, gt_assign) and 'box'; every stage's loss gradient
+                self.outputs.update(cascade=casc, g_boxes=g_boxes, losses=losses)
+            if iou is not None:     # target, area, counts, input, pred, g_pred of the MaskIoU head, the mask loss gradient and the pooled features
+                self.outputs.update(maskiou=iou, g_mask=g_mask, mask_pool=self.faster_rcnn.head.last_mask_pool, losses=losses)
+            if pt is not None:      # coords, rois, input, pred, target, g_pred of the point head (backward adds g_in), the mask loss gradient
+                self.outputs.update(point=pt, g_mask=g_mask, losses=losses)
 
     def _offset_of(self, prefix):
         cache = self.__dict__.setdefault('_offset_cache', {})

@@ -392,13 +392,8 @@ class MomentumSGD(object):
              'buffers': {k: v.detach().cpu() for k, v in ps.buffers.items()},
              't': self.t, 'lr': self.lr, 'sgd_momentum': self.momentum, 'weight_decay': self.weight_decay, 'samplers': {},
              'clip_threshold': self.clip_threshold, 'average_accumulated': self.average_accumulated}
-        for name in ('proposal_target_creator', 'anchor_target_creator'):
-            c = getattr(self.target, name, None)
-            if c is not None:
-                d['samplers'][name] = {'seed': c.seed, 'state': None if c._state is None else c._state.detach().cpu()}
-        if getattr(getattr(self.target, 'faster_rcnn', None), 'point_head', None) is not None:      # PointRend: the chain's own point keys
-            st = self.target._point_state
-            d['samplers']['point_rend'] = {'seed': self.target.point_seed, 'state': None if st is None else st.detach().cpu()}
+        for name, keys in getattr(self.target, 'key_streams', {}).items():
+            d['samplers'][name] = {'seed': keys.seed, 'state': None if keys.state is None else keys.state.detach().cpu()}
         return d
 
     def load_state_dict(self, d):
@@ -414,16 +409,11 @@ class MomentumSGD(object):
         self.clip_threshold = d.get('clip_threshold', 0.0)              # (files from before these existed: both off)
         self.average_accumulated = d.get('average_accumulated', False)
         self.pending = 0
+        streams = getattr(self.target, 'key_streams', {})
         for name, st in d.get('samplers', {}).items():
-            if name == 'point_rend':
-                if hasattr(self.target, '_point_state'):
-                    self.target.point_seed = st['seed']
-                    self.target._point_state = None if st['state'] is None else st['state'].to(ps.params.device)
-                continue
-            c = getattr(self.target, name, None)
-            if c is not None:
-                c.seed = st['seed']
-                c._state = None if st['state'] is None else st['state'].to(ps.params.device)
+            if name in streams:
+                streams[name].seed = st['seed']
+                streams[name].state = None if st['state'] is None else st['state'].to(ps.params.device)
 
     def update(self, lossfun=None, *args, **kwds):
         """Chainer semantics: with ``lossfun`` -> loss = lossfun(*args); backward; update.  Without: update only."""

@@ -28,11 +28,12 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', 'chainer-maskrc
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from chainer_maskrcnn._hip import ops  # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN  # noqa: E402
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss  # noqa: E402
+from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_keypoint_loss  # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay  # noqa: E402
 from chainer_maskrcnn.utils.synthetic import make_batch  # noqa: E402
 import box_iou_loss_reference as ref  # noqa: E402
 from loss_judge import EPS32, loss_close, ratio, rtol_from  # noqa: E402
+from tests import step_harness  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -254,27 +255,11 @@ def test_edge_geometry(case, kind):
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 
 
+_batch, _forward, _step = step_harness.batch, step_harness.forward, step_harness.step
+
+
 def _build(seed=7, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows='all', **kw)
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
-
-
-def _forward(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    return chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0)
-
-
-def _step(chain, b):
-    _forward(chain, b).backward()
-    torch.cuda.synchronize()
+    return step_harness.build(SHRINK, seed, chain_kw=kw)
 
 
 _SL1 = {}
@@ -286,7 +271,7 @@ def _smooth_l1_score_gradient():
         m, chain = _build()
         _forward(chain, _batch())
         torch.cuda.synchronize()
-        _SL1['g'] = chain._bwd[3][:, :m.head.LOC0].clone()
+        _SL1['g'] = chain.pending.g_box[:, :m.head.LOC0].clone()
     return _SL1['g']
 
 
@@ -298,7 +283,7 @@ def test_step_losses_equal_the_reference_on_the_step_own_tensors(kind, weight, r
     _forward(chain, b)
     torch.cuda.synchronize()
     head = m.head
-    g_box = chain._bwd[3]
+    g_box = chain.pending.g_box
     assert torch.equal(g_box[:, :head.LOC0], _smooth_l1_score_gradient())                # the classification gradient is untouched
     assert torch.isfinite(g_box).all() and bool((g_box[:, head.LOC0 + 4:] == 0).all())
     t = chain.targets
@@ -383,9 +368,7 @@ def test_graphed_step_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(box_loss='giou', rpn_box_loss='giou')
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]

@@ -156,6 +156,35 @@ def test_model_refuses_bad_cascades_and_the_legacy_heads():
     assert chain.proposal_target_creator.pos_iou_thresh == 0.5
 
 
+def test_loss_rows_are_the_written_out_table():
+    """The rows of the step's losses tensor and the observation keys, for 0 .. 3 later box stages with and without the MaskIoU and the
+    point head: the reference's five, the stages' (loc, cls) pairs, maskiou_loss, point_loss."""
+    from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, loss_rows
+    five = [('rpn_loc_loss', 0), ('rpn_cls_loss', 1), ('roi_loc_loss', 2), ('roi_cls_loss', 3), ('mask_loss', 4)]
+    s2, s3, s4 = ([('roi_loc_loss_s%d' % k, r), ('roi_cls_loss_s%d' % k, r + 1)] for k, r in ((2, 5), (3, 7), (4, 9)))
+    table = {(0, False, False): (five, 5),
+             (0, True, False): (five + [('maskiou_loss', 5)], 6),
+             (0, False, True): (five + [('point_loss', 5)], 6),
+             (0, True, True): (five + [('maskiou_loss', 5), ('point_loss', 6)], 7),
+             (1, False, False): (five + s2, 7),
+             (1, True, False): (five + s2 + [('maskiou_loss', 7)], 8),
+             (1, False, True): (five + s2 + [('point_loss', 7)], 8),
+             (1, True, True): (five + s2 + [('maskiou_loss', 7), ('point_loss', 8)], 9),
+             (2, False, False): (five + s2 + s3, 9),
+             (2, True, False): (five + s2 + s3 + [('maskiou_loss', 9)], 10),
+             (2, False, True): (five + s2 + s3 + [('point_loss', 9)], 10),
+             (2, True, True): (five + s2 + s3 + [('maskiou_loss', 9), ('point_loss', 10)], 11),
+             (3, False, False): (five + s2 + s3 + s4, 11),
+             (3, True, False): (five + s2 + s3 + s4 + [('maskiou_loss', 11)], 12),
+             (3, False, True): (five + s2 + s3 + s4 + [('point_loss', 11)], 12),
+             (3, True, True): (five + s2 + s3 + s4 + [('maskiou_loss', 11), ('point_loss', 12)], 13)}
+    for (later, mask_iou, point), want in table.items():
+        assert loss_rows(later, mask_iou, point) == want, (later, mask_iou, point)
+    assert loss_rows(0) == (five, 5)
+    chain = FPNMaskRCNNTrainChain(_model(cascade_ious=IOUS, mask_iou=True))        # the chain sizes its losses tensor from the model's heads
+    assert (chain._loss_rows, chain._n_loss_rows) == table[(2, True, False)]
+
+
 @pytest.mark.parametrize('keypoints', [False, True], ids=['mask', 'keypoint'])
 def test_cascade_adds_only_its_own_parameters_behind_the_head(keypoints):
     plain, none = _model(keypoints=keypoints), _model(keypoints=keypoints, cascade_ious=None)

@@ -2,6 +2,7 @@
 step on the fixed random geometries (integer outputs equal on every row - tests/test_cascade_cpu.py shows that no row of these cases is
 within 1e-5 of a decision boundary, so nothing is exempt; boxes and targets judged against float64 as tests/loss_judge.py does), its edges
 in exact arithmetic, and the inference score."""
+import functools
 import os
 import sys
 
@@ -138,7 +139,7 @@ def test_cascade_prob_is_the_mean_of_the_stage_softmaxes(n_class, K):
 
 
 # ---- the model, the training chain and inference ----------------------------------------------------------------------------------------
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_keypoint_loss, calc_mask_loss            # noqa: E402
+from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_keypoint_loss            # noqa: E402
 from chainer_maskrcnn.model.head.fpn_roi_mask_head import roi_align_fpn_bwd            # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN            # noqa: E402
 from chainer_maskrcnn.nn import core            # noqa: E402
@@ -146,30 +147,15 @@ from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay            # no
 from chainer_maskrcnn.utils.synthetic import make_batch            # noqa: E402
 import loss_reference as lr            # noqa: E402
 from loss_judge import loss_close            # noqa: E402
+from tests import step_harness            # noqa: E402
 
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 IOUS = (0.5, 0.6, 0.7)
 D64 = torch.float64
 
 
-def _build(seed=7, chain_kw=None, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, **kw)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows='all', **(chain_kw or {}))
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
-
-
-def _step(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
-    core.join_side_stream(torch.device(DEV))
-    torch.cuda.synchronize()
+_build, _batch, _step, _check = functools.partial(step_harness.build, SHRINK), step_harness.batch, step_harness.step, step_harness.check
+_predict_model = functools.partial(step_harness.predict_model, SHRINK)
 
 
 def _cascade_names(m, k=None):
@@ -215,17 +201,6 @@ def test_cascade_step_is_finite_and_bit_reproducible():
         assert torch.isfinite(g).all() and float(g.abs().max()) > 0, n
     _step(chain, b)
     assert torch.equal(g1, m.ps.grads)                      # no float atomics: the later stages accumulate in a fixed order
-
-
-def _check(name, got, want64, want32, bad):
-    """bar = max(1e-3, 3 x floor), as tests/test_groupnorm_gpu.py: floor = the same sum in float32."""
-    want64 = want64.to(D64)
-    scale = max(float(want64.abs().max()), 1e-30)
-    err = float((got.detach().cpu().to(D64) - want64).abs().max()) / scale
-    floor = float((want32.to(D64) - want64).abs().max()) / scale
-    print('%-28s err %.3e floor %.3e' % (name, err, floor))
-    if not err <= max(1e-3, 3 * floor):
-        bad.append((name, err, floor))
 
 
 def test_cascade_wiring():
@@ -327,9 +302,7 @@ def test_graphed_step_with_cascade_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(cascade_ious=IOUS)
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]
@@ -372,13 +345,6 @@ def test_keypoint_chain_with_two_stages_runs_one_step():
     assert torch.isfinite(m.ps.grads).all()
     for n in _cascade_names(m):
         assert float(m.ps.g(n).abs().max()) > 0, n
-
-
-def _predict_model(seed, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, min_size=160, max_size=260, **kw)
-    m.use_preset('evaluate')
-    m.score_thresh = 0.0125                         # random weights: ~uniform class probabilities (1/81 = 0.0123)
-    return m
 
 
 def test_cascade_predict(tmp_path):

@@ -17,6 +17,7 @@ over up to 1024 channels and up to 10800 list entries).  The values measured on 
 arithmetic does not depend on a size the comparison has NO bar: a column and an input-gradient channel depend on their own channel only and
 are added in entry and chunk order whatever C is, so a wide call equals, bit for bit, the same call on 64-channel slices; an image's results
 do not depend on the images beside it; nothing depends on the stride of the offset row."""
+import functools
 import os
 import sys
 
@@ -330,8 +331,7 @@ def test_offset_row_strides(shape, modulated, kind, ld_index):
 from chainer_maskrcnn.nn import core                                              # noqa: E402
 from chainer_maskrcnn.nn.core import DeformConv, ParamStore                        # noqa: E402
 from chainer_maskrcnn._hip import nn as hnn                                        # noqa: E402
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import (DEFAULT_GEMM_ARITHMETIC, FPNMaskRCNNTrainChain, calc_mask_loss,      # noqa: E402
-                                                             select_gemm_arithmetic)
+from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import DEFAULT_GEMM_ARITHMETIC, select_gemm_arithmetic      # noqa: E402
 
 
 class arithmetic(object):
@@ -501,7 +501,7 @@ def test_layer_with_its_offset_convolution(shape, modulated):
 from chainer_maskrcnn.model.extractor.feature_pyramid_network import FeaturePyramidNetwork       # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN                                             # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay                                 # noqa: E402
-from chainer_maskrcnn.utils.synthetic import make_batch                                          # noqa: E402
+from tests import step_harness                                                                   # noqa: E402
 
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 ALL_STAGES = ('res3', 'res4', 'res5')
@@ -579,24 +579,7 @@ def _blocks_inside_the_fpn(modulated, frozen, net, image, widths):
 
 
 # ---- the whole model -------------------------------------------------------------------------------------------------------------------------
-def _build(seed=7, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, **kw)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss)
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
-
-
-def _step(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
-    core.join_side_stream(torch.device(DEV))
-    torch.cuda.synchronize()
+_build, _batch, _step = functools.partial(step_harness.build, SHRINK, mask_rows='positives'), step_harness.batch, step_harness.step
 
 
 def _offset_names(m):
@@ -644,9 +627,7 @@ def test_graphed_step_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(dcn_stages=ALL_STAGES, dcn_modulated=True)
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]

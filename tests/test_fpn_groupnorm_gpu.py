@@ -14,11 +14,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from chainer_maskrcnn._hip import ops  # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN  # noqa: E402
 from chainer_maskrcnn.model.extractor.feature_pyramid_network import FeaturePyramidNetwork  # noqa: E402
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss  # noqa: E402
+from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_keypoint_loss  # noqa: E402
 from chainer_maskrcnn.nn import core  # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay  # noqa: E402
 from chainer_maskrcnn.utils.synthetic import make_batch  # noqa: E402
 import fpn_groupnorm_reference as fgr  # noqa: E402
+from tests import step_harness  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -219,15 +220,7 @@ def test_layer_takes_the_map_kernels_on_a_map_and_keeps_nothing_in_evaluation():
 
 
 # ---- the top-down pyramid against float64 autograd on the CPU ----------------------------------------------------------------------------
-def _check(name, got, want64, want32, bad):
-    """bar = max(1e-3, 3 x floor): 1e-3 the BASELINE north_star gradient bar, floor the same CPU computation in float32."""
-    want64 = want64.to(D)
-    scale = max(float(want64.abs().max()), 1e-30)
-    err = float((got.detach().cpu().to(D) - want64).abs().max()) / scale
-    floor = float((want32.to(D) - want64).abs().max()) / scale
-    print('%-28s err %.3e floor %.3e' % (name, err, floor))
-    if not err <= max(1e-3, 3 * floor):
-        bad.append((name, err, floor))
+_check = step_harness.check
 
 
 def test_pyramid_matches_float64_autograd():
@@ -275,16 +268,12 @@ def test_pyramid_matches_float64_autograd():
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 
 
-def _build(seed=7, **kw):
+_batch, _step = step_harness.batch, step_harness.step
+
+
+def _build(**kw):
     kw.setdefault('gn_groups', 16)
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, **kw)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows='all')
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
+    return step_harness.build(SHRINK, **kw)
 
 
 def _gn_gradients_are_live(m):
@@ -296,14 +285,6 @@ def _gn_gradients_are_live(m):
             assert torch.isfinite(g).all(), n
             conv = n.split('/gn/')[0]
             assert (float(g.abs().max()) > 0) == ('/conv_p6' not in n or float(m.ps.g(conv + '/W').abs().max()) > 0), n
-
-
-def _step(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
-    torch.cuda.synchronize()
 
 
 def test_step_with_fpn_norm_is_finite_and_bit_reproducible():
@@ -352,9 +333,7 @@ def test_graphed_step_with_fpn_norm_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(fpn_norm='gn')
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]

@@ -23,6 +23,7 @@ from chainer_maskrcnn.model.maskrcnn import MaskRCNN  # noqa: E402
 from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss  # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay, GraphedStep  # noqa: E402
 from chainer_maskrcnn.utils.synthetic import make_batch  # noqa: E402
+from tests import step_harness  # noqa: E402
 
 DEV = 'cuda:0'
 STAGES = (2, 1, 1, 1)
@@ -191,13 +192,7 @@ def test_frozen_layer_forward_has_the_inference_bits(relu, residual):
 
 
 # ---- 3. the whole frozen step against the oracle --------------------------------------------------------------------------------------
-def _grad_ok(got, want, err, floor, tol):
-    """The rule of tests/test_step_gpu.py: err < max(tol, 3 x the float32 oracle's own error) - or the deviation is ONE flipped ReLU
-    decision (a few entries move, the tensor as a whole does not: relative L2 error < tol, max error < 10 x tol)."""
-    if err < max(tol, 3 * floor):
-        return True
-    l2 = float((got - want).norm()) / max(float(want.norm()), 1e-30)
-    return l2 < tol and err < 10 * tol
+_grad_ok, _seeded = step_harness.grad_ok, step_harness.seed
 
 
 def _build(kind, seed=None):
@@ -295,12 +290,6 @@ def test_frozen_step_losses_and_gradients_match_oracle(kind, at, grad_tol=1e-3):
 
 
 # ---- 4. frozen means frozen -----------------------------------------------------------------------------------------------------------
-def _seeded(chain):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-
-
 def _is_prefix(n):
     return any(n.startswith('extractor/resnet/' + s) for s in ('conv1/', 'bn1/', 'res2/'))
 

@@ -2,6 +2,7 @@
 the kernels against the float64 reference of tests/groupnorm_reference.py at the BatchNorm bars of tests/test_nn_gpu.py, the bitwise
 properties of the backward, the heads against float64 autograd on the CPU, the whole training step, inference, and the untouched
 defaults."""
+import functools
 import os
 import sys
 
@@ -14,13 +15,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', 'chainer-maskrc
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from chainer_maskrcnn._hip import ops  # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN  # noqa: E402
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss  # noqa: E402
+from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_keypoint_loss  # noqa: E402
 from chainer_maskrcnn.model.head.fpn_roi_mask_head import FPNRoIMaskHead, roi_align_fpn_fwd, roi_align_fpn_bwd  # noqa: E402
 from chainer_maskrcnn.model.head.fpn_roi_keypoint_head import FPNRoIKeypointHead  # noqa: E402
 from chainer_maskrcnn.nn import core  # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay  # noqa: E402
 from chainer_maskrcnn.utils.synthetic import make_batch  # noqa: E402
 import groupnorm_reference as gnr  # noqa: E402
+from tests import step_harness  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -254,15 +256,7 @@ def _box_reference(head, P, pooled, masks, g_out, dtype):
     return o.detach(), [y.detach()], x.grad, {n: leaves[n].grad for n in leaves}
 
 
-def _check(name, got, want64, want32, bad):
-    """bar = max(1e-3, 3 x floor): 1e-3 the BASELINE north_star gradient bar, floor the same CPU computation in float32."""
-    want64 = want64.to(D)
-    scale = max(float(want64.abs().max()), 1e-30)
-    err = float((got.detach().cpu().to(D) - want64).abs().max()) / scale
-    floor = float((want32.to(D) - want64).abs().max()) / scale
-    print('%-28s err %.3e floor %.3e' % (name, err, floor))
-    if not err <= max(1e-3, 3 * floor):
-        bad.append((name, err, floor))
+_check = step_harness.check
 
 
 @pytest.mark.parametrize('kind,merge', [('mask', True), ('mask', False), ('keypoint', True)], ids=['mask_merged', 'mask_layerwise', 'keypoint'])
@@ -348,23 +342,8 @@ def test_box_branch_matches_float64_autograd():
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 
 
-def _build(seed=7, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, **kw)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows='all')
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
-
-
-def _step(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
-    torch.cuda.synchronize()
+_build, _batch, _step = functools.partial(step_harness.build, SHRINK), step_harness.batch, step_harness.step
+_predict_model = functools.partial(step_harness.predict_model, SHRINK, head_norm='gn')
 
 
 def test_step_with_group_norm_is_finite_and_bit_reproducible():
@@ -446,9 +425,7 @@ def test_graphed_step_with_group_norm_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(head_norm='gn')
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]
@@ -465,13 +442,6 @@ def test_graphed_step_with_group_norm_replays_the_eager_step():
 
 
 # ---- inference ----------------------------------------------------------------------------------------------------------------------------
-def _predict_model(seed):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, min_size=160, max_size=260, head_norm='gn')
-    m.use_preset('evaluate')
-    m.score_thresh = 0.0125                         # random weights: ~uniform class probabilities (1/81 = 0.0123)
-    return m
-
-
 def test_predict_in_evaluation_mode_and_npz_round_trip(tmp_path):
     from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz
     m = _predict_model(5)

@@ -1,6 +1,7 @@
 """Mask Scoring R-CNN on the GPU (csrc/maskiou.hip, MaskIoUHead, the training chain and inference) against
 tests/maskiou_reference.py.  The integer counts equal the reference's on every row; the target equals the float32 restatement bit for bit;
 input assembly, its backward and the rescoring equal NumPy bit for bit; the loss is judged against float64 as tests/loss_judge.py does."""
+import functools
 import os
 import sys
 
@@ -174,40 +175,20 @@ def test_rescore_equals_numpy():
 
 
 # ---- the model, the training chain and inference ------------------------------------------------------------------------------------------
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss            # noqa: E402
 from chainer_maskrcnn.model.head.fpn_roi_mask_head import roi_align_fpn_bwd            # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN            # noqa: E402
 from chainer_maskrcnn.nn import core            # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay            # noqa: E402
-from chainer_maskrcnn.utils.synthetic import make_batch            # noqa: E402
+from tests import step_harness            # noqa: E402
 
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 D64 = torch.float64
 SIX = {'rpn_loc_loss', 'rpn_cls_loss', 'roi_loc_loss', 'roi_cls_loss', 'mask_loss', 'loss'}
 
 
-def _build(seed=7, chain_kw=None, mask_rows='all', **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, **kw)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows=mask_rows, **(chain_kw or {}))
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
-
-
-def _forward(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    return chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0)
-
-
-def _step(chain, b):
-    _forward(chain, b).backward()
-    core.join_side_stream(torch.device(DEV))
-    torch.cuda.synchronize()
+_build, _batch, _check = functools.partial(step_harness.build, SHRINK), step_harness.batch, step_harness.check
+_forward, _step = step_harness.forward, step_harness.step
+_predict_model = functools.partial(step_harness.predict_model, SHRINK)
 
 
 def _own(m):
@@ -225,17 +206,6 @@ def test_defaults_are_untouched():
         res.append((m.ps.params.clone(), m.ps.grads.clone(), dict(m.ps.offsets)))
     assert res[0][2] == res[1][2] and torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert float(res[0][1].abs().max()) > 0
-
-
-def _check(name, got, want64, want32, bad):
-    """bar = max(1e-3, 3 x floor), as tests/test_cascade_gpu.py: floor = the same sum in float32."""
-    want64 = want64.to(D64)
-    scale = max(float(want64.abs().max()), 1e-30)
-    err = float((got.detach().cpu().to(D64) - want64).abs().max()) / scale
-    floor = float((want32.to(D64) - want64).abs().max()) / scale
-    print('%-28s err %.3e floor %.3e' % (name, err, floor))
-    if not err <= max(1e-3, 3 * floor):
-        bad.append((name, err, floor))
 
 
 @pytest.mark.parametrize('H,W', [(14, 14), (15, 9)])
@@ -345,7 +315,7 @@ def test_wiring(mask_rows):
     m0, chain0 = _build(mask_rows=mask_rows)
     chain0.EARLY_RPN_BACKWARD = False
     loss0 = _forward(chain0, b)
-    g_mask0 = chain0._bwd[4].clone()
+    g_mask0 = chain0.pending.g_mask.clone()
     loss0.backward()
     core.join_side_stream(torch.device(DEV))
     torch.cuda.synchronize()
@@ -459,9 +429,7 @@ def test_graphed_step_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(mask_iou=True)
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]
@@ -475,13 +443,6 @@ def test_graphed_step_replays_the_eager_step():
         res.append((m.ps.params.clone(), float(chain.observation['loss']), float(chain.observation['maskiou_loss'])))
     assert res[0][1:] == res[1][1:]
     assert torch.equal(res[0][0], res[1][0])
-
-
-def _predict_model(seed, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, min_size=160, max_size=260, **kw)
-    m.use_preset('evaluate')
-    m.score_thresh = 0.0125                         # random weights: ~uniform class probabilities (1/81 = 0.0123)
-    return m
 
 
 def test_predict_rescoring(tmp_path):

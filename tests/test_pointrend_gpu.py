@@ -1,6 +1,7 @@
 """PointRend on the GPU (csrc/pointrend.hip, PointHead, the training chain and inference) against
 tests/pointrend_reference.py: every sampling kernel equals the float32 restatement bit for bit and the float64 one within a derived bound,
 the selections equal the reference's exactly, the loss is judged as tests/loss_judge.py does."""
+import functools
 import os
 import sys
 
@@ -249,26 +250,20 @@ def test_ops_refuse_host_tensors():
 
 
 # ---- the model, the training chain and inference ------------------------------------------------------------------------------------------
-from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss            # noqa: E402
+from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain            # noqa: E402
 from chainer_maskrcnn.model.maskrcnn import MaskRCNN            # noqa: E402
 from chainer_maskrcnn.nn import core            # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay            # noqa: E402
-from chainer_maskrcnn.utils.synthetic import make_batch            # noqa: E402
+from tests import step_harness            # noqa: E402
 
 SHRINK = dict(stages=(1, 1, 1, 1), width_div=4)
 SIX = {'rpn_loc_loss', 'rpn_cls_loss', 'roi_loc_loss', 'roi_cls_loss', 'mask_loss', 'loss'}
 POINT = dict(point_rend=True, point_train_points=49)           # a quarter of the default points: the kernels' tests cover 196
 
 
-def _build(seed=7, chain_kw=None, mask_rows='all', **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, **kw)
-    return m, FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows=mask_rows, **(chain_kw or {}))
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
+_build, _batch, _rel = functools.partial(step_harness.build, SHRINK), step_harness.batch, step_harness.check
+_forward, _step = step_harness.forward, step_harness.step
+_predict_model = functools.partial(step_harness.predict_model, SHRINK)
 
 
 def _point_keys(chain, m, rows_total, seed=3):
@@ -279,32 +274,8 @@ def _point_keys(chain, m, rows_total, seed=3):
     return _t(rs.randint(0, 2 ** 32, (rows_total, n_keys), dtype=np.uint64).astype(np.uint32).view(np.int32))
 
 
-def _forward(chain, b):
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
-    return chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0)
-
-
-def _step(chain, b):
-    _forward(chain, b).backward()
-    core.join_side_stream(torch.device(DEV))
-    torch.cuda.synchronize()
-
-
 def _own(m):
     return [n for n in m.ps.names() if n.startswith('head/point/')]
-
-
-def _rel(name, got, want64, want32, bad):
-    """bar = max(1e-3, 3 x floor), as tests/test_cascade_gpu.py and tests/test_maskiou_gpu.py: floor = the same sums in float32."""
-    want64 = np.asarray(want64, F64)
-    scale = max(float(np.abs(want64).max()), 1e-30)
-    err = float(np.abs(np.asarray(got, F64) - want64).max()) / scale
-    floor = float(np.abs(np.asarray(want32, F64) - want64).max()) / scale
-    print('%-28s err %.3e floor %.3e' % (name, err, floor))
-    if not err <= max(1e-3, 3 * floor):
-        bad.append((name, err, floor))
 
 
 @pytest.mark.parametrize('mask_rows', ['all', 'positives'])
@@ -377,7 +348,7 @@ def test_wiring(mask_rows):
     chain0.EARLY_RPN_BACKWARD = False
     assert m0.ps.names() == m.ps.names()[:len(m0.ps.names())] and torch.equal(m0.ps.params, m.ps.params[:m0.ps.size])
     loss0 = _forward(chain0, b)
-    g_mask0 = chain0._bwd[4].clone()
+    g_mask0 = chain0.pending.g_mask.clone()
     loss0.backward()
     core.join_side_stream(torch.device(DEV))
     torch.cuda.synchronize()
@@ -408,24 +379,27 @@ def test_step_is_bit_reproducible_and_upstream_scales_the_seed():
     # the chain's own keys: another draw every step, no override needed
     chain.point_keys = None
     _step(chain, b)
-    c1 = chain._point_state.clone()
+    c1 = chain.key_streams['point_rend'].state.clone()
     _step(chain, b)
-    assert not torch.equal(c1, chain._point_state) and torch.isfinite(m.ps.grads).all()
+    assert not torch.equal(c1, chain.key_streams['point_rend'].state) and torch.isfinite(m.ps.grads).all()
     # the trainer state carries the seed state of the point keys: a resumed run draws the keys the original run would have drawn
     opt = MomentumSGD(lr=0.01, momentum=0.9).setup(chain)
     state = opt.state_dict()
-    assert torch.equal(state['samplers']['point_rend']['state'], chain._point_state.cpu())
+    assert torch.equal(state['samplers']['point_rend']['state'], chain.key_streams['point_rend'].state.cpu())
     chain.keep_outputs = True
     _step(chain, b)
     m2, chain2 = _build(**POINT)
     opt2 = MomentumSGD(lr=0.01, momentum=0.9).setup(chain2)
     opt2.load_state_dict(state)
-    assert torch.equal(chain2._point_state, state['samplers']['point_rend']['state'].to(DEV))
+    assert torch.equal(chain2.key_streams['point_rend'].state, state['samplers']['point_rend']['state'].to(DEV))
     chain2.keep_outputs = True
     _step(chain2, b)
     assert torch.equal(chain2.outputs['point']['coords'], chain.outputs['point']['coords'])
     plain_state = MomentumSGD(lr=0.01).setup(_build()[1]).state_dict()
     assert 'point_rend' not in plain_state['samplers']
+    creators = {'proposal_target_creator', 'anchor_target_creator'}         # the file format: these names, these two fields
+    for saved, names in ((state, creators | {'point_rend'}), (plain_state, creators)):
+        assert set(saved['samplers']) == names and all(set(entry) == {'seed', 'state'} for entry in saved['samplers'].values())
 
 
 def test_thirty_steps_reduce_the_loss():
@@ -459,9 +433,7 @@ def test_graphed_step_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build(**POINT)
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]
@@ -472,16 +444,9 @@ def test_graphed_step_replays_the_eager_step():
             for _ in range(4):
                 opt.update(chain, *batch, 1.0)
         torch.cuda.synchronize()
-        res.append((m.ps.params.clone(), float(chain.observation['loss']), float(chain.observation['point_loss']), chain._point_state.clone()))
+        res.append((m.ps.params.clone(), float(chain.observation['loss']), float(chain.observation['point_loss']), chain.key_streams['point_rend'].state.clone()))
     assert res[0][1:3] == res[1][1:3]
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][3], res[1][3])          # the point keys advance alike under replay
-
-
-def _predict_model(seed, **kw):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=SHRINK, min_size=160, max_size=260, **kw)
-    m.use_preset('evaluate')
-    m.score_thresh = 0.0125                         # random weights: ~uniform class probabilities (1/81 = 0.0123)
-    return m
 
 
 def test_predict_refines_the_masks():

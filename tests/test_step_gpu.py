@@ -14,33 +14,18 @@ from chainer_maskrcnn.model.maskrcnn import MaskRCNN  # noqa: E402
 from chainer_maskrcnn.model.fpn_maskrcnn_train_chain import FPNMaskRCNNTrainChain, calc_mask_loss, calc_keypoint_loss  # noqa: E402
 from chainer_maskrcnn.optimizers import MomentumSGD, WeightDecay  # noqa: E402
 from chainer_maskrcnn.utils.synthetic import make_batch  # noqa: E402
+from tests import step_harness  # noqa: E402
 
 DEV = 'cuda:0'
 STAGES = (2, 1, 1, 1)
+SHRINK = dict(stages=STAGES, width_div=2)
+
+
+_batch, _grad_ok = step_harness.batch, step_harness.grad_ok
 
 
 def _build(mask_rows, seed=7):
-    m = MaskRCNN(n_fg_class=80, device=DEV, seed=seed, _test_shrink=dict(stages=STAGES, width_div=2))
-    chain = FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows=mask_rows)
-    return m, chain
-
-
-def _batch(N=2, H=128, W=160, G=3):
-    b = make_batch(3, N, H, W, G=G)
-    b['bboxes'][:, :, 2:] = np.minimum(b['bboxes'][:, :, 2:], [H, W])
-    return {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
-
-
-def _grad_ok(got, want, err, floor, tol):
-    """err = max |got - want| / tensor scale, floor = the same for the float32 oracle.  Pass: err < max(tol, 3 x floor) - or
-    the deviation is ONE flipped ReLU decision: a pre-activation of fc1 / fc2 / a head convolution within rounding of zero
-    toggles a whole (RoI, unit) term, i.e. a few entries of the gradient move by up to ~5e-3 of its scale while the tensor
-    as a whole does not (relative L2 error < tol).  Measured: head/fc1/W differs by 4.4e-3 in max norm between two DEVICE
-    evaluations whose BatchNorm statistics differ by 1e-7 (features by 2e-6) - no float32 implementation is stable there."""
-    if err < max(tol, 3 * floor):
-        return True
-    l2 = float((got - want).norm()) / max(float(want.norm()), 1e-30)
-    return l2 < tol and err < 10 * tol
+    return step_harness.build(SHRINK, seed, mask_rows=mask_rows)
 
 
 @pytest.mark.parametrize('mask_rows', ['positives', 'all'])
@@ -144,14 +129,11 @@ def test_keypoint_step_matches_oracle():
 def test_step_is_bit_reproducible_and_sgd_updates():
     m, chain = _build('positives')
     b = _batch()
-    chain.sampler_keys = None
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
+    step_harness.seed(chain)
     chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
     g1 = m.ps.grads.clone()
     l1 = float(chain.observation['loss'])
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
+    step_harness.seed(chain)
     chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
     assert float(chain.observation['loss']) == l1
     assert torch.equal(g1, m.ps.grads)                      # no atomics anywhere on the path
@@ -176,8 +158,7 @@ def test_sectioned_update_gives_the_same_bits_as_the_single_pass():
     outs = []
     for sectioned in (False, True):
         m, chain = _build('positives')
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, sectioned_update=sectioned).setup(chain)
         opt.LOCAL_BUCKET_BYTES = 256 << 10
         opt.add_hook(WeightDecay(0.0005))
@@ -185,7 +166,7 @@ def test_sectioned_update_gives_the_same_bits_as_the_single_pass():
         inner = opt._sgd_section
 
         def spy(start, end, inner=inner, chain=chain, calls=calls):
-            calls.append((start, end, chain._bwd is not None))
+            calls.append((start, end, chain.pending is not None))
             inner(start, end)
         opt._sgd_section = spy
         losses = []
@@ -292,8 +273,7 @@ def test_user_supplied_mask_loss_fun_matches_fused_kernel(kind):
     for name, f in (('fused', fused_fun), ('user', user_fun)):
         chain = mk(f)
         assert chain.mask_loss_kind == ('generic' if name == 'user' else chain.mask_loss_kind)
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         loss = chain(*args)
         loss.backward()
         res[name] = (float(chain.observation['mask_loss']), float(loss.detach()), chain.faster_rcnn.ps.grads.clone())
@@ -305,8 +285,7 @@ def test_user_supplied_mask_loss_fun_matches_fused_kernel(kind):
     assert float((gf - gu).abs().max()) <= 2e-5 * float(gf.abs().max())
     # loss scaling: (loss * k).backward() scales every gradient by k (the upstream gradient is honoured)
     chain = mk(fused_fun)
-    chain.proposal_target_creator.set_seed(5)
-    chain.anchor_target_creator.set_seed(9)
+    step_harness.seed(chain)
     (chain(*args) * 4.0).backward()
     assert float((chain.faster_rcnn.ps.grads - 4.0 * gf).abs().max()) <= 1e-5 * 4.0 * float(gf.abs().max())
 
@@ -563,9 +542,7 @@ def test_early_rpn_backward_gives_the_same_gradients():
     for early in (False, True):
         m, chain = _build('all')
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         FPNMaskRCNNTrainChain.EARLY_RPN_BACKWARD = early
         try:
             opt = MomentumSGD(lr=0.0, momentum=0.0).setup(chain)       # lr 0: update() runs forward + backward and leaves the parameters alone
@@ -600,9 +577,7 @@ def test_graphed_step_replays_the_eager_step():
     for graphed in (False, True):
         m, chain = _build('all')
         b = _batch()
-        chain.sampler_keys = None
-        chain.proposal_target_creator.set_seed(5)
-        chain.anchor_target_creator.set_seed(9)
+        step_harness.seed(chain)
         opt = MomentumSGD(lr=1e-2, momentum=0.9, high_priority_stream=False).setup(chain)
         opt.add_hook(WeightDecay(0.0005))
         batch = [b['imgs'], b['bboxes'], b['labels'], b['masks']]
@@ -630,9 +605,7 @@ def test_laterals_off_the_chain_give_the_same_bits():
         try:
             m, chain = _build('all')
             b = _batch()
-            chain.sampler_keys = None
-            chain.proposal_target_creator.set_seed(5)
-            chain.anchor_target_creator.set_seed(9)
+            step_harness.seed(chain)
             chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
             torch.cuda.synchronize()
             g, l = m.ps.grads.clone(), float(chain.observation['loss'])
@@ -659,9 +632,7 @@ def test_small_rpn_levels_beside_p2_give_the_same_bits():
         try:
             m, chain = _build('all')
             b = _batch()
-            chain.sampler_keys = None
-            chain.proposal_target_creator.set_seed(5)
-            chain.anchor_target_creator.set_seed(9)
+            step_harness.seed(chain)
             chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
             torch.cuda.synchronize()
             g, l = m.ps.grads.clone(), float(chain.observation['loss'])
@@ -692,9 +663,7 @@ def test_composite_bottleneck_calls_give_the_same_bits(arith):
             chain = FPNMaskRCNNTrainChain(m, mask_loss_fun=calc_mask_loss, mask_rows='all', gemm_arithmetic=arith)
             chain.keep_outputs = True
             b = _batch()
-            chain.sampler_keys = None
-            chain.proposal_target_creator.set_seed(5)
-            chain.anchor_target_creator.set_seed(9)
+            step_harness.seed(chain)
             chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
             torch.cuda.synchronize()
             feats = [f.clone() for f in chain.outputs['features']]
@@ -727,9 +696,7 @@ def test_roi_align_backward_plans_built_beside_the_forward_give_the_same_bits():
         try:
             m, chain = _build('all')
             b = _batch()
-            chain.sampler_keys = None
-            chain.proposal_target_creator.set_seed(5)
-            chain.anchor_target_creator.set_seed(9)
+            step_harness.seed(chain)
             chain(b['imgs'], b['bboxes'], b['labels'], b['masks'], 1.0).backward()
             torch.cuda.synchronize()
             g, l = m.ps.grads.clone(), float(chain.observation['loss'])
