@@ -7,7 +7,9 @@ rows on an H x W canvas, as the large-scale-jitter stage leaves them (kept rows 
 Pasting example 1 onto example 0 covers A0 (dropped) and the lower half of A1 (its box shrinks to rows 30..34)."""
 import numpy as np
 
-CANVASES = [(64, 64), (61, 50)]         # the shapes of tests/test_lsj_gpu.py; the second has ragged rows (W % 16 != 0, W % 4 != 0)
+# the shapes of tests/test_lsj_gpu.py, one block per plane in the mask kernels; the second has ragged rows (W % 16 != 0, W % 4 != 0).  The
+# canvases of several blocks per plane - 128 x 128, 100 x 208, 100 x 200 (W % 4 == 0 only) - are tests/augment_edge_cases.py's
+CANVASES = [(64, 64), (61, 50)]
 
 
 def rect(H, W, ys, xs):

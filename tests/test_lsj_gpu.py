@@ -18,8 +18,9 @@ from chainer_maskrcnn._hip import ops  # noqa: E402
 from chainer_maskrcnn.dataset import augment  # noqa: E402
 from chainer_maskrcnn.dataset.augment import Augment, lsj_geometry  # noqa: E402
 from chainer_maskrcnn.dataset.loader import BatchLoader  # noqa: E402
-from chainer_maskrcnn.dataset.transforms import KeypointTransform, RawTransform, Transform, resize_linear, resize_nearest  # noqa: E402
+from chainer_maskrcnn.dataset.transforms import KeypointTransform, RawTransform, Transform, resize_linear  # noqa: E402
 from tests.augment_data import write_coco  # noqa: E402
+from tests.augment_edge_cases import np_crop as _np_crop  # noqa: E402  (the NumPy rule, shared with tests/test_augment_edges_gpu.py)
 
 DEV = 'cuda:0'
 CANVASES = [(64, 64), (61, 50)]          # the second: a ragged row (dst_w % 4 != 0, % 16 != 0) takes the scalar stores
@@ -96,22 +97,6 @@ def _mask_batch(flip, canvas):
     exs = [(np.stack(a), (80, 90, 10, 20, 64, 64)), (np.stack(b), (120, 120, 28, 28, 64, 64)),
            (np.stack(c), lsj_geometry(33, 47, 64, 1.7, 0.6, 0.3)), (np.zeros((0, 20, 30), np.uint8), lsj_geometry(20, 30, 64, 0.5, 0.0, 0.0))]
     return [(np.ascontiguousarray(m[:, :, ::-1]) if flip else m, flip, _fit(g, canvas)) for m, g in exs]
-
-
-def _np_crop(batch, labels_in, G):
-    """NumPy: the cropped planes of every instance, then boxes, labels, gather table and compacted planes."""
-    N = len(batch)
-    canvas_planes = []
-    bboxes, labels, gather = np.zeros((N, G, 4), np.float32), np.full((N, G), -1, np.int32), np.full((N, G), -1, np.int32)
-    for n, (m, flip, (oh, ow, y0, x0, ch, cw)) in enumerate(batch):
-        planes = [resize_nearest(p[:, ::-1] if flip else p, (oh, ow))[y0:y0 + ch, x0:x0 + cw] for p in m]
-        kept = [g for g, p in enumerate(planes) if p.any()][:G]
-        for j, g in enumerate(kept):
-            ys, xs = np.nonzero(planes[g])
-            bboxes[n, j] = (ys.min(), xs.min(), ys.max() + 1, xs.max() + 1)
-            labels[n, j], gather[n, j] = labels_in[n, g], g
-        canvas_planes.append((planes, kept))
-    return bboxes, labels, gather, canvas_planes
 
 
 def _run_boxes(batch, G, canvas):
