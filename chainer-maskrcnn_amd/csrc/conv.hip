@@ -893,7 +893,6 @@ int g_debug_skip = 0;
 // EXPLORATORY: forward-kind GEMM launches with three-term split-bf16 operands (mrcnn_conv2d_set_split_bf16).  Off by default;
 // results then differ from the float32 kernels by ~1e-5 relative per product.
 int g_split_mode[3] = {0, 0, 0};        // per pass (forward, backward-data, backward-filter): 0 float32, 1 bf16 planes, 2 half planes
-thread_local int g_cur_pass = 0;        // set by the entry points around their launches (PASS_*)
 
 // The tile and the operand arithmetic launch_conv really uses for a planned tile (also read by mrcnn_conv2d_plan_query): the image
 // layer has fixed tiles and only float32-MFMA instantiations, whatever split mode is set.
@@ -904,8 +903,19 @@ TileChoice launch_tile(const ConvP &p, TileChoice t) {
 }
 int launch_arithmetic(const ConvP &p, int pass) { return p.smallc ? 0 : g_split_mode[pass]; }
 
+// One k_conv_igemm launch of the planned tile in operand arithmetic SPLIT.
+template <int MODE, int SPLIT>
+void launch_tile_kernel(const ConvP &p, TileChoice t, dim3 grid, hipStream_t st) {
+    const dim3 blk(CONV_THREADS);
+    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 128, false, SPLIT>), grid, blk, 0, st, p);
+    else if (t.bm == 128 && t.bn == 64) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 64, false, SPLIT>), grid, blk, 0, st, p);
+    else if (t.bm == 64 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 128, false, SPLIT>), grid, blk, 0, st, p);
+    else hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 64, false, SPLIT>), grid, blk, 0, st, p);
+}
+
+// pass: the PASS_* of the entry point this launch serves (its operand arithmetic is set per pass)
 template <int MODE>
-void launch_conv(ConvP &p, int zdim, TileChoice t, hipStream_t st) {
+void launch_conv(ConvP &p, int zdim, TileChoice t, int pass, hipStream_t st) {
     // zdim: BWD_FILTER taps * ksplit; FWD / BWD_DATA ksplit
     t = launch_tile<MODE>(p, t);
     p.tiles_m = mrcnn::cdiv(p.M, t.bm);
@@ -925,36 +935,15 @@ void launch_conv(ConvP &p, int zdim, TileChoice t, hipStream_t st) {
         else hipLaunchKernelGGL((k_conv_igemm<MODE_BWD_FILTER, 64, 128, true>), grid, blk, 0, st, p);
         return;
     }
-    {   // exploratory opt-in: three-term split operands; the planes' type per PASS of the calling entry point
-        const int split = launch_arithmetic(p, g_cur_pass);
-        // (Sending the emulated launches with 64 x 64 / 128 x 64 / 64 x 128 tiles - MFMA-busy 0.12 - 0.24 - to the float32-MFMA kernel was
-        // measured in round 5, same-process A/B on the step: 21.72 ms emulated everywhere against 21.84 - 21.91 ms with any subset on float32.)
-        if (split == 1) {
-            if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 128, false, 1>), grid, blk, 0, st, p);
-            else if (t.bm == 128 && t.bn == 64) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 64, false, 1>), grid, blk, 0, st, p);
-            else if (t.bm == 64 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 128, false, 1>), grid, blk, 0, st, p);
-            else hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 64, false, 1>), grid, blk, 0, st, p);
-            return;
-        }
-        if (split == 3) {
-            if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 128, false, 3>), grid, blk, 0, st, p);
-            else if (t.bm == 128 && t.bn == 64) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 64, false, 3>), grid, blk, 0, st, p);
-            else if (t.bm == 64 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 128, false, 3>), grid, blk, 0, st, p);
-            else hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 64, false, 3>), grid, blk, 0, st, p);
-            return;
-        }
-        if (split == 2) {
-            if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 128, false, 2>), grid, blk, 0, st, p);
-            else if (t.bm == 128 && t.bn == 64) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 64, false, 2>), grid, blk, 0, st, p);
-            else if (t.bm == 64 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 128, false, 2>), grid, blk, 0, st, p);
-            else hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 64, false, 2>), grid, blk, 0, st, p);
-            return;
-        }
+    // exploratory opt-in: three-term split operands; the planes' type per PASS of the calling entry point
+    // (Sending the emulated launches with 64 x 64 / 128 x 64 / 64 x 128 tiles - MFMA-busy 0.12 - 0.24 - to the float32-MFMA kernel was
+    // measured in round 5, same-process A/B on the step: 21.72 ms emulated everywhere against 21.84 - 21.91 ms with any subset on float32.)
+    switch (launch_arithmetic(p, pass)) {
+    case 1: launch_tile_kernel<MODE, 1>(p, t, grid, st); break;
+    case 3: launch_tile_kernel<MODE, 3>(p, t, grid, st); break;
+    case 2: launch_tile_kernel<MODE, 2>(p, t, grid, st); break;
+    default: launch_tile_kernel<MODE, 0>(p, t, grid, st);
     }
-    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 128, false>), grid, blk, 0, st, p);
-    else if (t.bm == 128 && t.bn == 64) hipLaunchKernelGGL((k_conv_igemm<MODE, 128, 64, false>), grid, blk, 0, st, p);
-    else if (t.bm == 64 && t.bn == 128) hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 128, false>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((k_conv_igemm<MODE, 64, 64, false>), grid, blk, 0, st, p);
 }
 
 // Sum split-K slabs: out[i] = (accumulate ? out[i] : 0) + sum_s slab[s][i]  (deterministic order).
@@ -976,6 +965,11 @@ __global__ __launch_bounds__(256) void k_sum_slabs(const float *__restrict__ sla
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     *reinterpret_cast<float4 *>(out + i * 4) = s;
+}
+int sum_slabs(const float *slabs, float *out, size_t n4, int ksplit, int accumulate, hipStream_t st) {
+    if (!(g_debug_skip & 10)) hipLaunchKernelGGL(k_sum_slabs, dim3(mrcnn::cdiv(n4, 256)), dim3(256), 0, st, slabs, out, n4, ksplit, accumulate);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
 }
 
 // FWD / BWD_DATA split-K epilogue: out[m][n] = (accumulate ? out : 0) + sum_s slab[s][m][n] + bias[n], optional ReLU.
@@ -1107,34 +1101,55 @@ __global__ __launch_bounds__(CSF_CH * CSF_SL) void k_colsum_final(const float *_
         out[c] = (float)a + (accumulate ? out[c] : 0.0f);
     }
 }
+// out[c] = (accumulate ? out[c] : 0) + the column sums of g (P rows, C channels), through part (col_plan(P, C).nblk rows of C);
+// colsum_final alone where a transform kernel has already left `nrows` rows of partial sums in part.
+int colsum_final(const float *part, float *out, int nrows, int C, int accumulate, hipStream_t st) {
+    if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_final, dim3(mrcnn::cdiv(C, CSF_CH)), dim3(CSF_CH * CSF_SL), 0, st, part, out, nrows, C, accumulate);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+int colsum(const float *g, float *part, float *out, int P, int C, int accumulate, hipStream_t st) {
+    const ColPlan cp = col_plan(P, C);
+    if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_partial, dim3(cp.nblk), dim3(256), 0, st, g, part, P, C, cp.G, cp.RPI, cp.rows_per_blk);
+    MRCNN_LAUNCH_CHECK();
+    return colsum_final(part, out, cp.nblk, C, accumulate, st);
+}
 
 int conv_out(int in, int k, int s, int pad) { return (in + 2 * pad - k) / s + 1; }
 
-int check_conv(const void *a, const void *b, const void *c, int N, int H, int W, int Cin, int Cout, int KH,
-               int KW, int stride, int pad) {
+// The geometry of one convolution call as the entry points and size queries receive it; everything below them takes this record.
+struct ConvGeom {
+    int N, H, W, Cin, Cout, KH, KW, stride, pad;
+    bool valid() const { return N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0; }
+    int Ho() const { return conv_out(H, KH, stride, pad); }
+    int Wo() const { return conv_out(W, KW, stride, pad); }
+    // the same map with Cin and Cout exchanged: the pipeline the backward-data pass runs (from the layer's Cout to its Cin channels)
+    ConvGeom transposed() const { return {N, H, W, Cout, Cin, KH, KW, stride, pad}; }
+};
+
+int check_conv(const void *a, const void *b, const void *c, const ConvGeom &cg) {
     if (!a || !b || !c) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d: null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0)
-        return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d: bad sizes");
-    if ((Cin % BK && Cin != 4) || Cout % BK)
+    if (!cg.valid()) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d: bad sizes");
+    if ((cg.Cin % BK && cg.Cin != 4) || cg.Cout % BK)
         return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED,
-                               "conv2d: Cin (%d) must be 4 or a multiple of %d... Cout (%d) a multiple of %d (the host layer pads)", Cin, BK, Cout, BK);
-    if (conv_out(H, KH, stride, pad) <= 0 || conv_out(W, KW, stride, pad) <= 0)
-        return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d: empty output");
+                               "conv2d: Cin (%d) must be 4 or a multiple of %d... Cout (%d) a multiple of %d (the host layer pads)", cg.Cin, BK, cg.Cout, BK);
+    if (cg.Ho() <= 0 || cg.Wo() <= 0) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d: empty output");
     const long long lim = (1ll << 30) - 1;      // element offsets are 32-bit and byte sizes fit a buffer descriptor
-    const long long Ho_ = conv_out(H, KH, stride, pad), Wo_ = conv_out(W, KW, stride, pad);
-    if ((long long)N * H * W * Cin > lim || (long long)N * Ho_ * Wo_ * Cout > lim || (long long)Cout * KH * KW * Cin > lim ||
-        (long long)N * std::max<long long>(H * W, Ho_ * Wo_) >= (1ll << 24))
+    const long long Ho_ = cg.Ho(), Wo_ = cg.Wo();
+    if ((long long)cg.N * cg.H * cg.W * cg.Cin > lim || (long long)cg.N * Ho_ * Wo_ * cg.Cout > lim ||
+        (long long)cg.Cout * cg.KH * cg.KW * cg.Cin > lim || (long long)cg.N * std::max<long long>(cg.H * cg.W, Ho_ * Wo_) >= (1ll << 24))
         return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d: tensor too large for 32-bit offsets / 24-bit pixel indices");
     return 0;
 }
 
-ConvP make_p(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+ConvP make_p(const ConvGeom &cg) {
     ConvP p{};
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pad_w = pad;
-    p.Ho = conv_out(H, KH, stride, pad);
-    p.Wo = conv_out(W, KW, stride, pad);
+    p.N = cg.N; p.H = cg.H; p.W = cg.W; p.Cin = cg.Cin; p.Cout = cg.Cout; p.KH = cg.KH; p.KW = cg.KW;
+    p.stride = cg.stride; p.pad = cg.pad; p.pad_w = cg.pad;
+    p.Ho = cg.Ho();
+    p.Wo = cg.Wo();
     p.ksplit = 1;
-    p.smallc = (Cin == 4);
+    p.smallc = (cg.Cin == 4);
     p.bn_part = nullptr;
     return p;
 }
@@ -1243,10 +1258,10 @@ TileChoice data_launch_plan(ConvP &p, int nsteps, long long ldc, bool have_ws, s
 }
 
 template <int MODE>
-int run_data_conv(ConvP &p, int nsteps, long long ldc, void *ws, size_t ws_bytes, hipStream_t st) {
+int run_data_conv(ConvP &p, int nsteps, long long ldc, int pass, void *ws, size_t ws_bytes, hipStream_t st) {
     const TileChoice t = data_launch_plan<MODE>(p, nsteps, ldc, ws != nullptr, ws_bytes);
     if (p.ksplit > 1 || p.tail_ks) p.slab = (float *)ws;
-    launch_conv<MODE>(p, p.ksplit, t, st);
+    launch_conv<MODE>(p, p.ksplit, t, pass, st);
     MRCNN_LAUNCH_CHECK();
     if (p.tail_ks) {
         const int tiles = mrcnn::cdiv(p.M, t.bm) * mrcnn::cdiv(p.Ng, t.bn);
@@ -1305,9 +1320,10 @@ int wino_m(int H, int W, int pass) {
     const long long c2 = 16ll * ((H + 1) / 2) * ((W + 1) / 2), c4 = 36ll * ((H + 3) / 4) * ((W + 3) / 4);
     return c4 < c2 ? 4 : 2;
 }
-bool wino_ok(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int pass) {
+bool wino_ok(const ConvGeom &cg, int pass) {
+    const int N = cg.N, H = cg.H, W = cg.W, Cin = cg.Cin, Cout = cg.Cout;
     if (g_wino_pass_tile[pass] < 0) return false;
-    if (KH != 3 || KW != 3 || stride != 1 || pad != 1) return false;
+    if (cg.KH != 3 || cg.KW != 3 || cg.stride != 1 || cg.pad != 1) return false;
     // measured on gfx950 (tools/conv_bench.py): with >= 256 channels the GEMMs are deep enough (K >= 256) to win from
     // 2048 pixels up; at 128 channels Winograd ties the direct kernel, at 64 it loses; below 2048 pixels the four launches
     // are latency-bound
@@ -1321,28 +1337,29 @@ bool wino_ok(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
     return 16 * Tp < (1ll << 24) && 16 * Tp * std::max(Cin, Cout) < (1ll << 30);    // limits of the GEMM kernel's offsets
 }
 struct WinoGeom { int m, a, nk, th, tw; long long T, Tp; };
-WinoGeom wino_geom(int N, int H, int W, int pass) {
+WinoGeom wino_geom(const ConvGeom &cg, int pass) {
     WinoGeom g;
-    g.m = wino_m(H, W, pass); g.a = g.m + 2; g.nk = g.a * g.a;
-    g.th = (H + g.m - 1) / g.m; g.tw = (W + g.m - 1) / g.m;
-    g.T = (long long)N * g.th * g.tw;
+    g.m = wino_m(cg.H, cg.W, pass); g.a = g.m + 2; g.nk = g.a * g.a;
+    g.th = (cg.H + g.m - 1) / g.m; g.tw = (cg.W + g.m - 1) / g.m;
+    g.T = (long long)cg.N * g.th * g.tw;
     g.Tp = (g.T + WINO_ROWS - 1) / WINO_ROWS * WINO_ROWS;
     return g;
 }
 struct WinoLayout { size_t u, v, m, inner, total; WinoGeom g; };
-WinoLayout wino_layout(int N, int H, int W, int Cin, int Cout, int pass) {
+// cg: the geometry of the pipeline (the layer's, transposed() for backward-data)
+WinoLayout wino_layout(const ConvGeom &cg, int pass) {
     WinoLayout L;
-    L.g = wino_geom(N, H, W, pass);
+    L.g = wino_geom(cg, pass);
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     size_t o = 0;
-    L.u = o; o += al((size_t)L.g.nk * Cout * Cin * 6);          // float32, or three bf16 planes (plane GEMMs)
-    L.v = o; o += al((size_t)L.g.nk * L.g.Tp * Cin * 4);
-    L.m = o; o += al((size_t)L.g.nk * L.g.Tp * Cout * 4);
+    L.u = o; o += al((size_t)L.g.nk * cg.Cout * cg.Cin * 6);          // float32, or three bf16 planes (plane GEMMs)
+    L.v = o; o += al((size_t)L.g.nk * L.g.Tp * cg.Cin * 4);
+    L.m = o; o += al((size_t)L.g.nk * L.g.Tp * cg.Cout * 4);
     L.inner = o; o += (size_t)4 * g_cus() * 128 * 128 * sizeof(float);              // tail-split slabs of the GEMM launch
     L.total = o;
     return L;
 }
-size_t wino_ws_bytes(int N, int H, int W, int Cin, int Cout, int pass) { return wino_layout(N, H, W, Cin, Cout, pass).total; }
+size_t wino_ws_bytes(const ConvGeom &cg, int pass) { return wino_layout(cg, pass).total; }
 
 // ---- the 1-D transforms (T = float or V4) --------------------------------------------------------------------------
 struct V4 { float x, y, z, w; };
@@ -1949,14 +1966,15 @@ bool pg_big_g_ok(const WinoGeom &g, int Cin, int Cout) {
 struct WinoFLayout { size_t v, w, slabs, du, total; WinoGeom g; int ksplit, kchunk; int big; int ks32, kc32; };
 // the batched filter-gradient GEMM of the Winograd path as k_conv_igemm sees it: a 1x1 layer over Tp "pixels" per transform point
 ConvP wino_filter_p(const WinoGeom &g, int Cin, int Cout) {
-    ConvP p = make_p(1, 1, (int)g.Tp, Cin, Cout, 1, 1, 1, 0);
+    ConvP p = make_p(ConvGeom{1, 1, (int)g.Tp, Cin, Cout, 1, 1, 1, 0});
     p.wbatch_rows = (int)g.Tp; p.wbatch_n = g.nk;
     bwd_filter_gemm(p);
     return p;
 }
-WinoFLayout wino_filter_layout(int N, int H, int W, int Cin, int Cout) {
+WinoFLayout wino_filter_layout(const ConvGeom &cg) {
+    const int Cin = cg.Cin, Cout = cg.Cout;
     WinoFLayout L;
-    L.g = wino_geom(N, H, W, PASS_BWD_FILTER);
+    L.g = wino_geom(cg, PASS_BWD_FILTER);
     ConvP p = wino_filter_p(L.g, Cin, Cout);
     filter_plan(p, L.ksplit, L.kchunk);
     L.ks32 = L.ksplit; L.kc32 = L.kchunk;
@@ -1978,16 +1996,13 @@ WinoFLayout wino_filter_layout(int N, int H, int W, int Cin, int Cout) {
     return L;
 }
 
-// Set by the *_inbn entry points around their call of the ordinary entry point (which they have checked takes the Winograd path): the
-// input transform of that call applies this BatchNorm + ReLU on load.
-thread_local InBN t_inbn{};
-
 // bias_part / bias_rows (nullable): when the gy transform runs here and its blocks cover whole tiles, it also leaves the
 // bias gradient's partial column sums in bias_part and *bias_rows = their number (else *bias_rows = 0: the caller sums gy)
-int wino_bwd_filter(const float *x, const float *gy, float *gw, int N, int H, int W, int Cin, int Cout, int accumulate, void *ws,
+// inbn (the *_inbn entry points; empty otherwise): the input transform applies this BatchNorm + ReLU on load
+int wino_bwd_filter(const float *x, const float *gy, float *gw, const ConvGeom &cg, const InBN &inbn, int accumulate, void *ws,
                     hipStream_t st, const float *v_cached, const float *w_cached, float *bias_part = nullptr, int *bias_rows = nullptr) {
-    const InBN inbn = t_inbn;
-    const WinoFLayout L = wino_filter_layout(N, H, W, Cin, Cout);
+    const int N = cg.N, H = cg.H, W = cg.W, Cin = cg.Cin, Cout = cg.Cout;
+    const WinoFLayout L = wino_filter_layout(cg);
     const WinoGeom &g = L.g;
     char *base = (char *)ws;
     float *Vw = (float *)(base + L.v), *Wt = (float *)(base + L.w), *slabs = (float *)(base + L.slabs), *dU = (float *)(base + L.du);
@@ -2000,35 +2015,30 @@ int wino_bwd_filter(const float *x, const float *gy, float *gw, int N, int H, in
     const int big = (L.big && !w_cached) ? 1 : 0;           // (a cached W is float32: the shared-transform path keeps k_conv_igemm)
     if (!w_cached) WINO_LAUNCH(k_wino_gy, g, dim3((unsigned)((nout + 255) / 256)), gy, Wt, N, H, W, Cout, g.th, g.tw, g.T, g.Tp,
                                fuse_bias ? bias_part : (float *)nullptr, big);
+    const int ksplit = big ? L.ksplit : L.ks32;
+    const size_t n4 = (size_t)Cout * g.nk * Cin / 4;
     if (big) {
         PlaneGemmP q{};
         q.a = reinterpret_cast<const unsigned short *>(Wt); q.b = reinterpret_cast<const unsigned short *>(V);
-        q.c = L.ksplit > 1 ? slabs : dU;
-        q.M = Cout; q.N = Cin; q.K = (int)g.Tp; q.batch_rows = (int)g.Tp; q.nbatch = g.nk; q.ksplit = L.ksplit; q.kchunk = L.kchunk;
+        q.c = ksplit > 1 ? slabs : dU;
+        q.M = Cout; q.N = Cin; q.K = (int)g.Tp; q.batch_rows = (int)g.Tp; q.nbatch = g.nk; q.ksplit = ksplit; q.kchunk = L.kchunk;
         q.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cout * 6); q.bytes_b = (unsigned)((size_t)g.nk * g.Tp * Cin * 4);
         q.ldc = g.nk * Cin; q.dbg = 0; q.stamps = nullptr;
         if (!(g_debug_skip & 1)) launch_pgemm<5>(q, PGB_BM, PGB_BN, st);
         MRCNN_LAUNCH_CHECK();
-        if (L.ksplit > 1) {
-            const size_t n4 = (size_t)Cout * g.nk * Cin / 4;
-            if (!(g_debug_skip & 10)) hipLaunchKernelGGL(k_sum_slabs, dim3(mrcnn::cdiv(n4, 256)), dim3(256), 0, st, slabs, dU, n4, L.ksplit, 0);
-            MRCNN_LAUNCH_CHECK();
-        }
+        if (ksplit > 1) if (int e = sum_slabs(slabs, dU, n4, ksplit, 0, st)) return e;
         WINO_LAUNCH(k_wino_filter_grad, g, dim3(mrcnn::cdiv(Cout * Cin, 256)), dU, gw, Cout, Cin, accumulate, 1);
         return 0;
     }
     ConvP p = wino_filter_p(g, Cin, Cout);
-    p.ksplit = L.ks32; p.kchunk = L.kc32;
-    p.a = w_cached ? w_cached : Wt; p.b = V; p.c = p.ksplit > 1 ? slabs : dU;
+    p.ksplit = ksplit; p.kchunk = L.kc32;
+    p.a = w_cached ? w_cached : Wt; p.b = V; p.c = ksplit > 1 ? slabs : dU;
     p.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cout * 4); p.bytes_b = (unsigned)((size_t)g.nk * g.Tp * Cin * 4);
-    launch_conv<MODE_BWD_FILTER>(p, g.nk * p.ksplit, filter_tile(p), st);
+    launch_conv<MODE_BWD_FILTER>(p, g.nk * ksplit, filter_tile(p), PASS_BWD_FILTER, st);
     MRCNN_LAUNCH_CHECK();
-    if (p.ksplit > 1) {     // a separate, fully parallel slab sum: folding it into k_wino_filter_grad (Cout*Cin threads only) was
-                            // measured 20 % .. 4x slower (tools/wino_sweep.py)
-        const size_t n4 = (size_t)Cout * g.nk * Cin / 4;
-        if (!(g_debug_skip & 10)) hipLaunchKernelGGL(k_sum_slabs, dim3(mrcnn::cdiv(n4, 256)), dim3(256), 0, st, slabs, dU, n4, p.ksplit, 0);
-        MRCNN_LAUNCH_CHECK();
-    }
+    // a separate, fully parallel slab sum: folding it into k_wino_filter_grad (Cout*Cin threads only) was
+    // measured 20 % .. 4x slower (tools/wino_sweep.py)
+    if (ksplit > 1) if (int e = sum_slabs(slabs, dU, n4, ksplit, 0, st)) return e;
     WINO_LAUNCH(k_wino_filter_grad, g, dim3(mrcnn::cdiv(Cout * Cin, 256)), dU, gw, Cout, Cin, accumulate, 1);
     return 0;
 }
@@ -2050,26 +2060,28 @@ bool pg_big_ok(int pass, const WinoGeom &g, int K, int Nn) {
 // the batched GEMM of the Winograd forward / backward-data path as k_conv_igemm sees it: a 1x1 "convolution" over nk*Tp pixels, weight
 // matrix selected by the row block; returns its K steps
 int wino_gemm_p(ConvP &p, const WinoGeom &g, int Cin, int Cout) {
-    p = make_p(1, 1, (int)(g.nk * g.Tp), Cin, Cout, 1, 1, 1, 0);
+    p = make_p(ConvGeom{1, 1, (int)(g.nk * g.Tp), Cin, Cout, 1, 1, 1, 0});
     p.M = (int)(g.nk * g.Tp); p.Ng = Cout;
     p.wbatch_rows = (int)g.Tp; p.wbatch_n = g.nk;
     return Cin / BK;
 }
 
-// in (N,H,W,Cin) -> out (N,H,W,Cout); w is always the layer's (Cout_layer,3,3,Cin_layer) weight tensor: transposed selects
-// the backward-data filter (then Cin here = the layer's Cout and Cout here = the layer's Cin).
-int wino_conv(const float *in, const float *w, float *out, int N, int H, int W, int Cin, int Cout, bool transposed,
+// in (N,H,W,Cin) -> out (N,H,W,Cout), cg = the pipeline's geometry; w is always the layer's (Cout_layer,3,3,Cin_layer) weight tensor:
+// pass PASS_BWD_DATA selects the backward-data filter (then cg is the layer's geometry transposed(): Cin here = the layer's Cout
+// and Cout here = the layer's Cin).  inbn (forward only; empty otherwise): the input transform applies this BatchNorm + ReLU on load.
+int wino_conv(const float *in, const float *w, float *out, const ConvGeom &cg, int pass, const InBN &inbn,
               const float *bias, int relu, int accumulate, const float *relu_x, void *ws, size_t ws_bytes, hipStream_t st,
               float *v_keep, float *w_keep = nullptr, float *gbias = nullptr, int gbias_accumulate = 0, float *bn_part = nullptr) {
-    const InBN inbn = transposed ? InBN{} : t_inbn;
-    const WinoLayout L = wino_layout(N, H, W, Cin, Cout, transposed ? PASS_BWD_DATA : PASS_FWD);
+    const int N = cg.N, H = cg.H, W = cg.W, Cin = cg.Cin, Cout = cg.Cout;
+    const bool transposed = pass == PASS_BWD_DATA;
+    const WinoLayout L = wino_layout(cg, pass);
     const WinoGeom &g = L.g;
     char *base = (char *)ws;
     float *U = (float *)(base + L.u), *V = v_keep ? v_keep : (float *)(base + L.v), *Mb = (float *)(base + L.m);
     // the layer's weight tensor is (Cout_layer, 3, 3, Cin_layer): forward Cout_layer = Cout; transposed Cout_layer = Cin
     const long long nin = g.Tp * (Cin / 4), nout = g.T * (Cout / 4);       // k_wino_input zeroes the padded rows of V
     const unsigned fblocks = (unsigned)mrcnn::cdiv(Cout * Cin, 256);
-    const int big = pg_big_ok(transposed ? PASS_BWD_DATA : PASS_FWD, g, Cin, Cout) ? 1 : 0;
+    const int big = pg_big_ok(pass, g, Cin, Cout) ? 1 : 0;
     if (w_keep) WINO_LAUNCH(k_wino_filter, g, dim3(fblocks), w, U, transposed ? Cin : Cout, transposed ? Cout : Cin, transposed ? 1 : 0, big);
     if (w_keep) {           // backward pass: one read of gy feeds this GEMM, the filter-gradient GEMM and the bias gradient
         const bool wb = gbias && (256 % (Cin / 4)) == 0;
@@ -2077,16 +2089,9 @@ int wino_conv(const float *in, const float *w, float *out, int N, int H, int W, 
         float *bias_part = wb ? (float *)(base + L.m) : nullptr;          // M is written only after this kernel has finished
         WINO_LAUNCH(k_wino_gy_dual, g, dim3(nblk), in, V, w_keep, bias_part, N, H, W, Cin, g.th, g.tw, g.T, g.Tp);
         if (wb) {
-            if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_final, dim3(mrcnn::cdiv(Cin, CSF_CH)), dim3(CSF_CH * CSF_SL), 0, st, bias_part, gbias, nblk, Cin, gbias_accumulate);
-            MRCNN_LAUNCH_CHECK();
+            if (int e = colsum_final(bias_part, gbias, nblk, Cin, gbias_accumulate, st)) return e;
         } else if (gbias) {       // channel count that does not tile a 256-thread block: the ordinary two-kernel column sum
-            const int P = N * H * W;
-            const ColPlan cp = col_plan(P, Cin);
-            float *part = (float *)(base + L.m);
-            if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_partial, dim3(cp.nblk), dim3(256), 0, st, in, part, P, Cin, cp.G, cp.RPI, cp.rows_per_blk);
-            MRCNN_LAUNCH_CHECK();
-            if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_final, dim3(mrcnn::cdiv(Cin, CSF_CH)), dim3(CSF_CH * CSF_SL), 0, st, part, gbias, cp.nblk, Cin, gbias_accumulate);
-            MRCNN_LAUNCH_CHECK();
+            if (int e = colsum(in, (float *)(base + L.m), gbias, N * H * W, Cin, gbias_accumulate, st)) return e;
         }
     } else
         WINO_LAUNCH(k_wino_input_filter, g, dim3(fblocks + (unsigned)((nin + 255) / 256)), in, V, N, H, W, Cin, g.th, g.tw, g.T, g.Tp, w, U,
@@ -2107,26 +2112,27 @@ int wino_conv(const float *in, const float *w, float *out, int N, int H, int W, 
     const int nsteps = wino_gemm_p(p, g, Cin, Cout);
     p.a = V; p.b = U; p.c = Mb;
     p.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cin * 4); p.bytes_b = (unsigned)((size_t)g.nk * Cout * Cin * 4);
-    if (int e = run_data_conv<MODE_FWD>(p, nsteps, Cout, base + L.inner, ws_bytes - L.inner, st)) return e;
+    if (int e = run_data_conv<MODE_FWD>(p, nsteps, Cout, pass, base + L.inner, ws_bytes - L.inner, st)) return e;
     WINO_LAUNCH_OUT(g, dim3((unsigned)((nout + 255) / 256)), Mb, out, N, H, W, Cout, g.th, g.tw, g.T, g.Tp, bias, relu,
                 accumulate, relu_x, bn_part);
     return 0;
 }
 
 // Whether the forward / backward-data entry point takes the Winograd path with this workspace (entry points and
-// mrcnn_conv2d_plan_query).  Cin / Cout are the LAYER's: backward-data runs the pipeline from Cout to Cin channels.
-bool fwd_takes_wino(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool have_ws, size_t ws_bytes) {
-    return wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD) && have_ws && ws_bytes >= wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD);
+// mrcnn_conv2d_plan_query).  cg is the LAYER's: backward-data runs the pipeline from Cout to Cin channels.
+bool fwd_takes_wino(const ConvGeom &cg, bool have_ws, size_t ws_bytes) {
+    return wino_ok(cg, PASS_FWD) && have_ws && ws_bytes >= wino_ws_bytes(cg, PASS_FWD);
 }
-bool bwd_data_takes_wino(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool have_ws, size_t ws_bytes) {
-    return wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, PASS_BWD_DATA) && have_ws && ws_bytes >= wino_ws_bytes(N, H, W, Cout, Cin, PASS_BWD_DATA);
+bool bwd_data_takes_wino(const ConvGeom &cg, bool have_ws, size_t ws_bytes) {
+    const ConvGeom pipe = cg.transposed();
+    return wino_ok(pipe, PASS_BWD_DATA) && have_ws && ws_bytes >= wino_ws_bytes(pipe, PASS_BWD_DATA);
 }
 // what the backward-data entry point declines after check_conv
-int check_bwd_data(int Cin, int stride) {
-    if (stride != 1)
+int check_bwd_data(const ConvGeom &cg) {
+    if (cg.stride != 1)
         return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: stride %d (only 1; strided 1x1 convs are "
-                                                    "handled by the host as a subsample + stride-1 conv)", stride);
-    if (Cin == 4) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: Cin == 4 (image layer) has no data gradient");
+                                                    "handled by the host as a subsample + stride-1 conv)", cg.stride);
+    if (cg.Cin == 4) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: Cin == 4 (image layer) has no data gradient");
     return 0;
 }
 
@@ -2134,8 +2140,9 @@ int check_bwd_data(int Cin, int stride) {
 
 extern "C" size_t mrcnn_conv2d_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
     // upper bound for both the forward and the backward-data split-K slabs (16 splits of the larger output)
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return 0;
-    const long long Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (!cg.valid()) return 0;
+    const long long Ho = cg.Ho(), Wo = cg.Wo();
     if (Ho <= 0 || Wo <= 0) return 0;
     const long long a = (long long)N * Ho * Wo * Cout, b = (long long)N * H * W * Cin;
     const long long fill = (long long)g_plan_fill * g_cus();
@@ -2150,8 +2157,8 @@ extern "C" size_t mrcnn_conv2d_workspace_bytes(int N, int H, int W, int Cin, int
     // a deep forward launch under arithmetic 3 splits K whatever its tile count (data_plan)
     if (Cin % BK == 0 && deep_forward(KH * KW * (Cin / BK))) bytes = std::max(bytes, (size_t)a * DEEP_SPLIT * sizeof(float));
     // the same query serves forward (Cin->Cout) and backward-data (Cout->Cin)
-    if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD)) bytes = std::max(bytes, wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD));
-    if (wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, PASS_BWD_DATA)) bytes = std::max(bytes, wino_ws_bytes(N, H, W, Cout, Cin, PASS_BWD_DATA));
+    if (wino_ok(cg, PASS_FWD)) bytes = std::max(bytes, wino_ws_bytes(cg, PASS_FWD));
+    if (wino_ok(cg.transposed(), PASS_BWD_DATA)) bytes = std::max(bytes, wino_ws_bytes(cg.transposed(), PASS_BWD_DATA));
     return bytes;
 }
 
@@ -2277,14 +2284,13 @@ extern "C" int mrcnn_conv2d_set_debug_skip(int mask) {
 
 extern "C" long long mrcnn_conv2d_executed_macs(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int pass) {
     // multiply-accumulates the MFMA pipes actually execute for one pass (0 forward, 1 backward-data, 2 backward-filter)
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || pass < 0 || pass > 2) return 0;
-    const bool wk = pass == PASS_BWD_DATA ? wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, pass) : wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, pass);
-    if (wk) {
-        const WinoGeom g = wino_geom(N, H, W, pass);
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (!cg.valid() || pass < 0 || pass > 2) return 0;
+    if (wino_ok(pass == PASS_BWD_DATA ? cg.transposed() : cg, pass)) {
+        const WinoGeom g = wino_geom(cg, pass);
         return (long long)g.nk * g.Tp * Cin * Cout;
     }
-    const long long Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
-    return (long long)N * Ho * Wo * KH * KW * (Cin == 4 ? 4 : Cin) * Cout;
+    return (long long)N * cg.Ho() * cg.Wo() * KH * KW * (Cin == 4 ? 4 : Cin) * Cout;
 }
 
 extern "C" int mrcnn_conv2d_plan_query(int pass, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int *out, int n_out) {
@@ -2293,18 +2299,19 @@ extern "C" int mrcnn_conv2d_plan_query(int pass, int N, int H, int W, int Cin, i
     enum { F_PATH, F_BM, F_BN, F_KSPLIT, F_TAIL_KS, F_WINO_M, F_SMALLC, F_ARITH, F_PLANE_GEMM, F_COUNT };
     if (!out || n_out < F_COUNT) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d_plan_query: out must hold %d ints", (int)F_COUNT);
     if (pass < PASS_FWD || pass > PASS_BWD_FILTER) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d_plan_query: pass %d (0 forward, 1 backward-data, 2 backward-filter)", pass);
-    if (int e = check_conv(out, out, out, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    if (pass == PASS_BWD_DATA) if (int e = check_bwd_data(Cin, stride)) return e;
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (int e = check_conv(out, out, out, cg)) return e;
+    if (pass == PASS_BWD_DATA) if (int e = check_bwd_data(cg)) return e;
     for (int i = 0; i < F_COUNT; ++i) out[i] = 0;
-    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
+    ConvP p = make_p(cg);
     TileChoice t{0, 0};
     auto data_fields = [&](const ConvP &q) {       // a forward-kind launch planned by data_launch_plan
         out[F_PATH] = q.tail_ks ? 2 : q.ksplit > 1 ? 1 : 0;
         out[F_KSPLIT] = q.ksplit; out[F_TAIL_KS] = q.tail_ks;
     };
     if (pass == PASS_BWD_FILTER) {
-        if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_BWD_FILTER)) {
-            const WinoFLayout L = wino_filter_layout(N, H, W, Cin, Cout);        // (no cached transform of gy: the call as the wrappers make it)
+        if (wino_ok(cg, PASS_BWD_FILTER)) {
+            const WinoFLayout L = wino_filter_layout(cg);        // (no cached transform of gy: the call as the wrappers make it)
             p = wino_filter_p(L.g, Cin, Cout);
             out[F_PATH] = 3; out[F_WINO_M] = L.g.m; out[F_PLANE_GEMM] = L.big;
             out[F_KSPLIT] = L.big ? L.ksplit : L.ks32;
@@ -2319,18 +2326,17 @@ extern "C" int mrcnn_conv2d_plan_query(int pass, int N, int H, int W, int Cin, i
         const bool fwd = pass == PASS_FWD;
         const size_t ws_bytes = mrcnn_conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad);
         const bool have_ws = ws_bytes > 0;
-        const bool wino = fwd ? fwd_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, have_ws, ws_bytes)
-                              : bwd_data_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, have_ws, ws_bytes);
+        const bool wino = fwd ? fwd_takes_wino(cg, have_ws, ws_bytes) : bwd_data_takes_wino(cg, have_ws, ws_bytes);
         if (wino) {
-            const int ci = fwd ? Cin : Cout, co = fwd ? Cout : Cin;              // the pipeline's channels (wino_conv's Cin, Cout)
-            const WinoLayout L = wino_layout(N, H, W, ci, co, pass);
+            const ConvGeom pipe = fwd ? cg : cg.transposed();              // the pipeline's geometry (wino_conv's cg)
+            const WinoLayout L = wino_layout(pipe, pass);
             out[F_PATH] = 3; out[F_WINO_M] = L.g.m;
-            if (pg_big_ok(pass, L.g, ci, co)) {
+            if (pg_big_ok(pass, L.g, pipe.Cin, pipe.Cout)) {
                 out[F_PLANE_GEMM] = 1; out[F_KSPLIT] = 1;
                 t = TileChoice{PGB_BM, PGB_BN};
             } else {
-                const int nsteps = wino_gemm_p(p, L.g, ci, co);
-                t = launch_tile<MODE_FWD>(p, data_launch_plan<MODE_FWD>(p, nsteps, co, true, ws_bytes - L.inner));
+                const int nsteps = wino_gemm_p(p, L.g, pipe.Cin, pipe.Cout);
+                t = launch_tile<MODE_FWD>(p, data_launch_plan<MODE_FWD>(p, nsteps, pipe.Cout, true, ws_bytes - L.inner));
                 out[F_KSPLIT] = p.ksplit; out[F_TAIL_KS] = p.tail_ks;
             }
         } else if (fwd) {
@@ -2350,46 +2356,51 @@ extern "C" int mrcnn_conv2d_plan_query(int pass, int N, int H, int W, int Cin, i
 }
 
 extern "C" size_t mrcnn_conv2d_winograd_v_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return 0;
-    if (!wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD)) return 0;
-    const WinoGeom g = wino_geom(N, H, W, PASS_FWD);
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (!cg.valid() || !wino_ok(cg, PASS_FWD)) return 0;
+    const WinoGeom g = wino_geom(cg, PASS_FWD);
     return (size_t)g.nk * g.Tp * Cin * sizeof(float);
 }
 
+// The bodies of mrcnn_conv2d_fwd_f32, mrcnn_conv2d_fwd_bnstats_f32 and mrcnn_conv2d_bwd_filter_f32 take the on-load BatchNorm of the
+// *_inbn entry points as an argument (empty: the input is read as it is); only the Winograd input transforms apply it.
+static int conv_fwd(const float *x, const float *w, const float *bias, float *y, const ConvGeom &cg, int relu, float *wino_v, void *ws,
+                    size_t ws_bytes, hipStream_t st, const InBN &inbn = InBN{}) {
+    if (int e = check_conv(x, w, y, cg)) return e;
+    if (fwd_takes_wino(cg, ws != nullptr, ws_bytes))
+        return wino_conv(x, w, y, cg, PASS_FWD, inbn, bias, relu, 0, nullptr, ws, ws_bytes, st, wino_v);
+    ConvP p = make_p(cg);
+    p.a = x; p.b = w; p.c = y; p.bias = bias; p.relu = relu;
+    p.bytes_a = (unsigned)((size_t)cg.N * cg.H * cg.W * cg.Cin * 4); p.bytes_b = (unsigned)((size_t)cg.Cout * cg.KH * cg.KW * cg.Cin * 4);
+    const int nsteps = fwd_gemm(p);
+    return run_data_conv<MODE_FWD>(p, nsteps, cg.Cout, PASS_FWD, ws, ws_bytes, st);
+}
 extern "C" int mrcnn_conv2d_fwd_f32(const float *x, const float *w, const float *bias, float *y, int N, int H,
                                     int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu,
                                     float *wino_v, void *ws, size_t ws_bytes, void *stream) {
-    g_cur_pass = 0;
-    if (int e = check_conv(x, w, y, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    if (fwd_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, ws != nullptr, ws_bytes))
-        return wino_conv(x, w, y, N, H, W, Cin, Cout, false, bias, relu, 0, nullptr, ws, ws_bytes, (hipStream_t)stream, wino_v);
-    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
-    p.a = x; p.b = w; p.c = y; p.bias = bias; p.relu = relu;
-    p.bytes_a = (unsigned)((size_t)N * H * W * Cin * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
-    const int nsteps = fwd_gemm(p);
-    return run_data_conv<MODE_FWD>(p, nsteps, Cout, ws, ws_bytes, (hipStream_t)stream);
+    return conv_fwd(x, w, bias, y, ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad}, relu, wino_v, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // Forward convolution of a layer that feeds a training-mode BatchNorm (no bias, no ReLU): the epilogue also leaves the
 // per-channel sums / sums of squares of its output rows in bn_part (rows, 2, Cout) - the statistics pass of BatchNorm
 // (one read of the activation) disappears; mrcnn_bn_train_fwd_stats_f32 finishes from the partials.  rows = 0: this
 // geometry takes a path without the fused statistics (Winograd, split-K or tail-split launches) - call the plain entry.
-static int bnstats_plan(ConvP &p, TileChoice &t, bool &wino, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+static int bnstats_plan(ConvP &p, TileChoice &t, bool &wino, const ConvGeom &cg) {
     wino = false;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return 0;
-    if ((Cin % BK && Cin != 4) || Cout % BK || Cin == 4) return 0;
-    if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD)) {
+    if (!cg.valid()) return 0;
+    if ((cg.Cin % BK && cg.Cin != 4) || cg.Cout % BK || cg.Cin == 4) return 0;
+    if (wino_ok(cg, PASS_FWD)) {
         // Winograd forward: the output transform produces the partials, one row per 256-thread block of whole tiles
-        const int C4 = Cout / 4;
+        const int C4 = cg.Cout / 4;
         if (C4 > 256 || 256 % C4) return 0;
         wino = true;
-        const WinoGeom g = wino_geom(N, H, W, PASS_FWD);
+        const WinoGeom g = wino_geom(cg, PASS_FWD);
         return (int)((g.T * C4 + 255) / 256);
     }
-    p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
+    p = make_p(cg);
     if (p.Ho <= 0 || p.Wo <= 0) return 0;
-    p.M = N * p.Ho * p.Wo; p.Ng = Cout;
-    data_plan<MODE_FWD>(p, t, KH * KW * (Cin / BK));
+    p.M = cg.N * p.Ho * p.Wo; p.Ng = cg.Cout;
+    data_plan<MODE_FWD>(p, t, cg.KH * cg.KW * (cg.Cin / BK));
     if (p.ksplit > 1 || p.tail_ks) return 0;
     return mrcnn::cdiv(p.M, t.bm) * 2;
 }
@@ -2397,55 +2408,59 @@ extern "C" size_t mrcnn_conv2d_bnstats_rows(int N, int H, int W, int Cin, int Co
     ConvP p;
     TileChoice t;
     bool wino;
-    return (size_t)bnstats_plan(p, t, wino, N, H, W, Cin, Cout, KH, KW, stride, pad);
+    return (size_t)bnstats_plan(p, t, wino, ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad});
+}
+static int conv_fwd_bnstats(const float *x, const float *w, float *y, const ConvGeom &cg, float *bn_part, float *wino_v, void *ws,
+                            size_t ws_bytes, hipStream_t st, const InBN &inbn = InBN{}) {
+    if (int e = check_conv(x, w, y, cg)) return e;
+    ConvP p;
+    TileChoice t;
+    bool wino;
+    if (!bn_part || bnstats_plan(p, t, wino, cg) == 0)
+        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_fwd_bnstats: no fused statistics for this geometry (mrcnn_conv2d_bnstats_rows == 0)");
+    if (wino) {
+        if (!ws || ws_bytes < wino_ws_bytes(cg, PASS_FWD))
+            return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "conv2d_fwd_bnstats: workspace %zu < %zu", ws_bytes, wino_ws_bytes(cg, PASS_FWD));
+        return wino_conv(x, w, y, cg, PASS_FWD, inbn, nullptr, 0, 0, nullptr, ws, ws_bytes, st, wino_v, nullptr, nullptr, 0, bn_part);
+    }
+    p.a = x; p.b = w; p.c = y; p.bias = nullptr; p.relu = 0; p.bn_part = bn_part;
+    p.bytes_a = (unsigned)((size_t)cg.N * cg.H * cg.W * cg.Cin * 4); p.bytes_b = (unsigned)((size_t)cg.Cout * cg.KH * cg.KW * cg.Cin * 4);
+    launch_conv<MODE_FWD>(p, 1, t, PASS_FWD, st);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
 }
 extern "C" int mrcnn_conv2d_fwd_bnstats_f32(const float *x, const float *w, float *y, int N, int H, int W, int Cin, int Cout, int KH,
                                             int KW, int stride, int pad, float *bn_part, float *wino_v, void *ws, size_t ws_bytes,
                                             void *stream) {
-    g_cur_pass = 0;
-    if (int e = check_conv(x, w, y, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    ConvP p;
-    TileChoice t;
-    bool wino;
-    if (!bn_part || bnstats_plan(p, t, wino, N, H, W, Cin, Cout, KH, KW, stride, pad) == 0)
-        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_fwd_bnstats: no fused statistics for this geometry (mrcnn_conv2d_bnstats_rows == 0)");
-    if (wino) {
-        if (!ws || ws_bytes < wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD))
-            return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "conv2d_fwd_bnstats: workspace %zu < %zu", ws_bytes, wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD));
-        return wino_conv(x, w, y, N, H, W, Cin, Cout, false, nullptr, 0, 0, nullptr, ws, ws_bytes, (hipStream_t)stream, wino_v, nullptr, nullptr, 0, bn_part);
-    }
-    p.a = x; p.b = w; p.c = y; p.bias = nullptr; p.relu = 0; p.bn_part = bn_part;
-    p.bytes_a = (unsigned)((size_t)N * H * W * Cin * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
-    launch_conv<MODE_FWD>(p, 1, t, (hipStream_t)stream);
-    MRCNN_LAUNCH_CHECK();
-    return 0;
+    return conv_fwd_bnstats(x, w, y, ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad}, bn_part, wino_v, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- (r6, ABI v10) the layer's input is relu(BatchNorm(x)) of a training-mode BatchNorm with final statistics: applied on load by the
 // Winograd input transform (wino_input_body), never written.  Only for geometries whose forward AND filter-gradient passes take the
 // Winograd path under the settings in force (mrcnn_conv2d_inbn_ok): the caller keeps the materialised activation otherwise.
-extern "C" int mrcnn_conv2d_inbn_ok(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH != 3 || KW != 3 || stride != 1 || pad != 1 || (Cin % 4)) return 0;
-    return (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD) && wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_BWD_FILTER)) ? 1 : 0;
+static bool inbn_ok(const ConvGeom &cg) {
+    if (!cg.valid() || cg.KH != 3 || cg.KW != 3 || cg.stride != 1 || cg.pad != 1 || (cg.Cin % 4)) return false;
+    return wino_ok(cg, PASS_FWD) && wino_ok(cg, PASS_BWD_FILTER);
 }
-static int inbn_args(const float *g, const float *b, const float *m, const float *s, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
-                     int pad, const char *who) {
-    if (!g || !b || !m || !s) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: null BatchNorm pointer", who);
-    if (!mrcnn_conv2d_inbn_ok(N, H, W, Cin, Cout, KH, KW, stride, pad))
+extern "C" int mrcnn_conv2d_inbn_ok(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    return inbn_ok(ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad}) ? 1 : 0;
+}
+static int inbn_args(const InBN &inbn, const ConvGeom &cg, const char *who) {
+    if (!inbn.gamma || !inbn.beta || !inbn.mean || !inbn.invstd) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: null BatchNorm pointer", who);
+    if (!inbn_ok(cg))
         return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "%s: this geometry does not take the Winograd path in both passes (mrcnn_conv2d_inbn_ok == 0)", who);
     return 0;
 }
 extern "C" int mrcnn_conv2d_fwd_inbn_f32(const float *x, const float *in_gamma, const float *in_beta, const float *in_mean, const float *in_invstd,
                                          const float *w, float *y, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                          float *bn_part, float *wino_v, void *ws, size_t ws_bytes, void *stream) {
-    if (int e = inbn_args(in_gamma, in_beta, in_mean, in_invstd, N, H, W, Cin, Cout, KH, KW, stride, pad, "conv2d_fwd_inbn")) return e;
-    if (!ws || ws_bytes < wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD))
-        return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "conv2d_fwd_inbn: workspace %zu < %zu", ws_bytes, wino_ws_bytes(N, H, W, Cin, Cout, PASS_FWD));
-    t_inbn = InBN{in_gamma, in_beta, in_mean, in_invstd};
-    const int rc = bn_part ? mrcnn_conv2d_fwd_bnstats_f32(x, w, y, N, H, W, Cin, Cout, KH, KW, stride, pad, bn_part, wino_v, ws, ws_bytes, stream)
-                           : mrcnn_conv2d_fwd_f32(x, w, nullptr, y, N, H, W, Cin, Cout, KH, KW, stride, pad, 0, wino_v, ws, ws_bytes, stream);
-    t_inbn = InBN{};
-    return rc;
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    const InBN inbn{in_gamma, in_beta, in_mean, in_invstd};
+    if (int e = inbn_args(inbn, cg, "conv2d_fwd_inbn")) return e;
+    if (!ws || ws_bytes < wino_ws_bytes(cg, PASS_FWD))
+        return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "conv2d_fwd_inbn: workspace %zu < %zu", ws_bytes, wino_ws_bytes(cg, PASS_FWD));
+    return bn_part ? conv_fwd_bnstats(x, w, y, cg, bn_part, wino_v, ws, ws_bytes, (hipStream_t)stream, inbn)
+                   : conv_fwd(x, w, nullptr, y, cg, 0, wino_v, ws, ws_bytes, (hipStream_t)stream, inbn);
 }
 
 // Forward convolution with a rectangular kernel and per-axis padding (the 15x1 / 1x15 separable pairs of LightRoIMaskHead,
@@ -2453,135 +2468,122 @@ extern "C" int mrcnn_conv2d_fwd_inbn_f32(const float *x, const float *in_gamma, 
 extern "C" int mrcnn_conv2d_fwd_rect_f32(const float *x, const float *w, const float *bias, float *y, int N, int H, int W,
                                          int Cin, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int relu, void *ws,
                                          size_t ws_bytes, void *stream) {
-    g_cur_pass = 0;
     if (pad_h < 0 || pad_w < 0) return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d_fwd_rect: negative padding");
     // sizes and limits are validated for the larger of the two paddings (a superset of the real output)
-    if (int e = check_conv(x, w, y, N, H, W, Cin, Cout, KH, KW, stride, std::max(pad_h, pad_w))) return e;
+    ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, std::max(pad_h, pad_w)};
+    if (int e = check_conv(x, w, y, cg)) return e;
     if (conv_out(H, KH, stride, pad_h) <= 0 || conv_out(W, KW, stride, pad_w) <= 0 || Cin == 4)
         return mrcnn::fail_arg(MRCNN_E_INVALID, "conv2d_fwd_rect: empty output (or the 4-channel image layer)");
-    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad_h);
+    cg.pad = pad_h;
+    ConvP p = make_p(cg);
     p.pad_w = pad_w;
     p.Wo = conv_out(W, KW, stride, pad_w);
     p.a = x; p.b = w; p.c = y; p.bias = bias; p.relu = relu;
     p.bytes_a = (unsigned)((size_t)N * H * W * Cin * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
     p.M = N * p.Ho * p.Wo; p.Ng = Cout;
-    return run_data_conv<MODE_FWD>(p, KH * KW * (Cin / BK), Cout, ws, ws_bytes, (hipStream_t)stream);
+    return run_data_conv<MODE_FWD>(p, KH * KW * (Cin / BK), Cout, PASS_FWD, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// the shared transform of gy needs the backward-data and backward-filter passes on the same tile
+static size_t winograd_w_bytes(const ConvGeom &cg) {
+    if (!cg.valid() || !wino_ok(cg.transposed(), PASS_BWD_DATA) || !wino_ok(cg, PASS_BWD_FILTER)) return 0;
+    const WinoGeom g = wino_geom(cg, PASS_BWD_DATA);
+    if (g.m != wino_geom(cg, PASS_BWD_FILTER).m) return 0;
+    return (size_t)g.nk * g.Tp * cg.Cout * sizeof(float);
+}
 extern "C" size_t mrcnn_conv2d_winograd_w_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return 0;
-    // the shared transform of gy needs the backward-data and backward-filter passes on the same tile
-    if (!wino_ok(N, H, W, Cout, Cin, KH, KW, stride, pad, PASS_BWD_DATA) || !wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_BWD_FILTER)) return 0;
-    const WinoGeom g = wino_geom(N, H, W, PASS_BWD_DATA);
-    if (g.m != wino_geom(N, H, W, PASS_BWD_FILTER).m) return 0;
-    return (size_t)g.nk * g.Tp * Cout * sizeof(float);
+    return winograd_w_bytes(ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad});
 }
 
 extern "C" int mrcnn_conv2d_bwd_data_f32(const float *gy, const float *w, float *gx, const float *relu_x, int N, int H, int W,
                                          int Cin, int Cout, int KH, int KW, int stride, int pad,
                                          int accumulate, float *wino_w, float *gbias, int gbias_accumulate, void *ws,
                                          size_t ws_bytes, void *stream) {
-    g_cur_pass = 1;
-    if (int e = check_conv(gy, w, gx, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    if (int e = check_bwd_data(Cin, stride)) return e;
-    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (int e = check_conv(gy, w, gx, cg)) return e;
+    if (int e = check_bwd_data(cg)) return e;
+    ConvP p = make_p(cg);
     // relu_x with accumulate: every path (direct epilogue, split-K / tail-split sums, Winograd output transform) adds the old value
     // first and masks the TOTAL - the ReLU backward of the tensor gx is the gradient of, applied where its last contribution lands
-    if (bwd_data_takes_wino(N, H, W, Cin, Cout, KH, KW, stride, pad, ws != nullptr, ws_bytes))
-        return wino_conv(gy, w, gx, N, H, W, Cout, Cin, true, nullptr, 0, accumulate, relu_x, ws, ws_bytes, (hipStream_t)stream, nullptr,
-                         wino_w, wino_w ? gbias : nullptr, gbias_accumulate);
+    if (bwd_data_takes_wino(cg, ws != nullptr, ws_bytes))
+        return wino_conv(gy, w, gx, cg.transposed(), PASS_BWD_DATA, InBN{}, nullptr, 0, accumulate, relu_x, ws, ws_bytes, (hipStream_t)stream,
+                         nullptr, wino_w, wino_w ? gbias : nullptr, gbias_accumulate);
     if (wino_w || gbias) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: wino_w / gbias only on the Winograd path (mrcnn_conv2d_winograd_w_bytes() > 0)");
     p.a = gy; p.b = w; p.c = gx; p.accumulate = accumulate; p.relu_x = relu_x;
     p.bytes_a = (unsigned)((size_t)N * p.Ho * p.Wo * Cout * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
     const int nsteps = bwd_data_gemm(p);
-    return run_data_conv<MODE_BWD_DATA>(p, nsteps, Cin, ws, ws_bytes, (hipStream_t)stream);
+    return run_data_conv<MODE_BWD_DATA>(p, nsteps, Cin, PASS_BWD_DATA, ws, ws_bytes, (hipStream_t)stream);
 }
 
-extern "C" size_t mrcnn_conv2d_bwd_filter_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                                                          int stride, int pad) {
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return 0;
-    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
+static size_t bwd_filter_ws_bytes(const ConvGeom &cg) {
+    if (!cg.valid()) return 0;
+    ConvP p = make_p(cg);
     if (p.Ho <= 0 || p.Wo <= 0) return 0;
     int ksplit, kchunk;
     filter_plan(p, ksplit, kchunk);
-    const size_t wsz = (size_t)Cout * KH * KW * Cin * sizeof(float);
-    const size_t P = (size_t)N * p.Ho * p.Wo;
-    const size_t bias_part = (size_t)col_plan((int)P, Cout).nblk * Cout * sizeof(float);
-    if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_BWD_FILTER)) {
+    const size_t wsz = (size_t)cg.Cout * cg.KH * cg.KW * cg.Cin * sizeof(float);
+    const size_t P = (size_t)cg.N * p.Ho * p.Wo;
+    const size_t bias_part = (size_t)col_plan((int)P, cg.Cout).nblk * cg.Cout * sizeof(float);
+    if (wino_ok(cg, PASS_BWD_FILTER)) {
         // the gy transform leaves one row of bias-gradient partials per 256-thread block
-        const WinoFLayout L = wino_filter_layout(N, H, W, Cin, Cout);
-        const size_t rows = (size_t)((L.g.Tp * (Cout / 4) + 255) / 256);
-        return L.total + std::max(bias_part, rows * Cout * sizeof(float)) + 256;
+        const WinoFLayout L = wino_filter_layout(cg);
+        const size_t rows = (size_t)((L.g.Tp * (cg.Cout / 4) + 255) / 256);
+        return L.total + std::max(bias_part, rows * cg.Cout * sizeof(float)) + 256;
     }
     return wsz * ksplit + bias_part + 256;     // slabs are also used for ksplit == 1 when accumulating
 }
+extern "C" size_t mrcnn_conv2d_bwd_filter_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                                                          int stride, int pad) {
+    return bwd_filter_ws_bytes(ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad});
+}
 
-extern "C" int mrcnn_conv2d_bwd_filter_f32(const float *x, const float *gy, float *gw, float *gbias, int N,
-                                           int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                           int accumulate, const float *wino_v, const float *wino_w, void *ws, size_t ws_bytes,
-                                           void *stream) {
-    g_cur_pass = 2;
-    if (int e = check_conv(x, gy, gw, N, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
+static int conv_bwd_filter(const float *x, const float *gy, float *gw, float *gbias, const ConvGeom &cg, int accumulate, const float *wino_v,
+                           const float *wino_w, void *ws, size_t ws_bytes, hipStream_t st, const InBN &inbn = InBN{}) {
+    if (int e = check_conv(x, gy, gw, cg)) return e;
     if (g_debug_skip & 4) return 0;             // timing experiments only (tools/ab_step.py): what the whole pass costs the step
-    const size_t need = mrcnn_conv2d_bwd_filter_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad);
+    const size_t need = bwd_filter_ws_bytes(cg);
     if (!ws || ws_bytes < need) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "conv2d_bwd_filter: workspace %zu < %zu", ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    ConvP p = make_p(N, H, W, Cin, Cout, KH, KW, stride, pad);
-    if (wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_BWD_FILTER)) {
-        const WinoFLayout L = wino_filter_layout(N, H, W, Cin, Cout);
+    ConvP p = make_p(cg);
+    const int P = cg.N * p.Ho * p.Wo, Cout = cg.Cout;
+    if (wino_ok(cg, PASS_BWD_FILTER)) {
+        const WinoFLayout L = wino_filter_layout(cg);
         // the forward pass's transformed input is reusable only when that pass ran Winograd on the same tile
-        if (wino_v && !(wino_ok(N, H, W, Cin, Cout, KH, KW, stride, pad, PASS_FWD) && wino_geom(N, H, W, PASS_FWD).m == L.g.m)) wino_v = nullptr;
-        if (wino_w && mrcnn_conv2d_winograd_w_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad) == 0) wino_w = nullptr;
+        if (wino_v && !(wino_ok(cg, PASS_FWD) && wino_geom(cg, PASS_FWD).m == L.g.m)) wino_v = nullptr;
+        if (wino_w && winograd_w_bytes(cg) == 0) wino_w = nullptr;
         float *bias_part = (float *)((char *)ws + L.total);
         int bias_rows = 0;
-        if (int e = wino_bwd_filter(x, gy, gw, N, H, W, Cin, Cout, accumulate, ws, st, wino_v, wino_w, gbias ? bias_part : nullptr, &bias_rows)) return e;
-        if (gbias) {
-            int nrows = bias_rows;          // partial column sums from the gy transform, or a separate pass over gy
-            if (nrows == 0) {
-                const int P = N * p.Ho * p.Wo;
-                const ColPlan cp = col_plan(P, Cout);
-                if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_partial, dim3(cp.nblk), dim3(256), 0, st, gy, bias_part, P, Cout, cp.G, cp.RPI, cp.rows_per_blk);
-                MRCNN_LAUNCH_CHECK();
-                nrows = cp.nblk;
-            }
-            if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_final, dim3(mrcnn::cdiv(Cout, CSF_CH)), dim3(CSF_CH * CSF_SL), 0, st, bias_part, gbias, nrows, Cout, accumulate);
-            MRCNN_LAUNCH_CHECK();
-        }
-        return 0;
+        if (int e = wino_bwd_filter(x, gy, gw, cg, inbn, accumulate, ws, st, wino_v, wino_w, gbias ? bias_part : nullptr, &bias_rows)) return e;
+        if (!gbias) return 0;
+        // partial column sums from the gy transform, or a separate pass over gy
+        return bias_rows ? colsum_final(bias_part, gbias, bias_rows, Cout, accumulate, st) : colsum(gy, bias_part, gbias, P, Cout, accumulate, st);
     }
     filter_plan(p, p.ksplit, p.kchunk);
-    const size_t wcount = (size_t)Cout * KH * KW * Cin;
+    const size_t wcount = (size_t)Cout * cg.KH * cg.KW * cg.Cin;
     float *slabs = (float *)ws;
     float *bias_part = (float *)ws + wcount * p.ksplit;
     const bool use_slabs = p.ksplit > 1 || accumulate;
     p.a = gy; p.b = x; p.c = use_slabs ? slabs : gw;
-    p.bytes_a = (unsigned)((size_t)N * p.Ho * p.Wo * Cout * 4); p.bytes_b = (unsigned)((size_t)N * H * W * Cin * 4);
+    p.bytes_a = (unsigned)((size_t)P * Cout * 4); p.bytes_b = (unsigned)((size_t)cg.N * cg.H * cg.W * cg.Cin * 4);
     bwd_filter_gemm(p);
-    launch_conv<MODE_BWD_FILTER>(p, (p.smallc ? 1 : KH * KW) * p.ksplit, filter_tile(p), st);
+    launch_conv<MODE_BWD_FILTER>(p, (p.smallc ? 1 : cg.KH * cg.KW) * p.ksplit, filter_tile(p), PASS_BWD_FILTER, st);
     MRCNN_LAUNCH_CHECK();
-    if (use_slabs) {
-        const size_t n4 = wcount / 4;
-        if (!(g_debug_skip & 10)) hipLaunchKernelGGL(k_sum_slabs, dim3(mrcnn::cdiv(n4, 256)), dim3(256), 0, st, slabs, gw, n4, p.ksplit, accumulate);
-        MRCNN_LAUNCH_CHECK();
-    }
-    if (gbias) {
-        const int P = N * p.Ho * p.Wo;
-        const ColPlan cp = col_plan(P, Cout);
-        if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_partial, dim3(cp.nblk), dim3(256), 0, st, gy, bias_part, P, Cout, cp.G, cp.RPI, cp.rows_per_blk);
-        MRCNN_LAUNCH_CHECK();
-        if (!(g_debug_skip & 2)) hipLaunchKernelGGL(k_colsum_final, dim3(mrcnn::cdiv(Cout, CSF_CH)), dim3(CSF_CH * CSF_SL), 0, st, bias_part, gbias, cp.nblk, Cout, accumulate);
-        MRCNN_LAUNCH_CHECK();
-    }
-    return 0;
+    if (use_slabs) if (int e = sum_slabs(slabs, gw, wcount / 4, p.ksplit, accumulate, st)) return e;
+    return gbias ? colsum(gy, bias_part, gbias, P, Cout, accumulate, st) : 0;
+}
+extern "C" int mrcnn_conv2d_bwd_filter_f32(const float *x, const float *gy, float *gw, float *gbias, int N,
+                                           int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                           int accumulate, const float *wino_v, const float *wino_w, void *ws, size_t ws_bytes,
+                                           void *stream) {
+    return conv_bwd_filter(x, gy, gw, gbias, ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad}, accumulate, wino_v, wino_w, ws, ws_bytes,
+                           (hipStream_t)stream);
 }
 
 extern "C" int mrcnn_conv2d_bwd_filter_inbn_f32(const float *x, const float *in_gamma, const float *in_beta, const float *in_mean,
                                                 const float *in_invstd, const float *gy, float *gw, int N, int H, int W, int Cin, int Cout, int KH,
                                                 int KW, int stride, int pad, int accumulate, const float *wino_v, void *ws, size_t ws_bytes,
                                                 void *stream) {
-    if (int e = inbn_args(in_gamma, in_beta, in_mean, in_invstd, N, H, W, Cin, Cout, KH, KW, stride, pad, "conv2d_bwd_filter_inbn")) return e;
-    t_inbn = InBN{in_gamma, in_beta, in_mean, in_invstd};
-    const int rc = mrcnn_conv2d_bwd_filter_f32(x, gy, gw, nullptr, N, H, W, Cin, Cout, KH, KW, stride, pad, accumulate, wino_v, nullptr, ws, ws_bytes, stream);
-    t_inbn = InBN{};
-    return rc;
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    const InBN inbn{in_gamma, in_beta, in_mean, in_invstd};
+    if (int e = inbn_args(inbn, cg, "conv2d_bwd_filter_inbn")) return e;
+    return conv_bwd_filter(x, gy, gw, nullptr, cg, accumulate, wino_v, nullptr, ws, ws_bytes, (hipStream_t)stream, inbn);
 }

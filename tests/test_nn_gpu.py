@@ -409,6 +409,39 @@ def test_convolution_with_batchnorm_relu_on_load_equals_the_materialised_sequenc
         check(lib.mrcnn_conv2d_set_split_operands(*keep))
 
 
+def test_batchnorm_on_load_call_leaves_the_ordinary_entry_points_as_they_were():
+    """The on-load BatchNorm belongs to the one *_inbn call that names it: mrcnn_conv2d_fwd_f32 / mrcnn_conv2d_bwd_filter_f32 give the same
+    BITS before and after a mrcnn_conv2d_fwd_inbn_f32 / mrcnn_conv2d_bwd_filter_inbn_f32 call on the same tensor, and the *_inbn call itself
+    gives another result.  (1, 32, 64, 256, 256), 3x3 / stride 1 / pad 1: the smallest map that takes the Winograd path in forward and
+    filter gradient under the shipped tiles (2, 0, 0) - 2048 pixels, 256 channels."""
+    from chainer_maskrcnn import _hip
+    lib, check, ptr, sp = _hip.lib(), _hip.check, _hip.ptr, _hip.stream_ptr
+    N, H, W, Ci, Co = 1, 32, 64, 256, 256
+    geom = (N, H, W, Ci, Co, 3, 3, 1, 1)
+    assert lib.mrcnn_conv2d_inbn_ok(*geom)
+    g = torch.Generator(device='cpu').manual_seed(7)
+    mk = lambda *s: torch.randn(*s, generator=g).to(DEV)
+    x, w, gy = mk(N, H, W, Ci), mk(Co, 3, 3, Ci) * 0.03, mk(N, H, W, Co) * 1e-3
+    bn_tensors = (mk(Ci) * 0.3 + 1, mk(Ci) * 0.2, mk(Ci) * 0.5, mk(Ci).abs() + 0.5)        # gamma, beta, mean, invstd
+    bn = [ptr(t) for t in bn_tensors]
+    ws = torch.empty((lib.mrcnn_conv2d_workspace_bytes(*geom),), dtype=torch.uint8, device=DEV)
+    wsf = torch.empty((lib.mrcnn_conv2d_bwd_filter_workspace_bytes(*geom),), dtype=torch.uint8, device=DEV)
+    ys = [torch.empty((N, H, W, Co), device=DEV) for _ in range(3)]
+    for i, y in enumerate(ys):
+        if i == 1:
+            check(lib.mrcnn_conv2d_fwd_inbn_f32(ptr(x), *bn, ptr(w), ptr(y), *geom, None, None, ptr(ws), ws.numel(), sp()))
+        else:
+            check(lib.mrcnn_conv2d_fwd_f32(ptr(x), ptr(w), None, ptr(y), *geom, 0, None, ptr(ws), ws.numel(), sp()))
+    assert torch.equal(ys[0], ys[2]) and not torch.equal(ys[1], ys[0]) and all(torch.isfinite(y).all() for y in ys)
+    gws = [torch.empty_like(w) for _ in range(3)]
+    for i, gw in enumerate(gws):
+        if i == 1:
+            check(lib.mrcnn_conv2d_bwd_filter_inbn_f32(ptr(x), *bn, ptr(gy), ptr(gw), *geom, 0, None, ptr(wsf), wsf.numel(), sp()))
+        else:
+            check(lib.mrcnn_conv2d_bwd_filter_f32(ptr(x), ptr(gy), ptr(gw), None, *geom, 0, None, None, ptr(wsf), wsf.numel(), sp()))
+    assert torch.equal(gws[0], gws[2]) and not torch.equal(gws[1], gws[0]) and all(torch.isfinite(gw).all() for gw in gws)
+
+
 @pytest.mark.parametrize('seed', [0, 12345, 2 ** 63 - 1])
 @pytest.mark.parametrize('n', [1, 257, 1048577])
 def test_random_keys_dev_is_splitmix64_and_advances_its_state(n, seed):
