@@ -1401,6 +1401,7 @@ __global__ __launch_bounds__(256) void k_sum_level_slabs(const float *__restrict
     *reinterpret_cast<float4 *>(out + i * 4) = a;
 }
 
+// workspace of one backward call: the RoI-split slabs of the coarse levels
 size_t slab_ws_bytes(const int *Hs, const int *Ws, int L, int N, int C) {
     size_t b = 0;
     for (int l = 0; l < L; ++l) {
@@ -1408,10 +1409,6 @@ size_t slab_ws_bytes(const int *Hs, const int *Ws, int L, int N, int C) {
         if (sp > 1) b += (size_t)sp * N * Hs[l] * Ws[l] * C * sizeof(float);
     }
     return (b + 255) / 256 * 256;
-}
-// workspace of one backward call: the RoI-split slabs of the coarse levels
-size_t bwd_ws_bytes(const int *Hs, const int *Ws, int L, int N, int C, int R, int PH, int PW, int sr) {
-    return slab_ws_bytes(Hs, Ws, L, N, C);
 }
 
 size_t fwd_ws_bytes(int R) { return R > 0 ? ((size_t)R * sizeof(int32_t) + 255) / 256 * 256 : 0; }
@@ -1440,114 +1437,148 @@ void launch_fwd(Levels &lv, const float *rois, const int32_t *levels, int R, int
 // tensors >= 4 GiB; selectable so that the tests reach it on small inputs)
 int g_bwd_variant = 2;
 
-// entry-list plan buffer: [256-byte header][tile flags][nodes]; nodes = one per patch slot of the launch + a pool for the patches that
-// flush more than once
-size_t nplan_nodes(int total_tiles, int R, int PH, int PW) { return (size_t)total_tiles * BWD_WAVES * 2 + (size_t)R * PH * PW / 4 + 1024; }
-size_t nplan_stride(int PH, int PW) { return (PH <= 8 && PW <= 8) ? plan_node_stride<WaveLds<8>::QC>() : plan_node_stride<WaveLds<16>::QC>(); }
-int count_tiles(const int *Hs, const int *Ws, int L, int N, bool split) {
-    int total = 0;
-    for (int l = 0; l < L; ++l) total += mrcnn::cdiv(Ws[l], TW) * mrcnn::cdiv(Hs[l], TH) * N * (split ? level_split(Hs[l], Ws[l], N) : 1);
-    return total;
-}
-size_t nplan_bytes(const int *Hs, const int *Ws, int L, int N, int R, int PH, int PW, bool split) {
-    const int tiles = count_tiles(Hs, Ws, L, N, split);
-    return plan_nodes_off_ints(tiles) * sizeof(int) + nplan_nodes(tiles, R, PH, PW) * nplan_stride(PH, PW);
+// the RoI side of a backward call, in the kernels' argument order
+struct RoiArgs {
+    const float *rois;
+    const int32_t *levels;
+    int R, N, C, PH, PW, sr;
+};
+
+// f(std::integral_constant<int, PBT>): PBT = the pooled bins per axis that a backward kernel holds in LDS, 8 (7x7-class pooling) or 16
+template <class F> auto with_pbt(int PH, int PW, F f) {
+    if (PH <= 8 && PW <= 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
 }
 
-// nplan_mode 0: backward (fused; with `nplan` the lean path when the plan holds); 1: build the entry-list plan of these RoIs into `nplan`
-// (no gy / gx needed); split: in mode 1 whether the backward call will have its slab workspace (the coarse levels' RoI split)
-int launch_bwd_tiles(Levels &lv, int N, const float *gy, const float *rois, const int32_t *levels, int R,
-                     int C, int PH, int PW, int sr, int accumulate, void *ws, size_t ws_bytes, hipStream_t st,
-                     int *nplan = nullptr, size_t nplan_size = 0, int nplan_mode = 0, bool plan_split = false, bool plan_verified = false) {
+// Lays the levels out in tiles for one backward launch: fills tiles_x, tiles_y, split, slab (carved from slab_base in level order) and
+// tile_begin[0..L], returns the tile count.  The one statement of a level's tiles: the plan's size query, its builder and the backward
+// all count here, so a plan sized or built by one fits the backward tiled by another.
+int tile_levels(Levels &lv, int N, int C, bool split, float *slab_base) {
     int total = 0;
-    const size_t need = slab_ws_bytes(lv.H, lv.W, lv.L, N, C);
-    const bool can_split = nplan_mode == 1 ? (plan_split && R > 0) : (ws && ws_bytes >= need && R > 0);
-    float *wp = (float *)ws;
     for (int l = 0; l < lv.L; ++l) {
         lv.tiles_x[l] = mrcnn::cdiv(lv.W[l], TW);
         lv.tiles_y[l] = mrcnn::cdiv(lv.H[l], TH);
-        lv.split[l] = can_split ? level_split(lv.H[l], lv.W[l], N) : 1;
+        lv.split[l] = split ? level_split(lv.H[l], lv.W[l], N) : 1;
         lv.slab[l] = nullptr;
         if (lv.split[l] > 1) {
-            lv.slab[l] = wp;
-            wp += (size_t)lv.split[l] * N * lv.H[l] * lv.W[l] * C;
+            lv.slab[l] = slab_base;
+            slab_base += (size_t)lv.split[l] * N * lv.H[l] * lv.W[l] * C;
         }
         lv.tile_begin[l] = total;
         total += lv.tiles_x[l] * lv.tiles_y[l] * N * lv.split[l];
     }
     lv.tile_begin[lv.L] = total;
-    const int chunk = mrcnn::cdiv(total, 8);
-    bool waves_ok = g_bwd_variant >= 2 && (unsigned long long)R * PH * PW * C * 4ull < (1ull << 32) && R < (1 << 27) && total < (1 << 24);
-    for (int l = 0; l < lv.L; ++l) waves_ok = waves_ok && (unsigned long long)lv.H[l] * lv.W[l] * C * 4ull < (1ull << 32);
+    return total;
+}
+
+// the wave kernels (fused, plan builder, lean) address gy and every level through 32-bit buffer offsets and pack RoI and tile ids
+bool waves_ok(const Levels &lv, const RoiArgs &a, int total) {
+    bool ok = g_bwd_variant >= 2 && (unsigned long long)a.R * a.PH * a.PW * a.C * 4ull < (1ull << 32) && a.R < (1 << 27) && total < (1 << 24);
+    for (int l = 0; l < lv.L; ++l) ok = ok && (unsigned long long)lv.H[l] * lv.W[l] * a.C * 4ull < (1ull << 32);
+    return ok;
+}
+
+// entry-list plan buffer: [256-byte header][tile flags][nodes]; nodes = one per patch slot of the launch + a pool for the patches that
+// flush more than once
+size_t nplan_nodes(int total_tiles, int R, int PH, int PW) { return (size_t)total_tiles * BWD_WAVES * 2 + (size_t)R * PH * PW / 4 + 1024; }
+size_t nplan_stride(int PH, int PW) { return with_pbt(PH, PW, [](auto pbt) { return plan_node_stride<WaveLds<decltype(pbt)::value>::QC>(); }); }
+size_t nplan_bytes(const int *Hs, const int *Ws, int L, int N, int R, int PH, int PW, bool split) {
+    Levels lv{};
+    lv.L = L;
+    std::copy(Hs, Hs + L, lv.H);
+    std::copy(Ws, Ws + L, lv.W);
+    const int tiles = tile_levels(lv, N, 0, split, nullptr);
+    return plan_nodes_off_ints(tiles) * sizeof(int) + nplan_nodes(tiles, R, PH, PW) * nplan_stride(PH, PW);
+}
+
+// k_roi_align_bwd_waves<PBT, W2_DEPTH, false, MODE> over the tiled levels.  MODE 0: the fused backward, no plan (nodes_off = cap = 0,
+// plan = null); 1: the plan builder (no gy); 2: behind the lean kernel, for what the plan could not hold
+template <int MODE>
+void launch_waves(const Levels &lv, const RoiArgs &a, const float *gy, int chunk, int accumulate, int nodes_off, int cap, int *plan,
+                  hipStream_t st) {
+    with_pbt(a.PH, a.PW, [&](auto pbt) {
+        hipLaunchKernelGGL((k_roi_align_bwd_waves<decltype(pbt)::value, W2_DEPTH, false, MODE>), dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, gy,
+                           a.rois, a.levels, a.R, a.N, a.C, a.PH, a.PW, a.sr, chunk, accumulate, (unsigned long long *)nullptr, nodes_off, cap, plan);
+    });
+}
+
+// Builds the entry-list plan of these RoIs into `plan` (no gy / gx needed); split: whether the backward call will have its slab workspace
+// (the coarse levels' RoI split).  Needs the wave kernel's preconditions and a buffer of mrcnn_roi_align_fpn_bwd_plan_bytes(); otherwise the
+// header stays without its magic and the backward's MODE 2 launch computes every tile
+int build_plan(Levels &lv, const RoiArgs &a, bool split, int *plan, size_t plan_bytes, hipStream_t st) {
+    const int total = tile_levels(lv, a.N, a.C, split && a.R > 0, nullptr);
     const size_t nodes_off = plan_nodes_off_ints(total);
-    if (nplan_mode == 1) {
-        // plan builder: needs the wave kernel's preconditions and a buffer of mrcnn_roi_align_fpn_bwd_plan_bytes(); otherwise the header
-        // stays without its magic and the backward's MODE 2 launch computes every tile
-        if (!nplan || nplan_size < NP_HDR_INTS * sizeof(int)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "roi_align_bwd_plan: plan buffer too small");
-        const bool room = nplan_size >= (nodes_off + 64) * sizeof(int);
-        MRCNN_HIP_TRY(hipMemsetAsync(nplan, 0, (room ? nodes_off : (size_t)NP_HDR_INTS) * sizeof(int), st));
-        const size_t cap = room ? (nplan_size - nodes_off * sizeof(int)) / nplan_stride(PH, PW) : 0;
-        if (!waves_ok || R == 0 || cap < (size_t)total * BWD_WAVES || cap >= (1u << 30)) return 0;
-        if (PH <= 8 && PW <= 8)
-            hipLaunchKernelGGL((k_roi_align_bwd_waves<8, W2_DEPTH, false, 1>), dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, (const float *)nullptr, rois, levels,
-                               R, N, C, PH, PW, sr, chunk, 0, (unsigned long long *)nullptr, (int)nodes_off, (int)cap, nplan);
-        else
-            hipLaunchKernelGGL((k_roi_align_bwd_waves<16, W2_DEPTH, false, 1>), dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, (const float *)nullptr, rois, levels,
-                               R, N, C, PH, PW, sr, chunk, 0, (unsigned long long *)nullptr, (int)nodes_off, (int)cap, nplan);
-        MRCNN_LAUNCH_CHECK();
-        return 0;
+    if (!plan || plan_bytes < NP_HDR_INTS * sizeof(int)) return mrcnn::fail_arg(MRCNN_E_WORKSPACE, "roi_align_bwd_plan: plan buffer too small");
+    const bool room = plan_bytes >= (nodes_off + 64) * sizeof(int);
+    MRCNN_HIP_TRY(hipMemsetAsync(plan, 0, (room ? nodes_off : (size_t)NP_HDR_INTS) * sizeof(int), st));
+    const size_t cap = room ? (plan_bytes - nodes_off * sizeof(int)) / nplan_stride(a.PH, a.PW) : 0;
+    if (!waves_ok(lv, a, total) || a.R == 0 || cap < (size_t)total * BWD_WAVES || cap >= (1u << 30)) return 0;
+    launch_waves<1>(lv, a, nullptr, mrcnn::cdiv(total, 8), 0, (int)nodes_off, (int)cap, plan, st);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// k_roi_align_bwd_lean<PBT, DEPTH, OCC, WPB>; its grid is chunk * 8 * (8 / wpb) workgroups of wpb * 64 threads
+struct LeanKernel {
+    decltype(&k_roi_align_bwd_lean<8, 8, 8, 4>) kern;
+    int wpb;
+};
+template <int DEPTH, int OCC, int WPB> LeanKernel lean_kernel(int PH, int PW) {
+    return with_pbt(PH, PW, [](auto pbt) { return LeanKernel{k_roi_align_bwd_lean<decltype(pbt)::value, DEPTH, OCC, WPB>, WPB}; });
+}
+LeanKernel lean_variant(int variant, int PH, int PW) {          // g_lean_variant -> <DEPTH, OCC, WPB>
+    switch (variant) {
+    case 0: return lean_kernel<10, 8, 8>(PH, PW);
+    case 1: return lean_kernel<16, 7, 8>(PH, PW);
+    case 2: return lean_kernel<8, 8, 8>(PH, PW);
+    case 9: return lean_kernel<8, 8, 2>(PH, PW);
+    default: return lean_kernel<8, 8, 4>(PH, PW);       // 8
     }
+}
+
+// The backward over the tiled levels: along `plan` (the lean path) when there is one and it can hold, else fused; ws = the slab workspace
+// of the coarse levels' RoI split (used when it is large enough), summed into gx in level order at the end
+int run_backward(Levels &lv, const RoiArgs &a, const float *gy, int accumulate, void *ws, size_t ws_bytes, int *plan, size_t plan_bytes,
+                 bool plan_verified, hipStream_t st) {
+    const bool split = ws && ws_bytes >= slab_ws_bytes(lv.H, lv.W, lv.L, a.N, a.C) && a.R > 0;
+    const int total = tile_levels(lv, a.N, a.C, split, (float *)ws), chunk = mrcnn::cdiv(total, 8);
+    const bool waves = waves_ok(lv, a, total);
+    const size_t nodes_off = plan_nodes_off_ints(total), stride = nplan_stride(a.PH, a.PW);
     // a plan buffer that cannot even hold the patch slots of this launch was never filled by the builder: plain fused backward
-    if (nplan && nplan_size < nodes_off * sizeof(int) + (size_t)total * BWD_WAVES * nplan_stride(PH, PW)) nplan = nullptr;
-    if (!waves_ok || R == 0) nplan = nullptr;
-    if (nplan) {
+    if (plan && plan_bytes < nodes_off * sizeof(int) + (size_t)total * BWD_WAVES * stride) plan = nullptr;
+    if (!waves || a.R == 0) plan = nullptr;
+    if (plan) {
         // the lean kernel along the entry lists, then (unless the caller verified the plan) the wave kernel for whatever the plan could not hold;
         // have_cap: the nodes THIS call's buffer can hold - a plan built into a larger buffer does not validate (its chains could leave this one)
-        const int have_cap = (int)std::min<size_t>((nplan_size - nodes_off * sizeof(int)) / nplan_stride(PH, PW), (size_t)1 << 30);
-        auto lean = [&](auto kern, int wpb) {
-            hipLaunchKernelGGL(kern, dim3(chunk * 8 * (8 / wpb)), dim3(wpb * 64), 0, st, lv, gy, R, N, C, PH, PW, sr, chunk, accumulate, (const int *)nplan, (int)nodes_off,
-                               have_cap, g_lean_dbg, g_lean_stamps);
-        };
-        const bool small = PH <= 8 && PW <= 8;
-        switch (g_lean_variant) {
-        case 0: if (small) lean(k_roi_align_bwd_lean<8, 10, 8, 8>, 8); else lean(k_roi_align_bwd_lean<16, 10, 8, 8>, 8); break;
-        case 1: if (small) lean(k_roi_align_bwd_lean<8, 16, 7, 8>, 8); else lean(k_roi_align_bwd_lean<16, 16, 7, 8>, 8); break;
-        case 2: if (small) lean(k_roi_align_bwd_lean<8, 8, 8, 8>, 8); else lean(k_roi_align_bwd_lean<16, 8, 8, 8>, 8); break;
-        case 9: if (small) lean(k_roi_align_bwd_lean<8, 8, 8, 2>, 2); else lean(k_roi_align_bwd_lean<16, 8, 8, 2>, 2); break;
-        default: if (small) lean(k_roi_align_bwd_lean<8, 8, 8, 4>, 4); else lean(k_roi_align_bwd_lean<16, 8, 8, 4>, 4); break;       // 8
-        }
+        const int have_cap = (int)std::min<size_t>((plan_bytes - nodes_off * sizeof(int)) / stride, (size_t)1 << 30);
+        const LeanKernel k = lean_variant(g_lean_variant, a.PH, a.PW);
+        hipLaunchKernelGGL(k.kern, dim3(chunk * 8 * (8 / k.wpb)), dim3(k.wpb * 64), 0, st, lv, gy, a.R, a.N, a.C, a.PH, a.PW, a.sr, chunk, accumulate,
+                           (const int *)plan, (int)nodes_off, have_cap, g_lean_dbg, g_lean_stamps);
         MRCNN_LAUNCH_CHECK();
-        if (plan_verified) {}
-        else if (small)
-            hipLaunchKernelGGL((k_roi_align_bwd_waves<8, W2_DEPTH, false, 2>), dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, gy, rois, levels, R, N, C,
-                               PH, PW, sr, chunk, accumulate, (unsigned long long *)nullptr, (int)nodes_off, have_cap, nplan);
-        else
-            hipLaunchKernelGGL((k_roi_align_bwd_waves<16, W2_DEPTH, false, 2>), dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, gy, rois, levels, R, N, C,
-                               PH, PW, sr, chunk, accumulate, (unsigned long long *)nullptr, (int)nodes_off, have_cap, nplan);
-    } else if (waves_ok) {
-        const dim3 grid(chunk * 8);
-        if (PH <= 8 && PW <= 8)
-            hipLaunchKernelGGL((k_roi_align_bwd_waves<8, W2_DEPTH>), grid, dim3(BWD_THREADS), 0, st, lv, gy, rois, levels, R, N, C,
-                               PH, PW, sr, chunk, accumulate);
-        else
-            hipLaunchKernelGGL((k_roi_align_bwd_waves<16, W2_DEPTH>), grid, dim3(BWD_THREADS), 0, st, lv, gy, rois, levels, R, N, C,
-                               PH, PW, sr, chunk, accumulate);
+        if (!plan_verified) launch_waves<2>(lv, a, gy, chunk, accumulate, (int)nodes_off, have_cap, plan, st);
+    } else if (waves) {
+        launch_waves<0>(lv, a, gy, chunk, accumulate, 0, 0, nullptr, st);
+    } else {
+        with_pbt(a.PH, a.PW, [&](auto pbt) {
+            hipLaunchKernelGGL(k_roi_align_bwd_nhwc<decltype(pbt)::value>, dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, gy, a.rois, a.levels, a.R, a.N,
+                               a.C, a.PH, a.PW, a.sr, chunk, accumulate);
+        });
     }
-    else if (PH <= 8 && PW <= 8)
-        hipLaunchKernelGGL(k_roi_align_bwd_nhwc<8>, dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, gy, rois,
-                           levels, R, N, C, PH, PW, sr, chunk, accumulate);
-    else
-        hipLaunchKernelGGL(k_roi_align_bwd_nhwc<16>, dim3(chunk * 8), dim3(BWD_THREADS), 0, st, lv, gy, rois,
-                           levels, R, N, C, PH, PW, sr, chunk, accumulate);
     MRCNN_LAUNCH_CHECK();
     for (int l = 0; l < lv.L; ++l)
         if (lv.split[l] > 1) {
-            const size_t n4 = (size_t)N * lv.H[l] * lv.W[l] * C / 4;
+            const size_t n4 = (size_t)a.N * lv.H[l] * lv.W[l] * a.C / 4;
             hipLaunchKernelGGL(k_sum_level_slabs, dim3((unsigned)mrcnn::cdiv(n4, 256)), dim3(256), 0, st, lv.slab[l], lv.gx[l], n4,
                                lv.split[l], accumulate);
             MRCNN_LAUNCH_CHECK();
         }
     return 0;
+}
+
+Levels single_level(const float *x, float *gx, int H, int W, float scale) {
+    Levels lv{};
+    lv.L = 1; lv.x[0] = x; lv.gx[0] = gx; lv.H[0] = H; lv.W[0] = W; lv.scale[0] = scale;
+    return lv;
 }
 
 }  // namespace
@@ -1559,8 +1590,7 @@ extern "C" int mrcnn_roi_align_fwd_ws_f32(const float *x, int layout, int N, int
     if (R == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (layout == MRCNN_LAYOUT_NHWC && (C % 4) == 0) {
-        Levels lv{};
-        lv.L = 1; lv.x[0] = x; lv.H[0] = H; lv.W[0] = W; lv.scale[0] = spatial_scale;
+        Levels lv = single_level(x, nullptr, H, W, spatial_scale);
         launch_fwd(lv, rois, nullptr, R, N, C, PH, PW, sampling_ratio, y, st, ws, ws_bytes);
     } else {
         const long long total = (long long)R * C * PH * PW;
@@ -1591,9 +1621,8 @@ extern "C" int mrcnn_roi_align_bwd_ws_f32(const float *gy, int layout, int N, in
     if (int e = check_common(gy, rois, gx, layout, N, C, H, W, R, PH, PW, sampling_ratio)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (layout == MRCNN_LAYOUT_NHWC && fast_bwd_ok(C, PH, PW, sampling_ratio, R)) {
-        Levels lv{};
-        lv.L = 1; lv.gx[0] = gx; lv.H[0] = H; lv.W[0] = W; lv.scale[0] = spatial_scale;
-        return launch_bwd_tiles(lv, N, gy, rois, nullptr, R, C, PH, PW, sampling_ratio, 0, ws, ws_bytes, st);
+        Levels lv = single_level(nullptr, gx, H, W, spatial_scale);
+        return run_backward(lv, {rois, nullptr, R, N, C, PH, PW, sampling_ratio}, gy, 0, ws, ws_bytes, nullptr, 0, false, st);
     }
     MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)N * C * H * W, st));
     if (R == 0) return 0;
@@ -1625,6 +1654,17 @@ static int fill_levels(Levels &lv, const float *const *xs, float *const *gxs, co
     return 0;
 }
 
+// The argument checks and the Levels of the three fpn backward entry points.  who = the entry point's name in its messages; null_ptr =
+// its own pointer test (the pointers it takes differ); gxs = null for the plan builder
+static int fpn_bwd_levels(Levels &lv, const char *who, bool null_ptr, const RoiArgs &a, float *const *gxs, const int *Hs, const int *Ws,
+                          const float *scales, int L) {
+    if (null_ptr) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: null pointer", who);
+    if (a.N <= 0 || a.C <= 0 || a.PH <= 0 || a.PW <= 0 || a.R < 0) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: bad sizes", who);
+    if (!fast_bwd_ok(a.C, a.PH, a.PW, a.sr, a.R))
+        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "%s: needs C%%4==0, PH,PW<=%d, sampling_ratio>0", who, PB);
+    return fill_levels(lv, nullptr, gxs, Hs, Ws, scales, L);
+}
+
 extern "C" int mrcnn_roi_align_fpn_fwd_ws_f32(const float *const *xs, const int *Hs, const int *Ws,
                                               const float *scales, int L, int N, int C, const float *rois,
                                               const int32_t *levels, int R, int PH, int PW,
@@ -1651,13 +1691,10 @@ extern "C" int mrcnn_roi_align_fpn_bwd_f32(const float *gy, float *const *gxs, c
                                            const float *scales, int L, int N, int C, const float *rois,
                                            const int32_t *levels, int R, int PH, int PW,
                                            int sampling_ratio, int accumulate, void *ws, size_t ws_bytes, void *stream) {
-    if (!gxs || (R > 0 && (!rois || !levels || !gy))) return mrcnn::fail_arg(MRCNN_E_INVALID, "roi_align_fpn_bwd: null pointer");
-    if (N <= 0 || C <= 0 || PH <= 0 || PW <= 0 || R < 0) return mrcnn::fail_arg(MRCNN_E_INVALID, "roi_align_fpn_bwd: bad sizes");
-    if (!fast_bwd_ok(C, PH, PW, sampling_ratio, R))
-        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "roi_align_fpn_bwd: needs C%%4==0, PH,PW<=%d, sampling_ratio>0", PB);
+    const RoiArgs a{rois, levels, R, N, C, PH, PW, sampling_ratio};
     Levels lv{};
-    if (int e = fill_levels(lv, nullptr, gxs, Hs, Ws, scales, L)) return e;
-    return launch_bwd_tiles(lv, N, gy, rois, levels, R, C, PH, PW, sampling_ratio, accumulate, ws, ws_bytes, (hipStream_t)stream);
+    if (int e = fpn_bwd_levels(lv, "roi_align_fpn_bwd", !gxs || (R > 0 && (!rois || !levels || !gy)), a, gxs, Hs, Ws, scales, L)) return e;
+    return run_backward(lv, a, gy, accumulate, ws, ws_bytes, nullptr, 0, false, (hipStream_t)stream);
 }
 
 // ---- (ABI v9) entry-list plan of the backward, built ahead of time from the RoIs alone; a backward that follows it
@@ -1669,27 +1706,19 @@ extern "C" size_t mrcnn_roi_align_fpn_bwd_plan_bytes(const int *Hs, const int *W
 extern "C" int mrcnn_roi_align_fpn_bwd_plan_f32(const int *Hs, const int *Ws, const float *scales, int L, int N, int C, const float *rois,
                                                 const int32_t *levels, int R, int PH, int PW, int sampling_ratio, int split_levels,
                                                 void *plan, size_t plan_bytes, void *stream) {
-    if (!plan || (R > 0 && (!rois || (L > 1 && !levels)))) return mrcnn::fail_arg(MRCNN_E_INVALID, "roi_align_fpn_bwd_plan: null pointer");
-    if (N <= 0 || C <= 0 || PH <= 0 || PW <= 0 || R < 0) return mrcnn::fail_arg(MRCNN_E_INVALID, "roi_align_fpn_bwd_plan: bad sizes");
-    if (!fast_bwd_ok(C, PH, PW, sampling_ratio, R))
-        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "roi_align_fpn_bwd_plan: needs C%%4==0, PH,PW<=%d, sampling_ratio>0", PB);
+    const RoiArgs a{rois, levels, R, N, C, PH, PW, sampling_ratio};
     Levels lv{};
-    if (int e = fill_levels(lv, nullptr, nullptr, Hs, Ws, scales, L)) return e;
-    return launch_bwd_tiles(lv, N, nullptr, rois, levels, R, C, PH, PW, sampling_ratio, 0, nullptr, 0, (hipStream_t)stream, (int *)plan,
-                            plan_bytes, 1, split_levels != 0);
+    if (int e = fpn_bwd_levels(lv, "roi_align_fpn_bwd_plan", !plan || (R > 0 && (!rois || (L > 1 && !levels))), a, nullptr, Hs, Ws, scales, L)) return e;
+    return build_plan(lv, a, split_levels != 0, (int *)plan, plan_bytes, (hipStream_t)stream);
 }
 extern "C" int mrcnn_roi_align_fpn_bwd_planned_f32(const float *gy, float *const *gxs, const int *Hs, const int *Ws, const float *scales, int L,
                                                    int N, int C, const float *rois, const int32_t *levels, int R, int PH, int PW,
                                                    int sampling_ratio, int accumulate, void *ws, size_t ws_bytes, void *plan,
                                                    size_t plan_bytes, int plan_verified, void *stream) {
-    if (!gxs || (R > 0 && (!rois || (L > 1 && !levels) || !gy))) return mrcnn::fail_arg(MRCNN_E_INVALID, "roi_align_fpn_bwd_planned: null pointer");
-    if (N <= 0 || C <= 0 || PH <= 0 || PW <= 0 || R < 0) return mrcnn::fail_arg(MRCNN_E_INVALID, "roi_align_fpn_bwd_planned: bad sizes");
-    if (!fast_bwd_ok(C, PH, PW, sampling_ratio, R))
-        return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "roi_align_fpn_bwd_planned: needs C%%4==0, PH,PW<=%d, sampling_ratio>0", PB);
+    const RoiArgs a{rois, levels, R, N, C, PH, PW, sampling_ratio};
     Levels lv{};
-    if (int e = fill_levels(lv, nullptr, gxs, Hs, Ws, scales, L)) return e;
-    return launch_bwd_tiles(lv, N, gy, rois, levels, R, C, PH, PW, sampling_ratio, accumulate, ws, ws_bytes, (hipStream_t)stream, (int *)plan,
-                            plan ? plan_bytes : 0, 0, false, plan_verified != 0);
+    if (int e = fpn_bwd_levels(lv, "roi_align_fpn_bwd_planned", !gxs || (R > 0 && (!rois || (L > 1 && !levels) || !gy)), a, gxs, Hs, Ws, scales, L)) return e;
+    return run_backward(lv, a, gy, accumulate, ws, ws_bytes, (int *)plan, plan_bytes, plan_verified != 0, (hipStream_t)stream);
 }
 // status3 (host): [0] 1 = the header carries the builder's magic, [1] tiles the builder flagged (pool exhausted), [2] pool nodes used.
 // The ONE entry point of this library that waits for the device (it copies the header back and synchronises `stream`).
@@ -1707,27 +1736,23 @@ extern "C" int mrcnn_roi_align_bwd_plan_status(const void *plan, size_t plan_byt
 extern "C" size_t mrcnn_roi_align_fpn_bwd_workspace_bytes(const int *Hs, const int *Ws, int L, int N, int C, int R, int PH, int PW,
                                                           int sampling_ratio) {
     if (!Hs || !Ws || L <= 0 || L > MRCNN_MAX_LEVELS || N <= 0 || C <= 0) return 0;
-    return bwd_ws_bytes(Hs, Ws, L, N, C, R, PH, PW, sampling_ratio);
+    return slab_ws_bytes(Hs, Ws, L, N, C);
 }
 
 extern "C" size_t mrcnn_roi_align_bwd_workspace_bytes(int N, int C, int H, int W, int R, int PH, int PW, int sampling_ratio) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    return bwd_ws_bytes(&H, &W, 1, N, C, R, PH, PW, sampling_ratio);
+    return slab_ws_bytes(&H, &W, 1, N, C);
 }
 
 // Diagnostic: configs-style single-level backward with phase stamps (see k_roi_align_bwd_waves<.., STAMP>); stamps =
-// (grid workgroups x 4 waves x 8) u64, grid = 8 * ceil(tiles / 8).  Not part of the product path.
+// (grid workgroups x 4 waves x 12) u64, grid = 8 * ceil(tiles / 8).  Not part of the product path.
 extern "C" int mrcnn_debug_roi_align_bwd_stamps(const float *gy, int N, int C, int H, int W, const float *rois, int R, int PH,
                                                 int PW, float spatial_scale, int sampling_ratio, float *gx,
                                                 unsigned long long *stamps, void *stream) {
     if (!gy || !rois || !gx || !stamps || PH > 8 || PW > 8 || !fast_bwd_ok(C, PH, PW, sampling_ratio, R))
         return mrcnn::fail_arg(MRCNN_E_INVALID, "debug_roi_align_bwd_stamps: bad arguments (7x7-class pooling only)");
-    Levels lv{};
-    lv.L = 1; lv.gx[0] = gx; lv.H[0] = H; lv.W[0] = W; lv.scale[0] = spatial_scale;
-    lv.tiles_x[0] = mrcnn::cdiv(W, TW); lv.tiles_y[0] = mrcnn::cdiv(H, TH); lv.split[0] = 1; lv.tile_begin[0] = 0;
-    const int total = lv.tiles_x[0] * lv.tiles_y[0] * N;
-    lv.tile_begin[1] = total;
-    const int chunk = mrcnn::cdiv(total, 8);
+    Levels lv = single_level(nullptr, gx, H, W, spatial_scale);
+    const int chunk = mrcnn::cdiv(tile_levels(lv, N, C, false, nullptr), 8);
     hipLaunchKernelGGL((k_roi_align_bwd_waves<8, W2_DEPTH, true>), dim3(chunk * 8), dim3(BWD_THREADS), 0, (hipStream_t)stream, lv, gy, rois,
                        (const int32_t *)nullptr, R, N, C, PH, PW, sampling_ratio, chunk, 0, stamps);
     MRCNN_LAUNCH_CHECK();

@@ -166,8 +166,8 @@ int mrcnn_roi_align_bwd_plan_status(const void *plan, size_t plan_bytes, int *st
  * slower for the forward + backward pair and never shipped.) */
 int mrcnn_roi_align_set_bwd_variant(int variant);
 
-/* Diagnostic build of the backward kernel with s_memtime stamps at the phase boundaries of every wave (tools/roi_stamps.py;
- * measurement only).  stamps: 12 x u64 per wave, (8 * ceil(tiles / 8)) workgroups x 4 waves. */
+/* Diagnostic build of the backward kernel with s_memtime stamps at the phase boundaries of every wave (measurement
+ * only).  stamps: 12 x u64 per wave, (8 * ceil(tiles / 8)) workgroups x 4 waves. */
 int mrcnn_debug_roi_align_bwd_stamps(const float *gy, int N, int C, int H, int W, const float *rois, int R, int PH, int PW,
                                      float spatial_scale, int sampling_ratio, float *gx, unsigned long long *stamps,
                                      void *stream);

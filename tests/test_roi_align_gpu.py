@@ -118,6 +118,36 @@ def test_backward_many_rois_on_one_tile_and_segments(bwd_variant):
     np.testing.assert_allclose(gx.cpu().numpy(), want, rtol=2e-5, atol=1e-4 * np.abs(want).max())
 
 
+def test_stamps_entry_gives_the_backward_bits_inside_its_buffer():
+    """mrcnn_debug_roi_align_bwd_stamps (the measurement build of the wave kernel; the host side tiles the level like the product
+    backward): the same gx bits as mrcnn_roi_align_bwd_ws_f32 without a workspace, and no write behind the buffer sized as
+    include/mrcnn_hip.h states it - 12 u64 x 4 waves x 8 * ceil(tiles / 8) workgroups.  One level, 16 x 16 map: 4 tiles, grid 8."""
+    rs = np.random.RandomState(12)
+    N, C, H, W, scale, P, sr = 1, 8, 16, 16, 0.25, 7, 2
+    rois = _edge_rois(N, H, W, scale)
+    R = rois.shape[0]
+    rt = torch.from_numpy(rois).to(DEV)
+    gyt = torch.from_numpy(rs.standard_normal((R, P, P, C)).astype(np.float32)).to(DEV)
+    lib = _hip.lib()
+    want = torch.full((N, H, W, C), float('nan'), device=DEV)
+    _hip.check(lib.mrcnn_roi_align_bwd_ws_f32(_hip.ptr(gyt), 1, N, C, H, W, _hip.ptr(rt), R, P, P, scale, sr, _hip.ptr(want), None, 0,
+                                              _hip.stream_ptr()))
+    tiles = -(-H // 8) * -(-W // 8) * N
+    assert tiles == 4
+    n = 12 * 4 * 8 * -(-tiles // 8)
+    SENTINEL = 0x5A5A5A5A5A5A5A5A
+    stamps = torch.zeros((2 * n,), dtype=torch.int64, device=DEV)
+    stamps[n:] = SENTINEL
+    got = torch.full((N, H, W, C), float('nan'), device=DEV)
+    _hip.check(lib.mrcnn_debug_roi_align_bwd_stamps(_hip.ptr(gyt), N, C, H, W, _hip.ptr(rt), R, P, P, scale, sr, _hip.ptr(got),
+                                                    _hip.ptr(stamps), _hip.stream_ptr()))
+    torch.cuda.synchronize()
+    assert torch.isfinite(want).all()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert bool((stamps[n:] == SENTINEL).all())
+    assert bool((stamps[:n].view(-1, 12)[:tiles * 4, 0] != 0).all())           # every wave of the 4 tiles left its start stamp
+
+
 def test_empty_and_error_paths():
     x = torch.zeros((1, 8, 5, 5), device=DEV).contiguous(memory_format=torch.channels_last)
     x.requires_grad_(True)
