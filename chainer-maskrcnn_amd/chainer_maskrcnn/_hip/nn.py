@@ -164,8 +164,19 @@ def winograd_w_bytes(x_shape, w_shape, stride, pad):
     return lib().mrcnn_conv2d_winograd_w_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)
 
 
-def conv2d_bwd_data_raw(gy, w, x_shape, stride, pad, out=None, relu_x=None, emit_w=False, gb=None, gb_accumulate=False):
+def active_rows(n_pos, rows_per_block):
+    """uint8 (n_blocks * rows_per_block,): 1 where (row % rows_per_block) < n_pos[row // rows_per_block] - the rows of a row-blocked batch
+    that can carry gradient when every block has its n_pos live rows first.  One small launch; n_pos (int32) stays on the device."""
+    assert n_pos.dtype == torch.int32 and n_pos.is_contiguous()
+    active = torch.empty((n_pos.numel() * int(rows_per_block),), dtype=torch.uint8, device=n_pos.device)
+    check(lib().mrcnn_active_rows_u8(ptr(n_pos), n_pos.numel(), int(rows_per_block), ptr(active), stream_ptr()))
+    return active
+
+
+def conv2d_bwd_data_raw(gy, w, x_shape, stride, pad, out=None, relu_x=None, emit_w=False, gb=None, gb_accumulate=False, active=None):
     """out given => gx is accumulated into it (fan-out points of the graph), else allocated.
+    active (uint8 (N,), device; None = the plain call): 0 = gy is all zero on that image (active_rows) - where the layer's path can, it
+    leaves such images out; same result up to the sign of zero.  Not with emit_w.
     relu_x = the layer's input when it came out of a ReLU: gx is masked with (relu_x > 0) in the epilogue.
     emit_w (Winograd layers only): returns (gx, wino_w) - the filter-gradient operand computed from the same read of gy
     (pass it to conv2d_bwd_filter_raw); gb: the bias gradient is written there from that read too."""
@@ -181,6 +192,13 @@ def conv2d_bwd_data_raw(gy, w, x_shape, stride, pad, out=None, relu_x=None, emit
         wb = lib().mrcnn_conv2d_winograd_w_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)
         assert wb > 0, 'emit_w: the layer does not take the Winograd path'
         wt = torch.empty((wb // 4,), dtype=torch.float32, device=gy.device)
+    if active is not None:
+        assert not emit_w and active.dtype == torch.uint8 and active.is_contiguous()
+        with _prof('bwd_data', N * gy.shape[1] * gy.shape[2], KH, KW, Cin, Cout, (N, H, W, Cin, Cout, KH, KW, stride, pad)):
+            check(lib().mrcnn_conv2d_bwd_data_active_f32(ptr(gy), ptr(w), ptr(gx), ptr(relu_x), N, H, W, Cin, Cout, KH, KW,
+                                                         stride, pad, int(acc), ptr(active), active.numel(),
+                                                         ptr(ws), ws.numel() if ws is not None else 0, stream_ptr()))
+        return gx
     with _prof('bwd_data', N * gy.shape[1] * gy.shape[2], KH, KW, Cin, Cout, (N, H, W, Cin, Cout, KH, KW, stride, pad)):
         check(lib().mrcnn_conv2d_bwd_data_f32(ptr(gy), ptr(w), ptr(gx), ptr(relu_x), N, H, W, Cin, Cout, KH, KW,
                                               stride, pad, int(acc), ptr(wt), ptr(gb) if emit_w else None, int(gb_accumulate),
@@ -189,9 +207,10 @@ def conv2d_bwd_data_raw(gy, w, x_shape, stride, pad, out=None, relu_x=None, emit
 
 
 def conv2d_bwd_filter_raw(x, gy, w_shape, stride, pad, want_bias, gw=None, gb=None, accumulate=None, wino_v=None,
-                          wino_w=None):
+                          wino_w=None, active=None):
     """gw / gb given: written in place (accumulate=True adds - layers applied several times); else allocated.
-    wino_v: the transformed input kept by conv2d_fwd_raw(..., keep_v=True) of the same layer."""
+    wino_v: the transformed input kept by conv2d_fwd_raw(..., keep_v=True) of the same layer.
+    active: as in conv2d_bwd_data_raw (not with wino_w)."""
     N, H, W, Cin = x.shape
     Cout, KH, KW, _ = w_shape
     assert gy.is_contiguous() and x.is_contiguous()
@@ -201,6 +220,13 @@ def conv2d_bwd_filter_raw(x, gy, w_shape, stride, pad, want_bias, gw=None, gb=No
         gb = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
     nbytes = lib().mrcnn_conv2d_bwd_filter_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)
     ws = workspace(nbytes, x.device)
+    if active is not None:
+        assert wino_w is None and active.dtype == torch.uint8 and active.is_contiguous()
+        with _prof('bwd_filter', N * gy.shape[1] * gy.shape[2], KH, KW, Cin, Cout, (N, H, W, Cin, Cout, KH, KW, stride, pad)):
+            check(lib().mrcnn_conv2d_bwd_filter_active_f32(ptr(x), ptr(gy), ptr(gw), ptr(gb) if want_bias else None, N, H, W, Cin,
+                                                           Cout, KH, KW, stride, pad, int(acc), ptr(wino_v), ptr(active), active.numel(),
+                                                           ptr(ws), ws.numel(), stream_ptr()))
+        return gw, gb
     with _prof('bwd_filter', N * gy.shape[1] * gy.shape[2], KH, KW, Cin, Cout, (N, H, W, Cin, Cout, KH, KW, stride, pad)):
         check(lib().mrcnn_conv2d_bwd_filter_f32(ptr(x), ptr(gy), ptr(gw), ptr(gb) if want_bias else None, N, H, W, Cin,
                                                 Cout, KH, KW, stride, pad, int(acc), ptr(wino_v), ptr(wino_w), ptr(ws), ws.numel(),

@@ -267,6 +267,7 @@ class FPNMaskRCNNTrainChain(object):
                                                        getattr(faster_rcnn, 'point_head', None) is not None)
         self._row = dict(self._loss_rows)
         self.pending = None                 # the _PendingBackward of a forward pass whose backward pass has not run yet
+        self._mask_active = None            # active-row mask of the pending mask branch backward (_mask_loss; None = dense)
         self._arith_found = None            # the process's GEMM arithmetic before this chain selected its own (restored by backward())
 
     @property
@@ -399,13 +400,15 @@ class FPNMaskRCNNTrainChain(object):
         g_iou_in = m.maskiou_head.backward(st.g_iou) if st.g_iou is not None else None
         # the point head likewise (main stream): its input gradient waits for the ROIAlign backward passes below
         g_pt_in = m.point_head.backward(st.point['g_pred']) if st.point is not None else None
-        g_pool = m.head.backward_mask_convs(st.g_mask)    # main stream: the mask branch down to its pooled input
+        active = self._mask_active
+        self._mask_active = None
+        g_pool = m.head.backward_mask_convs(st.g_mask, active=active)    # main stream: the mask branch down to its pooled input
         if g_iou_in is not None:
             self._maskiou_input_backward(g_iou_in, g_pool)
         main.wait_stream(aux)
         if self.keep_outputs and g_iou_in is not None:       # parity tests: the pyramid gradient the box stages left
             self.outputs.update(g_feats_box=[g.clone() for g in g_feats])
-        m.head.backward_mask_pool(g_pool, g_feats)        # accumulates into g_feats (second pooled size)
+        m.head.backward_mask_pool(g_pool, g_feats, active=active)        # accumulates into g_feats (second pooled size)
         if g_pt_in is not None:
             self._point_input_backward(st.point, g_pt_in, g_feats)
         if self.keep_outputs and (st.g_later or g_iou_in is not None):       # parity tests: the mask branch's pooled gradient and the pyramid gradient behind the heads
@@ -521,7 +524,10 @@ class FPNMaskRCNNTrainChain(object):
 
     def _mask_loss(self, features, t, scales, losses):
         """The mask branch on its rows and the mask loss -> (the rows' rois, levels and labels, the NHWC logits, the loss gradient)."""
+        from chainer_maskrcnn.nn import core
+        from chainer_maskrcnn._hip import nn as hnn
         head = self.faster_rcnn.head
+        self._mask_active = None
         if self.mask_loss_kind == 'generic':
             g_mask = self._generic_mask_loss(t, features, scales, losses)
             return self._generic_inputs + (None, g_mask)
@@ -537,6 +543,13 @@ class FPNMaskRCNNTrainChain(object):
         out = losses[self._row['mask_loss']]
         if self.mask_loss_kind == 'mask_bce':
             _, g_mask = ops.mask_bce(mask_out, t['gt_roi_mask'], m_label, out=out)
+            # mask_rows='all': the loss reads the first n_pos rows of every image block only (label <= 0 behind them), so g_mask is an exact
+            # zero on the others and the backward pass may leave them out.  Not with a MaskIoU or PointRend head: their gradients reach
+            # the mask branch on rows of their own choosing.  The mask is built on this stream, beside the loss; n_pos stays on the device.
+            m = self.faster_rcnn
+            if (rows == S and core.MASK_BWD_SKIP_INACTIVE and getattr(m, 'maskiou_head', None) is None
+                    and getattr(m, 'point_head', None) is None):
+                self._mask_active = hnn.active_rows(t['n_pos'].to(torch.int32).contiguous(), S)
         else:
             Rm, Hm, Wm, Cm = mask_out.shape
             K = head.n_keypoints

@@ -394,8 +394,9 @@ class FPNRoIMaskHead(FPNRoIBoxHead):
         m = ops.pixel_shuffle2x(d, bias=bm)
         return m, (h, wm), None
 
-    def _merged_deconv_bwd(self, td, g_mask):
-        """Gradients of deconv1 / conv2 parameters from the merged layer; returns the gradient of the deconv input."""
+    def _merged_deconv_bwd(self, td, g_mask, active=None):
+        """Gradients of deconv1 / conv2 parameters from the merged layer; returns the gradient of the deconv input.
+        active: see backward_mask_convs (the 1x1 layer's kernels run dense on the zero rows; the mask travels with the calls)."""
         from chainer_maskrcnn._hip import nn as hnn
         dc, c2, C = self.deconv1, self.conv2, self.channels
         x_in, wm = td
@@ -403,9 +404,9 @@ class FPNRoIMaskHead(FPNRoIBoxHead):
         g4 = ops.pixel_shuffle2x(g_mask, inverse=True)
         hnn.LOGICAL = (dc.cin, 4 * c2.cout)
         try:
-            G, gb4 = hnn.conv2d_bwd_filter_raw(x_in, g4, tuple(wm.shape), 1, 0, True)
+            G, gb4 = hnn.conv2d_bwd_filter_raw(x_in, g4, tuple(wm.shape), 1, 0, True, active=active)
             # x_in is the ReLU output of the last mask conv (of its GroupNorm): its ReLU backward is fused here
-            g = hnn.conv2d_bwd_data_raw(g4, wm, tuple(x_in.shape), 1, 0, relu_x=x_in if self.mask_convs else None)
+            g = hnn.conv2d_bwd_data_raw(g4, wm, tuple(x_in.shape), 1, 0, relu_x=x_in if self.mask_convs else None, active=active)
         finally:
             hnn.LOGICAL = None
         ps = self.ps
@@ -441,20 +442,35 @@ class FPNRoIMaskHead(FPNRoIBoxHead):
         if g_mask is not None:
             self.backward_mask_pool(self.backward_mask_convs(g_mask), g_feats)
 
-    def backward_mask_convs(self, g_mask):
-        """Mask / keypoint branch backward down to the gradient of its pooled input."""
+    def _usable_active(self, active):
+        """The active-row mask the backward kernels may take, or None (the dense pass).  A row may be left out only where the gradient of
+        EVERYTHING between the mask loss and the pooled features is zero on it and no layer mixes rows: the conv + ReLU stacks, the
+        merged deconvolution and the pixel shuffle qualify (per-row maps without a bias in the backward pass); a GroupNorm in the mask
+        head is left dense, and so is the keypoint head's bilinear upsampling (its callers pass no mask anyway)."""
+        from chainer_maskrcnn.nn import core
+        if active is None or not core.MASK_BWD_SKIP_INACTIVE:
+            return None
+        if self.upsample2x or any(gn is not None for gn in self.mask_gns):
+            return None
+        return active
+
+    def backward_mask_convs(self, g_mask, active=None):
+        """Mask / keypoint branch backward down to the gradient of its pooled input.
+        active (uint8 (Rm,) on the device, hnn.active_rows; None = dense): 0 = row r of g_mask is all zero, so every gradient below it is -
+        the convolution backward passes leave such rows out (nn.core.MASK_BWD_SKIP_INACTIVE; same bits up to the sign of zero)."""
         from chainer_maskrcnn._hip import nn as hnn
+        active = self._usable_active(active)
         tapes, td, tc2, rois, levels, scales, _ = self.mask_tape
         if self.upsample2x:
             g_mask = ops.bilinear2x_bwd(g_mask)
         if self.merge_deconv:
-            g = self._merged_deconv_bwd(td, g_mask)
+            g = self._merged_deconv_bwd(td, g_mask, active)
             n = len(self.mask_convs)
             for i in range(n - 1, -1, -1):          # inputs of convs 1.. are ReLU outputs; conv 0 reads the pooled features
                 t, nt = tapes[i]
                 if self.mask_gns[i] is not None:    # the layer above masked g on this GroupNorm's output
                     g = self.mask_gns[i].bwd(nt, g, gy_masked=True)
-                g = self.mask_convs[i].bwd(t, g, gy_masked=True, mask_gx=(i > 0))
+                g = self.mask_convs[i].bwd(t, g, gy_masked=True, mask_gx=(i > 0), active=active)
             return g
         g = self.conv2.bwd(tc2, g_mask)
         # deconv bias gradient = column sums of g over all output pixels: the filter-gradient call on the shuffled
@@ -473,10 +489,12 @@ class FPNRoIMaskHead(FPNRoIBoxHead):
         for cv, gn, (t, nt) in zip(reversed(self.mask_convs), reversed(self.mask_gns), reversed(tapes)):
             if gn is not None:                      # nothing above masked g: the GroupNorm recomputes its ReLU mask from x
                 g = gn.bwd(nt, g)
-            g = cv.bwd(t, g)
+            g = cv.bwd(t, g, active=active)
         return g
 
-    def backward_mask_pool(self, g_pool, g_feats):
+    def backward_mask_pool(self, g_pool, g_feats, active=None):
+        """active: accepted for symmetry with backward_mask_convs; the ROIAlign backward stays dense (an inactive RoI scatters exact
+        zeros; 0.2 ms of the step, and its fused entry lists would have to be rebuilt around the mask)."""
         tapes, td, tc2, rois, levels, scales, plan = self.mask_tape
         roi_align_fpn_bwd(g_pool, g_feats, rois, levels, self.roi_size_mask, scales, accumulate=True, plan=plan)
         self.mask_tape = None

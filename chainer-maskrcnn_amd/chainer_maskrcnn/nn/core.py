@@ -31,6 +31,10 @@ FILTER_GRAD_ON_SIDE_STREAM = True
 # reads per step but the filter gradient then starts after the data gradient (less overlap): same-box A/B 26.80 vs 26.68
 # ms/step (tools/ab_step.py), so it is off.
 WINOGRAD_SHARED_GY_TRANSFORM = False
+# mask_rows='all': the backward pass of the mask branch leaves out the sampled rows the mask loss does not read (their gradient is an
+# exact zero from the loss down to the pooled features) inside the kernels - same launches, same plans, same bits.
+# False = the dense pass (tools/ab_step.py 'core.MASK_BWD_SKIP_INACTIVE=True' 'core.MASK_BWD_SKIP_INACTIVE=False').
+MASK_BWD_SKIP_INACTIVE = True
 # Per-layer Winograd tile of the FORWARD pass.  Measured on the full network (profiles/r02_winograd_layer_probe.txt): the
 # F(4x4,3x3) forward transform costs gradient accuracy ONLY in the ResNet conv2 layers (their 1e-4 output error passes
 # through training-mode BatchNorm and moves c4 / c5, hence the lateral / RPN gradients, by up to 2e-2); in the layers
@@ -257,17 +261,20 @@ class Conv(object):
         hnn.LOGICAL = None
         return y, (x, y if relu else None, v)
 
-    def bwd(self, ctx, gy, need_gx=True, gx_acc=None, accumulate_params=False, gy_masked=False, mask_gx=False):
+    def bwd(self, ctx, gy, need_gx=True, gx_acc=None, accumulate_params=False, gy_masked=False, mask_gx=False, active=None):
         """gy: gradient w.r.t. the (post-ReLU) output.  gx_acc: tensor to accumulate gx into.
         accumulate_params: add into the parameter gradients (layer applied several times).
         gy_masked: the producer of gy already applied this layer's ReLU mask (the layer above ran with mask_gx).
         mask_gx: this layer's input is itself a ReLU output - zero gx where x <= 0 in the data-gradient epilogue,
-        which is the ReLU backward of the layer below (call that layer with gy_masked=True)."""
+        which is the ReLU backward of the layer below (call that layer with gy_masked=True).
+        active (uint8 (N,) or None): 0 = gy is all zero on that image (hnn.active_rows); forwarded to the two backward calls."""
         with _layer_tiles(self):
-            return self._bwd(ctx, gy, need_gx, gx_acc, accumulate_params, gy_masked, mask_gx)
+            return self._bwd(ctx, gy, need_gx, gx_acc, accumulate_params, gy_masked, mask_gx, active)
 
-    def _bwd(self, ctx, gy, need_gx, gx_acc, accumulate_params, gy_masked, mask_gx):
+    def _bwd(self, ctx, gy, need_gx, gx_acc, accumulate_params, gy_masked, mask_gx, active=None):
         x, y, v = ctx
+        if WINOGRAD_SHARED_GY_TRANSFORM:        # (the shared transform of gy feeds the dense GEMMs)
+            active = None
         if y is not None and not gy_masked:
             gy = ops.relu_bwd(gy, y)
         gw = self.gW
@@ -298,21 +305,23 @@ class Conv(object):
                 side.wait_stream(main)                      # gy (and x) are complete on the main stream
                 with torch.cuda.stream(side):
                     hnn.conv2d_bwd_filter_raw(x, gy, tuple(gw.shape), self.stride, self.pad, self.has_bias, gw=gw, gb=gb,
-                                              accumulate=accumulate_params, wino_v=v)
+                                              accumulate=accumulate_params, wino_v=v, active=active)
                 gy.record_stream(side)                      # allocator: do not recycle gy before the side kernel is done
                 x.record_stream(side)
                 if v is not None:
                     v.record_stream(side)
+                if active is not None:
+                    active.record_stream(side)
             else:
                 hnn.conv2d_bwd_filter_raw(x, gy, tuple(gw.shape), self.stride, self.pad, self.has_bias, gw=gw, gb=gb,
-                                          accumulate=accumulate_params, wino_v=v)
+                                          accumulate=accumulate_params, wino_v=v, active=active)
             if not need_gx:
                 return None
             if self.stride == 1:
                 # (the epilogue masks the TOTAL: (old + product) where relu_x > 0 - direct, split-K and tail-split launches alike)
                 assert not (mask_gx and gx_acc is not None) or self.k == 1
                 return hnn.conv2d_bwd_data_raw(gy, self.W, tuple(x.shape), 1, self.pad, out=gx_acc,
-                                               relu_x=x if mask_gx else None)
+                                               relu_x=x if mask_gx else None, active=active)
             if self.k > 1:
                 # a strided k x k layer (the MaskIoU head's 3x3/2): the library's data gradient is stride 1 only, so gy is scattered onto
                 # the stride-1 output lattice (zeros between) and that layer's data gradient is taken - the same sums plus zero terms

@@ -1523,7 +1523,7 @@ struct InBN { const float *gamma, *beta, *mean, *invstd; };
 template <int M_>
 __device__ __forceinline__ void wino_input_body(const float *__restrict__ x, float *__restrict__ V, int N, int H, int W, int C,
                                                 int th, int tw, long long T, long long Tp, unsigned blk, const InBN bn = InBN{},
-                                                int panel = 0) {
+                                                int panel = 0, const unsigned char *__restrict__ active = nullptr) {
     constexpr int A_ = M_ + 2;
     // 32-bit index arithmetic (wino_ok(): 16 * Tp * C < 2^30): the 64-bit divisions this replaces were ~600 instructions of
     // branchy software division per thread
@@ -1561,6 +1561,9 @@ __device__ __forceinline__ void wino_input_body(const float *__restrict__ x, flo
     const int tx = (int)(t - trow * (unsigned)tw);
     const int n = (int)(trow / (unsigned)th);
     const int ty = (int)(trow - (unsigned)n * (unsigned)th);
+    // active (nullable; the data gradient of a layer whose gy is zero on the images with active[n] == 0): such a tile's rows of V are
+    // neither computed nor written - a GEMM row depends on its own row of V only, and k_wino_output does not read the rows of M they give
+    if (active && !active[n]) return;
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc((void *)x, 0, (unsigned)((size_t)N * H * W * C * 4), 0x00020000);
     const unsigned OOB = 0xFFFFFFFFu;
     unsigned rowo[A_], colo[A_];
@@ -1626,9 +1629,9 @@ template <int M_>
 __global__ __launch_bounds__(256) void k_wino_input_filter(const float *__restrict__ x, float *__restrict__ V, int N, int H, int W, int C,
                                                            int th, int tw, long long T, long long Tp, const float *__restrict__ w,
                                                            float *__restrict__ U, int Cout_w, int Cin_w, int transposed, unsigned fblocks,
-                                                           int banded, int uplanes, InBN bn) {
+                                                           int banded, int uplanes, InBN bn, const unsigned char *__restrict__ active) {
     if (blockIdx.x < fblocks) wino_filter_body<M_>(w, U, Cout_w, Cin_w, transposed, blockIdx.x, uplanes);
-    else wino_input_body<M_>(x, V, N, H, W, C, th, tw, T, Tp, xcd_banded(blockIdx.x, fblocks, gridDim.x - fblocks, banded), bn, banded);
+    else wino_input_body<M_>(x, V, N, H, W, C, th, tw, T, Tp, xcd_banded(blockIdx.x, fblocks, gridDim.x - fblocks, banded), bn, banded, active);
 }
 
 // y (m x m pixels of tile t) = A^T M A + bias, then ReLU | + old y (accumulate) | zeroed where relu_x <= 0.
@@ -1639,7 +1642,7 @@ template <int M_>
 __global__ __launch_bounds__(256) void k_wino_output(const float *__restrict__ Mb, float *__restrict__ y, int N, int H, int W, int C,
                                                      int th, int tw, long long T, long long Tp, const float *__restrict__ bias,
                                                      int relu, int accumulate, const float *__restrict__ relu_x,
-                                                     float *__restrict__ bn_part) {
+                                                     float *__restrict__ bn_part, const unsigned char *__restrict__ active) {
     constexpr int A_ = M_ + 2;
     __shared__ float4 sred[2][256];
     const unsigned C4 = (unsigned)C / 4u;
@@ -1660,50 +1663,64 @@ __global__ __launch_bounds__(256) void k_wino_output(const float *__restrict__ M
         const auto rsY = __builtin_amdgcn_make_buffer_rsrc((void *)y, 0, ybytes, 0x00020000);
         const auto rsR = __builtin_amdgcn_make_buffer_rsrc((void *)relu_x, 0, relu_x ? ybytes : 0u, 0x00020000);
         const unsigned mo = (unsigned)(((size_t)t * C + c) * 4);
-        V4 s[M_][A_];           // A^T m, column by column
+        // active (nullable; data gradient only - no bias, no ReLU, no bn_part, not accumulate with relu_x): an image with active[n] == 0 has
+        // a zero gradient.  Its rows of M were not computed and are not read: the tile is zero, or stays as it is when accumulating.
+        if (active && !active[n]) {
+            if (!accumulate) {
 #pragma unroll
-        for (int q = 0; q < A_; ++q) {
-            V4 m[A_], r[M_];
+                for (int a = 0; a < M_; ++a)
 #pragma unroll
-            for (int rr = 0; rr < A_; ++rr) m[rr] = v4buf_nt(rsM, mo, (unsigned)(rr * A_ + q) * ks);
-            wino_at<M_, V4>(m, r);
-#pragma unroll
-            for (int a = 0; a < M_; ++a) s[a][q] = r[a];
-        }
-        const V4 bv = bias ? v4ld(bias + c) : v4zero();
-        const unsigned OOB = 0xFFFFFFFFu;
-#pragma unroll
-        for (int a = 0; a < M_; ++a) {
-            V4 row[M_], old[M_], xm[M_];
-            wino_at<M_, V4>(s[a], row);
-            const int h = M_ * ty + a;
-            unsigned off[M_];
-#pragma unroll
-            for (int b = 0; b < M_; ++b) {
-                const int ww = M_ * tx + b;
-                off[b] = (h < H && ww < W) ? (unsigned)((((size_t)n * H + h) * W + ww) * C + c) * 4u : OOB;
+                    for (int b = 0; b < M_; ++b) {
+                        const int h = M_ * ty + a, ww = M_ * tx + b;
+                        v4bufst(rsY, (h < H && ww < W) ? (unsigned)((((size_t)n * H + h) * W + ww) * C + c) * 4u : 0xFFFFFFFFu, 0, v4zero());
+                    }
             }
-            // the optional reads of a row of pixels go out together (one block-uniform branch per row, not per pixel)
-            if (accumulate) {
+        } else {
+            V4 s[M_][A_];           // A^T m, column by column
 #pragma unroll
-                for (int b = 0; b < M_; ++b) old[b] = v4buf(rsY, off[b], 0);
+            for (int q = 0; q < A_; ++q) {
+                V4 m[A_], r[M_];
+#pragma unroll
+                for (int rr = 0; rr < A_; ++rr) m[rr] = v4buf_nt(rsM, mo, (unsigned)(rr * A_ + q) * ks);
+                wino_at<M_, V4>(m, r);
+#pragma unroll
+                for (int a = 0; a < M_; ++a) s[a][q] = r[a];
             }
-            if (relu_x) {
+            const V4 bv = bias ? v4ld(bias + c) : v4zero();
+            const unsigned OOB = 0xFFFFFFFFu;
 #pragma unroll
-                for (int b = 0; b < M_; ++b) xm[b] = v4buf(rsR, off[b], 0);
-            }
+            for (int a = 0; a < M_; ++a) {
+                V4 row[M_], old[M_], xm[M_];
+                wino_at<M_, V4>(s[a], row);
+                const int h = M_ * ty + a;
+                unsigned off[M_];
 #pragma unroll
-            for (int b = 0; b < M_; ++b) {
-                V4 v = row[b] + bv;
-                if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                if (accumulate) v = v + old[b];
-                if (relu_x) {
-                    v.x = xm[b].x > 0.f ? v.x : 0.f; v.y = xm[b].y > 0.f ? v.y : 0.f; v.z = xm[b].z > 0.f ? v.z : 0.f; v.w = xm[b].w > 0.f ? v.w : 0.f;
+                for (int b = 0; b < M_; ++b) {
+                    const int ww = M_ * tx + b;
+                    off[b] = (h < H && ww < W) ? (unsigned)((((size_t)n * H + h) * W + ww) * C + c) * 4u : OOB;
                 }
-                v4bufst(rsY, off[b], 0, v);
-                if (off[b] != OOB) {       // (statistics: only pixels of the image)
-                    bs = bs + v;
-                    bq.x = fmaf(v.x, v.x, bq.x); bq.y = fmaf(v.y, v.y, bq.y); bq.z = fmaf(v.z, v.z, bq.z); bq.w = fmaf(v.w, v.w, bq.w);
+                // the optional reads of a row of pixels go out together (one block-uniform branch per row, not per pixel)
+                if (accumulate) {
+#pragma unroll
+                    for (int b = 0; b < M_; ++b) old[b] = v4buf(rsY, off[b], 0);
+                }
+                if (relu_x) {
+#pragma unroll
+                    for (int b = 0; b < M_; ++b) xm[b] = v4buf(rsR, off[b], 0);
+                }
+#pragma unroll
+                for (int b = 0; b < M_; ++b) {
+                    V4 v = row[b] + bv;
+                    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                    if (accumulate) v = v + old[b];
+                    if (relu_x) {
+                        v.x = xm[b].x > 0.f ? v.x : 0.f; v.y = xm[b].y > 0.f ? v.y : 0.f; v.z = xm[b].z > 0.f ? v.z : 0.f; v.w = xm[b].w > 0.f ? v.w : 0.f;
+                    }
+                    v4bufst(rsY, off[b], 0, v);
+                    if (off[b] != OOB) {       // (statistics: only pixels of the image)
+                        bs = bs + v;
+                        bq.x = fmaf(v.x, v.x, bq.x); bq.y = fmaf(v.y, v.y, bq.y); bq.z = fmaf(v.z, v.z, bq.z); bq.w = fmaf(v.w, v.w, bq.w);
+                    }
                 }
             }
         }
@@ -1731,12 +1748,13 @@ __global__ __launch_bounds__(256) void k_wino_output(const float *__restrict__ M
 // when C/4 divides 256: the host passes bias_part only then); k_colsum_final adds the rows up.
 template <int M_>
 __global__ __launch_bounds__(256) void k_wino_gy(const float *__restrict__ gy, float *__restrict__ Wt, int N, int H, int W, int C,
-                                                 int th, int tw, long long T, long long Tp, float *__restrict__ bias_part, int wplanes) {
+                                                 int th, int tw, long long T, long long Tp, float *__restrict__ bias_part, int wplanes,
+                                                 const unsigned char *__restrict__ active) {
     constexpr int A_ = M_ + 2;
     __shared__ float4 sred[256];
     const unsigned C4 = (unsigned)C / 4u;
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    const bool in_range = i < (unsigned)Tp * C4;
+    bool in_range = i < (unsigned)Tp * C4;
     const unsigned t = in_range ? i / C4 : (unsigned)Tp;         // 32-bit index arithmetic, as in k_wino_input
     const int c = in_range ? (int)(i - t * C4) * 4 : 0;
     V4 bsum = v4zero();
@@ -1756,6 +1774,10 @@ __global__ __launch_bounds__(256) void k_wino_gy(const float *__restrict__ gy, f
         __builtin_amdgcn_raw_buffer_store_b64(u32x2{mid.x, mid.y}, rsW, off + (unsigned)C * 2u, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b64(u32x2{lo.x, lo.y}, rsW, off + (unsigned)C * 4u, 0, 0);
     };
+    // active (nullable; plane GEMM only): gy is zero on the images with active[n] == 0.  k_pgemm_gpp leaves out the 16-row K steps
+    // without an active image (the same pg_rows_active), so the rows of such a step are neither computed nor written; an inactive tile
+    // that shares its step with an active one is transformed like any other (zeros).  The bias partials get the zeros they would have.
+    if (in_range && active && !pg_rows_active(active, th * tw, (int)T, (int)(t & ~(unsigned)(PG_BK - 1)), PG_BK)) in_range = false;
     if (in_range && t >= (unsigned)T) {           // padded rows: zero
 #pragma unroll
         for (int k = 0; k < A_ * A_; ++k) put(vo + (unsigned)k * ks, v4zero());
@@ -2000,7 +2022,8 @@ WinoFLayout wino_filter_layout(const ConvGeom &cg) {
 // bias gradient's partial column sums in bias_part and *bias_rows = their number (else *bias_rows = 0: the caller sums gy)
 // inbn (the *_inbn entry points; empty otherwise): the input transform applies this BatchNorm + ReLU on load
 int wino_bwd_filter(const float *x, const float *gy, float *gw, const ConvGeom &cg, const InBN &inbn, int accumulate, void *ws,
-                    hipStream_t st, const float *v_cached, const float *w_cached, float *bias_part = nullptr, int *bias_rows = nullptr) {
+                    hipStream_t st, const float *v_cached, const float *w_cached, float *bias_part = nullptr, int *bias_rows = nullptr,
+                    const unsigned char *active = nullptr) {
     const int N = cg.N, H = cg.H, W = cg.W, Cin = cg.Cin, Cout = cg.Cout;
     const WinoFLayout L = wino_filter_layout(cg);
     const WinoGeom &g = L.g;
@@ -2013,8 +2036,11 @@ int wino_bwd_filter(const float *x, const float *gy, float *gw, const ConvGeom &
     const bool fuse_bias = bias_part && bias_rows && !w_cached && C4o <= 256 && 256 % C4o == 0 && !(g_debug_skip & 2);
     if (bias_rows) *bias_rows = fuse_bias ? (int)((nout + 255) / 256) : 0;
     const int big = (L.big && !w_cached) ? 1 : 0;           // (a cached W is float32: the shared-transform path keeps k_conv_igemm)
+    // active (nullable: gy is zero on the images with active[n] == 0): the gy transform and the plane GEMM leave out the same K steps.
+    // Every other launch of this layer (k_conv_igemm, a split of more steps than the GEMM's mask covers) runs dense on the zeros.
+    const unsigned char *act = (big && L.kchunk / PG_BK <= PGG_MASK_STEPS) ? active : nullptr;
     if (!w_cached) WINO_LAUNCH(k_wino_gy, g, dim3((unsigned)((nout + 255) / 256)), gy, Wt, N, H, W, Cout, g.th, g.tw, g.T, g.Tp,
-                               fuse_bias ? bias_part : (float *)nullptr, big);
+                               fuse_bias ? bias_part : (float *)nullptr, big, act);
     const int ksplit = big ? L.ksplit : L.ks32;
     const size_t n4 = (size_t)Cout * g.nk * Cin / 4;
     if (big) {
@@ -2024,6 +2050,7 @@ int wino_bwd_filter(const float *x, const float *gy, float *gw, const ConvGeom &
         q.M = Cout; q.N = Cin; q.K = (int)g.Tp; q.batch_rows = (int)g.Tp; q.nbatch = g.nk; q.ksplit = ksplit; q.kchunk = L.kchunk;
         q.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cout * 6); q.bytes_b = (unsigned)((size_t)g.nk * g.Tp * Cin * 4);
         q.ldc = g.nk * Cin; q.dbg = 0; q.stamps = nullptr;
+        q.active = act; q.act_per = g.th * g.tw; q.act_T = (int)g.T;
         if (!(g_debug_skip & 1)) launch_pgemm<5>(q, PGB_BM, PGB_BN, st);
         MRCNN_LAUNCH_CHECK();
         if (ksplit > 1) if (int e = sum_slabs(slabs, dU, n4, ksplit, 0, st)) return e;
@@ -2071,7 +2098,8 @@ int wino_gemm_p(ConvP &p, const WinoGeom &g, int Cin, int Cout) {
 // and Cout here = the layer's Cin).  inbn (forward only; empty otherwise): the input transform applies this BatchNorm + ReLU on load.
 int wino_conv(const float *in, const float *w, float *out, const ConvGeom &cg, int pass, const InBN &inbn,
               const float *bias, int relu, int accumulate, const float *relu_x, void *ws, size_t ws_bytes, hipStream_t st,
-              float *v_keep, float *w_keep = nullptr, float *gbias = nullptr, int gbias_accumulate = 0, float *bn_part = nullptr) {
+              float *v_keep, float *w_keep = nullptr, float *gbias = nullptr, int gbias_accumulate = 0, float *bn_part = nullptr,
+              const unsigned char *active = nullptr) {
     const int N = cg.N, H = cg.H, W = cg.W, Cin = cg.Cin, Cout = cg.Cout;
     const bool transposed = pass == PASS_BWD_DATA;
     const WinoLayout L = wino_layout(cg, pass);
@@ -2082,6 +2110,10 @@ int wino_conv(const float *in, const float *w, float *out, const ConvGeom &cg, i
     const long long nin = g.Tp * (Cin / 4), nout = g.T * (Cout / 4);       // k_wino_input zeroes the padded rows of V
     const unsigned fblocks = (unsigned)mrcnn::cdiv(Cout * Cin, 256);
     const int big = pg_big_ok(pass, g, Cin, Cout) ? 1 : 0;
+    // active (nullable, backward-data only: `in` = gy is zero on the images with active[n] == 0, so is their gx): the three launches of the
+    // plane-GEMM pipeline leave those images out.  Every other combination runs dense on the zeros: k_conv_igemm, the shared gy transform
+    // (w_keep), and accumulate with relu_x, where the dense pass still masks the old value of an inactive image.
+    const unsigned char *act = (big && pass == PASS_BWD_DATA && !w_keep && !v_keep && !bias && !relu && !bn_part && !(accumulate && relu_x)) ? active : nullptr;
     if (w_keep) WINO_LAUNCH(k_wino_filter, g, dim3(fblocks), w, U, transposed ? Cin : Cout, transposed ? Cout : Cin, transposed ? 1 : 0, big);
     if (w_keep) {           // backward pass: one read of gy feeds this GEMM, the filter-gradient GEMM and the bias gradient
         const bool wb = gbias && (256 % (Cin / 4)) == 0;
@@ -2095,17 +2127,18 @@ int wino_conv(const float *in, const float *w, float *out, const ConvGeom &cg, i
         }
     } else
         WINO_LAUNCH(k_wino_input_filter, g, dim3(fblocks + (unsigned)((nin + 255) / 256)), in, V, N, H, W, Cin, g.th, g.tw, g.T, g.Tp, w, U,
-                    transposed ? Cin : Cout, transposed ? Cout : Cin, transposed ? 1 : 0, fblocks, g_wino_banded, big, inbn);
+                    transposed ? Cin : Cout, transposed ? Cout : Cin, transposed ? 1 : 0, fblocks, g_wino_banded, big, inbn, act);
     if (big) {          // the plane GEMM: A = V (float32 rows), B = U (P16R4 planes), C = M
         PlaneGemmP q{};
         q.a = reinterpret_cast<const unsigned short *>(V); q.b = reinterpret_cast<const unsigned short *>(U); q.c = Mb;
         q.M = (int)(g.nk * g.Tp); q.N = Cout; q.K = Cin; q.batch_rows = (int)g.Tp; q.nbatch = g.nk; q.ksplit = 1; q.kchunk = Cin;
         q.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cin * 4); q.bytes_b = (unsigned)((size_t)g.nk * Cout * Cin * 6);
         q.ldc = Cout; q.dbg = 0; q.stamps = nullptr;
+        q.active = act; q.act_per = g.th * g.tw; q.act_T = (int)g.T;
         if (!(g_debug_skip & 1)) launch_pgemm<4>(q, PGB_BM, PGB_BN, st);
         MRCNN_LAUNCH_CHECK();
         WINO_LAUNCH_OUT(g, dim3((unsigned)((nout + 255) / 256)), Mb, out, N, H, W, Cout, g.th, g.tw, g.T, g.Tp, bias, relu,
-                    accumulate, relu_x, bn_part);
+                    accumulate, relu_x, bn_part, act);
         return 0;
     }
     ConvP p;
@@ -2114,7 +2147,7 @@ int wino_conv(const float *in, const float *w, float *out, const ConvGeom &cg, i
     p.bytes_a = (unsigned)((size_t)g.nk * g.Tp * Cin * 4); p.bytes_b = (unsigned)((size_t)g.nk * Cout * Cin * 4);
     if (int e = run_data_conv<MODE_FWD>(p, nsteps, Cout, pass, base + L.inner, ws_bytes - L.inner, st)) return e;
     WINO_LAUNCH_OUT(g, dim3((unsigned)((nout + 255) / 256)), Mb, out, N, H, W, Cout, g.th, g.tw, g.T, g.Tp, bias, relu,
-                accumulate, relu_x, bn_part);
+                accumulate, relu_x, bn_part, (const unsigned char *)nullptr);
     return 0;
 }
 
@@ -2495,11 +2528,16 @@ extern "C" size_t mrcnn_conv2d_winograd_w_bytes(int N, int H, int W, int Cin, in
     return winograd_w_bytes(ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad});
 }
 
-extern "C" int mrcnn_conv2d_bwd_data_f32(const float *gy, const float *w, float *gx, const float *relu_x, int N, int H, int W,
-                                         int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                         int accumulate, float *wino_w, float *gbias, int gbias_accumulate, void *ws,
-                                         size_t ws_bytes, void *stream) {
-    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+// active / n_active of the *_active entry points: one byte per image; 0 = the image's gy is all zero (the caller's promise)
+static int check_active(const unsigned char *active, int n_active, const ConvGeom &cg, const char *who) {
+    if (active && n_active != cg.N) return mrcnn::fail_arg(MRCNN_E_INVALID, "%s: active has %d entries, the call %d images", who, n_active, cg.N);
+    return 0;
+}
+
+static int conv_bwd_data(const float *gy, const float *w, float *gx, const float *relu_x, const ConvGeom &cg,
+                         int accumulate, float *wino_w, float *gbias, int gbias_accumulate, void *ws,
+                         size_t ws_bytes, void *stream, const unsigned char *active) {
+    const int N = cg.N, Cin = cg.Cin, Cout = cg.Cout, KH = cg.KH, KW = cg.KW;
     if (int e = check_conv(gy, w, gx, cg)) return e;
     if (int e = check_bwd_data(cg)) return e;
     ConvP p = make_p(cg);
@@ -2507,12 +2545,26 @@ extern "C" int mrcnn_conv2d_bwd_data_f32(const float *gy, const float *w, float 
     // first and masks the TOTAL - the ReLU backward of the tensor gx is the gradient of, applied where its last contribution lands
     if (bwd_data_takes_wino(cg, ws != nullptr, ws_bytes))
         return wino_conv(gy, w, gx, cg.transposed(), PASS_BWD_DATA, InBN{}, nullptr, 0, accumulate, relu_x, ws, ws_bytes, (hipStream_t)stream,
-                         nullptr, wino_w, wino_w ? gbias : nullptr, gbias_accumulate);
+                         nullptr, wino_w, wino_w ? gbias : nullptr, gbias_accumulate, nullptr, active);
     if (wino_w || gbias) return mrcnn::fail_arg(MRCNN_E_UNSUPPORTED, "conv2d_bwd_data: wino_w / gbias only on the Winograd path (mrcnn_conv2d_winograd_w_bytes() > 0)");
     p.a = gy; p.b = w; p.c = gx; p.accumulate = accumulate; p.relu_x = relu_x;
     p.bytes_a = (unsigned)((size_t)N * p.Ho * p.Wo * Cout * 4); p.bytes_b = (unsigned)((size_t)Cout * KH * KW * Cin * 4);
     const int nsteps = bwd_data_gemm(p);
     return run_data_conv<MODE_BWD_DATA>(p, nsteps, Cin, PASS_BWD_DATA, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int mrcnn_conv2d_bwd_data_f32(const float *gy, const float *w, float *gx, const float *relu_x, int N, int H, int W,
+                                         int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                         int accumulate, float *wino_w, float *gbias, int gbias_accumulate, void *ws,
+                                         size_t ws_bytes, void *stream) {
+    return conv_bwd_data(gy, w, gx, relu_x, ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad}, accumulate, wino_w, gbias, gbias_accumulate, ws,
+                         ws_bytes, stream, nullptr);
+}
+extern "C" int mrcnn_conv2d_bwd_data_active_f32(const float *gy, const float *w, float *gx, const float *relu_x, int N, int H, int W,
+                                                int Cin, int Cout, int KH, int KW, int stride, int pad, int accumulate,
+                                                const unsigned char *active, int n_active, void *ws, size_t ws_bytes, void *stream) {
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (int e = check_active(active, n_active, cg, "conv2d_bwd_data_active")) return e;
+    return conv_bwd_data(gy, w, gx, relu_x, cg, accumulate, nullptr, nullptr, 0, ws, ws_bytes, stream, active);
 }
 
 static size_t bwd_filter_ws_bytes(const ConvGeom &cg) {
@@ -2538,7 +2590,8 @@ extern "C" size_t mrcnn_conv2d_bwd_filter_workspace_bytes(int N, int H, int W, i
 }
 
 static int conv_bwd_filter(const float *x, const float *gy, float *gw, float *gbias, const ConvGeom &cg, int accumulate, const float *wino_v,
-                           const float *wino_w, void *ws, size_t ws_bytes, hipStream_t st, const InBN &inbn = InBN{}) {
+                           const float *wino_w, void *ws, size_t ws_bytes, hipStream_t st, const InBN &inbn = InBN{},
+                           const unsigned char *active = nullptr) {
     if (int e = check_conv(x, gy, gw, cg)) return e;
     if (g_debug_skip & 4) return 0;             // timing experiments only (tools/ab_step.py): what the whole pass costs the step
     const size_t need = bwd_filter_ws_bytes(cg);
@@ -2552,7 +2605,7 @@ static int conv_bwd_filter(const float *x, const float *gy, float *gw, float *gb
         if (wino_w && winograd_w_bytes(cg) == 0) wino_w = nullptr;
         float *bias_part = (float *)((char *)ws + L.total);
         int bias_rows = 0;
-        if (int e = wino_bwd_filter(x, gy, gw, cg, inbn, accumulate, ws, st, wino_v, wino_w, gbias ? bias_part : nullptr, &bias_rows)) return e;
+        if (int e = wino_bwd_filter(x, gy, gw, cg, inbn, accumulate, ws, st, wino_v, wino_w, gbias ? bias_part : nullptr, &bias_rows, active)) return e;
         if (!gbias) return 0;
         // partial column sums from the gy transform, or a separate pass over gy
         return bias_rows ? colsum_final(bias_part, gbias, bias_rows, Cout, accumulate, st) : colsum(gy, bias_part, gbias, P, Cout, accumulate, st);
@@ -2576,6 +2629,15 @@ extern "C" int mrcnn_conv2d_bwd_filter_f32(const float *x, const float *gy, floa
                                            void *stream) {
     return conv_bwd_filter(x, gy, gw, gbias, ConvGeom{N, H, W, Cin, Cout, KH, KW, stride, pad}, accumulate, wino_v, wino_w, ws, ws_bytes,
                            (hipStream_t)stream);
+}
+
+extern "C" int mrcnn_conv2d_bwd_filter_active_f32(const float *x, const float *gy, float *gw, float *gbias, int N,
+                                                  int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                                  int accumulate, const float *wino_v, const unsigned char *active, int n_active, void *ws,
+                                                  size_t ws_bytes, void *stream) {
+    const ConvGeom cg{N, H, W, Cin, Cout, KH, KW, stride, pad};
+    if (int e = check_active(active, n_active, cg, "conv2d_bwd_filter_active")) return e;
+    return conv_bwd_filter(x, gy, gw, gbias, cg, accumulate, wino_v, nullptr, ws, ws_bytes, (hipStream_t)stream, InBN{}, active);
 }
 
 extern "C" int mrcnn_conv2d_bwd_filter_inbn_f32(const float *x, const float *in_gamma, const float *in_beta, const float *in_mean,

@@ -40,7 +40,21 @@ struct PlaneGemmP {
     int ldc;                   // F: N.  G: nbatch * N
     unsigned long long *stamps; // measurement (nullable): 4 x u64 per workgroup - s_memtime start, end; s_memrealtime start, end; [hw id | xcc id << 32] in slot 4
     int dbg;                   // measurement (mrcnn_debug_conv_parts bits 16..): 1 no MFMA, 2 every tile reads tile 0's operands (L2-resident), 4 no epilogue, 8 no loads
+    // Active-image mask of a Winograd gradient GEMM (nullable; k_pgemm_pp and k_pgemm_gpp only).  Row t of a batch is tile t of the layer:
+    // image t / act_per, rows >= act_T are padding.  An image n with active[n] == 0 has an all-zero output gradient, so its rows add exact
+    // zeros: k_pgemm_pp leaves out the tiles, k_pgemm_gpp the K steps, whose rows are all inactive - grid, plan and order of the sums stay.
+    const unsigned char *active;
+    int act_per, act_T;
 };
+
+// whether any of the tile rows [t0, t0 + nrows) of a Winograd operand belongs to an active image (rows >= T: padding, never active)
+__device__ __forceinline__ bool pg_rows_active(const unsigned char *__restrict__ active, int per, int T, int t0, int nrows) {
+    const int t1 = min(t0 + nrows, T);
+    bool any = false;
+    if (t0 < t1)
+        for (int n = t0 / per, n1 = (t1 - 1) / per; n <= n1; ++n) any |= active[n] != 0;
+    return any;
+}
 
 __device__ __forceinline__ void pg_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char *lds, unsigned voff, unsigned soff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, 0, 0);
@@ -570,7 +584,20 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_pp(PlaneGemmP p) {
     unsigned long long st_t0 = 0, st_r0 = 0;
     if (p.stamps) { st_t0 = pg_now(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
     const int ntiles = p.tiles_m * p.tiles_n;
-    const int nj = vid0 < ntiles ? (ntiles - vid0 + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    const int nj_all = vid0 < ntiles ? (ntiles - vid0 + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    // p.active: bit j of `am` = the workgroup's tile ordinal j has a row of an active image.  The other tiles drop out of the stream (no
+    // load, no MFMA, no store: the output transform does not read their rows of C); the walk over the remaining ones is the same.
+    const bool masked = p.active != nullptr && nj_all <= 64;
+    unsigned long long am = 0;
+    if (masked) {
+        bool a = false;
+        if (lane < nj_all) {
+            const int m0 = (vid0 + lane * (int)gridDim.x) / p.tiles_n * PGB_BM;
+            a = pg_rows_active(p.active, p.act_per, p.act_T, m0 % p.batch_rows, PGB_BM);
+        }
+        am = __ballot(a);
+    }
+    const int nj = masked ? __popcll(am) : nj_all;
     const unsigned rowbytesA = (unsigned)p.K * 4u;
     const unsigned kblocks = (unsigned)p.K / 16u;
     const int nsteps = (int)kblocks;
@@ -580,7 +607,8 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_pp(PlaneGemmP p) {
     const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void *)p.b, 0, p.bytes_b, 0x00020000);
     // issue side: the tile and K step of the next stage to load, and that tile's per-lane source offsets
     unsigned voffA[2], voffB[3];
-    int ij = 0, is = 0;
+    unsigned long long ri = am, rc = am;          // tile ordinals still to load / to compute (masked)
+    int ij = (masked && am) ? __builtin_ctzll(am) : 0, is = 0;
     auto setup = [&](int j) {
         const int tile = vid0 + j * (int)gridDim.x;
         const int bx = tile / p.tiles_n, by = tile - bx * p.tiles_n;
@@ -610,7 +638,11 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_pp(PlaneGemmP p) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) pg_dma16(rsB, sb + (wave + 8 * i) * 1024, voffB[i], soffB);
         }
-        if (++is == nsteps) { is = 0; ++ij; }
+        if (++is == nsteps) {
+            is = 0;
+            if (masked) { ri &= ri - 1; ij = ri ? __builtin_ctzll(ri) : nj_all; }
+            else ++ij;
+        }
     };
 
     f32x16 acc[2][4];
@@ -636,7 +668,7 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_pp(PlaneGemmP p) {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (half) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
-    int cs = 0, cj = 0;               // compute side: K step within the tile, tile ordinal
+    int cs = 0, cj = (masked && am) ? __builtin_ctzll(am) : 0;              // compute side: K step within the tile, tile ordinal
     for (int g = 0; g < S; ++g) {
         // ---- X(g): the loads of stage g + 2, this step's fragments, the split of the A fragments
         if (g + 2 < S) issue_next(b2);
@@ -719,7 +751,9 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_pp(PlaneGemmP p) {
                         acc[tm][tn][e] = 0.0f;
                     }
                 }
-            cs = 0; ++cj;
+            cs = 0;
+            if (masked) { rc &= rc - 1; cj = rc ? __builtin_ctzll(rc) : nj_all; }
+            else ++cj;
         }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -745,6 +779,7 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_pp(PlaneGemmP p) {
 //       with four ds_read2st64_b32 and splits it into the three planes in registers.
 // Wave group g owns output rows [128 g, 128 g + 128); its four waves own 64 columns each: 4 x 2 MFMA tiles, four W fragments (free) and
 // two V fragments (68 VALU instructions) per step.  Output: slab (split, M, nbatch, N) partial sums, straight from the accumulators.
+constexpr int PGG_MASK_STEPS = 128;          // K steps per split that the active-image mask of k_pgemm_gpp covers
 __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_gpp(PlaneGemmP p) {
     constexpr int W_ROW = 3 * 512, W_STAGE = 16 * W_ROW, V_ROW = 1024, V_STAGE = 16 * V_ROW;       // 24 KB + 16 KB = PGB_STAGE
     static_assert(W_STAGE + V_STAGE == PGB_STAGE, "stage size");
@@ -762,7 +797,24 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_gpp(PlaneGemmP p) {
     const int batch = vid % p.nbatch, split = vid / p.nbatch;
     const int m0 = bx * PGB_BM, n0 = by * PGB_BN;
     const int kbeg = split * p.kchunk, kend = min(p.K, kbeg + p.kchunk);
-    const int nsteps = kend > kbeg ? (kend - kbeg) / PG_BK : 0;
+    const int nsteps_all = kend > kbeg ? (kend - kbeg) / PG_BK : 0;
+    // p.active: bit s of (am0, am1) = K step s of this split has a row of an active image; the other steps are left out (k_wino_gy did
+    // not write their rows of W).  PGG_MASK_STEPS steps at most: the host passes the mask to both kernels only then.
+    const bool masked = p.active != nullptr && nsteps_all <= PGG_MASK_STEPS;
+    unsigned long long am0 = 0, am1 = 0;
+    if (masked) {
+        am0 = __ballot(lane < nsteps_all && pg_rows_active(p.active, p.act_per, p.act_T, kbeg + lane * PG_BK, PG_BK));
+        am1 = __ballot(lane + 64 < nsteps_all && pg_rows_active(p.active, p.act_per, p.act_T, kbeg + (lane + 64) * PG_BK, PG_BK));
+    }
+    const int nsteps = masked ? __popcll(am0) + __popcll(am1) : nsteps_all;       // steps of the ring
+    unsigned knext = 0;
+    auto take = [&]() -> unsigned {              // the K step the next stage loads
+        if (!masked) return knext++;
+        unsigned s;
+        if (am0) { s = (unsigned)__builtin_ctzll(am0); am0 &= am0 - 1; }
+        else { s = 64u + (unsigned)__builtin_ctzll(am1); am1 &= am1 - 1; }
+        return s;
+    };
     const unsigned rowW = (unsigned)p.M * 6u, rowV = (unsigned)p.N * 4u;          // bytes per row t
 
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, p.bytes_a, 0x00020000);
@@ -815,7 +867,7 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_gpp(PlaneGemmP p) {
     const bool loads = !(p.dbg & 8), mfma = !(p.dbg & 1);
     unsigned b0 = 0, b1 = PGB_STAGE, b2 = 2 * PGB_STAGE;
     if (nsteps > 0) {
-        if (loads) { issue(b0, 0); if (nsteps > 1) issue(b1, 1); }
+        if (loads) { issue(b0, take()); if (nsteps > 1) issue(b1, take()); }
         if (nsteps > 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -826,7 +878,7 @@ __global__ __launch_bounds__(PGB_THREADS, 2) void k_pgemm_gpp(PlaneGemmP p) {
 #define PG_DSTR(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
 #define PG_DSR2ST64(DST, ADDR, O0, O1) asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(DST) : "v"(ADDR), "n"(O0), "n"(O1) : "memory")
     for (int s = 0; s < nsteps; ++s) {
-        if (s + 2 < nsteps && loads) issue(b2, (unsigned)(s + 2));
+        if (s + 2 < nsteps && loads) issue(b2, take());
         // V columns first (their split is the VALU work of the phase), then the W transpose reads
         pg_u32x2 rv[2][4];
         const unsigned av = offV + b0;

@@ -493,3 +493,27 @@ extern "C" int mrcnn_anchor_target_f32(const float *anchors, int A, const float 
     MRCNN_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- active rows of the mask branch --------------------------------------------------------------------------------------------
+// The sampler puts the n_pos[i] positives of image block i first, and the mask loss reads those rows only: the loss gradient of every
+// other row is zero.  active[r] = 1 for the rows that can carry gradient; the convolution backward passes that take it
+// (mrcnn_conv2d_bwd_data_active_f32, mrcnn_conv2d_bwd_filter_active_f32) leave the other rows out.  The count never visits the host.
+namespace {
+__global__ __launch_bounds__(256) void k_active_rows(const int32_t *__restrict__ n_pos, int rows_per_block, int R, unsigned char *__restrict__ active) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const int blk = r / rows_per_block;
+    active[r] = (r - blk * rows_per_block) < n_pos[blk] ? 1 : 0;
+}
+}  // namespace
+
+extern "C" int mrcnn_active_rows_u8(const int32_t *n_pos, int n_blocks, int rows_per_block, unsigned char *active, void *stream) {
+    if (n_blocks < 0 || rows_per_block <= 0 || (long long)n_blocks * rows_per_block >= (1ll << 31))
+        return mrcnn::fail_arg(MRCNN_E_INVALID, "active_rows: bad sizes (%d blocks of %d rows)", n_blocks, rows_per_block);
+    if (n_blocks == 0) return 0;
+    if (!n_pos || !active) return mrcnn::fail_arg(MRCNN_E_INVALID, "active_rows: null pointer");
+    const int R = n_blocks * rows_per_block;
+    hipLaunchKernelGGL(k_active_rows, dim3(mrcnn::cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, n_pos, rows_per_block, R, active);
+    MRCNN_LAUNCH_CHECK();
+    return 0;
+}

@@ -324,6 +324,21 @@ int mrcnn_conv2d_bwd_filter_f32(const float *x, const float *gy, float *gw, floa
                                 int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int accumulate,
                                 const float *wino_v, const float *wino_w,
                                 void *ws, size_t ws_bytes, void *stream);
+/* The two backward passes of a layer whose output gradient is zero on whole images of the batch (the rows of the mask branch that
+ * the mask loss does not read).  active (nullable; n_active == N bytes on the device, else MRCNN_E_INVALID): active[n] == 0 is the
+ * caller's promise that gy is all zero on image n.  The Winograd layers on the plane GEMMs then leave those images out of their
+ * transforms and GEMMs (no launch changes its grid, plan or order of sums: a skipped term is an exact zero); every other path runs
+ * the dense pass.  Results equal the plain entry points' up to the sign of zero; gx of an inactive image is zero, or unchanged with
+ * accumulate.  A NULL active is the plain call.  mrcnn_active_rows_u8 writes the mask of a row-blocked batch on the device:
+ * active[r] = (r % rows_per_block) < n_pos[r / rows_per_block] for r < n_blocks * rows_per_block. */
+int mrcnn_conv2d_bwd_data_active_f32(const float *gy, const float *w, float *gx, const float *relu_x, int N, int H, int W, int Cin,
+                                     int Cout, int KH, int KW, int stride, int pad, int accumulate, const unsigned char *active,
+                                     int n_active, void *ws, size_t ws_bytes, void *stream);
+int mrcnn_conv2d_bwd_filter_active_f32(const float *x, const float *gy, float *gw, float *gbias, int N, int H,
+                                       int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int accumulate,
+                                       const float *wino_v, const unsigned char *active, int n_active,
+                                       void *ws, size_t ws_bytes, void *stream);
+int mrcnn_active_rows_u8(const int32_t *n_pos, int n_blocks, int rows_per_block, unsigned char *active, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backbone / head layer kernels (nn.hip), NHWC fp32, "(P, C)" = P pixels x C channels, C % 4 == 0.
