@@ -17,8 +17,8 @@
 //   full_est = ((float)gt28 * (float)full) / (float)crop      the 28x28 target's area scaled up to the part of the mask outside the RoI
 //   uni      = ((float)pred + full_est) - (float)ovr
 //   target   = (float)ovr / fmaxf(uni, 1.0f)
-// and 0 where crop == 0, full == 0, the RoI has no integer extent, or the row is padding (r % rows >= n_pos[i], channel < 0, no assignment
-// below n_gt[i]).
+// and 0 where crop == 0, full == 0, the RoI has no integer extent, or the row is padding (r % rows >= n_pos[i], channel outside
+// [0, n_channels), no assignment below n_gt[i]).
 #include "common.h"
 #include "loss_common.h"
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(TB) void k_maskiou_target(
     const int32_t *__restrict__ part, int32_t *__restrict__ area,
     const float *__restrict__ sample_roi, const int32_t *__restrict__ gt_assign, const int32_t *__restrict__ label,
     const int32_t *__restrict__ n_pos, int n_sample, int rows, int Rm, const float *__restrict__ mask_out, int msz, int Cp,
-    const int32_t *__restrict__ gt_roi_mask, int label_base, float *__restrict__ target, int32_t *__restrict__ counts) {
+    int n_channels, const int32_t *__restrict__ gt_roi_mask, int label_base, float *__restrict__ target, int32_t *__restrict__ counts) {
     if ((int)blockIdx.x >= Rm) {
         const int m = ((int)blockIdx.x - Rm) * TB + threadIdx.x;
         if (m < N * G) {
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(TB) void k_maskiou_target(
     const int srow = img * n_sample + j;
     const int ch = label[r] - label_base;
     const int g = gt_assign[srow];
-    const bool live = j < n_pos[img] && ch >= 0 && ch < Cp && g >= 0 && g < G && g < n_gt[img];
+    const bool live = j < n_pos[img] && ch >= 0 && ch < n_channels && g >= 0 && g < G && g < n_gt[img];
     int v[4] = {0, 0, 0, 0};        // crop, pred, gt28, ovr
     int full = 0;
     if (live) {
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(TB) void k_maskiou_target(
 // logit - fmaxf(fmaxf(fmaxf(m[2y][2x], m[2y][2x+1]), m[2y+1][2x]), m[2y+1][2x+1]) - or 0 for a row without a channel, the rest zeros.
 __global__ __launch_bounds__(NT) void k_maskiou_input_fwd(const float *__restrict__ feat, const float *__restrict__ mask_out,
                                                           const int32_t *__restrict__ label, int label_base, size_t n4, int P, int C4,
-                                                          int Cp, int cin4, float *__restrict__ out) {
+                                                          int Cp, int n_channels, int cin4, float *__restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
         const int q = (int)(i % cin4);
         const size_t pix = i / cin4;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(NT) void k_maskiou_input_fwd(const float *__restric
             const int x = (int)(pix % P), y = (int)((pix / P) % P);
             const size_t r = pix / ((size_t)P * P);
             const int ch = label[r] - label_base;
-            if (ch >= 0 && ch < Cp) {
+            if (ch >= 0 && ch < n_channels) {
                 const float *m = mask_out + ((r * 2 * P + 2 * y) * 2 * P + 2 * x) * Cp + ch;
                 const size_t line = (size_t)2 * P * Cp;
                 o.x = fmaxf(fmaxf(fmaxf(m[0], m[Cp]), m[line]), m[line + Cp]);
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(NT) void k_maskiou_input_bwd(const float *__restric
 // PHASE 0: (weight * sum of 0.5 d^2, count) over the rows with target > 0, d = pred[r, label - label_base] - target[r].
 // PHASE 1: every element of gx (Rm, ld): d * (weight * (1 / count)) at that column of those rows, 0 elsewhere.
 template <int PHASE>
-__global__ __launch_bounds__(NT) void k_maskiou_l2(const float *__restrict__ pred, int ld, const float *__restrict__ target,
+__global__ __launch_bounds__(NT) void k_maskiou_l2(const float *__restrict__ pred, int ld, int n_channels, const float *__restrict__ target,
                                                    const int32_t *__restrict__ label, int label_base, int Rm, float weight,
                                                    float *__restrict__ part, const float *__restrict__ norm, float *__restrict__ gx) {
     if (PHASE == 0) {
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(NT) void k_maskiou_l2(const float *__restrict__ pre
         for (int r = blockIdx.x * NT + threadIdx.x; r < Rm; r += gridDim.x * NT) {
             const int ch = label[r] - label_base;
             const float t = target[r];
-            if (!(t > 0.f) || ch < 0 || ch >= ld) continue;
+            if (!(t > 0.f) || ch < 0 || ch >= n_channels) continue;
             const float d = pred[(size_t)r * ld + ch] - t;
             ls += 0.5f * d * d;
             cnt += 1.f;
@@ -221,19 +221,19 @@ __global__ __launch_bounds__(NT) void k_maskiou_l2(const float *__restrict__ pre
         const float scale = weight * (1.0f / norm[1]);
         const size_t n = (size_t)Rm * ld;
         for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
-            const int r = (int)(i / ld), c = (int)(i % ld);
+            const int r = (int)(i / ld), c = (int)(i % ld), ch = label[r] - label_base;
             const float t = target[r];
-            gx[i] = (t > 0.f && c == label[r] - label_base) ? (pred[i] - t) * scale : 0.f;
+            gx[i] = (t > 0.f && ch >= 0 && ch < n_channels && c == ch) ? (pred[i] - t) * scale : 0.f;
         }
     }
 }
 
 __global__ __launch_bounds__(NT) void k_maskiou_rescore(const float *__restrict__ score, const float *__restrict__ pred, int ld,
-                                                        const int32_t *__restrict__ label, int D, float *__restrict__ out) {
+                                                        int n_channels, const int32_t *__restrict__ label, int D, float *__restrict__ out) {
     const int d = blockIdx.x * NT + threadIdx.x;
     if (d >= D) return;
     const int ch = label[d];
-    const float iou = (ch >= 0 && ch < ld) ? pred[(size_t)d * ld + ch] : 0.f;
+    const float iou = (ch >= 0 && ch < n_channels) ? pred[(size_t)d * ld + ch] : 0.f;
     out[d] = score[d] * fminf(fmaxf(iou, 0.f), 1.f);
 }
 
@@ -269,7 +269,7 @@ extern "C" int mrcnn_maskiou_target(const uint8_t *masks, int N, int G, int H, i
     hipLaunchKernelGGL(k_mask_area, dim3(MI_CHUNKS, G, N), dim3(NT), 0, st, masks, G, (long long)H * W, n_gt, part);
     MRCNN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_maskiou_target, dim3(Rm + mrcnn::cdiv(N * G, TB)), dim3(TB), 0, st, masks, N, G, H, W, n_gt, part, area, sample_roi,
-                       gt_assign, label, n_pos, n_sample, rows, Rm, mask_out, mask_size, Cp, gt_roi_mask, label_base, target, counts);
+                       gt_assign, label, n_pos, n_sample, rows, Rm, mask_out, mask_size, Cp, n_channels, gt_roi_mask, label_base, target, counts);
     MRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -284,7 +284,7 @@ extern "C" int mrcnn_maskiou_input_fwd(const float *feat, const float *mask_out,
     if (!feat || !mask_out || !label || !out) return mrcnn::fail_arg(MRCNN_E_INVALID, "maskiou_input_fwd: null pointer");
     const size_t n4 = (size_t)Rm * P * P * (cin_p / 4);
     hipLaunchKernelGGL(k_maskiou_input_fwd, dim3(ew_blocks(n4)), dim3(NT), 0, (hipStream_t)stream, feat, mask_out, label, label_base, n4, P,
-                       C / 4, Cp, cin_p / 4, out);
+                       C / 4, Cp, n_channels, cin_p / 4, out);
     MRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -311,13 +311,14 @@ extern "C" int mrcnn_maskiou_l2(const float *pred, int ld, int n_channels, const
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)ws;
     const int nb = grid_for(Rm);
-    hipLaunchKernelGGL(k_maskiou_l2<0>, dim3(nb), dim3(NT), 0, st, pred, ld, target, label, label_base, Rm, weight, part, nullptr, nullptr);
+    hipLaunchKernelGGL(k_maskiou_l2<0>, dim3(nb), dim3(NT), 0, st, pred, ld, n_channels, target, label, label_base, Rm, weight, part, nullptr,
+                       nullptr);
     MRCNN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, st, part, nb, loss_out);
     MRCNN_LAUNCH_CHECK();
     if (gx && Rm > 0) {
-        hipLaunchKernelGGL(k_maskiou_l2<1>, dim3(grid_for((long long)Rm * ld)), dim3(NT), 0, st, pred, ld, target, label, label_base, Rm,
-                           weight, part, loss_out, gx);
+        hipLaunchKernelGGL(k_maskiou_l2<1>, dim3(grid_for((long long)Rm * ld)), dim3(NT), 0, st, pred, ld, n_channels, target, label, label_base,
+                           Rm, weight, part, loss_out, gx);
         MRCNN_LAUNCH_CHECK();
     }
     return 0;
@@ -330,7 +331,7 @@ extern "C" int mrcnn_maskiou_rescore(const float *score, const float *pred, int 
         return mrcnn::fail_arg(MRCNN_E_INVALID, "maskiou_rescore: %d label channels outside the %d columns of pred", n_channels, ld);
     if (D == 0) return 0;
     if (!score || !pred || !label || !out) return mrcnn::fail_arg(MRCNN_E_INVALID, "maskiou_rescore: null pointer");
-    hipLaunchKernelGGL(k_maskiou_rescore, dim3(mrcnn::cdiv(D, NT)), dim3(NT), 0, (hipStream_t)stream, score, pred, ld, label, D, out);
+    hipLaunchKernelGGL(k_maskiou_rescore, dim3(mrcnn::cdiv(D, NT)), dim3(NT), 0, (hipStream_t)stream, score, pred, ld, n_channels, label, D, out);
     MRCNN_LAUNCH_CHECK();
     return 0;
 }

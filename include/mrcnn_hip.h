@@ -1138,7 +1138,7 @@ int mrcnn_cascade_prob_f32(const float *box_out0, const float *box_out1, const f
  * correctly rounded divisions, no float atomics: the same bits on every run.  Every launch is capture-safe.
  * n_channels: the logical class channels a label may select (label - label_base in [0, n_channels)); MRCNN_E_INVALID when it is not in
  *   [1, Cp] / [1, ld].  label_base: 1 for the sampler's labels (0 = background), 0 for the labels MaskRCNN.predict returns.  A row whose
- *   channel is negative has no class: target 0, logit channel 0, no loss.
+ *   channel is outside [0, n_channels) has no class: target 0 with zero counts, logit channel 0, no loss and a zero gradient row.
  * maskiou_target: two launches.  masks (N,G,H,W) u8; n_gt (N) device; sample_roi (N*n_sample,4) (y1,x1,y2,x2), gt_assign (N*n_sample),
  *   n_pos (N): the sampler's outputs; the mask block has Rm = N * rows rows, row r being sampler row (r / rows) * n_sample + r % rows;
  *   label (Rm), mask_out (Rm,mask_size,mask_size,Cp), gt_roi_mask (Rm,mask_size,mask_size) int32.
@@ -1158,7 +1158,7 @@ int mrcnn_cascade_prob_f32(const float *box_out0, const float *box_out1, const f
  *   loss_out[1] = max(count, 1) (the (sum, count) form of mrcnn_smooth_l1_f32: block partials, one finalising wave in double);
  *   gx (Rm,ld), nullable: d * (weight * (1 / loss_out[1])) at that column, 0 in every other element.  No such row: loss 0, gx 0.
  *   ws: mrcnn_loss_workspace_bytes().
- * maskiou_rescore: out[d] = score[d] * fminf(fmaxf(pred[d*ld + label[d]], 0), 1); label 0-based; a label outside [0, ld) gives 0.
+ * maskiou_rescore: out[d] = score[d] * fminf(fmaxf(pred[d*ld + label[d]], 0), 1); label 0-based; a label outside [0, n_channels) gives 0.
  * Rm == 0 / D == 0 succeed without a launch.
  * ---------------------------------------------------------------------------------------- */
 size_t mrcnn_maskiou_target_workspace_bytes(int N, int G);

@@ -27,7 +27,9 @@ def crop_rect(roi, H, W):
 
 
 def target_counts(c, label_base=1):
-    """counts (Rm,5) int64 = (full, crop, pred, gt28, ovr) of every mask row of case ``c``; zeros for padding rows."""
+    """counts (Rm,5) int64 = (full, crop, pred, gt28, ovr) of every mask row of case ``c``; zeros for padding rows and for rows whose
+    channel is outside [0, n_channels): a label that selects a padding channel of mask_out has no class.  n_channels = c['n_fg']; every
+    channel of mask_out for a case without that key."""
     masks, n_gt = c['masks'], c['n_gt']
     N, G, H, W = masks.shape
     rows, S = c['rows'], c['n_sample']
@@ -38,7 +40,7 @@ def target_counts(c, label_base=1):
         srow = i * S + j
         ch = int(c['label'][r]) - label_base
         g = int(c['gt_assign'][srow])
-        if not (j < c['n_pos'][i] and 0 <= ch < c['mask_out'].shape[3] and 0 <= g < min(G, int(n_gt[i]))):
+        if not (j < c['n_pos'][i] and 0 <= ch < c.get('n_fg', c['mask_out'].shape[3]) and 0 <= g < min(G, int(n_gt[i]))):
             continue
         y0, y1, x0, x1 = crop_rect(c['sample_roi'][srow], H, W)
         crop = np.count_nonzero(masks[i, g, y0:y1, x0:x1]) if y1 > y0 and x1 > x0 else 0
@@ -65,15 +67,17 @@ def target(c, label_base=1, dtype=np.float64):
 
 
 # ---- the head's input ---------------------------------------------------------------------------------------------------------------------
-def input_fwd(feat, mask_out, label, cin_p, label_base=1):
+def input_fwd(feat, mask_out, label, cin_p, label_base=1, n_channels=None):
     """(Rm,P,P,cin_p): channels [0,C) = feat, channel C = max(max(max(m[2y][2x], m[2y][2x+1]), m[2y+1][2x]), m[2y+1][2x+1]) of the row's
-    channel (0 for a row without one), zeros behind."""
+    channel (0 for a row without one: label - label_base outside [0, n_channels)), zeros behind.  n_channels None: every channel of
+    mask_out is a class channel."""
+    n_channels = mask_out.shape[3] if n_channels is None else n_channels
     Rm, P, _, C = feat.shape
     out = np.zeros((Rm, P, P, cin_p), feat.dtype)
     out[..., :C] = feat
     for r in range(Rm):
         ch = int(label[r]) - label_base
-        if 0 <= ch < mask_out.shape[3]:
+        if 0 <= ch < n_channels:
             m = mask_out[r, :, :, ch]
             out[r, :, :, C] = np.fmax(np.fmax(np.fmax(m[0::2, 0::2], m[0::2, 1::2]), m[1::2, 0::2]), m[1::2, 1::2])
     return out
@@ -85,13 +89,14 @@ def input_bwd(g_in, g_pool):
 
 
 # ---- the loss and the rescoring -----------------------------------------------------------------------------------------------------------
-def l2(pred, tgt, label, weight=1.0, label_base=1, dtype=np.float64):
-    """(loss, count, gx): loss = weight * sum(0.5 d^2) / count over the rows with target > 0, d = pred[r, label - label_base] - target;
-    gx = d * (weight * (1 / count)) in that column, zeros elsewhere; count = max(#rows, 1)."""
+def l2(pred, tgt, label, weight=1.0, label_base=1, dtype=np.float64, n_channels=None):
+    """(loss, count, gx): loss = weight * sum(0.5 d^2) / count over the rows with target > 0 and label - label_base in [0, n_channels)
+    (None: every column of pred), d = pred[r, label - label_base] - target; gx = d * (weight * (1 / count)) in that column, zeros
+    elsewhere; count = max(#rows, 1)."""
     pred, tgt = np.asarray(pred, dtype), np.asarray(tgt, dtype)
     Rm, ld = pred.shape
     ch = np.asarray(label, np.int64) - label_base
-    on = (tgt > 0) & (ch >= 0) & (ch < ld)
+    on = (tgt > 0) & (ch >= 0) & (ch < (ld if n_channels is None else n_channels))
     rows = np.nonzero(on)[0]
     d = pred[rows, ch[rows]] - tgt[rows]
     count = dtype(max(len(rows), 1))
@@ -101,9 +106,11 @@ def l2(pred, tgt, label, weight=1.0, label_base=1, dtype=np.float64):
     return dtype(loss), float(count), gx
 
 
-def rescore(score, pred, label):
-    """score * min(max(pred[d, label[d]], 0), 1) in score's dtype."""
-    iou = pred[np.arange(pred.shape[0]), np.asarray(label, np.int64)]
+def rescore(score, pred, label, n_channels=None):
+    """score * min(max(pred[d, label[d]], 0), 1) in score's dtype; a label outside [0, n_channels) (None: the columns of pred) gives 0."""
+    label = np.asarray(label, np.int64)
+    ok = (label >= 0) & (label < (pred.shape[1] if n_channels is None else n_channels))
+    iou = np.where(ok, pred[np.arange(pred.shape[0]), np.where(ok, label, 0)], pred.dtype.type(0))
     return score * np.fmin(np.fmax(iou, pred.dtype.type(0)), pred.dtype.type(1))
 
 
@@ -272,3 +279,62 @@ def target_cases():
         out.append(('random %dx%d c80 positives' % (H, W), random_case(H + 7, H, W, 80, rows=8, n_pos=(8, 3))))
     out.append(('random 37x45 c3 no positives in image 1', random_case(99, 37, 45, 3, n_gt=(3, 0), n_pos=(6, 0), junk=255)))
     return out
+
+
+def area_case(N, G, H, W, seed=0, junk=255):
+    """Tiny masks for the area pass alone: random bytes (half of them zero, the others any value), n_gt random per image with the LAST
+    image full (so mask N * G - 1 is read), image 0 at 0 and image 1 one below G, ``junk`` in the slots at and beyond n_gt; one live row per image on a
+    1 x 1 logit map keeps the target pass cheap."""
+    rs = np.random.RandomState(seed + N * G + H * W)
+    masks = ((rs.rand(N, G, H, W) < 0.5) * rs.randint(1, 256, (N, G, H, W))).astype(np.uint8)
+    masks[N - 1, G - 1].flat[0] = 3
+    n_gt = rs.randint(1, G + 1, N).astype(np.int32)
+    n_gt[N - 1] = G
+    if N > 1:
+        n_gt[0] = 0
+    if N > 2:
+        n_gt[1] = G - 1
+    for i in range(N):
+        masks[i, n_gt[i]:] = junk
+    return dict(masks=masks, n_gt=n_gt, sample_roi=np.tile(np.array([0, 0, H, W], np.float32), (N, 1)),
+                gt_assign=np.maximum(n_gt - 1, 0).astype(np.int32), label=np.ones((N,), np.int32), n_pos=np.ones((N,), np.int32), n_sample=1,
+                rows=1, mask_out=np.ones((N, 1, 1, 32), np.float32), gt_roi_mask=np.ones((N, 1, 1), np.int32), n_fg=3)
+
+
+CROP_WIDTHS, CROP_RESIDUES, CROP_HEIGHTS = (1, 15, 16, 17, 33), (0, 1, 15), (1, 40)
+
+
+def crop_rects():
+    """[(y0, x0, h, w)]: every width of CROP_WIDTHS at every start column residue mod 16 of CROP_RESIDUES, heights 1 and 40 in turn."""
+    out = []
+    for a, w in enumerate(CROP_WIDTHS):
+        for b, res in enumerate(CROP_RESIDUES):
+            out.append((2 + a, res + 16 * ((a + b) % 2), CROP_HEIGHTS[(a + b) % 2], w))
+    return out
+
+
+def crop_case(mask_size, H=48, W=51, n_fg=3, seed=0):
+    """N = 2, G = 2, n_sample = 20, rows = 17 < n_sample: sampler row j crops crop_rects()[j] for j < 15 (fractional corners that truncate
+    to it), row 15 is a live-looking row on a 30 x 40 crop whose label selects the first PADDING channel of mask_out (label = n_fg + 1: no class), row 16
+    lies behind n_pos.  Every channel of mask_out, the padded ones included, is non-zero; gt_roi_mask is random 0 / 1."""
+    rs = np.random.RandomState(seed + mask_size)
+    N, G, S, rows = 2, 2, 20, 17
+    Cp = pad32(n_fg)
+    rects = crop_rects()
+    masks = ((rs.rand(N, G, H, W) < 0.6) * rs.randint(1, 256, (N, G, H, W))).astype(np.uint8)
+    roi = np.zeros((N * S, 4), np.float32)
+    gt_assign = np.zeros((N * S,), np.int32)
+    for i in range(N):
+        for j in range(S):
+            y0, x0, h, w = (4, 3, 30, 40) if j == 15 else rects[j % len(rects)]
+            roi[i * S + j] = (y0 + 0.25, x0 + 0.5, y0 + h + 0.75, x0 + w + 0.25)
+            gt_assign[i * S + j] = (i + j) % G
+    label = rs.randint(1, n_fg + 1, N * rows).astype(np.int32)
+    label[15::rows] = n_fg + 1
+    mask_out = (rs.standard_normal((N * rows, mask_size, mask_size, Cp)) * 2).astype(np.float32)
+    mask_out[mask_out == 0] = 1.0
+    mask_out[15::rows, :, :, n_fg] = np.abs(mask_out[15::rows, :, :, n_fg])         # the padding channel would predict a full mask
+    gt_roi_mask = (rs.rand(N * rows, mask_size, mask_size) < 0.6).astype(np.int32)
+    gt_roi_mask[15::rows] = 1
+    return dict(masks=masks, n_gt=np.array([G, G], np.int32), sample_roi=roi, gt_assign=gt_assign, label=label,
+                n_pos=np.array([16, 16], np.int32), n_sample=S, rows=rows, mask_out=mask_out, gt_roi_mask=gt_roi_mask, n_fg=n_fg)

@@ -49,6 +49,17 @@ def point_sample(amap, px, py, dt, clamp=False):
     return s
 
 
+def abs_bits(val):
+    """The ranking key of the kernels: the uint32 bits of |value| in float32.  Ascending in |value| for finite input; +-0 -> 0, denormals
+    above it, +-inf above every finite value, a NaN (its sign cleared) above inf."""
+    return np.abs(np.asarray(val).astype(np.float32)).view(np.uint32)
+
+
+def rank(val):
+    """Indices of ``val`` in ascending abs_bits order, ties to the lower index (a stable sort)."""
+    return np.argsort(abs_bits(np.asarray(val).reshape(-1)), kind='stable')
+
+
 def frame(rois_xy5, coords, dt):
     """X = x1 + u (x2 - x1), Y = y1 + v (y2 - y1) for coords (rows,P,2) of boxes (rows,5) (idx,x1,y1,x2,y2)."""
     r = np.asarray(rois_xy5).astype(dt)
@@ -97,9 +108,24 @@ def features_bwd(g_in, coords, rois_xy5, scale, g_map, dt, unit_weights=False):
     return out
 
 
+def candidate_values(keys, coarse, label, n_fg, n_cand, label_base=1, dt=np.float32):
+    """(rows,n_cand): the coarse logit of the row's channel sampled at every candidate; zeros for a row without a channel."""
+    keys = np.asarray(keys)
+    rows, S0 = coarse.shape[0], coarse.shape[1]
+    unit = key_unit(keys, dt)
+    val = np.zeros((rows, n_cand), dt)
+    with np.errstate(invalid='ignore'):
+        for r in range(rows):
+            ch = int(label[r]) - label_base
+            if 0 <= ch < n_fg:
+                val[r] = point_sample(coarse[r][..., ch], unit[r, 0:2 * n_cand:2] * dt(S0), unit[r, 1:2 * n_cand:2] * dt(S0), dt)
+    return val
+
+
 def train_coords(keys, coarse, label, n_fg, P, n_cand, n_imp, label_base=1, dt=np.float32):
-    """coords (rows,P,2) and the ranked candidate indices (rows,n_imp).  The ranking is the kernel's: ascending |coarse logit at the
-    candidate| in float32, ties to the lower candidate index (a stable sort); a row without a channel has uncertainty 0 everywhere."""
+    """coords (rows,P,2) and the ranked candidate indices (rows,n_imp).  The ranking is the kernel's: ascending uint32 bits of |coarse
+    logit at the candidate| in float32 (abs_bits), ties to the lower candidate index (a stable sort); a row without a channel has
+    uncertainty 0 everywhere."""
     keys = np.asarray(keys)
     rows, S0 = coarse.shape[0], coarse.shape[1]
     unit = key_unit(keys, dt)
@@ -110,8 +136,9 @@ def train_coords(keys, coarse, label, n_fg, P, n_cand, n_imp, label_base=1, dt=n
         u, v = unit[r, 0:2 * n_cand:2], unit[r, 1:2 * n_cand:2]
         val = np.zeros((n_cand,), dt)
         if 0 <= ch < n_fg:
-            val = point_sample(coarse[r][..., ch], u * dt(S0), v * dt(S0), dt)
-        order = np.argsort(np.abs(val), kind='stable')[:n_imp]
+            with np.errstate(invalid='ignore'):
+                val = point_sample(coarse[r][..., ch], u * dt(S0), v * dt(S0), dt)
+        order = rank(val)[:n_imp]
         picked[r] = order
         coords[r, :n_imp, 0], coords[r, :n_imp, 1] = u[order], v[order]
         rest = unit[r, 2 * n_cand:2 * n_cand + 2 * (P - n_imp)]
@@ -179,16 +206,31 @@ def upsample2x(grid, dt):
 
 def subdivide(grid, n_points, dt=np.float32):
     """grid (D,S,S) -> (up (D,2S,2S), index (D,n_sel) ascending flat cells, coords (D,n_sel,2)): the n_sel = min(n_points, 4 S^2) cells of
-    smallest |up|, ties to the lower flat index."""
+    smallest |up| by abs_bits, ties to the lower flat index."""
     D, S = grid.shape[:2]
     n_sel = min(n_points, 4 * S * S)
-    up = np.stack([upsample2x(g, dt) for g in grid]) if D else np.zeros((0, 2 * S, 2 * S), dt)
+    with np.errstate(invalid='ignore'):
+        up = np.stack([upsample2x(g, dt) for g in grid]) if D else np.zeros((0, 2 * S, 2 * S), dt)
     index = np.zeros((D, n_sel), np.int32)
     for d in range(D):
-        index[d] = np.sort(np.argsort(np.abs(up[d].reshape(-1)), kind='stable')[:n_sel])
+        index[d] = np.sort(rank(up[d])[:n_sel])
     x, y = index % (2 * S), index // (2 * S)
     coords = np.stack([(x.astype(dt) + dt(0.5)) / dt(2 * S), (y.astype(dt) + dt(0.5)) / dt(2 * S)], -1)
     return up, index, coords
+
+
+def concat_fwd(h, x0, c0, n_coarse, cin_p):
+    """[h (n,Ch) | x0 (n,ld0)[:, c0 : c0 + n_coarse] | zeros] -> (n,cin_p): a copy, no arithmetic."""
+    n, Ch = h.shape
+    out = np.zeros((n, cin_p), h.dtype)
+    out[:, :Ch] = h
+    out[:, Ch:Ch + n_coarse] = x0[:, c0:c0 + n_coarse]
+    return out
+
+
+def concat_bwd(g_in, Ch):
+    """g_in (n,cin_p)[:, :Ch]: the hidden part of the gradient; the coarse part is dropped."""
+    return np.ascontiguousarray(g_in[:, :Ch])
 
 
 # ---- the point head ---------------------------------------------------------------------------------------------------------------------
@@ -250,6 +292,31 @@ def feature_case(H, W, C, P, n_fg=3, S0=6, seed=0):
                 coarse=(rs.standard_normal((5, S0, S0, Cp)) * 3).astype(np.float32), n_fg=n_fg, cin_p=pad32(C + n_fg),
                 g_in=rs.standard_normal((5, P, pad32(C + n_fg))).astype(np.float32),
                 g_map=rs.standard_normal((2, H, W, C)).astype(np.float32))
+
+
+def general_feature_case(N, H, W, C, P, rows, n_fg, S0, cin_p, seed, rois=None, ld=None, coords=None):
+    """Any sizes: ``rows`` random boxes around the stride-4 map's frame (some partly outside), image indices cycling over [0, N), or the
+    boxes given (rows,5).  coarse (rows,S0,S0,Cp) is non-zero in EVERY channel, the padded ones included; g_in (rows,P,ld) is non-zero
+    behind the fine channels too (ld defaults to cin_p)."""
+    rs = np.random.RandomState(seed)
+    fh, fw = 4.0 * H, 4.0 * W
+    if rois is None:
+        rois = np.zeros((rows, 5), np.float32)
+        rois[:, 0] = np.arange(rows) % N
+        x1, y1 = rs.uniform(-0.1, 0.7, rows) * fw, rs.uniform(-0.1, 0.7, rows) * fh
+        rois[:, 1], rois[:, 2] = x1, y1
+        rois[:, 3], rois[:, 4] = x1 + rs.uniform(0.05, 0.5, rows) * fw, y1 + rs.uniform(0.05, 0.5, rows) * fh
+    rois = np.asarray(rois, np.float32)
+    assert rois.shape == (rows, 5)
+    if coords is None:
+        coords = rs.rand(rows, P, 2).astype(np.float32)
+    Cp = pad32(n_fg)
+    ld = cin_p if ld is None else ld
+    coarse = (rs.standard_normal((rows, S0, S0, Cp)) * 3).astype(np.float32)
+    coarse[coarse == 0] = 1.0
+    return dict(rois=rois, coords=np.asarray(coords, np.float32), fmap=rs.standard_normal((N, H, W, C)).astype(np.float32), coarse=coarse,
+                n_fg=n_fg, cin_p=cin_p, g_in=rs.standard_normal((rows, P, ld)).astype(np.float32),
+                g_map=rs.standard_normal((N, H, W, C)).astype(np.float32))
 
 
 def target_case(H=37, W=45, P=9, seed=1):
