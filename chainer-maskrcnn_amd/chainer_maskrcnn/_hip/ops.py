@@ -1199,6 +1199,72 @@ def mask_iou_counts(a, b, a_label=None, b_label=None):
     return inter, area_a, area_b
 
 
+BOUNDARY_MAX_DILATION = 63      # csrc/evaluate.hip kMaxDilation: a horizontal shift stays within the neighbouring word
+BOUNDARY_BAND_ROWS = 64         # csrc/evaluate.hip kBandRows: image rows of one tile of the boundary kernel
+BOUNDARY_BAND_COLS = 8          # csrc/evaluate.hip kBandCols: 64-pixel word columns of one tile
+
+
+def _boundary_args(who, masks, dilation):
+    """(D, H, W, dilation) of (D,H,W) bool / uint8 masks; dilation None = evaluations.boundary_dilation(H, W)."""
+    for m in masks:
+        if m.dim() != 3:
+            raise ValueError('%s: (D,H,W) masks expected, got %s' % (who, tuple(m.shape)))
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise TypeError('%s: bool or uint8 masks expected, got %s' % (who, m.dtype))
+    H, W = int(masks[0].shape[1]), int(masks[0].shape[2])
+    if H * W > 0x7FFFFFFF:
+        raise ValueError('%s: %d pixels per mask > 2^31 - 1' % (who, H * W))
+    if dilation is None:
+        from chainer_maskrcnn.evaluations import boundary_dilation
+        dilation = boundary_dilation(H, W)
+    if isinstance(dilation, bool) or int(dilation) != dilation or not 1 <= dilation <= BOUNDARY_MAX_DILATION:
+        raise ValueError('%s: dilation must be an integer in 1..%d, got %r' % (who, BOUNDARY_MAX_DILATION, dilation))
+    return H, W, int(dilation)
+
+
+def mask_boundary_iou_counts(a, b, a_label=None, b_label=None, dilation=None):
+    """Mask and boundary-band overlap counts of two mask sets (Boundary IoU, Cheng et al. 2021): a (Da,H,W), b (Db,H,W) bool / uint8
+    device tensors (any nonzero byte is a set pixel).  The band of a mask M is M & ~erode(M, dilation), the erosion by a 3 x 3 block of
+    ones with the outside of the image as background; dilation None = evaluations.boundary_dilation(H, W), else 1..63.  Returns (inter
+    (Da,Db), area_a (Da,), area_b (Db,), binter (Da,Db), barea_a (Da,), barea_b (Db,)) int32 on the device: the first three are
+    mask_iou_counts', the last three the same counts of the bands.  Labels as in mask_iou_counts."""
+    if (a_label is None) != (b_label is None):
+        raise ValueError('mask_boundary_iou_counts: give both label arrays or neither')
+    _hip.require_cuda(a, b, a_label, b_label)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[1:] != b.shape[1:]:
+        raise ValueError('mask_boundary_iou_counts: (D,H,W) masks of one size expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    H, W, dilation = _boundary_args('mask_boundary_iou_counts', (a, b), dilation)
+    Da, Db = a.shape[0], b.shape[0]
+    dev = a.device
+    a = a.contiguous().view(torch.uint8)
+    b = b.contiguous().view(torch.uint8)
+    if a_label is not None and Da and Db:
+        a_label = a_label.to(i32).contiguous()
+        b_label = b_label.to(i32).contiguous()
+    else:                       # labels change nothing when one side is empty
+        a_label = b_label = None
+    out = [torch.empty(s, dtype=i32, device=dev) for s in ((Da, Db), (Da,), (Db,)) * 2]
+    nb = lib().mrcnn_mask_boundary_workspace_bytes(Da, Db, H, W)
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
+    check(lib().mrcnn_mask_boundary_iou_counts_u8(ptr(a), Da, ptr(a_label), ptr(b), Db, ptr(b_label), H, W, dilation, ptr(ws), nb,
+                                                  *[ptr(o) for o in out], stream_ptr()))
+    return tuple(out)
+
+
+def mask_boundary_words(masks, dilation=None):
+    """The boundary bands of masks (D,H,W) bool / uint8 (the first stage of mask_boundary_iou_counts) as bit-packed rows: (D, H,
+    ceil(W/64)) int64 on the device, bit k of word w of a row = band pixel 64 w + k, tail bits zero."""
+    _hip.require_cuda(masks)
+    H, W, dilation = _boundary_args('mask_boundary_words', (masks,), dilation)
+    D = masks.shape[0]
+    masks = masks.contiguous().view(torch.uint8)
+    out = torch.empty((D, H, (W + 63) // 64), dtype=torch.int64, device=masks.device)
+    nb = lib().mrcnn_mask_boundary_workspace_bytes(D, 0, H, W)
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=masks.device)
+    check(lib().mrcnn_mask_boundary_words_u8(ptr(masks), D, H, W, dilation, ptr(ws), nb, ptr(out), stream_ptr()))
+    return out
+
+
 def keypoint_decode(heat, bbox, K, return_index=False):
     """Keypoints from the keypoint branch's heat maps: heat (D,S,S,Cp) float32 NHWC (FPNRoIMaskHead.mask_branch of the keypoint head,
     Cp = pad32(K)), bbox (D,4) float32 (y1,x1,y2,x2) in image coordinates.  Returns (D,K,4) float32 (y, x, logit, prob) on the device:

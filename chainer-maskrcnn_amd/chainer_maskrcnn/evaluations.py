@@ -415,6 +415,46 @@ def segm_iou_from_counts(inter, dt_area, gt_area, gt_crowd):
         return np.where(inter > 0, inter / union, 0.0)
 
 
+# ---- Boundary IoU (Cheng et al., "Boundary IoU: Improving Object-Centric Image Segmentation Evaluation", CVPR 2021) ---------------------
+# COCO's matching with another IoU: min(mask IoU, IoU of the two masks' boundary bands).  The band of a mask is what d erosions by a 3 x 3
+# block of ones remove, the outside of the image counting as background; d = 2 % of the image diagonal.
+BOUNDARY_DILATION_RATIO = 0.02
+
+
+def boundary_dilation(H, W, ratio=BOUNDARY_DILATION_RATIO):
+    """The band width d of an H x W image: int(round(ratio * sqrt(H^2 + W^2))) in float64 with Python's round (half to even), at
+    least 1."""
+    return max(int(round(float(ratio) * float(np.sqrt(np.float64(int(H)) * int(H) + np.float64(int(W)) * int(W))))), 1)
+
+
+def mask_boundary(mask, dilation):
+    """The boundary band of mask(s) (..., H, W) (any nonzero value is a set pixel) as bool: M & ~E, E[y, x] = 1 iff M is 1 on the whole
+    (2 d + 1)^2 square around (y, x) and that square lies inside the image.  Separable: per axis a cumulative sum counts the set pixels
+    of each 2 d + 1 window (two passes in all, whatever d)."""
+    d = int(dilation)
+    if d < 1:
+        raise ValueError('mask_boundary: dilation %r < 1' % (dilation,))
+    m = np.asarray(mask) != 0
+    if m.ndim < 2:
+        raise ValueError('mask_boundary: (..., H, W) masks expected, got %s' % (m.shape,))
+    e = m
+    for axis in (m.ndim - 1, m.ndim - 2):
+        n = e.shape[axis]
+        pad = [(0, 0)] * m.ndim
+        pad[axis] = (d + 1, d)                                                # zeros outside the image; one more in front for the difference
+        c = np.cumsum(np.pad(e, pad).astype(np.int32), axis=axis, dtype=np.int32)
+        hi = np.take(c, np.arange(2 * d + 1, 2 * d + 1 + n), axis=axis)       # sum of positions <= i + d
+        lo = np.take(c, np.arange(0, n), axis=axis)                           # sum of positions <  i - d
+        e = (hi - lo) == 2 * d + 1
+    return m & ~e
+
+
+def boundary_iou_from_counts(inter, dt_area, gt_area, binter, dt_barea, gt_barea, gt_crowd):
+    """(D, G) float64 Boundary IoU from exact integer counts: min(mask IoU, band IoU), each by segm_iou_from_counts' rule (I / (A_dt +
+    A_gt - I), I / A_dt for crowd ground truth, 0 where I == 0) - the mask counts first, the band counts second."""
+    return np.minimum(segm_iou_from_counts(inter, dt_area, gt_area, gt_crowd), segm_iou_from_counts(binter, dt_barea, gt_barea, gt_crowd))
+
+
 def bbox_iou_xywh(dt_xywh, gt_xywh, gt_crowd):
     """(D, G) float64 box IoU of (x, y, w, h) boxes (maskApi.c bbIou): the overlap w * h over da + ga - overlap, or over da for crowd
     ground truth; 0 where the boxes do not overlap."""
@@ -594,12 +634,12 @@ def _load_results(results):
 
 def evaluate_coco_results(gt_annotation_file, results, iou_type, img_ids=None):
     """COCOeval(cocoGt, cocoGt.loadRes(results), iou_type) over ``img_ids`` (default: every image of the annotation file) and all its
-    categories, on the host: ``results`` is a COCO results file or list ({'image_id', 'category_id', 'segmentation' (RLE) or 'bbox',
+    categories, on the host ('boundary': a segm results file scored with min(mask IoU, band IoU), mask_boundary on the host): ``results`` is a COCO results file or list ({'image_id', 'category_id', 'segmentation' (RLE) or 'bbox',
     'score'}); masks are decoded with dataset.coco_api.  As in COCO.loadRes, a segm detection's area is its pixel count unless the
     results carry boxes too (then w * h: loadRes takes such a list as box results).  Returns summarize()'s dict of the 12 stats."""
     from chainer_maskrcnn.dataset.coco_api import COCO, rle_decode, rle_from_string
-    if iou_type not in ('segm', 'bbox'):
-        raise ValueError("evaluate_coco_results: iou_type 'segm' or 'bbox', got %r" % (iou_type,))
+    if iou_type not in ('segm', 'bbox', 'boundary'):
+        raise ValueError("evaluate_coco_results: iou_type 'segm', 'bbox' or 'boundary', got %r" % (iou_type,))
     gt = COCO(gt_annotation_file)
     cat_ids = set(gt.getCatIds())
     img_ids = sorted(set(gt.getImgIds() if img_ids is None else img_ids))
@@ -620,7 +660,7 @@ def evaluate_coco_results(gt_annotation_file, results, iou_type, img_ids=None):
         gt_crowd = np.array([bool(a.get('iscrowd', 0)) for a in anns], bool)
         dt_cat = np.array([d['category_id'] for d in dts], np.int64)
         dt_score = np.array([d['score'] for d in dts], np.float64)
-        if iou_type == 'segm':
+        if iou_type in ('segm', 'boundary'):
             def mask(s):
                 c = s['counts']
                 return rle_decode(rle_from_string(c) if isinstance(c, (str, bytes)) else np.asarray(c, np.int64), *s['size'])
@@ -628,6 +668,11 @@ def evaluate_coco_results(gt_annotation_file, results, iou_type, img_ids=None):
             gm = np.array([gt.annToMask(a) for a in anns], np.float64).reshape(len(anns), h * w)
             dt_area = dm.sum(axis=1)
             iou = segm_iou_from_counts(dm @ gm.T, dt_area, gm.sum(axis=1), gt_crowd)
+            if iou_type == 'boundary':
+                d = boundary_dilation(h, w)
+                db = mask_boundary(dm.reshape(-1, h, w), d).reshape(len(dts), h * w).astype(np.float64)
+                gb = mask_boundary(gm.reshape(-1, h, w), d).reshape(len(anns), h * w).astype(np.float64)
+                iou = np.minimum(iou, segm_iou_from_counts(db @ gb.T, db.sum(axis=1), gb.sum(axis=1), gt_crowd))
             if box_area:
                 db = np.array([d['bbox'] for d in dts], np.float64).reshape(-1, 4)
                 dt_area = db[:, 2] * db[:, 3]

@@ -277,11 +277,15 @@ class InstanceSegmentationCOCOEvaluator(_Evaluator):
     also ``mask_rle_encode`` on the device and one more copy (offsets and counts); one COCO results entry per detection is appended:
     {'image_id', 'category_id', 'segmentation': {'size': [H, W], 'counts': <compressed RLE>}, 'bbox': [x, y, w, h], 'score'}
     (split_coco_results makes the two results files).  No mask is kept on the host.  ``target``'s preset is used as it is, and its
-    training state is restored afterwards."""
+    training state is restored afterwards.
+
+    With 'boundary' among ``iou_types`` (off by default) Boundary AP (Cheng et al., CVPR 2021) is reported under
+    'main/boundary/': segm's matching on min(mask IoU, boundary-band IoU).  The per-image device call is then
+    ``mask_boundary_iou_counts``, whose three band arrays ride in the same copy; the 'segm' and 'bbox' numbers do not change."""
 
     def __init__(self, dataset, target, label_names=None, cat_ids=None, iou_types=('segm', 'bbox'), results=None):
-        if not iou_types or any(t not in ('segm', 'bbox') for t in iou_types):
-            raise ValueError("InstanceSegmentationCOCOEvaluator: iou_types from ('segm', 'bbox'), got %r" % (iou_types,))
+        if not iou_types or any(t not in ('segm', 'bbox', 'boundary') for t in iou_types):
+            raise ValueError("InstanceSegmentationCOCOEvaluator: iou_types from ('segm', 'bbox', 'boundary'), got %r" % (iou_types,))
         self.dataset = dataset
         self.target = target
         self.label_names = label_names
@@ -302,7 +306,7 @@ class InstanceSegmentationCOCOEvaluator(_Evaluator):
         for t, acc in accs.items():
             pr = acc.precision_recall()
             s = self.stats[t] = acc.summarize(pr)
-            prefix = 'main/' if t == 'segm' else 'main/bbox/'
+            prefix = 'main/' if t == 'segm' else 'main/%s/' % t
             report.update({prefix + k: s[name] for k, name in _COCO_KEYS})
             if t == 'segm' and self.label_names is not None:
                 ap = acc.category_ap(pr)
@@ -322,17 +326,21 @@ class InstanceSegmentationCOCOEvaluator(_Evaluator):
         H, W = int(mask.shape[1]), int(mask.shape[2])
         if D:
             bbox = self.target.last_bboxes[0].to(torch.float32).contiguous()
-            overlap = ops.mask_iou_counts(mask, device_tensor(gt_mask, dev).reshape(G, H, W), label, torch.from_numpy(gt_label).to(dev))
-            dt_label, dt_score, yx, inter_h, area_dt_h, area_gt_h = copy_to_host(label, score, bbox, *overlap)     # the one copy of this image
+            counts = ops.mask_boundary_iou_counts if 'boundary' in accs else ops.mask_iou_counts
+            overlap = counts(mask, device_tensor(gt_mask, dev).reshape(G, H, W), label, torch.from_numpy(gt_label).to(dev))
+            dt_label, dt_score, yx, inter_h, area_dt_h, area_gt_h, *band_h = copy_to_host(label, score, bbox, *overlap)     # the one copy of this image
             yx = yx.astype(np.float64)
             xywh = np.stack([yx[:, 1], yx[:, 0], yx[:, 3] - yx[:, 1], yx[:, 2] - yx[:, 0]], axis=1)
         else:
             dt_label, dt_score = np.zeros((0,), np.int32), np.zeros((0,), np.float32)
             xywh, inter_h, area_dt_h, area_gt_h = np.zeros((0, 4)), np.zeros((0, G)), np.zeros((0,)), np.zeros((G,))
+            band_h = [inter_h, area_dt_h, area_gt_h]
         dt_cat, gt_cat = self._cat(dt_label), self._cat(gt_label)
         for t, acc in accs.items():
             if t == 'segm':
                 iou, dt_area = evaluations.segm_iou_from_counts(inter_h, area_dt_h, area_gt_h, gt_crowd), area_dt_h
+            elif t == 'boundary':
+                iou, dt_area = evaluations.boundary_iou_from_counts(inter_h, area_dt_h, area_gt_h, *band_h, gt_crowd), area_dt_h
             else:
                 iou, dt_area = evaluations.bbox_iou_xywh(xywh, gt_bbox, gt_crowd), xywh[:, 2] * xywh[:, 3]
             acc.add_image(iou, dt_cat, dt_score, dt_area, gt_cat, gt_area, gt_crowd)

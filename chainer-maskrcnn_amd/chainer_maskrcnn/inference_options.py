@@ -89,6 +89,28 @@ def boxpost_settings(soft_nms, sigma, vote_thresh, max_detections, prefix='--'):
             'vote_thresh': float(vote_thresh) if vote_thresh else None, 'max_detections': int(max_detections) if max_detections else None}
 
 
+def add_boundary_flag(parser, prefix='--'):
+    """--boundary of evaluate.py; with the prefix '--eval-' the flag of train.py's periodic evaluator (--eval-boundary)."""
+    parser.add_argument(prefix + 'boundary', type=int, default=0, choices=[0, 1],
+                        help='1: also report Boundary AP (Cheng et al., CVPR 2021): COCO mask AP with min(mask IoU, IoU of the masks\' '
+                             'boundary bands) as the IoU (InstanceSegmentationCOCOEvaluator iou_types); off by default')
+
+
+def boundary_iou_types(boundary, eval_metric='mask_coco', keypoints=False, prefix='--'):
+    """The COCO evaluator's iou_types from the flag (--boundary of evaluate.py; --eval-boundary of train.py, which needs --eval-metric
+    mask_coco and a mask head).  ValueError for a combination that has no Boundary AP."""
+    flag = prefix + 'boundary'
+    if boundary not in (0, 1):
+        raise ValueError('%s must be 0 or 1, got %r' % (flag, boundary))
+    if not boundary:
+        return ('segm', 'bbox')
+    if keypoints:
+        raise ValueError('%s 1: Boundary AP is a mask metric; keypoint heads (train_keypoints.py) have none' % flag)
+    if eval_metric != 'mask_coco':
+        raise ValueError('%s 1: Boundary AP is computed by the COCO evaluator; it needs --eval-metric mask_coco, not %s' % (flag, eval_metric))
+    return ('segm', 'bbox', 'boundary')
+
+
 def use_boxpost(model, settings):
     """Applies boxpost_settings' result (None: nothing) to the model."""
     if settings is None:

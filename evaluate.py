@@ -8,7 +8,8 @@
 --eval-images of them when given; --synthetic 1 the deterministic make_batch val split of train.py --eval-metric mask_coco.  Writes
 <out>/segm_results.json and <out>/bbox_results.json ({"image_id", "category_id", "segmentation": RLE / "bbox", "score"}; not with
 --no-results) and <out>/metrics.json (all 12 stats per type, and the test-time augmentation under "tta" when it is on), and prints
-COCOeval's summary lines.  --tta-sizes / --tta-hflip 1 score with test-time augmentation (MaskRCNN.use_test_augmentation):
+COCOeval's summary lines.  --boundary 1 adds Boundary AP (Cheng et al., CVPR 2021): a third block of lines and a "boundary" entry in
+metrics.json.  --tta-sizes / --tta-hflip 1 score with test-time augmentation (MaskRCNN.use_test_augmentation):
 
   python evaluate.py --weight result/model_90000.npz --tta-sizes 640 800 1000 --tta-hflip 1  Keypoint heads are scored by
 train_keypoints.py --eval-metric keypoint_coco.
@@ -22,7 +23,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 sys.path.insert(0, ROOT)
 
-from chainer_maskrcnn.inference_options import (add_boxpost_flags, add_dcn_flags, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model, dcn_settings_of,  # noqa: E402
+from chainer_maskrcnn.inference_options import (add_boundary_flag, add_boxpost_flags, add_dcn_flags, boundary_iou_types, add_extension_flags, add_tta_flags, boxpost_settings, build_inference_model, dcn_settings_of,  # noqa: E402
                                                 extension_settings, read_labels, tta_settings, use_boxpost, use_tta)
 
 SYNTHETIC_VAL_IMAGES = 16           # train.py's synthetic val split of --eval-images 0
@@ -48,6 +49,7 @@ def build_parser():
     add_dcn_flags(parser)
     add_tta_flags(parser)
     add_boxpost_flags(parser)
+    add_boundary_flag(parser)
     parser.add_argument('--out', '-o', default='result_eval', help='Output directory')
     return parser
 
@@ -60,6 +62,7 @@ def check_args(args):
         raise ValueError('evaluate.py runs in a single process; with %d ranks it is not supported' % world)
     extension_settings(args)
     dcn_settings_of(args)
+    boundary_iou_types(args.boundary)
     return boxpost_settings(args.soft_nms, args.soft_nms_sigma, args.box_vote_thresh, args.max_detections)
 
 
@@ -79,7 +82,7 @@ def build_dataset(args, n_fg_class):
 
 
 def run(args):
-    """Evaluates and writes the files; returns {'segm': 12 stats, 'bbox': 12 stats}."""
+    """Evaluates and writes the files; returns {'segm': 12 stats, 'bbox': 12 stats} (and 'boundary' with --boundary 1)."""
     from chainer_maskrcnn import evaluations
     from chainer_maskrcnn.evaluator import InstanceSegmentationCOCOEvaluator, split_coco_results
     boxpost = check_args(args)
@@ -89,7 +92,8 @@ def run(args):
     use_tta(model, tta)
     data = build_dataset(args, model.n_class - 1)
     results = None if args.no_results else []
-    ev = InstanceSegmentationCOCOEvaluator(data, model, results=results)
+    iou_types = boundary_iou_types(args.boundary)
+    ev = InstanceSegmentationCOCOEvaluator(data, model, results=results, iou_types=iou_types)
     ev.evaluate()
     os.makedirs(args.out, exist_ok=True)
     if results is not None:
@@ -100,7 +104,7 @@ def run(args):
     with open(os.path.join(args.out, 'metrics.json'), 'w') as f:
         extra = {k: v for k, v in (('tta', tta), ('boxpost', boxpost)) if v is not None}
         json.dump(dict(ev.stats, **extra) if extra else ev.stats, f, indent=1)
-    for t in ('segm', 'bbox'):
+    for t in iou_types:
         print(evaluations.format_coco_stats(ev.stats[t], t))
     return ev.stats
 

@@ -722,6 +722,30 @@ int mrcnn_mask_iou_counts_u8(const unsigned char *a, int Da, const int32_t *a_la
                              int32_t *area_b, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Boundary-IoU counts of the COCO evaluator's Boundary AP (evaluate.hip; Cheng et al., "Boundary IoU", CVPR 2021).  The boundary
+ * band of a mask M is B = M & ~E, E = M eroded `dilation` times by a 3 x 3 block of ones with everything outside the image
+ * background: E[y, x] = 1 iff M is 1 on the whole (2 d + 1) x (2 d + 1) square around (y, x) and that square lies inside the image.
+ *   a (Da,H,W), b (Db,H,W) uint8, contiguous (no alignment needed); any nonzero byte is a set pixel
+ *   a_label, b_label: as in mrcnn_mask_iou_counts_u8; cross-label pairs get 0 in inter and binter and do no word work
+ *   dilation: the band width d, 1 <= d <= 63 (the host's rule: evaluations.boundary_dilation)
+ *   inter, area_a, area_b: the mask counts, equal to those of mrcnn_mask_iou_counts_u8 on the same inputs
+ *   binter (Da,Db), barea_a (Da), barea_b (Db) int32: |B(a_i) & B(b_j)|, |B(a_i)|, |B(b_j)|, exact, independent of the launch split
+ *   ws: device scratch of mrcnn_mask_boundary_workspace_bytes(Da, Db, H, W) bytes (the row-aligned packed masks and bands)
+ * mrcnn_mask_boundary_words_u8 is the first stage alone: bwords (D,H,ceil(W/64)) 64-bit words, bit k of word w of a row = band
+ * pixel 64 w + k, tail bits zero; ws of mrcnn_mask_boundary_workspace_bytes(D, 0, H, W) bytes.
+ * Empty sides (Da == 0, Db == 0, H * W == 0) are valid (the outputs of the other side are written, the rest zeroed).  Errors, before
+ * any launch: MRCNN_E_INVALID for a negative size, dilation < 1, a NULL pointer of a non-empty side, or one label array only;
+ * MRCNN_E_UNSUPPORTED for dilation > 63 or H * W > 2^31 - 1; MRCNN_E_WORKSPACE for a short workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t mrcnn_mask_boundary_workspace_bytes(int Da, int Db, int H, int W);
+int mrcnn_mask_boundary_words_u8(const unsigned char *masks, int D, int H, int W, int dilation, void *ws, size_t ws_bytes,
+                                 void *bwords, void *stream);
+int mrcnn_mask_boundary_iou_counts_u8(const unsigned char *a, int Da, const int32_t *a_label, const unsigned char *b, int Db,
+                                      const int32_t *b_label, int H, int W, int dilation, void *ws, size_t ws_bytes, int32_t *inter,
+                                      int32_t *area_a, int32_t *area_b, int32_t *binter, int32_t *barea_a, int32_t *barea_b,
+                                      void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint heat-map decode (keypoints.hip; MaskRCNN.predict_keypoints).  Replaces the host NumPy of the reference's viewer.py:86-107
  * (argmax over the cells of predict()'s (D, K, S*S) heat maps, maskrcnn.py:247-251, mapped into the box).
  *   heat (D,S,S,Cp) float32 NHWC, 16-byte aligned, Cp % 4 == 0, Cp >= K: the keypoint branch's output; channels k >= K are not used

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-maskrcnn_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chainer_maskrcnn.inference_options import (DCN_NOUN, EXTENSIONS, NO_DCN, add_boxpost_flags, add_dcn_flags, add_extension_flags, add_tta_flags, boxpost_settings, chain_kwargs,  # noqa: E402
+from chainer_maskrcnn.inference_options import (DCN_NOUN, EXTENSIONS, NO_DCN, add_boundary_flag, add_boxpost_flags, add_dcn_flags, add_extension_flags, add_tta_flags, boundary_iou_types, boxpost_settings, chain_kwargs,  # noqa: E402
                                                 check_resume, dcn_model_kwargs, dcn_settings_of, extension_settings, model_kwargs, read_labels, state_records, tta_settings, use_boxpost,
                                                 use_tta)
 from chainer_maskrcnn.utils.chainer_npz import load_npz, save_npz  # noqa: E402  (load_npz: strict=False, like train.py:99-101)
@@ -94,6 +94,7 @@ def build_parser(keypoints=False):
                              'keypoint_coco = COCO keypoint AP over OKS .50:.95 (keypoint heads, KeypointCOCOEvaluator)')
     add_tta_flags(parser, '--eval-')
     add_boxpost_flags(parser, '--eval-')
+    add_boundary_flag(parser, '--eval-')
     parser.add_argument('--hflip', type=int, default=0, choices=[0, 1],
                         help='1: mirror each training example with probability 0.5 (images, masks, boxes; keypoints with their left / right '
                              'channels swapped); --synthetic 0 only')
@@ -277,6 +278,9 @@ def run(args, keypoints=False):
         raise ValueError('--eval-interval: evaluation runs in single-process training only; with %d ranks it is not supported '
                          '(the reference\'s multi-GPU branch has no test iterator either, train.py:117-121, and would fail there)' % world)
     _check_augment_args(args, keypoints)
+    boundary_iou_types(args.eval_boundary, args.eval_metric, keypoints, '--eval-')
+    if args.eval_boundary and args.eval_interval <= 0:
+        raise ValueError('--eval-boundary 1 adds a metric to the periodic evaluator: it needs --eval-interval > 0')
     eval_boxpost = _eval_boxpost_settings(args)
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume else None
     extensions = extension_settings(args, '--eval-tta-', training=True, keypoints=keypoints)
@@ -507,7 +511,8 @@ def _make_evaluator(args, faster_rcnn, labels, n_fg, K=None):
             from chainer_maskrcnn.dataset.coco_dataset import COCOInstanceEvalDataset
             data = COCOInstanceEvalDataset(anno_dir=args.anno_dir, img_dir=args.img_dir, split='val', data_type=args.data_type,
                                            category_filter=labels, n=args.eval_images or None)
-        return InstanceSegmentationCOCOEvaluator(data, faster_rcnn, label_names=getattr(data, 'label_names', None) or labels)
+        return InstanceSegmentationCOCOEvaluator(data, faster_rcnn, label_names=getattr(data, 'label_names', None) or labels,
+                                                 iou_types=boundary_iou_types(args.eval_boundary, args.eval_metric, prefix='--eval-'))
     if args.synthetic:
         H, W = args.image_size
         data = SyntheticEvalDataset(args.eval_images or SYNTHETIC_VAL_IMAGES, H, W, n_fg_class=n_fg)
